@@ -4,14 +4,18 @@
     train img/s @ 500x500, bs=12/GPU  (configs[2]: synthetic crops + random boxes, dense_overlap targets on
     the GPU, forward, criterion, backward, [RCCL gradient all-reduce], fused SGD), bf16 MFMA compute.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
 One JSON line on rank 0.  `value` = whole-job images/s with every input already resident in HBM when the timed
-region starts.  Extra objects: `roofline` (dominant MFMA kernel, HIP-event timed inside the timed region),
-`cpu_baseline` (the CPU oracle = port of the reference's torch-CPU path, bounded sample, N=1 only) and `eval`
-(configs[1]: ms/image for a 3-scale pyramid of a 1280x960 image: forward x3 + decode + NMS).
+region starts; `ms_per_step` = wall time of one timed step.  A plain run sets up, warms up, times the steps and prints
+the line.  --dump-outputs DIR writes what the last timed step computed (dump_outputs) as .npy files.  --full adds
+everything else, outside the timed region unless noted: `roofline` / `kernels` (dominant MFMA kernel, HIP events
+around 1 launch in PROFILE_EVERY INSIDE the timed region), the forward pass and single-stream kernel tables, `allreduce`
+(N > 1), `fp32_path`, `eval` (configs[1]: ms/image for a 3-scale pyramid of a 1280x960 image: forward x3 + decode +
+NMS), `eval_hard` (configs[4]) and `cpu_baseline` (the CPU oracle = port of the reference's torch-CPU path, bounded
+sample, N=1 only); the --no-* options trim a --full run.
 """
 import argparse
 import ctypes as C
@@ -29,6 +33,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 PEAK_TFLOPS = {"bf16": 2500.0, "fp32": 157.3}       # dense MFMA peaks, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_SAMPLE = 1 << 21                                 # --dump-outputs: seeded sample of the 42.5 M flat weights (8 MB)
+DUMP_IMAGES = 12                                      # --dump-outputs: target maps of the first 12 images of the batch (24 MB): 32 MB in all
 PEAK_HBM_GBS = 8000.0
 FWD_GFLOP_PER_IMG = 73.559                           # BASELINE.md section 3 (2*MACs of all 97 convs @500x500)
 PROFILE_EVERY = 23                                    # roofline timing: HIP events around every 23rd MFMA launch (287 launches per step is not a multiple: the sample rotates over the layers; 11 in rounds 1-2, ~1 % of the step)
@@ -631,6 +637,21 @@ def roof_of(flops, nbytes, seconds, peak_tflops):
             "frac_mfma": round(frac_m, 4), "frac_hbm": round(frac_h, 4)}
 
 
+def dump_outputs(path, eng, loss2, class_map, regression_map):
+    """What the last timed step handed its caller, as DIR/<name>.npy: the [cls, reg] loss sums it returned (float64), the class map it
+    mined in place and the regression targets it trained on (float32, 25 / 100 x 63 x 63 for the first DUMP_IMAGES images), and -- the
+    flat buffer holds 42.5 M values -- seeded DUMP_SAMPLE positions of the fp32 master weights it updated.  That step starts from the
+    seeded initial weights and momentum (main: `initial`), so its inputs are the same in every run and two runs differ by the rounding of
+    one step's fp32-atomic sums only."""
+    os.makedirs(path, exist_ok=True)
+    n = eng.flat_p.numel()
+    idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))).to(eng.flat_p.device)
+    arrays = {"loss": loss2.double(), "class_map": class_map[:DUMP_IMAGES].float(), "regression_map": regression_map[:DUMP_IMAGES].float(),
+              "weights_sample": eng.flat_p[idx].float()}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -651,6 +672,12 @@ def main():
     ap.add_argument("--no-fp32-path", action="store_true", help="skip the fp32 parity-path throughput leg (a second model + arena, ~1 s of GPU time)")
     ap.add_argument("--no-eval-hard", action="store_true", help="skip the configs[4] leg (5000-px fp16 pyramid + batched NMS)")
     ap.add_argument("--cpu-full", action="store_true", help="CPU baseline with the full BASELINE.md protocol (3 + 5 training steps, 3 + 20 images) instead of the bounded sample")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: kernel sampling in the timed region (roofline, kernels), forward-pass and single-stream "
+                         "kernel tables, the N > 1 exchange, the fp32 path, the eval pyramids and the CPU baseline (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, seeded inputs: "
+                         "runs with the same arguments are comparable output for output)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(self_launch(args.gpus))      # `python bench.py --gpus N`: this process becomes the launcher of N ranks
@@ -702,6 +729,11 @@ def main():
     if os.environ.get("TINYFACES_BENCH_SKIP_ALLREDUCE"):      # diagnostic: the process group exists, the steps never use it
         eng.skip_allreduce = True
     pool = [synthetic_batch(1000 * s + rank, args.batch, device, t_d) for s in range(4)]
+    # --dump-outputs: the last timed step restarts from the seeded initial weights and momentum.  This random-init training is chaotic: the
+    # fp32 atomics of the BN statistics and split-K weight gradients make every step differ from run to run in the last bits, and the next
+    # steps amplify that to O(1) in the weights within tens of steps -- only a step whose model state is the same in every run computes
+    # the same outputs every run.  The restore is one device copy (~0.1 ms) inside the timed region, before that step.
+    initial = (eng.flat_p.clone(), eng.flat_m.clone()) if args.dump_outputs else None
 
     raw = None
     if args.with_augment:
@@ -748,6 +780,13 @@ def main():
             return out
         return step_(i)
 
+    last = {}          # --dump-outputs: the target maps of the latest step (held only when asked)
+
+    def train(x, cm, rm):
+        if args.dump_outputs:
+            last["maps"] = (cm, rm)
+        return eng.step(x, cm, rm)
+
     def step_(i):
         if raw is not None:               # the real input pipeline of a training step, minus the JPEG decode
             x, cm, rm = build_batch(i)
@@ -755,29 +794,32 @@ def main():
             cur.wait_stream(in_stream)
             for t in (x, cm, rm):
                 t.record_stream(cur)
-            return eng.step(x, cm, rm)
+            return train(x, cm, rm)
         b = pool[i % len(pool)]
         if in_stream is None:
             cm, rm = ops.dense_overlap_targets_device(b["boxes"], b["offs"], b["total"], t_d, paste_d=b["paste"], seed=i * world + rank)
-            return eng.step(b["x"], cm, rm)
+            return train(b["x"], cm, rm)
         with torch.cuda.stream(in_stream):
             cm, rm = ops.dense_overlap_targets_device(b["boxes"], b["offs"], b["total"], t_d, paste_d=b["paste"], seed=i * world + rank)
         cur = torch.cuda.current_stream()
         cur.wait_stream(in_stream)
         cm.record_stream(cur); rm.record_stream(cur)
-        return eng.step(b["x"], cm, rm)
+        return train(b["x"], cm, rm)
 
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
-    if not args.no_profile:
+    profile = (args.full or args.layer_table) and not args.no_profile
+    if profile:
         _hip.lib().tf_profile_enable(1 if args.layer_table else PROFILE_EVERY)     # HIP events around 1 MFMA launch in PROFILE_EVERY (an event pair costs ~5 us of stream time)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     host_n, host_dt = min(4, args.steps), 0.0
     for i in range(args.steps):
+        if initial is not None and i == args.steps - 1:
+            eng.flat_p.copy_(initial[0]); eng.flat_m.copy_(initial[1])
         loss2 = step(args.warmup + i)
         if i + 1 == host_n:
             host_dt = time.perf_counter() - t0          # the host has ENQUEUED the first steps here (no synchronisation inside a step; later
@@ -793,11 +835,13 @@ def main():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax.item())
     loss_v = loss2.tolist()
+    if args.dump_outputs and rank == 0:       # before anything below runs more steps on the model
+        dump_outputs(args.dump_outputs, eng, loss2, *last["maps"])
 
     # ---- N > 1: size of the exchange (achieved bus GB/s and the fraction hidden under the backward pass).  Outside
     #      the timed region, on every rank (collectives), and never allowed to cost the headline line
     comm = None
-    if world > 1:
+    if world > 1 and args.full:
         try:
             dist = torch.distributed
             g = eng.model._grad_flat_persistent
@@ -845,14 +889,14 @@ def main():
                        bytes=srows[i * 12 + 10], xflops=srows[i * 12 + 11]) for i in range(ns)]
         return prof, shapes
 
-    prof, shapes = collect()
+    prof, shapes = collect() if profile else ([], [])
     if rank != 0:
         return
     # ---- outside the timed region (N = 1): (a) the forward pass alone (north_star states its MFMA target on it), (b) three steps with
     #      EVERY MFMA launch bracketed and the weight gradients on the caller's stream, so that per-kernel times are free of
     #      two-stream contention and add up to less than the step they were taken from
     extra = {}
-    if world == 1 and not args.no_profile and not args.layer_table:       # (--layer-table keeps the shapes of the TIMED region)
+    if world == 1 and args.full and not args.no_profile and not args.layer_table:       # (--layer-table keeps the shapes of the TIMED region)
         try:
             b = pool[0]
             m = eng.model
@@ -893,7 +937,7 @@ def main():
                       "weights": "random init (tamed kaiming), fp32 master + " + args.dtype + " MFMA operands"},
            "precision_note": "bf16 MFMA operands, fp32 accumulation and master weights (bars at this size: forward maps <= 1.8e-2 of a 1.19 range, gradient "
                              "cosine >= 0.90 except <= 2 layer-1 BN sums >= 0.85: tests/test_gpu_fullsize.py); the equal-precision number of the reference's "
-                             "fp32 arithmetic is `fp32_path` in this line (1e-3 bar)",
+                             "fp32 arithmetic is `fp32_path` in the --full line (1e-3 bar)",
            "loss": {"cls": round(loss_v[0], 3), "reg": round(loss_v[1], 3)},
            "step_tflops": round(3 * FWD_GFLOP_PER_IMG * args.batch / ms_per_step, 2)}
     if prof:
@@ -964,15 +1008,16 @@ def main():
                             for r in extra["ss_prof"]]}
         if "error" in extra:
             out["kernels_single_stream"] = {"error": extra["error"]}
-    out["profiles_identity"] = profile_staleness(_hip.identity())
+    if args.full:
+        out["profiles_identity"] = profile_staleness(_hip.identity())
     if comm is not None:
         out["allreduce"] = comm
-    if world == 1 and args.dtype == "bf16" and not args.no_fp32_path:
+    if args.full and world == 1 and args.dtype == "bf16" and not args.no_fp32_path:
         try:
             out["fp32_path"] = bench_fp32_path(device, rank, args.batch)
         except Exception as e:
             out["fp32_path"] = {"error": repr(e)}
-    if world == 1 and not args.no_eval:
+    if args.full and world == 1 and not args.no_eval:
         try:
             out["eval_forward_bs12_500"] = bench_eval_forward(model, device, bs=args.batch)
         except Exception as e:
@@ -981,12 +1026,12 @@ def main():
             out["eval"] = bench_eval(model, templates, device)
         except Exception as e:   # the headline number must still be printed
             out["eval"] = {"error": repr(e)}
-    if world == 1 and not args.no_eval and not args.no_eval_hard:
+    if args.full and world == 1 and not args.no_eval and not args.no_eval_hard:
         try:
             out["eval_hard"] = bench_eval_hard(model, templates, device)
         except Exception as e:
             out["eval_hard"] = {"error": repr(e)}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(warmup=3, steps=5, eval_warmup=3, eval_runs=20) if args.cpu_full else cpu_baseline()
     os.write(json_fd, (json.dumps(out) + "\n").encode())
 

@@ -92,7 +92,7 @@ print(d['value'], d['ms_per_step'], 'frac', r.get('frac'), 'fwd', r.get('forward
     bash "$0" prof train; cp "$R/gpurun_out/prof/train_kernel_stats.csv" "$R/profiles/${rp}_train_bs12_bf16_kernel_stats.csv"
     python scripts/stamp_profiles.py "$R/profiles/${rp}_stamp.json" > /dev/null; cp "$R/profiles/${rp}_stamp.json" "$R/gpurun_out/stamp.json"     # the library these profiles belong to
     bash "$0" pmc-traffic; cp "$R/gpurun_out/pmc_bench/traffic.json" "$R/profiles/${rp}_pmc_traffic.json"; cp "$R/gpurun_out/pmc_bench/traffic_fp32.json" "$R/profiles/${rp}_pmc_traffic_fp32.json"
-    bash "$0" bench
+    bash "$0" bench --full
     bash "$0" tests; cp "$R/gpurun_out/parity_report.txt" "$R/gpurun_out/parity_report_full.txt" 2>/dev/null
     bash "$0" layer-table; bash "$0" timeline; bash "$0" prof eval; bash "$0" eval-table
     python scripts/gridbar.py 2>&1 | grep -v amdgpu.ids > "$R/gpurun_out/gridbar.txt"; tail -5 "$R/gpurun_out/gridbar.txt"

@@ -55,3 +55,36 @@ def test_main_and_evaluate_model_scripts(tmp_path):
     assert files == ["img_0.txt", "img_1.txt"]
     lines = open(tmp_path / "res" / "synthetic" / "img_0.txt").read().split("\n")
     assert lines[0] == "img_0.jpg" and int(lines[1]) == len([l for l in lines[2:] if l.strip()])       # any count, 0 included: the format is the contract
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run times exactly --steps steps and prints the headline alone (everything else is --full); --dump-outputs
+    writes the last timed step's results: its loss pair (the line's `loss`), the mined class map, the regression targets and a sample of the
+    updated weights, float32 / float64 and 64 MB at most.  That step starts from the seeded initial model, so two runs with the same
+    arguments write the same outputs up to the rounding of one step's fp32-atomic sums."""
+    import json
+    import numpy as np
+
+    def run(name, steps, warmup):
+        out = _run([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path / name)], tmp_path)
+        lines = [ln for ln in out.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0]), {f[:-4]: np.load(tmp_path / name / f) for f in os.listdir(tmp_path / name)}
+
+    d, files = run("a", 3, 1)
+    assert d["steps"] == 3 and d["unit"] == "img/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["value"] > 0 and abs(d["value"] - 12 / (d["ms_per_step"] * 1e-3)) < 0.02 * d["value"]
+    assert not {"roofline", "kernels", "profiles_identity", "fp32_path", "eval", "eval_hard", "cpu_baseline"} & set(d), sorted(d)
+    assert sorted(files) == ["class_map", "loss", "regression_map", "weights_sample"]
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert np.allclose(files["loss"], [d["loss"]["cls"], d["loss"]["reg"]], atol=1e-3, rtol=0)
+    assert files["class_map"].shape == (12, 25, 63, 63) and set(np.unique(files["class_map"])) <= {-1.0, 0.0, 1.0}
+    assert files["regression_map"].shape == (12, 100, 63, 63) and files["weights_sample"].shape == (1 << 21,)
+    again = run("b", 3, 1)[1]
+    assert np.array_equal(again["regression_map"], files["regression_map"])
+    assert np.mean(again["class_map"] != files["class_map"]) < 1e-4
+    # the loss sums see one step of bf16 operand rounding (the regression sum runs over a few hundred mined anchors: 2.5e-4 measured);
+    # half a bf16 ulp bounds it.  Runs from drifted weights differed by 1 % here.
+    assert np.allclose(again["loss"], files["loss"], rtol=2e-3, atol=0)
+    assert np.allclose(again["weights_sample"], files["weights_sample"], rtol=0, atol=2e-4)
