@@ -368,7 +368,8 @@ int tf_reduce_partials(const float* partial, int nblk, int nk, int k, int ld, in
 
 /* ---- the detector network as one native graph executor -----------------------------
  * Replaces DetectionModel.forward (tinyfaces/models/model.py:89-128) and its autograd
- * backward (tinyfaces/trainer.py:78,86): ResNet-101 trunk minus layer4, heads, upsample+add.
+ * backward (tinyfaces/trainer.py:78,86): ResNet-101 trunk minus layer4, heads, upsample+add
+ * (ResNet-50 / ResNet-152 trunks: the tf_detnet_trunk_* forms further below).
  * params / grads: tables of device pointers in tf_detnet_param_name(i) order (fp32, the
  * layouts of the reference state_dict: OIHW conv weights, [C] BN vectors).
  * ws: scratch of tf_detnet_workspace_bytes() bytes, carved deterministically per call; the
@@ -424,6 +425,24 @@ int tf_detnet_backward(int dtype, const float* x_nchw, int N, int H, int W, int 
                        void* const* params, void* const* grads, const float* gout_nchw,
                        void* grad_flat, size_t grad_flat_bytes,
                        void* ws, size_t ws_bytes, void* stream);
+/* ---- trunk-aware forms (version 610) -------------------------------------------------------------------------------------------------
+ * The entry points above describe ONE network: the ResNet-101 trunk.  The forms below take the trunk as its Bottleneck block counts in
+ * layers 1-3, blocks[3]: {3, 4, 6} (torchvision resnet50), {3, 4, 23} (resnet101) or {3, 8, 36} (resnet152); blocks = NULL means
+ * {3, 4, 23}.  Every other argument, the parameter table order (stem, the bottlenecks in order, heads, upsample) and every error code are
+ * those of the form without `trunk_`; with blocks = {3, 4, 23} or NULL they are the same call.  Another block count: the queries return
+ * TF_ERR_UNSUPPORTED (num_params, param_numel), NULL (param_name) or 0 (the byte counts), the passes TF_ERR_UNSUPPORTED.
+ * tf_detnet_trunk_param_name's pointers stay valid for the life of the process (one table per trunk, built once, thread-safe). */
+int tf_detnet_trunk_num_params(const int* blocks);                 /* resnet50 220, resnet101 475, resnet152 730 */
+const char* tf_detnet_trunk_param_name(const int* blocks, int i);
+int64_t tf_detnet_trunk_param_numel(const int* blocks, int i, int num_out);
+size_t tf_detnet_trunk_workspace_bytes(const int* blocks, int dtype, int N, int H, int W, int num_out, int training);
+size_t tf_detnet_trunk_param_region_bytes(const int* blocks, int dtype, int num_out, int training);
+int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* ctx, int single_stream, int dtype, int training, const float* x_nchw, int N, int H,
+                                int W, int num_out, void* const* params, float bn_eps, float bn_momentum, float* out_nchw, void* ws, size_t ws_bytes,
+                                int flags, void* stream);
+int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* ctx, const tf_detnet_hooks* hooks, int dtype, const float* x_nchw, int N, int H,
+                                 int W, int num_out, void* const* params, void* const* grads, const float* gout_nchw, void* grad_flat,
+                                 size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- gradient exchange of the data-parallel path over RCCL (the reference has no distributed code) -------------
  * One process per GPU; the gradients are SUMMED over the ranks bucket by bucket while the backward pass runs, the 1/world goes into

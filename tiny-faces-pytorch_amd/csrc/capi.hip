@@ -20,6 +20,8 @@ static const char* const kSymbols[] = {
     "tf_detnet_num_params", "tf_detnet_param_name", "tf_detnet_param_numel", "tf_detnet_workspace_bytes",
     "tf_detnet_out_shape", "tf_detnet_param_region_bytes", "tf_detnet_forward", "tf_detnet_backward", "tf_detnet_ctx_create", "tf_detnet_ctx_destroy", "tf_detnet_forward_ctx", "tf_detnet_backward_ctx", "tf_comm_available", "tf_comm_unique_id", "tf_comm_init", "tf_comm_destroy", "tf_comm_rank", "tf_comm_world", "tf_allreduce_bucket", "tf_comm_join", "tf_comm_allreduce_hook",
     "tf_detnet_set_dual_stream", "tf_detnet_set_grad_events", "tf_detnet_set_grad_callback",
+    "tf_detnet_trunk_num_params", "tf_detnet_trunk_param_name", "tf_detnet_trunk_param_numel", "tf_detnet_trunk_workspace_bytes",
+    "tf_detnet_trunk_param_region_bytes", "tf_detnet_trunk_forward_ctx", "tf_detnet_trunk_backward_ctx",
     "tf_set_stat_rows", "tf_get_stat_rows", "tf_profile_enable", "tf_profile_collect", "tf_profile_shapes",
 };
 
@@ -29,7 +31,7 @@ void set_next_stop_event(hipEvent_t e) { g_next_stop_event = e; }
 hipEvent_t take_next_stop_event() { hipEvent_t e = g_next_stop_event; g_next_stop_event = nullptr; return e; }
 }  // namespace tf
 
-extern "C" int tf_version(void) { return 600; }   // r6: tf_build_id; r5: tf_conv2d_bnfwd; r4: context + hooks + communicator entry points
+extern "C" int tf_version(void) { return 610; }   // tf_detnet_trunk_* (ResNet-50 / -152 trunks); r6: tf_build_id; r5: tf_conv2d_bnfwd; r4: context + hooks + communicator entry points
 #ifndef TF_BUILD_ID
 #define TF_BUILD_ID "unstamped"
 #endif

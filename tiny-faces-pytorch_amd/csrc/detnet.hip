@@ -1,8 +1,9 @@
 // The detector network as a native graph executor: every kernel launch of a forward or a
 // backward pass is issued from here (one C-ABI call per pass, no Python in the loop), with all
 // activations carved from one caller-provided arena.
-// Replaces DetectionModel.forward (tinyfaces/models/model.py:89-128) over the torchvision
-// ResNet-101 trunk (Bottleneck x [3,4,23], stride on the 3x3) and the autograd backward that
+// Replaces DetectionModel.forward (tinyfaces/models/model.py:89-128) over a torchvision
+// Bottleneck trunk (stride on the 3x3): ResNet-101 [3,4,23] by default, ResNet-50 [3,4,6] and
+// ResNet-152 [3,8,36] through the tf_detnet_trunk_* entry points; and the autograd backward that
 // tinyfaces/trainer.py:86 triggers.
 //
 // Data layout in HBM: activations NHWC ("pixels x channels"), dtype bf16 (fast) or fp32
@@ -85,7 +86,7 @@ struct ConvUnit {               // one conv + (optional) BN, with indices into t
 struct Block { ConvUnit c1, c2, c3, ds; bool has_ds; int planes, stride, cin; };
 struct Arch {
   ConvUnit stem;
-  std::vector<Block> blocks;    // 30 bottlenecks
+  std::vector<Block> blocks;    // 16 / 30 / 47 bottlenecks (resnet50 / 101 / 152)
   int layer_end[3];             // index of the last block of layer1/2/3
   ConvUnit head3, head4;
   int upsample_w;
@@ -103,39 +104,56 @@ ConvUnit make_unit(Arch& a, const std::string& conv, const std::string& bn, int 
   return u;
 }
 
-const Arch& arch() {
-  static Arch a = [] {
-    Arch a;
-    a.stem = make_unit(a, "model.conv1", "model.bn1", 3, 64, 7, 2, 3);
-    const int nblk[3] = {3, 4, 23}, planes[3] = {64, 128, 256};
-    int inpl = 64;
-    for (int L = 0; L < 3; ++L) {
-      for (int b = 0; b < nblk[L]; ++b) {
-        Block B;
-        const std::string p = "model.layer" + std::to_string(L + 1) + "." + std::to_string(b);
-        B.planes = planes[L]; B.stride = (b == 0 && L > 0) ? 2 : 1; B.cin = inpl;
-        B.c1 = make_unit(a, p + ".conv1", p + ".bn1", inpl, planes[L], 1, 1, 0);
-        B.c2 = make_unit(a, p + ".conv2", p + ".bn2", planes[L], planes[L], 3, B.stride, 1);
-        B.c3 = make_unit(a, p + ".conv3", p + ".bn3", planes[L], planes[L] * 4, 1, 1, 0);
-        B.has_ds = (b == 0);
-        if (B.has_ds) B.ds = make_unit(a, p + ".downsample.0", p + ".downsample.1", inpl, planes[L] * 4, 1, B.stride, 0);
-        inpl = planes[L] * 4;
-        a.blocks.push_back(B);
-      }
-      a.layer_end[L] = (int)a.blocks.size() - 1;
+// The trunks the executor takes: torchvision's Bottleneck ResNets (groups 1, width 64) by their block counts in layers 1-3.  Every
+// bottleneck of every trunk has the shape of the same bottleneck of ResNet-101; only the number of identity blocks per layer differs.
+constexpr int kTrunks[3][3] = {{3, 4, 6}, {3, 4, 23}, {3, 8, 36}};     // resnet50, resnet101 (the default), resnet152
+constexpr int kDefaultTrunk = 1;
+
+Arch build_arch(const int* nblk) {
+  Arch a;
+  a.stem = make_unit(a, "model.conv1", "model.bn1", 3, 64, 7, 2, 3);
+  const int planes[3] = {64, 128, 256};
+  int inpl = 64;
+  for (int L = 0; L < 3; ++L) {
+    for (int b = 0; b < nblk[L]; ++b) {
+      Block B;
+      const std::string p = "model.layer" + std::to_string(L + 1) + "." + std::to_string(b);
+      B.planes = planes[L]; B.stride = (b == 0 && L > 0) ? 2 : 1; B.cin = inpl;
+      B.c1 = make_unit(a, p + ".conv1", p + ".bn1", inpl, planes[L], 1, 1, 0);
+      B.c2 = make_unit(a, p + ".conv2", p + ".bn2", planes[L], planes[L], 3, B.stride, 1);
+      B.c3 = make_unit(a, p + ".conv3", p + ".bn3", planes[L], planes[L] * 4, 1, 1, 0);
+      B.has_ds = (b == 0);
+      if (B.has_ds) B.ds = make_unit(a, p + ".downsample.0", p + ".downsample.1", inpl, planes[L] * 4, 1, B.stride, 0);
+      inpl = planes[L] * 4;
+      a.blocks.push_back(B);
     }
-    auto head = [&](const std::string& n, int cin) {
-      ConvUnit u; u.name = n; u.cin = cin; u.cout = -1; u.k = 1; u.stride = 1; u.pad = 0;
-      u.w = add_param(a, n + ".weight"); u.bias = add_param(a, n + ".bias");
-      u.gamma = u.beta = u.rmean = u.rvar = -1;
-      return u;
-    };
-    a.head3 = head("score_res3", 512);
-    a.head4 = head("score_res4", 1024);
-    a.upsample_w = add_param(a, "score4_upsample.weight");
-    return a;
-  }();
+    a.layer_end[L] = (int)a.blocks.size() - 1;
+  }
+  auto head = [&](const std::string& n, int cin) {
+    ConvUnit u; u.name = n; u.cin = cin; u.cout = -1; u.k = 1; u.stride = 1; u.pad = 0;
+    u.w = add_param(a, n + ".weight"); u.bias = add_param(a, n + ".bias");
+    u.gamma = u.beta = u.rmean = u.rvar = -1;
+    return u;
+  };
+  a.head3 = head("score_res3", 512);
+  a.head4 = head("score_res4", 1024);
+  a.upsample_w = add_param(a, "score4_upsample.weight");
   return a;
+}
+
+// The Arch of a trunk (blocks = its block counts in layers 1-3; NULL = ResNet-101), or NULL when the executor does not take it.  All of them
+// are built once, under the thread-safe initialisation of a function-local static, and never move: tf_detnet_trunk_param_name hands out
+// pointers into them.
+const Arch* find_arch(const int* blocks) {
+  static const std::vector<Arch> cache = [] {
+    std::vector<Arch> v;
+    for (const auto& t : kTrunks) v.push_back(build_arch(t));
+    return v;
+  }();
+  if (!blocks) return &cache[kDefaultTrunk];
+  for (int k = 0; k < 3; ++k)
+    if (blocks[0] == kTrunks[k][0] && blocks[1] == kTrunks[k][1] && blocks[2] == kTrunks[k][2]) return &cache[k];
+  return nullptr;
 }
 
 // r4: the weight gradients of the identity bottlenecks of layer 3 (22 blocks of identical shape) are differentiated in GROUPS of up to
@@ -199,8 +217,7 @@ struct Plan {                    // everything a forward carves; backward re-der
 
 size_t packed_bytes(int dtype, int rows, int taps, int cols) { return (size_t)((rows + 127) / 128 * 128) * taps * cols * esize(dtype); }
 
-void build_plan(Plan& P, Arena& ar, int dtype, int N, int H, int W, int nout, int training) {
-  const Arch& A = arch();
+void build_plan(const Arch& A, Plan& P, Arena& ar, int dtype, int N, int H, int W, int nout, int training) {
   const size_t es = esize(dtype);
   P.dtype = dtype; P.N = N; P.H = H; P.W = W; P.nout = nout; P.training = training;
   P.H1 = down2(H); P.W1 = down2(W); P.H2 = down2(P.H1); P.W2 = down2(P.W1);
@@ -443,13 +460,18 @@ tf_bn_bwd_desc bwd_desc(const Ctx& c, const ConvUnit& u, const BnBuf& b, const f
 
 }  // namespace
 
-extern "C" int tf_detnet_num_params(void) { return (int)arch().names.size(); }
-extern "C" const char* tf_detnet_param_name(int i) {
-  const Arch& a = arch();
-  return (i >= 0 && i < (int)a.names.size()) ? a.names[i].c_str() : nullptr;
+extern "C" int tf_detnet_trunk_num_params(const int* blocks) {
+  const Arch* a = find_arch(blocks);
+  return a ? (int)a->names.size() : TF_ERR_UNSUPPORTED;
 }
-extern "C" int64_t tf_detnet_param_numel(int i, int nout) {
-  const Arch& a = arch();
+extern "C" const char* tf_detnet_trunk_param_name(const int* blocks, int i) {
+  const Arch* a = find_arch(blocks);
+  return (a && i >= 0 && i < (int)a->names.size()) ? a->names[i].c_str() : nullptr;
+}
+extern "C" int64_t tf_detnet_trunk_param_numel(const int* blocks, int i, int nout) {
+  const Arch* ap = find_arch(blocks);
+  if (!ap) return TF_ERR_UNSUPPORTED;
+  const Arch& a = *ap;
   auto unit = [&](const ConvUnit& u, int cout) -> int64_t {
     if (i == u.w) return (int64_t)cout * u.cin * u.k * u.k;
     if (i == u.gamma || i == u.beta || i == u.rmean || i == u.rvar || i == u.bias) return cout;
@@ -468,6 +490,9 @@ extern "C" int64_t tf_detnet_param_numel(int i, int nout) {
   if (i == a.upsample_w) return (int64_t)nout * nout * 16;
   return -1;
 }
+extern "C" int tf_detnet_num_params(void) { return tf_detnet_trunk_num_params(nullptr); }
+extern "C" const char* tf_detnet_param_name(int i) { return tf_detnet_trunk_param_name(nullptr, i); }
+extern "C" int64_t tf_detnet_param_numel(int i, int nout) { return tf_detnet_trunk_param_numel(nullptr, i, nout); }
 
 extern "C" int tf_detnet_out_shape(int H, int W, int* H3, int* W3) {
   if (H3) *H3 = down2(down2(down2(H)));
@@ -475,17 +500,25 @@ extern "C" int tf_detnet_out_shape(int H, int W, int* H3, int* W3) {
   return TF_OK;
 }
 
-extern "C" size_t tf_detnet_workspace_bytes(int dtype, int N, int H, int W, int nout, int training) {
+extern "C" size_t tf_detnet_trunk_workspace_bytes(const int* blocks, int dtype, int N, int H, int W, int nout, int training) {
+  const Arch* A = find_arch(blocks);
+  if (!A) return 0;
   Plan P; Arena ar(nullptr, 0);
-  build_plan(P, ar, dtype, N, H, W, nout, training);
+  build_plan(*A, P, ar, dtype, N, H, W, nout, training);
   return P.total + 4096;
 }
+extern "C" size_t tf_detnet_workspace_bytes(int dtype, int N, int H, int W, int nout, int training) {
+  return tf_detnet_trunk_workspace_bytes(nullptr, dtype, N, H, W, nout, training);
+}
 
-extern "C" size_t tf_detnet_param_region_bytes(int dtype, int nout, int training) {
+extern "C" size_t tf_detnet_trunk_param_region_bytes(const int* blocks, int dtype, int nout, int training) {
+  const Arch* A = find_arch(blocks);
+  if (!A) return 0;
   Plan P; Arena ar(nullptr, 0);
-  build_plan(P, ar, dtype, 1, 32, 32, nout, training);
+  build_plan(*A, P, ar, dtype, 1, 32, 32, nout, training);
   return P.param_bytes;
 }
+extern "C" size_t tf_detnet_param_region_bytes(int dtype, int nout, int training) { return tf_detnet_trunk_param_region_bytes(nullptr, dtype, nout, training); }
 
 // The executor's second stream (weight gradients of the backward pass; r3: the packing of the layer-3 weights beside the start of the
 // forward pass), one per device, created on first use at the DEFAULT priority.
@@ -558,15 +591,18 @@ extern "C" int tf_detnet_ctx_destroy(tf_detnet_ctx* x) {
 // legacy process-wide switches (tf_detnet_set_dual_stream / _grad_events / _grad_callback): hooks of the context-free entry points
 static bool g_force_single = false;      // tf_detnet_set_dual_stream(0): everything on the caller's stream
 
-extern "C" int tf_detnet_forward_ctx(tf_detnet_ctx* xctx, int single_stream, int dtype, int training, const float* x, int N, int H, int W, int nout,
-                                     void* const* params, float eps, float mom, float* out, void* ws, size_t ws_bytes, int flags, void* stream_) {
+extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xctx, int single_stream, int dtype, int training, const float* x, int N,
+                                           int H, int W, int nout, void* const* params, float eps, float mom, float* out, void* ws, size_t ws_bytes,
+                                           int flags, void* stream_) {
+  const Arch* Ap = find_arch(blocks);
+  if (!Ap) return TF_ERR_UNSUPPORTED;
   if (!xctx) xctx = default_ctx();
   if (!x || !params || !out || !ws || nout <= 0 || nout > kHeadLd) return TF_ERR_ARG;
   if (dtype != TF_BF16 && dtype != TF_F32 && dtype != TF_F16) return TF_ERR_UNSUPPORTED;
   if (dtype == TF_F16 && training) return TF_ERR_UNSUPPORTED;       // fp16 operands: the inference graph only (BASELINE.json configs[4])
-  const Arch& A = arch();
+  const Arch& A = *Ap;
   Plan P; Arena ar(ws, ws_bytes);
-  build_plan(P, ar, dtype, N, H, W, nout, training);
+  build_plan(A, P, ar, dtype, N, H, W, nout, training);
   if (!ar.ok) return TF_ERR_WORKSPACE;
   Ctx c{dtype, (hipStream_t)stream_, params, nullptr, TF_OK};
   tf_conv_args a;
@@ -796,6 +832,10 @@ extern "C" int tf_detnet_forward_ctx(tf_detnet_ctx* xctx, int single_stream, int
   if (hipGetLastError() != hipSuccess && c.rc == TF_OK) c.rc = TF_ERR_LAUNCH;
   return c.rc;
 }
+extern "C" int tf_detnet_forward_ctx(tf_detnet_ctx* xctx, int single_stream, int dtype, int training, const float* x, int N, int H, int W, int nout,
+                                     void* const* params, float eps, float mom, float* out, void* ws, size_t ws_bytes, int flags, void* stream_) {
+  return tf_detnet_trunk_forward_ctx(nullptr, xctx, single_stream, dtype, training, x, N, H, W, nout, params, eps, mom, out, ws, ws_bytes, flags, stream_);
+}
 extern "C" int tf_detnet_forward(int dtype, int training, const float* x, int N, int H, int W, int nout, void* const* params, float eps,
                                  float mom, float* out, void* ws, size_t ws_bytes, int flags, void* stream_) {
   return tf_detnet_forward_ctx(nullptr, g_force_single ? 1 : 0, dtype, training, x, N, H, W, nout, params, eps, mom, out, ws, ws_bytes, flags, stream_);
@@ -888,16 +928,18 @@ static bool grad_event_registered(const tf_detnet_hooks* h, int block) {
 // 1 = weight gradients on a second stream (default), 0 = everything on the caller's stream (A/B + race tests)
 extern "C" int tf_detnet_set_dual_stream(int on) { g_force_single = !on; return TF_OK; }
 
-extern "C" int tf_detnet_backward_ctx(tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x, int N, int H, int W, int nout,
-                                      void* const* params, void* const* grads, const float* gout, void* grad_flat, size_t grad_flat_bytes,
-                                      void* ws, size_t ws_bytes, void* stream_) {
+extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x, int N,
+                                            int H, int W, int nout, void* const* params, void* const* grads, const float* gout, void* grad_flat,
+                                            size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream_) {
+  const Arch* Ap = find_arch(blocks);
+  if (!Ap) return TF_ERR_UNSUPPORTED;
   if (!x || !params || !grads || !gout || !ws) return TF_ERR_ARG;
   if (hooks && (hooks->n < 0 || (hooks->n > 0 && !hooks->blocks))) return TF_ERR_ARG;
   if (!xctx) xctx = default_ctx();
   if (dtype != TF_BF16 && dtype != TF_F32) return TF_ERR_UNSUPPORTED;
-  const Arch& A = arch();
+  const Arch& A = *Ap;
   Plan P; Arena ar(ws, ws_bytes);
-  build_plan(P, ar, dtype, N, H, W, nout, 1);
+  build_plan(A, P, ar, dtype, N, H, W, nout, 1);
   if (!ar.ok) return TF_ERR_WORKSPACE;
   Ctx c{dtype, (hipStream_t)stream_, params, grads, TF_OK};   // (grads_zeroed / jobs default-initialised)
   const bool g_single_env = tf::tuning().single_stream;
@@ -929,7 +971,7 @@ extern "C" int tf_detnet_backward_ctx(tf_detnet_ctx* xctx, const tf_detnet_hooks
     else c.chk(tf_stem_im2col(x, N, H, W, dtype, P.col, kStemK, c.stream));
   }
   const bool group_on = wgrad_group_mode(dtype, 1) && fused;
-  const int first_id = A.layer_end[1] + 2, last_id = A.layer_end[2];           // the identity bottlenecks of layer 3: blocks 8 .. 29
+  const int first_id = A.layer_end[1] + 2, last_id = A.layer_end[2];           // the identity bottlenecks of layer 3 (ResNet-101: blocks 8 .. 29)
   if (grad_flat && grad_flat_bytes) {                     // one memset for every weight gradient (atomics accumulate into them) ...
     // r4: ... except where nothing accumulates: the grouped weight gradients OVERWRITE theirs, and the BatchNorm gradients in between are
     // published with plain stores (bn_fused.hip) -- the 22 identity bottlenecks of layer 3 are 98 of the 111 MB of the flat gradient.
@@ -1018,7 +1060,7 @@ extern "C" int tf_detnet_backward_ctx(tf_detnet_ctx* xctx, const tf_detnet_hooks
   std::vector<int> group_close;                                                 // block index that closes each group (descending)
   if (group_on) {
     const int nid = last_id - first_id + 1, gs = wgrad_group_size(), ng = (nid + gs - 1) / gs;
-    for (int g = 1; g <= ng; ++g) group_close.push_back(last_id + 1 - (int)(((long long)nid * g + ng - 1) / ng));      // balanced: 8 + 7 + 7
+    for (int g = 1; g <= ng; ++g) group_close.push_back(last_id + 1 - (int)(((long long)nid * g + ng - 1) / ng));      // balanced: 8 + 7 + 7 (ResNet-101)
   }
   std::vector<tf_wgrad_args> pend_pw, pend_c3;
   std::vector<int> pend_blocks;
@@ -1262,6 +1304,12 @@ extern "C" int tf_detnet_backward_ctx(tf_detnet_ctx* xctx, const tf_detnet_hooks
   record_grad_events(hooks, -1, c.stream, c.rc);
   if (hipGetLastError() != hipSuccess && c.rc == TF_OK) c.rc = TF_ERR_LAUNCH;
   return c.rc;
+}
+extern "C" int tf_detnet_backward_ctx(tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x, int N, int H, int W, int nout,
+                                      void* const* params, void* const* grads, const float* gout, void* grad_flat, size_t grad_flat_bytes,
+                                      void* ws, size_t ws_bytes, void* stream_) {
+  return tf_detnet_trunk_backward_ctx(nullptr, xctx, hooks, dtype, x, N, H, W, nout, params, grads, gout, grad_flat, grad_flat_bytes, ws, ws_bytes,
+                                      stream_);
 }
 
 // context-free form (rounds 1-3): the default context of the current device + the process-wide hooks registered with tf_detnet_set_*

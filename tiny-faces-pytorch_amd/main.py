@@ -18,6 +18,7 @@ from tinyfaces import parallel, trainer, transforms
 from tinyfaces.datasets import get_dataloader
 from tinyfaces.engine import TrainEngine
 from tinyfaces.models.loss import DetectionCriterion
+from tinyfaces.models import model as model_zoo
 from tinyfaces.models.model import DetectionModel
 
 NUM_TEMPLATES = 25
@@ -37,7 +38,7 @@ EXTRA_FLAGS = [
     ("--fused", dict(dest="fused", action="store_true", default=True)), ("--no-fused", dict(dest="fused", action="store_false")),
     ("--dtype", dict(default="bf16", choices=["bf16", "fp32"])), ("--synthetic-len", dict(dest="synthetic_len", default=240, type=int)),
     ("--seed", dict(default=0, type=int, help="synthetic data / sampling seed (each rank derives its own from it)")),
-    ("--pretrained", dict(default="", help="local torchvision-format resnet101 state_dict (.pth) for the trunk: the reference starts "
+    ("--pretrained", dict(default="", help="local torchvision-format state_dict (.pth) of the --base-model trunk: the reference starts "
                                            "from ResNet101_Weights.IMAGENET1K_V1 (model.py:13-14), which it downloads; there is no network here")),
     ("--init", dict(default="tame", choices=["tame", "kaiming"],
                     help="from-scratch runs only (no --resume / --pretrained): `tame` = the last BN of every bottleneck at 0.1 and the head weights x 0.05 "
@@ -61,11 +62,26 @@ def tame_init_(model):
     return model
 
 
+TRUNK_HELP = ("--base-model {resnet50,resnet101,resnet152}: trunk of the detector (DetectionModel(base_model=...), model.py:12-23), "
+              "default resnet101 (the reference's)")
+
+
 def arguments(argv=None):
-    parser = argparse.ArgumentParser()
+    parser = argparse.ArgumentParser(epilog=TRUNK_HELP)
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
+
+
+def trunk_arguments(argv=None):
+    """`arguments` plus `base_model` from --base-model.  Parsed apart, so that `arguments` keeps resolving exactly the reference's options
+    and the additions above."""
+    parser = argparse.ArgumentParser(add_help=False)
+    parser.add_argument("--base-model", dest="base_model", default="resnet101", choices=list(model_zoo.TRUNKS), help=TRUNK_HELP)
+    known, rest = parser.parse_known_args(argv)
+    args = arguments(rest)
+    args.base_model = known.base_model
+    return args
 
 
 def lr_at(base_lr, epoch):
@@ -85,28 +101,33 @@ def run_fused_epoch(engine, loss_fn, loader, epoch, device, base_lr):
 def load_pretrained_trunk(model, path):
     """The reference's default `pretrained_weights=ResNet101_Weights.IMAGENET1K_V1` (model.py:13-14,20) from a local file:
     a torchvision resnet101 state_dict (keys `conv1.weight`, `layer1.0...`, `fc.*`; `layer4.*` is dropped like model.py:23)
-    or a checkpoint of this package / the reference (`{"model": {...}}` with `model.`-prefixed keys)."""
+    or a checkpoint of this package / the reference (`{"model": {...}}` with `model.`-prefixed keys); the same for resnet50 / resnet152
+    when the model has that trunk (--base-model), and another trunk's file is refused."""
     sd = torch.load(path, map_location="cpu", weights_only=True)      # a state_dict of tensors: nothing else is unpickled
     sd = sd.get("model", sd)
+    try:
+        model.check_trunk_of(sd, f"--pretrained {path}")
+    except ValueError as e:
+        raise SystemExit(str(e))
     if any(k.startswith("model.") for k in sd):
         missing, unexpected = model.load_state_dict(sd, strict=False)
     else:
         sd = {k: v for k, v in sd.items() if not k.startswith("layer4.")}
         missing, unexpected = model.model.load_state_dict(sd, strict=False)
     if unexpected:
-        raise SystemExit(f"--pretrained {path}: unexpected keys {list(unexpected)[:5]} ... (not a resnet101 state_dict?)")
+        raise SystemExit(f"--pretrained {path}: unexpected keys {list(unexpected)[:5]} ... (not a {model.trunk_name} state_dict?)")
     return missing
 
 
 def main():
-    args = arguments()
+    args = trunk_arguments()
     if not torch.cuda.is_available():
         raise SystemExit("this build of the tiny-faces hot path runs on MI355X only (no CPU fallback)")
     parallel.init_from_env(os.environ.get("TINYFACES_DIST_BACKEND"))      # (gloo: several ranks on one device, the functional tests of a 1-GPU box)
     device = torch.device("cuda", torch.cuda.current_device())
     preprocess = transforms.Compose([transforms.ToTensor(), transforms.Normalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225])])
     train_loader, _ = get_dataloader(args.traindata, args, NUM_TEMPLATES, img_transforms=preprocess)
-    model = DetectionModel(num_objects=1, num_templates=NUM_TEMPLATES).set_compute_dtype(args.dtype)
+    model = DetectionModel(base_model=getattr(model_zoo, args.base_model), num_objects=1, num_templates=NUM_TEMPLATES).set_compute_dtype(args.dtype)
     loss_fn = DetectionCriterion(NUM_TEMPLATES, seed=args.seed * parallel.world_size() + parallel.rank(), lazy_meters=True)
     loss_fn.ohem_thresh = args.ohem_thresh
 

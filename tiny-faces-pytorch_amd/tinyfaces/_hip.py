@@ -150,6 +150,13 @@ _SIGNATURES = {
     "tf_detnet_ctx_destroy": (i32, [vp]),
     "tf_detnet_forward_ctx": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, f32, f32, vp, vp, sz, i32, vp]),
     "tf_detnet_backward_ctx": (i32, [vp, C.POINTER(DetnetHooks), i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, sz, vp]),
+    "tf_detnet_trunk_num_params": (i32, [vp]),
+    "tf_detnet_trunk_param_name": (C.c_char_p, [vp, i32]),
+    "tf_detnet_trunk_param_numel": (i64, [vp, i32, i32]),
+    "tf_detnet_trunk_workspace_bytes": (sz, [vp, i32, i32, i32, i32, i32, i32]),
+    "tf_detnet_trunk_param_region_bytes": (sz, [vp, i32, i32, i32]),
+    "tf_detnet_trunk_forward_ctx": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, f32, f32, vp, vp, sz, i32, vp]),
+    "tf_detnet_trunk_backward_ctx": (i32, [vp, vp, C.POINTER(DetnetHooks), i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, sz, vp]),
     "tf_pack_weights_batched": (i32, [i32, vp, i32, vp]),
     "tf_pack_weights_tiled": (i32, [i32, vp, i32, vp]),
     "tf_detnet_set_dual_stream": (i32, [i32]),

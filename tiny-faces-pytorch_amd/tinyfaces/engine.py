@@ -55,34 +55,59 @@ class TrainEngine:
         if parallel.is_distributed() or self.sgd_per_bucket:
             self._setup_overlap()
 
-    # first bottleneck (executor index: layer1 0-2, layer2 3-6, layer3 7-29) of each bucket, in backward order: the coarse
-    # 4-bucket cut of round 1, kept as an explicit choice (bucket_mb=0)
-    _BUCKET_FIRST_BLOCK = (22, 14, 7)
-    _BLOCK_NAMES = tuple(f"model.{l}.{i}." for l, n in (("layer1", 3), ("layer2", 4), ("layer3", 23)) for i in range(n))
+    # The bottlenecks in executor order (the block ids of the gradient-ready hooks) and the bucket cuts are those of the model's trunk
+    # (DetectionModel.trunk: block counts of layers 1-3), read off the flat-gradient segments.  ResNet-101: layer1 0-2, layer2 3-6, layer3 7-29.
+    @staticmethod
+    def block_names(blocks):
+        """["model.layer1.0.", ...]: the state_dict prefix of every bottleneck, in executor order."""
+        return tuple(f"model.layer{L + 1}.{i}." for L, n in enumerate(blocks) for i in range(n))
+
+    @staticmethod
+    def trunk_of(segments):
+        """Block counts of layers 1-3 of the trunk whose parameters `segments` ({state_dict key: (offset, numel)}) holds."""
+        counts = [0, 0, 0]
+        for k in segments:
+            parts = k.split(".")
+            if len(parts) > 3 and parts[0] == "model" and parts[1] in ("layer1", "layer2", "layer3"):
+                L = int(parts[1][-1]) - 1
+                counts[L] = max(counts[L], int(parts[2]) + 1)
+        return tuple(counts)
+
+    @staticmethod
+    def coarse_first_blocks(blocks):
+        """The coarse 4-bucket cut of round 1, kept as an explicit choice (bucket_mb=0): first bottleneck of each bucket in backward order,
+        layer 3 in thirds (ResNet-101: 22, 14, 7)."""
+        l3, n3 = blocks[0] + blocks[1], blocks[2]
+        return (l3 + 2 * n3 // 3, l3 + n3 // 3, l3)
 
     @classmethod
     def auto_first_blocks(cls, segments, total, bucket_mb):
         """First bottleneck of each bucket (backward order) so that every bucket but the last carries >= bucket_mb MB of fp32
-        gradient: walk the bottlenecks from layer3.22 down, close a bucket as soon as it is big enough; layer 1/2 + stem (6 MB)
-        always form the final bucket (event -1 = end of the backward pass)."""
+        gradient: walk the bottlenecks from the last one of layer 3 down, close a bucket as soon as it is big enough; layer 1/2 + stem
+        (6 MB for ResNet-101) always form the final bucket (event -1 = end of the backward pass)."""
+        blocks = cls.trunk_of(segments)
+        names, l3 = cls.block_names(blocks), blocks[0] + blocks[1]
         want = bucket_mb * (1 << 20) / 4
         firsts, end = [], total
-        for b in range(len(cls._BLOCK_NAMES) - 1, 6, -1):             # layer 3 only: 29 .. 7
-            start = min(o for k, (o, _) in segments.items() if k.startswith(cls._BLOCK_NAMES[b]))
+        for b in range(len(names) - 1, l3 - 1, -1):                   # layer 3 only (ResNet-101: 29 .. 7)
+            start = min(o for k, (o, _) in segments.items() if k.startswith(names[b]))
             if end - start >= want:
                 firsts.append(b)
                 end = start
-        if not firsts or firsts[-1] != 7:
-            firsts.append(7)                                            # whatever is left of layer 3
+        if not firsts or firsts[-1] != l3:
+            firsts.append(l3)                                           # whatever is left of layer 3
         return tuple(firsts)
 
-    @staticmethod
-    def bucket_ranges(segments, total, first_blocks=_BUCKET_FIRST_BLOCK):
+    @classmethod
+    def bucket_ranges(cls, segments, total, first_blocks=None):
         """[(event block, start, end)] in backward order: bucket k covers the flat-gradient elements of every bottleneck
         >= first_blocks[k] not covered by an earlier bucket (plus the heads for k = 0); the last bucket (block -1 = "end
         of the backward pass") takes the rest (layer1, layer2, stem).  `segments` = DetectionModel._segments
-        ({state_dict key: (offset, numel)} in executor order)."""
-        names = [f"model.{l}.{i}." for l, n in (("layer1", 3), ("layer2", 4), ("layer3", 23)) for i in range(n)]
+        ({state_dict key: (offset, numel)} in executor order); first_blocks None = the coarse cut of the segments' trunk."""
+        blocks = cls.trunk_of(segments)
+        names = cls.block_names(blocks)
+        if first_blocks is None:
+            first_blocks = cls.coarse_first_blocks(blocks)
         ranges, end = [], total
         for b in first_blocks:
             start = min(o for k, (o, _) in segments.items() if k.startswith(names[b]))
@@ -93,7 +118,8 @@ class TrainEngine:
 
     def _setup_overlap(self):
         total = self.flat_p.numel()
-        firsts = self.auto_first_blocks(self.model._segments, total, self.bucket_elems * 4 / (1 << 20)) if self.bucket_elems > 0 else self._BUCKET_FIRST_BLOCK
+        firsts = (self.auto_first_blocks(self.model._segments, total, self.bucket_elems * 4 / (1 << 20)) if self.bucket_elems > 0
+                  else self.coarse_first_blocks(self.model.trunk))
         ranges = [r for r in self.bucket_ranges(self.model._segments, total, firsts) if r[2] > r[1]]
         events = []
         for _ in ranges:

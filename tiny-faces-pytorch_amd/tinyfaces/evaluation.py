@@ -9,15 +9,16 @@ import numpy as np
 import torch
 
 from . import ops, transforms
-from .models.model import DetectionModel
+from .models.model import DetectionModel, base_model_of
 
 
 def get_model(checkpoint=None, num_templates=25):
-    """evaluation.py:12-17."""
-    model = DetectionModel(num_templates=num_templates)
-    if checkpoint:
-        checkpoint = torch.load(checkpoint, map_location="cpu")
-        model.load_state_dict(checkpoint["model"])
+    """evaluation.py:12-17; the trunk (resnet50 / resnet101 / resnet152) is the one the checkpoint's keys hold."""
+    if not checkpoint:
+        return DetectionModel(num_templates=num_templates)
+    checkpoint = torch.load(checkpoint, map_location="cpu")
+    model = DetectionModel(base_model=base_model_of(checkpoint["model"]), num_templates=num_templates)
+    model.load_state_dict(checkpoint["model"])
     return model
 
 

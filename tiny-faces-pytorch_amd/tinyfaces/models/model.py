@@ -6,6 +6,8 @@ What is kept from the reference:
   * the exact state_dict (571 entries: torchvision resnet101 names under `model.` incl. the dead
     `model.fc.*` that model.py:23 leaves behind, `score_res3.*`, `score_res4.*`,
     `score4_upsample.weight` initialised to the bilinear kernel of model.py:45-65)
+  * the trunk parameter `base_model` (model.py:12-23): resnet101 by default, resnet50 / resnet152
+    (265 / 877 state_dict entries) or a torchvision module of the same shape -- see TRUNKS
   * real nn.Parameters, so torch.optim.SGD / StepLR (main.py:67-83) work unchanged.
 What is different: forward/backward never run torch ops.  One C-ABI call per pass launches the
 hand-written gfx950 kernels; a CPU tensor raises (there is no CPU fallback).
@@ -41,20 +43,33 @@ class _Bottleneck(nn.Module):
         self.stride = stride
 
 
-class _ResNet101Trunk(nn.Module):
-    """Parameter container with torchvision resnet101's names; `layer4` is deleted by the owner
+# Bottleneck block counts of layers 1-3 of the trunks the executor takes (torchvision's Bottleneck ResNets with groups=1 and width 64;
+# `layer4` is deleted like model.py:23).  Every bottleneck has the shape of the same bottleneck of resnet101, only the counts differ.
+TRUNKS = {"resnet50": (3, 4, 6), "resnet101": (3, 4, 23), "resnet152": (3, 8, 36)}
+_TRUNK_NAMES = {v: k for k, v in TRUNKS.items()}
+_TRUNK_ARGS = {}                 # block counts -> the `const int blocks[3]` argument of the tf_detnet_trunk_* entry points
+
+
+def _trunk_arg(blocks):
+    if blocks not in _TRUNK_ARGS:
+        _TRUNK_ARGS[blocks] = (C.c_int * 3)(*blocks)
+    return _TRUNK_ARGS[blocks]
+
+
+class _BottleneckTrunk(nn.Module):
+    """Parameter container with torchvision resnet50 / resnet101 / resnet152's names; `layer4` is deleted by the owner
     exactly like model.py:23, `avgpool`/`fc` stay (dead, but part of the checkpoint contract)."""
 
-    def __init__(self):
+    def __init__(self, blocks=TRUNKS["resnet101"]):
         super().__init__()
         self.inplanes = 64
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, stride=2, padding=1)
-        self.layer1 = self._make_layer(64, 3)
-        self.layer2 = self._make_layer(128, 4, stride=2)
-        self.layer3 = self._make_layer(256, 23, stride=2)
+        self.layer1 = self._make_layer(64, blocks[0])
+        self.layer2 = self._make_layer(128, blocks[1], stride=2)
+        self.layer3 = self._make_layer(256, blocks[2], stride=2)
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
         self.fc = nn.Linear(2048, 1000)
         for m in self.modules():
@@ -72,9 +87,77 @@ class _ResNet101Trunk(nn.Module):
         return nn.Sequential(*layers)
 
 
+def resnet50(weights=None, **_):
+    """Stand-in for `torchvision.models.resnet50` (the same names and initialisation)."""
+    return _BottleneckTrunk(TRUNKS["resnet50"])
+
+
 def resnet101(weights=None, **_):
     """Stand-in for `torchvision.models.resnet101` in the constructor signature (model.py:13)."""
-    return _ResNet101Trunk()
+    return _BottleneckTrunk(TRUNKS["resnet101"])
+
+
+def resnet152(weights=None, **_):
+    """Stand-in for `torchvision.models.resnet152` (the same names and initialisation)."""
+    return _BottleneckTrunk(TRUNKS["resnet152"])
+
+
+def trunk_blocks(trunk):
+    """The Bottleneck block counts of layers 1-3 of `trunk` (the module `base_model` returned, layer4 deleted or not), or ValueError when the
+    executor does not take it: BasicBlock trunks (resnet18 / 34), grouped (resnext) or wider (wide_resnet) bottlenecks, other depths."""
+    supported = ", ".join(f"{k} {v}" for k, v in TRUNKS.items())
+
+    def refuse(why):
+        raise ValueError(f"DetectionModel: unsupported trunk ({why}). Supported: torchvision Bottleneck ResNets with groups=1 and width 64, "
+                         f"block counts of layers 1-3: {supported}")
+    stem = getattr(trunk, "conv1", None)
+    if not isinstance(stem, nn.Conv2d) or stem.out_channels != 64 or stem.kernel_size != (7, 7):
+        refuse("no 7x7 / 64-channel conv1")
+    counts = []
+    for L, planes in enumerate((64, 128, 256), start=1):
+        layer = getattr(trunk, f"layer{L}", None)
+        if not isinstance(layer, nn.Sequential) or len(layer) == 0:
+            refuse(f"no layer{L}")
+        for i, b in enumerate(layer):
+            convs = [getattr(b, n, None) for n in ("conv1", "conv2", "conv3")]
+            if not all(isinstance(c, nn.Conv2d) for c in convs):
+                refuse(f"layer{L}.{i} is not a Bottleneck")
+            c1, c2, c3 = convs
+            if any(c.groups != 1 for c in convs):
+                refuse(f"layer{L}.{i} has grouped convolutions")
+            if (c1.out_channels, c2.out_channels, c3.out_channels) != (planes, planes, 4 * planes):
+                refuse(f"layer{L}.{i} is not 64 wide")
+            stride = 2 if i == 0 and L > 1 else 1
+            if c2.kernel_size != (3, 3) or c2.stride != (stride, stride) or c1.stride != (1, 1):
+                refuse(f"layer{L}.{i} does not stride on its 3x3")
+            if (getattr(b, "downsample", None) is not None) != (i == 0):
+                refuse(f"layer{L}.{i}: a downsample branch on a block other than the first")
+        counts.append(len(layer))
+    if tuple(counts) not in _TRUNK_NAMES:
+        refuse(f"block counts {tuple(counts)}")
+    return tuple(counts)
+
+
+def _state_dict_blocks(sd, prefix):
+    """Block counts of layers 1-3 in a state_dict (keys `<prefix>layerL.i.`), None when it has no such keys."""
+    counts = [0, 0, 0]
+    for k in sd:
+        parts = k[len(prefix):].split(".") if k.startswith(prefix) else ()
+        if len(parts) > 2 and parts[0] in ("layer1", "layer2", "layer3") and parts[1].isdigit():
+            L = int(parts[0][-1]) - 1
+            counts[L] = max(counts[L], int(parts[1]) + 1)
+    return tuple(counts) if any(counts) else None
+
+
+def base_model_of(sd):
+    """The stand-in (resnet50 / resnet101 / resnet152) of the trunk a DetectionModel state_dict holds (`model.layerL.i.` keys);
+    resnet101 when it has none."""
+    blocks = _state_dict_blocks(sd, "model.")
+    if blocks is None:
+        return resnet101
+    if blocks not in _TRUNK_NAMES:
+        raise ValueError(f"state_dict holds a trunk with block counts {blocks}; supported: {TRUNKS}")
+    return {"resnet50": resnet50, "resnet101": resnet101, "resnet152": resnet152}[_TRUNK_NAMES[blocks]]
 
 
 class _DetNetFunction(torch.autograd.Function):
@@ -124,9 +207,10 @@ class DetectionModel(nn.Module):
         super().__init__()
         output = (num_objects + 4) * num_templates                       # model.py:19
         self.num_out = output
-        self.model = base_model(weights=None) if callable(base_model) else _ResNet101Trunk()
+        self.model = base_model(weights=None) if callable(base_model) else _BottleneckTrunk()
         if hasattr(self.model, "layer4"):
             del self.model.layer4                                        # model.py:23
+        self.trunk = trunk_blocks(self.model)                            # what the executor runs (ValueError: a trunk it does not take)
         self.score_res3 = nn.Conv2d(512, output, 1)                      # model.py:25-28
         self.score_res4 = nn.Conv2d(1024, output, 1)                     # model.py:29-32
         self.score4_upsample = nn.ConvTranspose2d(output, output, 4, stride=2, padding=1, bias=False)   # :34-39
@@ -144,6 +228,7 @@ class DetectionModel(nn.Module):
         if isinstance(pretrained_weights, (str, os.PathLike)):           # no network here: a local file only
             sd = torch.load(pretrained_weights, map_location="cpu", weights_only=True)
             sd = sd.get("model", sd)
+            self.check_trunk_of(sd, pretrained_weights)
             if any(k.startswith("model.") for k in sd):
                 self.load_state_dict(sd, strict=False)
             else:                                                        # a bare torchvision resnet101 state_dict
@@ -155,6 +240,18 @@ class DetectionModel(nn.Module):
             warnings.warn(f"DetectionModel: pretrained_weights={pretrained_weights!r} is not a local file -- ignored, the trunk "
                           "keeps its RANDOM kaiming initialisation (no network to download ImageNet weights). Pass a path to a "
                           "torchvision resnet101 state_dict instead.", RuntimeWarning, stacklevel=2)
+
+    @property
+    def trunk_name(self):
+        """"resnet50", "resnet101" or "resnet152"."""
+        return _TRUNK_NAMES[self.trunk]
+
+    def check_trunk_of(self, sd, what="state_dict"):
+        """ValueError when `sd` (a torchvision trunk state_dict, or a checkpoint with `model.`-prefixed keys) holds another trunk than this model's."""
+        got = _state_dict_blocks(sd, "model." if any(k.startswith("model.") for k in sd) else "")
+        if got is not None and got != self.trunk:
+            name = _TRUNK_NAMES.get(got, f"a trunk with block counts {got}")
+            raise ValueError(f"{what}: holds {name}, the model is {self.trunk_name} {self.trunk}")
 
     # ---- reference surface ---------------------------------------------------------------
     def _init_bilinear(self):
@@ -252,7 +349,7 @@ class DetectionModel(nn.Module):
         N, _, H, W = x.shape
         H3, W3 = C.c_int(), C.c_int()
         lib().tf_detnet_out_shape(H, W, C.byref(H3), C.byref(W3))
-        nbytes = lib().tf_detnet_workspace_bytes(self.compute_dtype, N, H, W, self.num_out, 0)
+        nbytes = lib().tf_detnet_trunk_workspace_bytes(_trunk_arg(self.trunk), self.compute_dtype, N, H, W, self.num_out, 0)
         if lane["ws"] is None or lane["ws"].device != x.device or lane["ws"].numel() < nbytes:
             lane["ws"] = None
             lane["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
@@ -263,9 +360,10 @@ class DetectionModel(nn.Module):
         lane["ready"] = key
         bn = self.model.bn1
         with torch.cuda.device(x.device):
-            check(lib().tf_detnet_forward_ctx(self._ctx(x.device), int(self.single_stream), self.compute_dtype, 0, ptr(x), N, H, W, self.num_out, self._param_ptrs,
-                                              float(bn.eps), float(bn.momentum), ptr(out), ptr(ws), ws.numel(), flags, lane["stream"].cuda_stream),
-                  "tf_detnet_forward_ctx")
+            check(lib().tf_detnet_trunk_forward_ctx(_trunk_arg(self.trunk), self._ctx(x.device), int(self.single_stream), self.compute_dtype, 0, ptr(x),
+                                                    N, H, W, self.num_out, self._param_ptrs, float(bn.eps), float(bn.momentum), ptr(out), ptr(ws),
+                                                    ws.numel(), flags, lane["stream"].cuda_stream),
+                  "tf_detnet_trunk_forward_ctx")
         return out
 
     # ---- executor plumbing ---------------------------------------------------------------
@@ -302,8 +400,9 @@ class DetectionModel(nn.Module):
             if self._frozen_version == _REGISTRATIONS[0] and all(t.data_ptr() == p for t, p in zip(self._frozen_tensors, self._table_key)):
                 return
         named = self._named_tensors()
-        n = lib().tf_detnet_num_params()
-        names = self._names if getattr(self, "_names", None) and len(self._names) == n else [lib().tf_detnet_param_name(i).decode() for i in range(n)]
+        tr = _trunk_arg(self.trunk)
+        n = lib().tf_detnet_trunk_num_params(tr)
+        names = self._names if getattr(self, "_names", None) and len(self._names) == n else [lib().tf_detnet_trunk_param_name(tr, i).decode() for i in range(n)]
         key = tuple(named[k].data_ptr() for k in names)
         if key == self._table_key:
             return
@@ -313,7 +412,7 @@ class DetectionModel(nn.Module):
                 raise RuntimeError(f"parameter {k} is on {t.device}, input on {device}: call model.to(device) first")
             if not t.is_contiguous() or t.dtype != torch.float32:
                 raise RuntimeError(f"parameter {k} must be contiguous float32")
-            want = lib().tf_detnet_param_numel(i, self.num_out)
+            want = lib().tf_detnet_trunk_param_numel(tr, i, self.num_out)
             if t.numel() != want:
                 raise RuntimeError(f"parameter {k}: {t.numel()} elements, executor expects {want}")
         up = self.score4_upsample.weight.detach()
@@ -413,7 +512,7 @@ class DetectionModel(nn.Module):
         the workspace for the largest input up front so that it is not re-allocated (which would drop the packed copy)."""
         if reserve is not None:
             dev = next(self.parameters()).device
-            self._workspace(dev, lib().tf_detnet_workspace_bytes(self.compute_dtype, *reserve, self.num_out, 0))
+            self._workspace(dev, lib().tf_detnet_trunk_workspace_bytes(_trunk_arg(self.trunk), self.compute_dtype, *reserve, self.num_out, 0))
         if self._session_depth == 0:
             self._ready_key = None
             self._session_serial = getattr(self, "_session_serial", 0) + 1     # the lanes of forward_levels re-pack once per session too
@@ -429,7 +528,7 @@ class DetectionModel(nn.Module):
         N, _, H, W = x.shape
         H3, W3 = C.c_int(), C.c_int()
         lib().tf_detnet_out_shape(H, W, C.byref(H3), C.byref(W3))
-        nbytes = lib().tf_detnet_workspace_bytes(self.compute_dtype, N, H, W, self.num_out, int(training))
+        nbytes = lib().tf_detnet_trunk_workspace_bytes(_trunk_arg(self.trunk), self.compute_dtype, N, H, W, self.num_out, int(training))
         ws = self._workspace(x.device, nbytes)
         self._ws_generation += 1
         self._ws_shape = (N, H, W)
@@ -444,9 +543,10 @@ class DetectionModel(nn.Module):
                 flags = TF_DETNET_WEIGHTS_READY
             self._ready_key = key
         with torch.cuda.device(x.device):
-            check(lib().tf_detnet_forward_ctx(self._ctx(x.device), int(self.single_stream), self.compute_dtype, int(training), ptr(x), N, H, W, self.num_out,
-                                              self._param_ptrs, float(bn.eps), float(bn.momentum), ptr(out), ptr(ws), ws.numel(), flags, stream()),
-                  "tf_detnet_forward_ctx")
+            check(lib().tf_detnet_trunk_forward_ctx(_trunk_arg(self.trunk), self._ctx(x.device), int(self.single_stream), self.compute_dtype, int(training),
+                                                    ptr(x), N, H, W, self.num_out, self._param_ptrs, float(bn.eps), float(bn.momentum), ptr(out), ptr(ws),
+                                                    ws.numel(), flags, stream()),
+                  "tf_detnet_trunk_forward_ctx")
         if training:
             if getattr(self, "_flat_nbt", None) is not None:
                 self._flat_nbt += 1                                      # all 94 counters in one launch
@@ -492,8 +592,9 @@ class DetectionModel(nn.Module):
         hooks.user = getattr(self, "_grad_callback_user", None) if cb is not None else None
         hooks.single_stream = int(self.single_stream)
         with torch.cuda.device(x.device):
-            check(lib().tf_detnet_backward_ctx(self._ctx(x.device), C.byref(hooks), self.compute_dtype, ptr(x), N, H, W, self.num_out, self._param_ptrs, table,
-                                               ptr(gout), ptr(gflat), gflat.numel() * 4, ptr(self._ws), self._ws.numel(), stream()), "tf_detnet_backward_ctx")
+            check(lib().tf_detnet_trunk_backward_ctx(_trunk_arg(self.trunk), self._ctx(x.device), C.byref(hooks), self.compute_dtype, ptr(x), N, H, W,
+                                                     self.num_out, self._param_ptrs, table, ptr(gout), ptr(gflat), gflat.numel() * 4, ptr(self._ws),
+                                                     self._ws.numel(), stream()), "tf_detnet_trunk_backward_ctx")
         self._last_grad_flat = gflat
         if persistent:
             return gflat
