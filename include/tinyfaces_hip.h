@@ -132,6 +132,13 @@ int tf_criterion_fwd_bwd(const float* output, float* class_map, const float* reg
  * Replaces torch.optim.SGD.step as configured at main.py:67-70 for one parameter group. */
 int tf_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n,
                 float lr, float momentum, float weight_decay, float grad_scale, void* stream);
+/* The same update over a TABLE of element ranges of the three flat buffers: host_segments[nseg][2] = (start, end), ascending and disjoint
+ * (HOST memory; the table travels as kernel arguments, TF_SGD_MAX_SEGMENTS ranges per launch).  Elements outside the ranges are neither
+ * read nor written: no weight decay, no momentum.  Replaces torch.optim.SGD.step (main.py:67-70) for a parameter group whose BatchNorm
+ * vectors have no gradient (requires_grad = False: torch skips them) while they sit interleaved with the conv weights in the flat buffer. */
+#define TF_SGD_MAX_SEGMENTS 128
+int tf_sgd_step_segments(float* param, const float* grad, float* momentum_buf, const int64_t* host_segments, int nseg,
+                         float lr, float momentum, float weight_decay, float grad_scale, void* stream);
 
 /* ---- convolution as MFMA implicit GEMM (NHWC) --------------------------------------
  * Replaces every nn.Conv2d on the path (tinyfaces/models/model.py:25-32,90-106 and the
@@ -227,6 +234,10 @@ int tf_pack_weights_batched(int dtype, const tf_pack_job* host_jobs, int njobs, 
 typedef struct tf_pack2_job {
   const float* src; void* dst; void* dst_t;
   int cout, cin, taps, rows_pad, cols_pad, rows_pad_t, cols_pad_t;
+  /* frozen-BN graph: dst_t[ci][tap][co] = src * scale_t[co] (a BatchNorm folded to its per-channel scale rides in the data-gradient
+   * operand of the conv in front of it: autograd of tinyfaces/trainer.py:86 over model.py:89-128 with the trunk's BN in eval mode);
+   * dst is never scaled.  NULL: off. */
+  const float* scale_t;
 } tf_pack2_job;
 int tf_pack_weights_tiled(int dtype, const tf_pack2_job* host_jobs, int njobs, void* stream);
 
@@ -246,6 +257,10 @@ typedef struct tf_wgrad_args {
   void* partial_ws;   /* optional scratch of >= tf_wgrad_workspace_bytes(a) bytes: the all-taps 3x3 kernel then reduces its split-K */
   size_t partial_ws_bytes;   /* slices through it (plain stores + one summing kernel) instead of fp32 atomics; NULL / too small: atomics */
   /* tile: 0 = auto, 1 = per-tap LDS-DMA kernel, 3 = all-taps 3x3 kernel (stride 1, pad 1, bf16), 64 / 128 = register-staged kernel */
+  const float* row_scale;    /* frozen-BN graph: dW[co][...] = row_scale[co] * (the gradient above) -- the folded scale of the BatchNorm behind the conv,
+                                applied to the tile before it is stored / added (autograd of tinyfaces/trainer.py:86 with the trunk's BN in eval mode).
+                                Pointwise problems and the register-staged kernel; the all-taps 3x3 kernels do not take it (tf_conv2d_wgrad then uses
+                                the per-tap kernel, a 3x3 tf_conv2d_wgrad_group returns TF_ERR_UNSUPPORTED).  NULL: off. */
 } tf_wgrad_args;
 int tf_conv2d_wgrad(const tf_wgrad_args* a, void* stream);
 size_t tf_wgrad_workspace_bytes(const tf_wgrad_args* a);   /* 0 when the all-taps kernel does not apply to `a` */
@@ -377,6 +392,10 @@ int tf_reduce_partials(const float* partial, int nblk, int nk, int k, int ld, in
 int tf_detnet_num_params(void);
 const char* tf_detnet_param_name(int i);      /* state_dict key, e.g. "model.layer3.22.bn3.running_var" */
 int64_t tf_detnet_param_numel(int i, int num_out);
+/* training: 0 = evaluation graph (BN folded into the conv epilogues, no backward), 1 = batch-statistics training graph,
+ * 2 = FROZEN BatchNorm (TF_DETNET_FROZEN_BN): the launches of the evaluation forward plus what tf_detnet_backward_frozen_ctx needs (max-pool
+ * arg-max, transposed weight operands, per-block gradient buffers); running statistics, gamma and beta are read, never written. */
+#define TF_DETNET_FROZEN_BN 2
 size_t tf_detnet_workspace_bytes(int dtype, int N, int H, int W, int num_out, int training);
 int tf_detnet_out_shape(int H, int W, int* H3, int* W3);
 /* flags: TF_DETNET_WEIGHTS_READY (eval only) = the front of `ws` (tf_detnet_param_region_bytes bytes, whose layout depends on
@@ -443,6 +462,21 @@ int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* ctx, int singl
 int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* ctx, const tf_detnet_hooks* hooks, int dtype, const float* x_nchw, int N, int H,
                                  int W, int num_out, void* const* params, void* const* grads, const float* gout_nchw, void* grad_flat,
                                  size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream);
+/* ---- frozen BatchNorm (fine-tuning on the pretrained statistics) ----------------------------------------------------------------------
+ * The backward pass of a forward run with training = TF_DETNET_FROZEN_BN: autograd of tinyfaces/trainer.py:86 over model.py:89-128 with
+ * every BatchNorm2d of the trunk in eval() mode and its parameters requires_grad = False (torchvision's FrozenBatchNorm2d).  Every BN is
+ * the constant map v -> v * s + h (tf_bn_fold), so a bottleneck's chain is its three data-gradient convs: the scale of bn1 / bn2 rides in
+ * the epilogue of the data gradient above it (TF_EPI_AFFINE | TF_EPI_MASK, the stored post-ReLU activation is its own mask), the scale of
+ * bn3 / the downsample BN in the transposed packed operand (tf_pack2_job.scale_t) and in the weight-gradient rows (tf_wgrad_args.row_scale).
+ * Same arguments, hooks, streams and error codes as tf_detnet_trunk_backward_ctx; the conv weights, head weights and head biases receive
+ * their gradients, the entries of `grads` that belong to BN gamma / beta are left untouched except inside the range of grad_flat that the
+ * split memset skips, where they are zeroed. */
+int tf_detnet_trunk_backward_frozen_ctx(const int* blocks, tf_detnet_ctx* ctx, const tf_detnet_hooks* hooks, int dtype, const float* x_nchw, int N,
+                                        int H, int W, int num_out, void* const* params, void* const* grads, const float* gout_nchw,
+                                        void* grad_flat, size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream);
+int tf_detnet_backward_frozen_ctx(tf_detnet_ctx* ctx, const tf_detnet_hooks* hooks, int dtype, const float* x_nchw, int N, int H, int W,
+                                  int num_out, void* const* params, void* const* grads, const float* gout_nchw,
+                                  void* grad_flat, size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- gradient exchange of the data-parallel path over RCCL (the reference has no distributed code) -------------
  * One process per GPU; the gradients are SUMMED over the ranks bucket by bucket while the backward pass runs, the 1/world goes into

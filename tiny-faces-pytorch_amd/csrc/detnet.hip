@@ -76,6 +76,8 @@ bool stem_direct_mode(int dtype, bool training, bool fused) {
   return !off && dtype != TF_F32 && (!training || fused);
 }
 constexpr int kHeadLd = 128;    // 125 outputs padded
+constexpr int kConstC = 1024;   // widest channel count of the trunk (layer 3 output)
+constexpr int kFrozen = TF_DETNET_FROZEN_BN;     // `training` = 2: the evaluation forward + a backward through the folded BN
 
 struct ConvUnit {               // one conv + (optional) BN, with indices into the parameter table
   std::string name;             // e.g. "model.layer1.0.conv1"
@@ -207,6 +209,7 @@ struct Plan {                    // everything a forward carves; backward re-der
   };
   std::vector<Blk> blk;
   void *w_h3, *w_h4, *w_h3t, *w_h4t, *s3, *s4; float *hbias3, *hbias4, *ones, *wup_diag;
+  float *c_one, *c_zero;         // frozen BN: kConstC ones / zeros (mask_scale / mask_shift and epi_shift of the AFFINE | MASK data gradients)
   float *partial, *partial_b; size_t partial_floats;      // per-tile partial rows of the forward / backward pass (each behind its statistic region)
   float *stat_fwd, *stat_bwd; size_t stat_fwd_floats, stat_bwd_floats;   // per-BN statistic regions (fused finalize)
   // backward-only
@@ -266,6 +269,9 @@ void build_plan(const Arch& A, Plan& P, Arena& ar, int dtype, int N, int H, int 
   P.w_h4t = training ? ar.get(packed_bytes(dtype, 1024, 1, kHeadLd)) : nullptr;
   P.hbias3 = ar.f32(kHeadLd); P.hbias4 = ar.f32(kHeadLd); P.ones = ar.f32(kHeadLd);
   P.wup_diag = ar.f32((size_t)nout * 16);
+  P.c_one = P.c_zero = nullptr;
+  if (training == kFrozen) { P.c_one = ar.f32(kConstC); P.c_zero = ar.f32(kConstC); }
+  const bool stats = training != 0 && training != kFrozen;              // the batch-statistics graph: statistic regions, a1 / a2 / c3, the BN-backward operand of the downsample branch
   P.param_bytes = ar.off;
   // ---- per-BN statistic regions, contiguous so that one memset per pass clears them
   {
@@ -278,14 +284,14 @@ void build_plan(const Arch& A, Plan& P, Arena& ar, int dtype, int N, int H, int 
     size_t nf = 0, nb = 0;
     // forward region of a BN: TF_STAT_ROWS x (sum, sum of squares) + ONE row holding the shift the producer subtracted (r3)
     for (BnBuf* q : bns) { nf += (size_t)(TF_STAT_ROWS * 2 + 1) * q->C; nb += (size_t)TF_STAT_ROWS * 3 * q->C; }
-    P.stat_fwd_floats = training ? nf : 0; P.stat_bwd_floats = training ? nb : 0;
+    P.stat_fwd_floats = stats ? nf : 0; P.stat_bwd_floats = stats ? nb : 0;
     // r4: [forward statistic rows | forward partial rows] and [backward statistic rows | backward partial rows] are contiguous pairs, so that
     // ONE memset per pass clears the statistic region AND the head of the pass's partial buffer (two dispatches per pass in rounds 1-3)
     P.stat_fwd = ar.f32(P.stat_fwd_floats); P.partial = ar.f32(P.partial_floats);
     P.stat_bwd = ar.f32(P.stat_bwd_floats); P.partial_b = training ? ar.f32(P.partial_floats) : nullptr;
     size_t of = 0, ob = 0;
     for (BnBuf* q : bns) {
-      q->fst = training && P.stat_fwd ? P.stat_fwd + of : nullptr; q->bst = training && P.stat_bwd ? P.stat_bwd + ob : nullptr;
+      q->fst = stats && P.stat_fwd ? P.stat_fwd + of : nullptr; q->bst = stats && P.stat_bwd ? P.stat_bwd + ob : nullptr;
       of += (size_t)(TF_STAT_ROWS * 2 + 1) * q->C; ob += (size_t)TF_STAT_ROWS * 3 * q->C;
     }
   }
@@ -303,8 +309,8 @@ void build_plan(const Arch& A, Plan& P, Arena& ar, int dtype, int N, int H, int 
     const size_t Min = (size_t)N * h * w, Mout = (size_t)N * b.Hout * b.Wout;
     const int pl = B.planes, c4 = pl * 4;
     b.c1 = ar.get(Min * pl * es); b.c2 = ar.get(Mout * pl * es);
-    b.a1 = training ? ar.get(Min * pl * es) : nullptr; b.a2 = training ? ar.get(Mout * pl * es) : nullptr;
-    b.c3 = training ? ar.get(Mout * c4 * es) : nullptr;
+    b.a1 = stats ? ar.get(Min * pl * es) : nullptr; b.a2 = stats ? ar.get(Mout * pl * es) : nullptr;
+    b.c3 = stats ? ar.get(Mout * c4 * es) : nullptr;
     b.d = B.has_ds ? ar.get(Mout * c4 * es) : nullptr;
     b.y = ar.get(Mout * c4 * es);
     // r4: every block owns its backward operands (g_c3, g_c2, g_c1, downsample-branch gradient).  Rounds 1-3 shared two parity sets and
@@ -313,7 +319,9 @@ void build_plan(const Arch& A, Plan& P, Arena& ar, int dtype, int N, int H, int 
     b.gT1 = b.gT2 = b.gU1 = b.gT3 = nullptr;
     if (training) {
       b.gT1 = ar.get(Mout * c4 * es); b.gT2 = ar.get(Mout * pl * es); b.gU1 = ar.get(Min * pl * es);
-      if (B.has_ds) b.gT3 = ar.get(Mout * c4 * es);
+      // (frozen BN: gT1 holds the block's OWN masked output gradient gm -- the weight gradients of conv3 and of the downsample conv read it
+      //  on the second stream -- and the downsample branch has no BN-backward operand)
+      if (B.has_ds && stats) b.gT3 = ar.get(Mout * c4 * es);
     }
     if (Min * (size_t)B.cin * es > max_act) max_act = Min * B.cin * es;
     if (Mout * c4 * es > max_act) max_act = Mout * c4 * es;
@@ -327,7 +335,8 @@ void build_plan(const Arch& A, Plan& P, Arena& ar, int dtype, int N, int H, int 
   P.s3 = ar.get(M3 * kHeadLd * es); P.s4 = ar.get(M4 * kHeadLd * es);
   if (training) {
     P.g3 = ar.get(M3 * kHeadLd * es); P.g4 = ar.get(M4 * kHeadLd * es);
-    P.G0 = ar.get(max_act); P.G1 = ar.get(max_act); P.T4 = ar.get(max_act); P.R3 = ar.get(max_act);
+    P.G0 = stats ? ar.get(max_act) : nullptr; P.G1 = stats ? ar.get(max_act) : nullptr;      // (frozen BN: the gradients ping-pong through the blocks' own gT1)
+    P.T4 = ar.get(max_act); P.R3 = ar.get(max_act);
     if (packed_bytes(dtype, 1024, 1, kHeadLd) > max_wt) max_wt = packed_bytes(dtype, 1024, 1, kHeadLd);
     P.wt = ar.get(max_wt);
     // scratch of the 3x3 weight gradients: the partial [slice][tile][tap][64][64] tiles of the all-taps kernel (one block per CU:
@@ -338,6 +347,19 @@ void build_plan(const Arch& A, Plan& P, Arena& ar, int dtype, int N, int H, int 
     P.g3 = P.g4 = P.G0 = P.G1 = P.T4 = P.R3 = P.wt = nullptr; P.dwp = nullptr; P.dwp_floats = 0;
   }
   P.total = ar.off;
+}
+
+__global__ void fill_const_kernel(float* one, float* zero, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) one[i] = 1.f; else if (i < 2 * n) zero[i - n] = 0.f;
+}
+// zero up to kZeroRanges ranges per launch (frozen BN: the BN segments inside the range of the flat gradient the split memset skips)
+constexpr int kZeroRanges = 128;
+struct ZeroRanges { float* p[kZeroRanges]; int n[kZeroRanges]; };
+__global__ void zero_ranges_kernel(const ZeroRanges r) {
+  float* p = r.p[blockIdx.y];
+  const int n = r.n[blockIdx.y];
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0.f;
 }
 
 __global__ void head_vectors_kernel(const float* b3, const float* b4, const float* wup, int nout, float* hb3, float* hb4, float* ones,
@@ -412,13 +434,14 @@ void pack(Ctx& c, const ConvUnit& u, int cout, void* out, bool transpose, int ci
 }
 
 // forward operand [cout pad 128][taps][cin] and (training) data-gradient operand [cin pad 128][taps][cout] in one job
-void pack2(Ctx& c, const ConvUnit& u, int cout, void* out, void* out_t, int cin_override = 0, int cols_pad_override = 0, int k_override = 0) {
+void pack2(Ctx& c, const ConvUnit& u, int cout, void* out, void* out_t, int cin_override = 0, int cols_pad_override = 0, int k_override = 0,
+           const float* scale_t = nullptr) {
   const int cin = cin_override ? cin_override : u.cin;
   const int k = k_override ? k_override : u.k;
   tf_pack2_job j;
   j.src = c.P(u.w); j.dst = out; j.dst_t = out_t; j.cout = cout; j.cin = cin; j.taps = k * k;
   j.rows_pad = (cout + 127) / 128 * 128; j.cols_pad = cols_pad_override ? cols_pad_override : cin;
-  j.rows_pad_t = (cin + 127) / 128 * 128; j.cols_pad_t = cout;
+  j.rows_pad_t = (cin + 127) / 128 * 128; j.cols_pad_t = cout; j.scale_t = scale_t;
   c.jobs2.push_back(j);
 }
 
@@ -606,9 +629,11 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
   if (!ar.ok) return TF_ERR_WORKSPACE;
   Ctx c{dtype, (hipStream_t)stream_, params, nullptr, TF_OK};
   tf_conv_args a;
-  const bool tr = training != 0;
+  const bool tr = training != 0 && training != kFrozen;      // the batch-statistics graph
+  const bool fz = training == kFrozen;     // frozen BN: the evaluation graph's launches + what the backward needs
+  const bool step = tr || fz;              // a training step: the weights are re-packed, the transposed operands too
   // eval only: the packed weights, folded BN affines and head vectors at the front of `ws` are already those of `params`
-  const bool ready = !tr && (flags & TF_DETNET_WEIGHTS_READY);
+  const bool ready = !step && (flags & TF_DETNET_WEIGHTS_READY);
 
   c.skip_fold = ready;
   // statistics folded into <= TF_STAT_ROWS rows: the elementwise consumers finalize them in-kernel (bn_fused.hip);
@@ -631,8 +656,8 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
   // at bs = 12, instead of in front of them.  TINYFACES_PACK_SPLIT_OFF=1: everything inline.
   const bool pack_split_off = tf::tuning().pack_split_off;
   const bool single_env = tf::tuning().single_stream;
-  const bool pack_split = tr && !ready && !pack_side_env && !pack_split_off && !single_env && !single_stream && xctx;
-  bool pack_side = tr && !ready && (pack_side_env || pack_split);
+  const bool pack_split = step && !ready && !pack_side_env && !pack_split_off && !single_env && !single_stream && xctx;
+  bool pack_side = step && !ready && (pack_side_env || pack_split);
   if (pack_side) {
     g_pack_stream = ctx_side(xctx);
     if (g_pack_stream && !xctx->pack_fork && (hipEventCreateWithFlags(&xctx->pack_fork, hipEventDisableTiming) != hipSuccess ||
@@ -645,6 +670,20 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
   // step (beside it the conv takes 99 instead of 56 us): 1273.0 / 1274.2 against 1276.1 / 1276.1 img/s -- the packing then overlaps layer 1
   const bool fork_late_env = tf::tuning().pack_fork_late;
   const bool pack_late = pack_side && pack_split && stem_direct && fork_late_env;
+  if (fz) {
+    // frozen BN: every fold first -- the scales of bn3 / the downsample BN ride in the transposed operands packed below (possibly on the
+    // second stream), and the backward pass reads all of them.  Same kernel, same values as the evaluation graph's folds.
+    auto fold = [&](const ConvUnit& u, int C, BnBuf& b) { c.chk(tf_bn_fold(c.P(u.gamma), c.P(u.beta), c.P(u.rmean), c.P(u.rvar), eps, C, b.scale, b.shift, c.stream)); };
+    fold(A.stem, 64, P.bn_stem);
+    for (size_t i = 0; i < A.blocks.size(); ++i) {
+      const Block& B = A.blocks[i];
+      Plan::Blk& b = P.blk[i];
+      fold(B.c1, B.planes, b.b1); fold(B.c2, B.planes, b.b2); fold(B.c3, B.planes * 4, b.b3);
+      if (B.has_ds) fold(B.ds, B.planes * 4, b.bd);
+    }
+    c.skip_fold = true;
+    hipLaunchKernelGGL(fill_const_kernel, dim3((2 * kConstC + 255) / 256), dim3(256), 0, c.stream, P.c_one, P.c_zero, kConstC);
+  }
   if (pack_side && !pack_late) {           // everything enqueued so far (the previous step's SGD: the masters) precedes the packing
     if (hipEventRecord(xctx->pack_fork, c.stream) != hipSuccess || hipStreamWaitEvent(g_pack_stream, xctx->pack_fork, 0) != hipSuccess) c.chk(TF_ERR_LAUNCH);
   }
@@ -667,13 +706,14 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
         if (hipEventRecord(xctx->pack_join0, g_pack_stream) != hipSuccess || hipStreamWaitEvent(c.stream, xctx->pack_join0, 0) != hipSuccess) c.chk(TF_ERR_LAUNCH);
       }
     }
-    pack2(c, B.c1, B.planes, b.w1, b.w1t); pack2(c, B.c2, B.planes, b.w2, b.w2t); pack2(c, B.c3, B.planes * 4, b.w3, b.w3t);
-    if (B.has_ds) pack2(c, B.ds, B.planes * 4, b.wd, b.wdt);
+    pack2(c, B.c1, B.planes, b.w1, b.w1t); pack2(c, B.c2, B.planes, b.w2, b.w2t);
+    pack2(c, B.c3, B.planes * 4, b.w3, b.w3t, 0, 0, 0, fz ? b.b3.scale : nullptr);       // frozen BN: (W3 diag(s3))^T
+    if (B.has_ds) pack2(c, B.ds, B.planes * 4, b.wd, b.wdt, 0, 0, 0, fz ? b.bd.scale : nullptr);
   }
   {
     tf_pack2_job j;
     j.src = c.P(A.head3.w); j.dst = P.w_h3; j.dst_t = P.w_h3t; j.cout = nout; j.cin = 512; j.taps = 1;
-    j.rows_pad = kHeadLd; j.cols_pad = 512; j.rows_pad_t = 512; j.cols_pad_t = kHeadLd;
+    j.rows_pad = kHeadLd; j.cols_pad = 512; j.rows_pad_t = 512; j.cols_pad_t = kHeadLd; j.scale_t = nullptr;
     c.jobs2.push_back(j);
     j.src = c.P(A.head4.w); j.dst = P.w_h4; j.dst_t = P.w_h4t; j.cin = 1024; j.cols_pad = 1024; j.rows_pad_t = 1024;
     c.jobs2.push_back(j);
@@ -714,7 +754,7 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
     if (hipEventRecord(xctx->pack_join, g_pack_stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
   }
   c.chk(tf_maxpool_fwd(dtype, P.cstem, N, P.H1, P.W1, 64, tr ? P.bn_stem.scale : nullptr, tr ? P.bn_stem.shift : nullptr, P.pool,
-                       tr ? P.pool_idx : nullptr, c.stream));
+                       step ? P.pool_idx : nullptr, c.stream));
 
   // ---- bottlenecks
   const void* yin = P.pool;
@@ -1310,6 +1350,258 @@ extern "C" int tf_detnet_backward_ctx(tf_detnet_ctx* xctx, const tf_detnet_hooks
                                       void* ws, size_t ws_bytes, void* stream_) {
   return tf_detnet_trunk_backward_ctx(nullptr, xctx, hooks, dtype, x, N, H, W, nout, params, grads, gout, grad_flat, grad_flat_bytes, ws, ws_bytes,
                                       stream_);
+}
+
+// ------------------------------------------------------------------------------------------------
+// backward through the FROZEN-BN graph (forward with training = TF_DETNET_FROZEN_BN).  Every BN is the constant map v -> v * s + h, so with
+// gm = g_y * (y > 0) arriving from the block above, a1 / a2 the stored post-ReLU activations (c1 / c2 of the evaluation plan; a post-ReLU
+// tensor is its own mask) and s1, s2, s3, sd the folded scales:
+//   dW3 = diag(s3) (gm^T a2)            g2 = (W3 diag(s3))^T gm * (a2 > 0) * s2         [row scale | scaled transposed operand, AFFINE | MASK]
+//   dW2 = g2^T (*) a1                   g1 = W2^T (*) g2 * (a1 > 0) * s1                [AFFINE | MASK]
+//   dW1 = g1^T x                        gm_prev = (W1^T g1 + skip) * (x > 0)            [RES | MASK2]
+//   skip = gm (identity) | (Wd diag(sd))^T gm, dWd = diag(sd) (gm^T x)                  [in place for stride 2]
+// Three data-gradient launches per identity bottleneck and nothing else on the caller's stream.  gm lives in the block's own gT1 (the weight
+// gradients of conv3 / the downsample conv read it on the second stream), g2 in gT2, g1 in gU1: the chain never waits for a weight gradient.
+// Forks: ONE per block, carried by the conv2 data gradient (the kernel that produces the block's last weight-gradient operand); the grouped
+// identity bottlenecks of layer 3 fork once per group, as in the batch-statistics graph.
+extern "C" int tf_detnet_trunk_backward_frozen_ctx(const int* blocks, tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x,
+                                                   int N, int H, int W, int nout, void* const* params, void* const* grads, const float* gout,
+                                                   void* grad_flat, size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream_) {
+  const Arch* Ap = find_arch(blocks);
+  if (!Ap) return TF_ERR_UNSUPPORTED;
+  if (!x || !params || !grads || !gout || !ws) return TF_ERR_ARG;
+  if (hooks && (hooks->n < 0 || (hooks->n > 0 && !hooks->blocks))) return TF_ERR_ARG;
+  if (!xctx) xctx = default_ctx();
+  if (dtype != TF_BF16 && dtype != TF_F32) return TF_ERR_UNSUPPORTED;
+  const Arch& A = *Ap;
+  Plan P; Arena ar(ws, ws_bytes);
+  build_plan(A, P, ar, dtype, N, H, W, nout, kFrozen);
+  if (!ar.ok) return TF_ERR_WORKSPACE;
+  Ctx c{dtype, (hipStream_t)stream_, params, grads, TF_OK};
+  if (!tf::tuning().single_stream && !(hooks && hooks->single_stream) && xctx) { c.side = ctx_side(xctx); c.events = &xctx->events; }
+  tf_conv_args a;
+  const int M3 = N * P.H3 * P.W3, M4 = N * P.H4 * P.W4;
+  const void* res3 = P.blk[A.layer_end[1]].y;
+  const void* res4 = P.blk[A.layer_end[2]].y;
+  const int nblocks = (int)A.blocks.size();
+  // the head-bias column sums fold into the head of this pass's partial buffer: zero on entry
+  if (hipMemsetAsync(P.partial_b, 0, (size_t)TF_STAT_ROWS * 3 * 1024 * 4, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+  const bool stem_direct = stem_direct_mode(dtype, false, false);      // (what the frozen forward took)
+  const bool group_on = wgrad_group_mode(dtype, 1);
+  const int first_id = A.layer_end[1] + 2, last_id = A.layer_end[2];
+  if (grad_flat && grad_flat_bytes) {
+    // the split memset of the batch-statistics graph: [layer3.1.conv1.weight, score_res3.weight) is skipped, the grouped weight gradients
+    // overwrite theirs.  The BN segments inside that range have NO writer here: zero_ranges_kernel clears them, so that the optimizer, the
+    // all-reduce buckets and a checkpoint never see what an earlier (batch-statistics) step left there.
+    char* lo = group_on ? (char*)c.G(A.blocks[first_id].c1.w) : nullptr;
+    char* hi = group_on ? (char*)c.G(A.head3.w) : nullptr;
+    char* g0 = (char*)grad_flat; char* g1 = g0 + grad_flat_bytes;
+    bool split = lo && hi && lo >= g0 && hi <= g1 && lo < hi;
+    std::vector<std::pair<float*, int>> zr;           // the BN slices inside the range, adjacent ones (gamma | beta of one BN) merged
+    for (int i = first_id; split && i <= last_id; ++i) {
+      const Block& B = A.blocks[i];
+      const int widx[3] = {B.c1.w, B.c2.w, B.c3.w};
+      for (int q : widx) { char* t = (char*)c.G(q); split = split && t >= lo && t < hi; }
+      const int bidx[6] = {B.c1.gamma, B.c1.beta, B.c2.gamma, B.c2.beta, B.c3.gamma, B.c3.beta};
+      const int bC[6] = {B.planes, B.planes, B.planes, B.planes, B.planes * 4, B.planes * 4};
+      for (int q = 0; q < 6; ++q) {
+        char* t = (char*)c.G(bidx[q]);
+        if (!t) continue;                                   // (a table without BN gradient slots: nothing to zero)
+        split = split && t >= lo && t + (size_t)bC[q] * 4 <= hi;
+        if (!zr.empty() && zr.back().first + zr.back().second == (float*)t) zr.back().second += bC[q];
+        else zr.emplace_back((float*)t, bC[q]);
+      }
+    }
+    for (int q = 0; split && q < (int)A.names.size(); ++q) {       // nothing else may lie inside the range
+      char* t = (char*)c.G(q);
+      if (!t || t < lo || t >= hi) continue;
+      bool mine = false;
+      for (int i = first_id; i <= last_id && !mine; ++i) {
+        const Block& B = A.blocks[i];
+        mine = q == B.c1.w || q == B.c1.gamma || q == B.c1.beta || q == B.c2.w || q == B.c2.gamma || q == B.c2.beta || q == B.c3.w || q == B.c3.gamma || q == B.c3.beta;
+      }
+      split = split && mine;
+    }
+    if (split && !tf::tuning().grad_memset_full) {
+      if (lo > g0 && hipMemsetAsync(g0, 0, (size_t)(lo - g0), c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+      if (g1 > hi && hipMemsetAsync(hi, 0, (size_t)(g1 - hi), c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+      // one launch per kZeroRanges ranges (ResNet-101: 66 ranges, ResNet-152: 105 -- one launch; the table travels as kernel arguments)
+      for (size_t at = 0; at < zr.size(); at += kZeroRanges) {
+        ZeroRanges tab;
+        const int nz = (int)(zr.size() - at < (size_t)kZeroRanges ? zr.size() - at : (size_t)kZeroRanges);
+        for (int q = 0; q < kZeroRanges; ++q) { tab.p[q] = q < nz ? zr[at + q].first : nullptr; tab.n[q] = q < nz ? zr[at + q].second : 0; }
+        hipLaunchKernelGGL(zero_ranges_kernel, dim3(1, nz), dim3(256), 0, c.stream, tab);
+      }
+    } else if (hipMemsetAsync(grad_flat, 0, grad_flat_bytes, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+    c.grads_zeroed = true;
+  }
+
+  // ---- heads (as in the batch-statistics graph)
+  c.chk(tf_upsample_add_crop_bwd(dtype, gout, P.wup_diag, N, nout, kHeadLd, P.H3, P.W3, P.H4, P.W4, P.g3, P.g4, c.stream));
+  {
+    const int nb3 = tf_colstats_blocks(M3, kHeadLd, dtype), nb4 = tf_colstats_blocks(M4, kHeadLd, dtype);
+    c.chk(tf_colstats(dtype, P.g3, nullptr, nullptr, nullptr, M3, kHeadLd, kHeadLd, P.partial_b, c.stream));
+    c.chk(tf_reduce_partials(P.partial_b, nb3, 1, 0, kHeadLd, nout, c.G(A.head3.bias), 1, c.stream));
+    c.chk(tf_colstats(dtype, P.g4, nullptr, nullptr, nullptr, M4, kHeadLd, kHeadLd, P.partial_b, c.stream));
+    c.chk(tf_reduce_partials(P.partial_b, nb4, 1, 0, kHeadLd, nout, c.G(A.head4.bias), 1, c.stream));
+  }
+  {
+    ConvUnit h3 = A.head3, h4 = A.head4;
+    c.fork();
+    wgrad(c, h3, nout, N, P.H3, P.W3, P.H3, P.W3, res3, 512, P.g3, kHeadLd, nullptr);
+    wgrad(c, h4, nout, N, P.H4, P.W4, P.H4, P.W4, res4, 1024, P.g4, kHeadLd, nullptr);
+  }
+  {   // score4_upsample.weight has lr 0 (model.py:84): its gradient is defined as zero
+    char* u = (char*)c.G(A.upsample_w);
+    const bool covered = c.grads_zeroed && u >= (char*)grad_flat && u + (size_t)nout * nout * 16 * 4 <= (char*)grad_flat + grad_flat_bytes;
+    if (u && !covered && hipMemsetAsync(u, 0, (size_t)nout * nout * 16 * 4, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+  }
+  // gm of the last block: the head's data gradient, masked by the block's own output
+  conv_fill(a, dtype, 1, N, P.H4, P.W4, kHeadLd, P.H4, P.W4, 1024, 1, 1, 0, 1024, P.g4, P.w_h4t, P.blk[nblocks - 1].gT1);
+  a.alg_k = nout; a.epi = TF_EPI_MASK2; a.aux2 = P.blk[nblocks - 1].y;
+  c.chk(tf_conv2d(&a, c.stream));
+  conv_fill(a, dtype, 1, N, P.H3, P.W3, kHeadLd, P.H3, P.W3, 512, 1, 1, 0, 512, P.g3, P.w_h3t, P.R3);
+  a.alg_k = nout;
+  c.chk(tf_conv2d(&a, c.stream));
+
+  std::vector<int> group_close;
+  if (group_on) {
+    const int nid = last_id - first_id + 1, gs = wgrad_group_size(), ng = (nid + gs - 1) / gs;
+    for (int g = 1; g <= ng; ++g) group_close.push_back(last_id + 1 - (int)(((long long)nid * g + ng - 1) / ng));
+  }
+  std::vector<tf_wgrad_args> pend_pw, pend_c3;
+  std::vector<int> pend_blocks;
+  auto flush_group = [&]() {
+    if (pend_blocks.empty()) return;
+    if (!tf::tuning().dbg_skip_wgrad) {
+      // a refused group falls back to the per-problem split-K kernels, which ACCUMULATE: the split memset skipped these tensors, zero each one
+      auto fallback = [&](const std::vector<tf_wgrad_args>& v) {
+        for (const tf_wgrad_args& w : v) {
+          if (hipMemsetAsync(w.dw_oihw, 0, (size_t)w.Cout * w.dw_ld * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+          c.chk(tf_conv2d_wgrad(&w, c.wstream()));
+        }
+      };
+      const bool force_refuse = tf::tuning().dbg_group_refuse;
+      int rc = force_refuse ? TF_ERR_UNSUPPORTED : tf_conv2d_wgrad_group(pend_c3.data(), (int)pend_c3.size(), c.wstream());
+      if (rc == TF_ERR_UNSUPPORTED) fallback(pend_c3); else c.chk(rc);
+      const int pw_split = tf::tuning().wgradg_split;
+      const int npw = (int)pend_pw.size(), per = (npw + pw_split - 1) / pw_split;
+      rc = TF_OK;
+      for (int at = 0; at < npw && rc == TF_OK; at += per)
+        rc = force_refuse ? TF_ERR_UNSUPPORTED : tf_conv2d_wgrad_group(pend_pw.data() + at, npw - at < per ? npw - at : per, c.wstream());
+      if (rc == TF_ERR_UNSUPPORTED) fallback(pend_pw); else c.chk(rc);
+    }
+    for (int blk : pend_blocks) record_grad_events(hooks, blk, c.wstream(), c.rc);
+    pend_pw.clear(); pend_c3.clear(); pend_blocks.clear();
+  };
+
+  // ---- bottlenecks in reverse
+  for (int i = nblocks - 1; i >= 0; --i) {
+    const Block& B = A.blocks[i];
+    Plan::Blk& b = P.blk[i];
+    const int pl = B.planes, c4 = pl * 4;
+    const void* yin = i == 0 ? P.pool : P.blk[i - 1].y;
+    const void* extra = (i == A.layer_end[1] + 1) ? P.R3 : nullptr;     // the block whose INPUT is res3
+    const bool grouped = group_on && i >= first_id && i <= last_id;
+    bool closes_group = false;
+    if (grouped) for (int gc : group_close) closes_group |= gc == i;
+    void *gm = b.gT1, *T2 = b.gT2, *U1 = b.gU1;
+    void* gprev = i > 0 ? P.blk[i - 1].gT1 : P.R3;      // (block 0: the gradient of the max-pool output; R3's last reader is far ahead on this stream)
+    // (1) g2 = (W3 diag(s3))^T gm * (a2 > 0) * s2
+    conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hout, b.Wout, pl, 1, 1, 0, pl, gm, b.w3t, T2);
+    a.epi = TF_EPI_AFFINE | TF_EPI_MASK; a.epi_scale = b.b2.scale; a.epi_shift = P.c_zero; a.aux = b.c2; a.mask_scale = P.c_one; a.mask_shift = P.c_zero;
+    c.chk(tf_conv2d(&a, c.stream));
+    // (2) g1 = W2^T (*) g2 * (a1 > 0) * s1; it completes the block's weight-gradient operands: the launch carries the fork
+    conv_fill(a, dtype, 1, N, b.Hout, b.Wout, pl, b.Hin, b.Win, pl, 3, B.stride, 1, pl, T2, b.w2t, U1);
+    a.epi = TF_EPI_AFFINE | TF_EPI_MASK; a.epi_scale = b.b1.scale; a.epi_shift = P.c_zero; a.aux = b.c1; a.mask_scale = P.c_one; a.mask_shift = P.c_zero;
+    // (a stride-2 3x3 data gradient is four parity-class launches: the first would carry the event away -- a plain fork behind all four)
+    if ((!grouped || closes_group) && B.stride == 1) c.arm_fork();
+    c.chk(tf_conv2d(&a, c.stream));
+    // (3) weight gradients, on the second stream
+    tf_wgrad_args w3 = wgrad_args(c, B.c3, c4, N, b.Hout, b.Wout, b.Hout, b.Wout, b.c2, pl, gm, c4);
+    w3.row_scale = b.b3.scale;
+    tf_wgrad_args w1 = wgrad_args(c, B.c1, pl, N, b.Hin, b.Win, b.Hin, b.Win, yin, B.cin, U1, pl);
+    if (grouped) {
+      pend_pw.push_back(w3); pend_pw.push_back(w1);
+      pend_c3.push_back(wgrad_args(c, B.c2, pl, N, b.Hin, b.Win, b.Hout, b.Wout, b.c1, pl, T2, pl));
+      pend_blocks.push_back(i);
+      if (closes_group) { c.fork_armed(); flush_group(); }
+    } else {
+      c.fork_armed();
+      if (!tf::tuning().dbg_skip_wgrad) {
+        if (!c.grads_zeroed && hipMemsetAsync(w3.dw_oihw, 0, (size_t)c4 * w3.dw_ld * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+        c.chk(tf_conv2d_wgrad(&w3, c.wstream()));
+      }
+      wgrad(c, B.c2, pl, N, b.Hin, b.Win, b.Hout, b.Wout, b.c1, pl, T2, pl, nullptr, 0, 0, 0, P.dwp, P.dwp_floats);
+      wgrad(c, B.c1, pl, N, b.Hin, b.Win, b.Hin, b.Win, yin, B.cin, U1, pl, nullptr);
+      if (B.has_ds && !tf::tuning().dbg_skip_wgrad) {
+        tf_wgrad_args wd = wgrad_args(c, B.ds, c4, N, b.Hin, b.Win, b.Hout, b.Wout, yin, B.cin, gm, c4);
+        wd.row_scale = b.bd.scale;
+        if (!c.grads_zeroed && hipMemsetAsync(wd.dw_oihw, 0, (size_t)c4 * wd.dw_ld * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+        c.chk(tf_conv2d_wgrad(&wd, c.wstream()));
+      }
+      record_grad_events(hooks, i, c.wstream(), c.rc);
+    }
+    // (4) gm_prev = (W1^T g1 + skip) * (x > 0) -> the previous block's gT1 (block 0: no ReLU between the max-pool and its input)
+    auto hand_over = [&](tf_conv_args& q) { if (i > 0) { q.epi |= TF_EPI_MASK2; q.aux2 = yin; } };
+    if (B.has_ds) {
+      const bool ds_inplace = i > 0 && B.stride == 2 && !tf::tuning().ds_inplace_off;
+      if (ds_inplace) {
+        // the raster first (residual = the head gradient where there is one), then the stride-2 downsample gradient accumulates IN PLACE
+        conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, U1, b.w1t, gprev);
+        if (extra) { a.epi = TF_EPI_RES; a.aux = extra; }
+        hand_over(a);
+        c.chk(tf_conv2d(&a, c.stream));
+        conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hin, b.Win, B.cin, 1, B.stride, 0, B.cin, gm, b.wdt, gprev);
+        a.epi = TF_EPI_RES; a.aux = gprev;
+        hand_over(a);
+        c.chk(tf_conv2d(&a, c.stream));
+      } else {
+        conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hin, b.Win, B.cin, 1, B.stride, 0, B.cin, gm, b.wdt, P.T4);
+        if (extra) { a.epi = TF_EPI_RES; a.aux = extra; }
+        c.chk(tf_conv2d(&a, c.stream));
+        conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, U1, b.w1t, gprev);
+        a.epi = TF_EPI_RES; a.aux = P.T4;
+        hand_over(a);
+        c.chk(tf_conv2d(&a, c.stream));
+      }
+    } else {
+      conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, U1, b.w1t, gprev);
+      a.epi = TF_EPI_RES; a.aux = gm;                       // identity branch: gm is already g_y * (y > 0)
+      hand_over(a);
+      c.chk(tf_conv2d(&a, c.stream));
+    }
+  }
+
+  // ---- stem: max-pool backward masks through relu (the stored cstem is post-ReLU: scale 1, shift 0), the BN scale rides in the weight gradient
+  const int M1 = N * P.H1 * P.W1;
+  void* gz = P.T4;
+  c.chk(tf_maxpool_bwd(dtype, P.R3, P.pool_idx, P.cstem, P.c_one, P.c_zero, N, P.H1, P.W1, 64, gz, c.stream));
+  {
+    ConvUnit s = A.stem; s.stride = 1; s.pad = 0;
+    c.fork();
+    if (stem_direct) {
+      if (!c.grads_zeroed && hipMemsetAsync(c.G(A.stem.w), 0, (size_t)64 * 147 * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+      // operand = cA * g + cB * x_conv + cD with cA = the folded scale, cB = cD = 0
+      c.chk(tf_stem_wgrad(dtype, x, N, H, W, gz, P.cstem, P.bn_stem.scale, P.c_zero, P.c_zero, c.G(A.stem.w), c.wstream()));
+    } else if (!tf::tuning().dbg_skip_wgrad) {
+      // (P.col still holds the im2col matrix of this forward)
+      tf_wgrad_args w = wgrad_args(c, s, 64, 1, 1, M1, 1, M1, P.col, kStemK, gz, 64, 147, 1, 147);
+      w.row_scale = P.bn_stem.scale;
+      if (!c.grads_zeroed && hipMemsetAsync(w.dw_oihw, 0, (size_t)64 * 147 * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+      c.chk(tf_conv2d_wgrad(&w, c.wstream()));
+    }
+  }
+  c.wait_on_main(c.mark_side());           // join: the caller's stream sees every weight gradient
+  record_grad_events(hooks, -1, c.stream, c.rc);
+  if (hipGetLastError() != hipSuccess && c.rc == TF_OK) c.rc = TF_ERR_LAUNCH;
+  return c.rc;
+}
+extern "C" int tf_detnet_backward_frozen_ctx(tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x, int N, int H, int W, int nout,
+                                             void* const* params, void* const* grads, const float* gout, void* grad_flat, size_t grad_flat_bytes,
+                                             void* ws, size_t ws_bytes, void* stream_) {
+  return tf_detnet_trunk_backward_frozen_ctx(nullptr, xctx, hooks, dtype, x, N, H, W, nout, params, grads, gout, grad_flat, grad_flat_bytes, ws,
+                                             ws_bytes, stream_);
 }
 
 // context-free form (rounds 1-3): the default context of the current device + the process-wide hooks registered with tf_detnet_set_*

@@ -126,7 +126,12 @@ __global__ void __launch_bounds__(256) pack2_kernel(const Pack2Jobs jobs, int nj
       const int co = co0 + 4 * q, ci = ci0 + cl;
       if (ci < J.rows_pad_t && co < J.cols_pad_t) {
         const float* t0 = tile + (4 * q) * pitch + cl * taps + tap;
-        store4(out + ((size_t)ci * taps + tap) * J.cols_pad_t + co, t0[0], t0[pitch], t0[2 * pitch], t0[3 * pitch]);
+        float s0 = 1.f, s1 = 1.f, s2 = 1.f, s3 = 1.f;          // frozen-BN graph: the BN behind the conv, folded to its scale, per output channel
+        if (J.scale_t) {
+          s0 = co < J.cout ? J.scale_t[co] : 0.f; s1 = co + 1 < J.cout ? J.scale_t[co + 1] : 0.f;
+          s2 = co + 2 < J.cout ? J.scale_t[co + 2] : 0.f; s3 = co + 3 < J.cout ? J.scale_t[co + 3] : 0.f;
+        }
+        store4(out + ((size_t)ci * taps + tap) * J.cols_pad_t + co, t0[0] * s0, t0[pitch] * s1, t0[2 * pitch] * s2, t0[3 * pitch] * s3);
       }
     }
   }

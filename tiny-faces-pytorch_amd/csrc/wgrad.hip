@@ -30,7 +30,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct WgK {
   const char* x; const char* dy; float* dw;
-  const float* pro_scale; const float* pro_shift;
+  const float* pro_scale; const float* pro_shift; const float* row_scale;
   int H, W, Cin, OH, OW, Cout, KH, KW, stride, pad;
   int M, OHW, ldx, lddy, dw_ld, pro_relu, ci_stride, tap_stride;
   int nco, nci, ntaps, splitk, chunk;
@@ -50,7 +50,9 @@ __device__ __forceinline__ bf16x8 frag_tr(const char* tile, int pitch, int pk0, 
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-template <typename T, int BC>   // BC = channels per tile side (co and ci): 128 or 64
+// BC = channels per tile side (co and ci): 128 or 64.  RS: tf_wgrad_args.row_scale (frozen-BN graph), a compile-time form of its own so that
+// the default instantiation is the kernel it always was (as a run-time branch it cost wgrad_dma_kernel 0.6 % of the step)
+template <typename T, int BC, bool RS = false>
 __global__ void __launch_bounds__(256) wgrad_kernel(const WgK a) {
   constexpr int PK = WgTraits<T>::PK;
   constexpr int EPS = tf::Elem<T>::kPer16B;
@@ -181,7 +183,11 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const WgK a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int co = co0 + wco * WC + n * 16 + lg * 4 + r;
-        if (co < a.Cout && ci < a.Cin) atomicAdd(a.dw + (size_t)co * a.dw_ld + (size_t)ci * a.ci_stride + (size_t)tap * a.tap_stride, acc[n][m][r]);
+        if constexpr (RS) {                                            // frozen-BN graph: the BN behind the conv, folded to its scale
+          if (co < a.Cout && ci < a.Cin) atomicAdd(a.dw + (size_t)co * a.dw_ld + (size_t)ci * a.ci_stride + (size_t)tap * a.tap_stride, acc[n][m][r] * a.row_scale[co]);
+        } else {
+          if (co < a.Cout && ci < a.Cin) atomicAdd(a.dw + (size_t)co * a.dw_ld + (size_t)ci * a.ci_stride + (size_t)tap * a.tap_stride, acc[n][m][r]);
+        }
       }
     }
 }
@@ -190,7 +196,7 @@ template <typename T, int BC>
 int launch_wgrad(const tf_wgrad_args* A, hipStream_t stream) {
   constexpr int PK = WgTraits<T>::PK;
   WgK k;
-  k.x = (const char*)A->x; k.dy = (const char*)A->dy; k.dw = A->dw_oihw; k.pro_scale = A->pro_scale; k.pro_shift = A->pro_shift;
+  k.x = (const char*)A->x; k.dy = (const char*)A->dy; k.dw = A->dw_oihw; k.pro_scale = A->pro_scale; k.pro_shift = A->pro_shift; k.row_scale = A->row_scale;
   k.H = A->H; k.W = A->W; k.Cin = A->Cin; k.OH = A->OH; k.OW = A->OW; k.Cout = A->Cout; k.KH = A->KH; k.KW = A->KW;
   k.stride = A->stride; k.pad = A->pad; k.M = A->N * A->OH * A->OW; k.OHW = A->OH * A->OW;
   k.ldx = A->ldx; k.lddy = A->lddy; k.dw_ld = A->dw_ld; k.pro_relu = A->pro_relu;
@@ -211,11 +217,13 @@ int launch_wgrad(const tf_wgrad_args* A, hipStream_t stream) {
   static tf::PerDevice attr_set;
   if (attr_set.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, BC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, BC, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
   const double es = sizeof(T), Md = k.M;
   tf::ProfScope prof(8 + (sizeof(T) == 2 ? 2 : 0) + (BC == 128 ? 1 : 0), 2.0 * Md * A->Cout * A->Cin * k.ntaps,
                      (Md * A->Cout + (double)A->N * A->H * A->W * A->Cin) * es + (double)A->Cout * A->Cin * k.ntaps * 4, stream);
-  hipLaunchKernelGGL((wgrad_kernel<T, BC>), dim3(tiles * k.splitk), dim3(256), lds, stream, k);
+  if (k.row_scale) hipLaunchKernelGGL((wgrad_kernel<T, BC, true>), dim3(tiles * k.splitk), dim3(256), lds, stream, k);
+  else hipLaunchKernelGGL((wgrad_kernel<T, BC>), dim3(tiles * k.splitk), dim3(256), lds, stream, k);
   return hipGetLastError() == hipSuccess ? TF_OK : TF_ERR_LAUNCH;
 }
 
@@ -232,7 +240,8 @@ extern "C" int tf_conv2d_wgrad(const tf_wgrad_args* a, void* stream_) {
   //       1 = force the per-tap DMA kernel, 3 = force the all-taps kernel, 64 / 128 = register-staged kernel
   if ((a->tile == 0 || a->tile == 3) && a->dtype == TF_BF16 && !a->pro_scale) {
     const bool w3_off = tf::tuning().wgrad3_off;          // A/B knob
-    const int rc = (w3_off && a->tile == 0) ? TF_ERR_UNSUPPORTED : tf_wgrad3x3_launch(a, stream);
+    // (the all-taps kernel has no row scale: such a problem keeps the per-tap kernel)
+    const int rc = ((w3_off && a->tile == 0) || a->row_scale) ? TF_ERR_UNSUPPORTED : tf_wgrad3x3_launch(a, stream);
     if (rc != TF_ERR_UNSUPPORTED || a->tile == 3) return rc;
   }
   if ((a->tile == 0 || a->tile == 1) && a->dtype == TF_BF16 && !a->pro_scale) return tf_wgrad_dma_launch(a, stream);
@@ -253,6 +262,7 @@ extern "C" int tf_conv2d_wgrad_group(const tf_wgrad_args* probs, int n, void* st
     if (a.dtype != TF_BF16 || a.pro_scale) return TF_ERR_UNSUPPORTED;
     if (a.ldx % 8 || a.lddy % 8 || a.ldx < a.Cin || a.lddy < a.Cout) return TF_ERR_ARG;
     if (a.KH != probs[0].KH || a.KW != probs[0].KW) return TF_ERR_UNSUPPORTED;
+    if (a.row_scale && !(a.KH == 1 && a.KW == 1)) return TF_ERR_UNSUPPORTED;       // the pointwise group only
   }
   if (probs[0].KH == 1 && probs[0].KW == 1) return tf_wgrad_pw_group_launch(probs, n, stream);
   if (probs[0].KH == 3 && probs[0].KW == 3) return tf_wgrad3x3_group_launch(probs, n, stream);

@@ -20,7 +20,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ uint4 g_wzero_page[8];
 
 struct WdK {
-  const char* x; const char* dy; float* dw;
+  const char* x; const char* dy; float* dw; const float* row_scale;
   int H, W, Cin, OH, OW, Cout, KW, stride, pad;
   int M, OHW, ldx, lddy, dw_ld, ci_stride, tap_stride;
   int nco, nci, splitk, chunk;
@@ -58,7 +58,8 @@ __device__ __forceinline__ bf16x8 frag_tr(const char* tile, int pk0, int c0) {
 }
 
 // KIND 1: pointwise (1x1, stride 1, pad 0): X row of pixel p is row p.  KIND 0: generic tap gather.
-template <int KIND, int NS = 3, bool HIDDEN = true>
+// RS: tf_wgrad_args.row_scale (frozen-BN graph) -- a compile-time form of its own, so that the default instantiation is the kernel it always was
+template <int KIND, int NS = 3, bool HIDDEN = true, bool RS = false>
 __global__ void __launch_bounds__(256) wgrad_dma_kernel(const WdK a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int b = blockIdx.x;
@@ -166,7 +167,11 @@ __global__ void __launch_bounds__(256) wgrad_dma_kernel(const WdK a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int co = co0 + wco * 32 + n * 16 + lg * 4 + r;
-        if (co < a.Cout && ci < a.Cin) atomicAdd(a.dw + (size_t)co * a.dw_ld + (size_t)ci * a.ci_stride + (size_t)tap * a.tap_stride, acc[n][m][r]);
+        if constexpr (RS) {                                            // frozen-BN graph: the BN behind the conv, folded to its scale
+          if (co < a.Cout && ci < a.Cin) atomicAdd(a.dw + (size_t)co * a.dw_ld + (size_t)ci * a.ci_stride + (size_t)tap * a.tap_stride, acc[n][m][r] * a.row_scale[co]);
+        } else {
+          if (co < a.Cout && ci < a.Cin) atomicAdd(a.dw + (size_t)co * a.dw_ld + (size_t)ci * a.ci_stride + (size_t)tap * a.tap_stride, acc[n][m][r]);
+        }
       }
     }
 }
@@ -177,7 +182,7 @@ __global__ void __launch_bounds__(256) wgrad_dma_kernel(const WdK a) {
 int tf_wgrad_dma_launch(const tf_wgrad_args* A, hipStream_t stream) {
   if (A->dtype != TF_BF16 || A->pro_scale) return TF_ERR_UNSUPPORTED;
   WdK k;
-  k.x = (const char*)A->x; k.dy = (const char*)A->dy; k.dw = A->dw_oihw;
+  k.x = (const char*)A->x; k.dy = (const char*)A->dy; k.dw = A->dw_oihw; k.row_scale = A->row_scale;
   k.H = A->H; k.W = A->W; k.Cin = A->Cin; k.OH = A->OH; k.OW = A->OW; k.Cout = A->Cout; k.KW = A->KW; k.stride = A->stride; k.pad = A->pad;
   k.M = A->N * A->OH * A->OW; k.OHW = A->OH * A->OW; k.ldx = A->ldx; k.lddy = A->lddy; k.dw_ld = A->dw_ld;
   if (A->packed) { k.ci_stride = 1; k.tap_stride = A->Cin; } else { k.ci_stride = A->KH * A->KW; k.tap_stride = 1; }
@@ -205,7 +210,10 @@ int tf_wgrad_dma_launch(const tf_wgrad_args* A, hipStream_t stream) {
                      A->Cin * ntaps, ntaps, 2, 0, -1.0, true);
   const bool builtin_dma = tf::tuning().dma_builtin;       // A/B: the compiler-visible DMA of rounds 1-3 (drained every stage)
   const dim3 grid(tiles * k.splitk);
-  if (builtin_dma) {
+  if (A->row_scale) {
+    if (pointwise) TF_LAUNCH_TIMED((wgrad_dma_kernel<1, 3, true, true>), grid, dim3(256), lds3(), stream, k);
+    else TF_LAUNCH_TIMED((wgrad_dma_kernel<0, 3, true, true>), grid, dim3(256), lds3(), stream, k);
+  } else if (builtin_dma) {
     if (pointwise) TF_LAUNCH_TIMED((wgrad_dma_kernel<1, 3, false>), grid, dim3(256), lds3(), stream, k);
     else TF_LAUNCH_TIMED((wgrad_dma_kernel<0, 3, false>), grid, dim3(256), lds3(), stream, k);
   } else if (pointwise) {

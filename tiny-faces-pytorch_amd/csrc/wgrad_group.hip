@@ -43,7 +43,7 @@ constexpr int GP_STAGE = 4 * GP_SUB;         // dY[co 0-63], dY[co 64-127], X[ci
 constexpr int GP_L = 4;                      // DMA instructions per thread and stage
 constexpr int GP_MAX = 48;                   // problems per launch (the table travels as kernel arguments)
 
-struct GpProb { const char* x; const char* dy; float* dw; int Cin, Cout, ldx, lddy, dw_ld, nci, tile0, pad_; };
+struct GpProb { const char* x; const char* dy; float* dw; const float* rs; int Cin, Cout, ldx, lddy, dw_ld, nci, tile0, pad_; };     // rs: tf_wgrad_args.row_scale
 struct GpK { int M, nprob, ntiles, pad_; GpProb p[GP_MAX]; };
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -173,10 +173,11 @@ __global__ void __launch_bounds__(256, 2) wgrad_group_kernel(const GpK a) {
       const int co = co0 + wco * 64 + n * 16 + lg * 4 + r;
       if (co < P.Cout) {
         float* drow = P.dw + (size_t)co * P.dw_ld;
+        const float rs = P.rs ? P.rs[co] : 1.f;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           const int ci = ci0 + wci * 64 + m * 16 + li;
-          if (ci < P.Cin) drow[ci] = acc[n][m][r];
+          if (ci < P.Cin) drow[ci] = acc[n][m][r] * rs;
         }
       }
     }
@@ -310,9 +311,11 @@ __global__ void __launch_bounds__(256, NS <= 4 ? 2 : 1) wgrad_group_fast_kernel(
   for (int n = 0; n < 4; ++n)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float* drow = P.dw + (size_t)(co0 + wco * 64 + n * 16 + lg * 4 + r) * P.dw_ld + ci0 + wci * 64 + li;
+      const int co = co0 + wco * 64 + n * 16 + lg * 4 + r;
+      float* drow = P.dw + (size_t)co * P.dw_ld + ci0 + wci * 64 + li;
+      const float rs = P.rs ? P.rs[co] : 1.f;             // frozen-BN graph: the BN behind the conv, folded to its scale (block-uniform branch)
 #pragma unroll
-      for (int m = 0; m < 4; ++m) drow[m * 16] = acc[n][m][r];
+      for (int m = 0; m < 4; ++m) drow[m * 16] = acc[n][m][r] * rs;
     }
 }
 
@@ -332,7 +335,7 @@ int tf_wgrad_pw_group_launch(const tf_wgrad_args* A, int n, hipStream_t stream) 
     if (q.KH != 1 || q.KW != 1 || q.stride != 1 || q.pad != 0 || q.H != q.OH || q.W != q.OW) return TF_ERR_UNSUPPORTED;
     if (q.N * q.OH * q.OW != k.M || q.ldx % 8 || q.lddy % 8 || q.ldx < q.Cin || q.lddy < q.Cout) return TF_ERR_UNSUPPORTED;
     GpProb& p = k.p[i];
-    p.x = (const char*)q.x; p.dy = (const char*)q.dy; p.dw = q.dw_oihw; p.Cin = q.Cin; p.Cout = q.Cout; p.ldx = q.ldx; p.lddy = q.lddy;
+    p.x = (const char*)q.x; p.dy = (const char*)q.dy; p.dw = q.dw_oihw; p.rs = q.row_scale; p.Cin = q.Cin; p.Cout = q.Cout; p.ldx = q.ldx; p.lddy = q.lddy;
     p.dw_ld = q.dw_ld ? q.dw_ld : q.Cin; p.nci = (q.Cin + 127) / 128; p.tile0 = tiles; p.pad_ = 0;
     tiles += ((q.Cout + 127) / 128) * p.nci;
     flops += 2.0 * k.M * q.Cout * q.Cin;

@@ -66,21 +66,27 @@ TRUNK_HELP = ("--base-model {resnet50,resnet101,resnet152}: trunk of the detecto
               "default resnet101 (the reference's)")
 
 
+FREEZE_HELP = ("--freeze-bn: fine-tune with every BatchNorm of the trunk frozen on its pretrained statistics and affine "
+               "(DetectionModel.freeze_batchnorm: torchvision's FrozenBatchNorm2d), default off")
+
+
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog=TRUNK_HELP)
+    parser = argparse.ArgumentParser(epilog=TRUNK_HELP + "; " + FREEZE_HELP)
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
 
 
 def trunk_arguments(argv=None):
-    """`arguments` plus `base_model` from --base-model.  Parsed apart, so that `arguments` keeps resolving exactly the reference's options
+    """`arguments` plus `base_model` from --base-model and `freeze_bn` from --freeze-bn.  Parsed apart, so that `arguments` keeps resolving exactly the reference's options
     and the additions above."""
     parser = argparse.ArgumentParser(add_help=False)
     parser.add_argument("--base-model", dest="base_model", default="resnet101", choices=list(model_zoo.TRUNKS), help=TRUNK_HELP)
+    parser.add_argument("--freeze-bn", dest="freeze_bn", action="store_true", help=FREEZE_HELP)
     known, rest = parser.parse_known_args(argv)
     args = arguments(rest)
     args.base_model = known.base_model
+    args.freeze_bn = known.freeze_bn
     return args
 
 
@@ -128,6 +134,7 @@ def main():
     preprocess = transforms.Compose([transforms.ToTensor(), transforms.Normalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225])])
     train_loader, _ = get_dataloader(args.traindata, args, NUM_TEMPLATES, img_transforms=preprocess)
     model = DetectionModel(base_model=getattr(model_zoo, args.base_model), num_objects=1, num_templates=NUM_TEMPLATES).set_compute_dtype(args.dtype)
+    model.freeze_batchnorm(args.freeze_bn)
     loss_fn = DetectionCriterion(NUM_TEMPLATES, seed=args.seed * parallel.world_size() + parallel.rank(), lazy_meters=True)
     loss_fn.ohem_thresh = args.ohem_thresh
 

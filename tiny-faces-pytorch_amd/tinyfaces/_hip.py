@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libtinyfaces_hip.so")
 
 TF_F32, TF_BF16, TF_F16 = 0, 1, 2
 TF_COMM_ID_BYTES = 128
+TF_DETNET_FROZEN_BN = 2            # `training` argument of the executor: the evaluation forward + a backward through the folded BN
 EPI_AFFINE, EPI_RES, EPI_RELU, EPI_STATS, EPI_MASK, EPI_STATS2, EPI_JOIN, EPI_MASK2, EPI_STATS3 = 1, 2, 4, 8, 16, 32, 64, 128, 256
 ERRORS = {-1: "TF_ERR_ARG", -2: "TF_ERR_LAUNCH", -3: "TF_ERR_UNSUPPORTED", -4: "TF_ERR_WORKSPACE"}
 
@@ -34,7 +35,7 @@ class ImagePrepareArgs(C.Structure):
 class Pack2Job(C.Structure):
     """tf_pack2_job (include/tinyfaces_hip.h)."""
     _fields_ = [("src", vp), ("dst", vp), ("dst_t", vp), ("cout", i32), ("cin", i32), ("taps", i32), ("rows_pad", i32), ("cols_pad", i32),
-                ("rows_pad_t", i32), ("cols_pad_t", i32)]
+                ("rows_pad_t", i32), ("cols_pad_t", i32), ("scale_t", vp)]
 
 
 class BnFwdDesc(C.Structure):
@@ -78,7 +79,8 @@ class WgradArgs(C.Structure):
                 ("KH", i32), ("KW", i32), ("stride", i32), ("pad", i32),
                 ("ldx", i32), ("lddy", i32), ("pro_relu", i32),
                 ("x", vp), ("dy", vp), ("dw_oihw", vp), ("pro_scale", vp), ("pro_shift", vp),
-                ("dw_ld", i32), ("splitk", i32), ("tile", i32), ("packed", i32), ("partial_ws", vp), ("partial_ws_bytes", sz)]
+                ("dw_ld", i32), ("splitk", i32), ("tile", i32), ("packed", i32), ("partial_ws", vp), ("partial_ws_bytes", sz),
+                ("row_scale", vp)]
 
 
 _SIGNATURES = {
@@ -101,6 +103,7 @@ _SIGNATURES = {
     "tf_criterion_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, f32, vp, vp, u64, vp, vp, vp, vp, vp, sz, vp]),
     "tf_image_prepare": (i32, [C.POINTER(ImagePrepareArgs), vp]),
     "tf_sgd_step": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, vp]),
+    "tf_sgd_step_segments": (i32, [vp, vp, vp, C.POINTER(i64), i32, f32, f32, f32, f32, vp]),
     "tf_conv_mtiles": (i32, [C.POINTER(ConvArgs)]),
     "tf_conv2d": (i32, [C.POINTER(ConvArgs), vp]),
     "tf_pack_weight": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp]),
@@ -157,6 +160,8 @@ _SIGNATURES = {
     "tf_detnet_trunk_param_region_bytes": (sz, [vp, i32, i32, i32]),
     "tf_detnet_trunk_forward_ctx": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, f32, f32, vp, vp, sz, i32, vp]),
     "tf_detnet_trunk_backward_ctx": (i32, [vp, vp, C.POINTER(DetnetHooks), i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, sz, vp]),
+    "tf_detnet_trunk_backward_frozen_ctx": (i32, [vp, vp, C.POINTER(DetnetHooks), i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, sz, vp]),
+    "tf_detnet_backward_frozen_ctx": (i32, [vp, C.POINTER(DetnetHooks), i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, sz, vp]),
     "tf_pack_weights_batched": (i32, [i32, vp, i32, vp]),
     "tf_pack_weights_tiled": (i32, [i32, vp, i32, vp]),
     "tf_detnet_set_dual_stream": (i32, [i32]),

@@ -437,12 +437,34 @@ class TrainEngine:
                 if w is not None:
                     w.wait()                              # the second stream (not the host, with RCCL) waits for this bucket's sum
                 for a, b, mult in self.group_slices(self.groups, start, end):
-                    ops.sgd_step(self.flat_p[a:b], gflat[a:b], self.flat_m[a:b], self.lr * mult, self.momentum, self.weight_decay, scale)
+                    self._sgd(gflat, a, b, mult, scale)
         cur.wait_stream(comm)
+
+    def _trained_segments(self):
+        """Frozen BatchNorm: [(start, end)] of the flat buffer that the optimizer touches -- every segment that is not a BatchNorm weight /
+        bias, ascending.  The BN vectors sit in between (the trunk group is ONE range): a plain tf_sgd_step over the group would decay them
+        through weight decay although their gradient is zero."""
+        key = id(self.model._segments)
+        if getattr(self, "_trained_key", None) != key:
+            bn = self.model._bn_param_names
+            self._trained = sorted((o, o + n) for k, (o, n) in self.model._segments.items() if k not in bn)
+            self._trained_key = key
+        return self._trained
+
+    def _sgd(self, gflat, a, b, mult, scale):
+        """The SGD update of the flat range [a, b) (inside one parameter group, lr multiplier `mult`).  With the model's BatchNorm frozen
+        only the trained segments of the range are touched, in one launch per TF_SGD_MAX_SEGMENTS segments (ops.sgd_step_segments)."""
+        if not self.model.batchnorm_frozen:
+            ops.sgd_step(self.flat_p[a:b], gflat[a:b], self.flat_m[a:b], self.lr * mult, self.momentum, self.weight_decay, scale)
+            return
+        segs = [(max(s, a), min(e, b)) for s, e in self._trained_segments() if e > a and s < b]
+        ops.sgd_step_segments(self.flat_p, gflat, self.flat_m, segs, self.lr * mult, self.momentum, self.weight_decay, scale)
 
     def step(self, x, class_map, regression_map):
         """x (B,3,H,W) f32, class_map (B,nt,h,w) f32 (mined in place), regression_map (B,4nt,h,w) f32: all on the device.
-        Returns the device tensor [sum cls loss, sum reg loss] (float64) without synchronising."""
+        Returns the device tensor [sum cls loss, sum reg loss] (float64) without synchronising.
+        The step follows the model's BatchNorm mode (DetectionModel.freeze_batchnorm): frozen, the forward and backward run the folded-BN
+        graph, and the update skips the BatchNorm vectors (no weight decay, no momentum: their momentum buffers stay zero)."""
         m, c = self.model, self.criterion
         m._sync_tables(x.device)
         out = m._run_forward(x, training=True)
@@ -469,7 +491,7 @@ class TrainEngine:
             for s, e, mult in self.groups:
                 if mult == 0.0:
                     continue                              # score4_upsample: lr 0 (model.py:84) -> nothing to do
-                ops.sgd_step(self.flat_p[s:e], gflat[s:e], self.flat_m[s:e], self.lr * mult, self.momentum, self.weight_decay, scale)
+                self._sgd(gflat, s, e, mult, scale)
         self.steps += 1
         if hasattr(c, "_pending") and (parallel.rank() == 0 or not parallel.is_distributed()):
             c._pending.append((loss2, x.shape[0]))       # only the logging rank ever flushes the meters

@@ -179,6 +179,9 @@ class _DetNetFunction(torch.autograd.Function):
             raise RuntimeError("DetectionModel: the activation arena was reused by a later forward before this "
                                "backward ran (one in-flight training step per model)")
         grads = owner._run_backward(x, gout.contiguous().float())
+        if owner._ws_mode == _hip.TF_DETNET_FROZEN_BN:         # frozen BatchNorm: weight / bias have NO gradient (FrozenBatchNorm2d)
+            bn = owner._bn_param_names
+            grads = [None if k in bn else g for k, g in zip(owner._grad_names, grads)]
         return (None, None) + tuple(grads)
 
 
@@ -220,6 +223,8 @@ class DetectionModel(nn.Module):
         self._ws_generation = 0
         self._table_key = None
         self._frozen_tensors, self._frozen_version = (), -1
+        self._bn_frozen = False          # freeze_batchnorm(): a mode like train() / eval(), not part of the state_dict
+        self._ws_mode = 0                # the executor mode (0 eval, 1 batch statistics, 2 frozen BN) of the forward whose activations sit in the workspace
         self._session_depth = 0          # constant_weights() nesting
         self._ready_key = None           # (workspace ptr, dtype, table key) whose packed eval weights sit in the workspace
         self._lanes = []                 # forward_levels: extra (workspace, HIP stream, ready key) triples beside the model's own
@@ -273,6 +278,29 @@ class DetectionModel(nn.Module):
                 {"params": self.score_res4.parameters(), "lr": 1 * lr},
                 {"params": self.score4_upsample.parameters(), "lr": 0}]
 
+    def freeze_batchnorm(self, on=True):
+        """Fine-tune on the statistics and affine the trunk was pretrained with (torchvision's FrozenBatchNorm2d; `bn.eval()` on every
+        BatchNorm2d with its parameters `requires_grad = False`): every BatchNorm is the constant map v -> v * s + h with
+        s = weight / sqrt(running_var + eps), h = bias - running_mean * s.  A mode like train() / eval(): it is not part of the
+        state_dict and survives .train(), .eval() and .to().  While it is on
+
+        * train() with gradients enabled runs the folded-BN graph forward AND backward (the forward is the evaluation forward bit for bit);
+          running_mean, running_var, num_batches_tracked, weight and bias of every BatchNorm are read, never written; BN weight / bias get
+          no gradient (`.grad` stays None, TrainEngine applies neither weight decay nor momentum to them); every conv weight and the head
+          weights / biases get the gradient autograd gives the reference model with its BatchNorm2d modules in eval();
+        * train() under no_grad runs the folded forward and writes nothing;
+        * eval() is unchanged.
+
+        Per-module modes are NOT honoured: the executor looks at the model's own flags only, `model.model.layer1[0].bn1.eval()` is
+        ignored exactly as without this switch.  fp16 stays an inference-only operand type.  Returns self."""
+        self._bn_frozen = bool(on)
+        return self
+
+    @property
+    def batchnorm_frozen(self):
+        """True while freeze_batchnorm() is on."""
+        return self._bn_frozen
+
     def set_compute_dtype(self, dtype):
         """torch.float32 (exact-fp32 MFMA, parity path), torch.bfloat16 (fast path, training and inference) or torch.float16
         (fp16 MFMA operands, inference only: the hard-setting evaluation of BASELINE.json configs[4])."""
@@ -288,7 +316,8 @@ class DetectionModel(nn.Module):
         if self.training and torch.is_grad_enabled():
             params = [p for p in self._grad_params]
             return _DetNetFunction.apply(x, self, *params)
-        return self._run_forward(x, training=self.training)
+        # (frozen BatchNorm under no_grad: the folded forward, nothing written -- not the statistics update of a plain train() forward)
+        return self._run_forward(x, training=self.training and not self._bn_frozen)
 
     def forward_levels(self, xs, lanes=None):
         """`[self(x) for x in xs]` for the pyramid levels of ONE image (evaluation.py:49-68 runs them one after the other), eval mode only,
@@ -376,8 +405,9 @@ class DetectionModel(nn.Module):
         # pickling / copy.deepcopy: the executor's derived state (ctypes pointer tables, workspaces, streams) belongs to THIS object's storages;
         # a copy rebuilds it on its first call
         d = dict(self.__dict__)
-        d.update(_table_key=None, _tables_frozen=False, _frozen_tensors=(), _frozen_version=-1, _ws=None, _ready_key=None, _lanes=[], _session_depth=0)
-        for k in ("_param_ptrs", "_grad_params", "_bn_modules"):
+        d.update(_table_key=None, _tables_frozen=False, _frozen_tensors=(), _frozen_version=-1, _ws=None, _ready_key=None, _lanes=[], _session_depth=0,
+                 _ws_mode=0)
+        for k in ("_param_ptrs", "_grad_params", "_bn_modules", "_bn_param_names"):
             d.pop(k, None)
         return d
 
@@ -429,6 +459,7 @@ class DetectionModel(nn.Module):
         self._grad_params = [pd[k] for k in self._grad_names]
         self._grad_numels = [pd[k].numel() for k in self._grad_names]
         self._bn_modules = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
+        self._bn_param_names = frozenset(f"{n}.{w}" for n, m in self.named_modules() if isinstance(m, nn.BatchNorm2d) for w in ("weight", "bias"))
         self._table_key = key
         self._frozen_tensors = [named[k] for k in names]
         self._frozen_version = _REGISTRATIONS[0]
@@ -528,9 +559,12 @@ class DetectionModel(nn.Module):
         N, _, H, W = x.shape
         H3, W3 = C.c_int(), C.c_int()
         lib().tf_detnet_out_shape(H, W, C.byref(H3), C.byref(W3))
-        nbytes = lib().tf_detnet_trunk_workspace_bytes(_trunk_arg(self.trunk), self.compute_dtype, N, H, W, self.num_out, int(training))
+        # the executor mode: 0 evaluation, 1 batch statistics, 2 frozen BatchNorm (the evaluation forward + what its backward needs)
+        mode = (_hip.TF_DETNET_FROZEN_BN if getattr(self, "_bn_frozen", False) else 1) if training else 0
+        nbytes = lib().tf_detnet_trunk_workspace_bytes(_trunk_arg(self.trunk), self.compute_dtype, N, H, W, self.num_out, mode)
         ws = self._workspace(x.device, nbytes)
         self._ws_generation += 1
+        self._ws_mode = mode
         self._ws_shape = (N, H, W)
         out = torch.empty(N, self.num_out, H3.value, W3.value, dtype=torch.float32, device=x.device)
         bn = self.model.bn1
@@ -543,11 +577,11 @@ class DetectionModel(nn.Module):
                 flags = TF_DETNET_WEIGHTS_READY
             self._ready_key = key
         with torch.cuda.device(x.device):
-            check(lib().tf_detnet_trunk_forward_ctx(_trunk_arg(self.trunk), self._ctx(x.device), int(self.single_stream), self.compute_dtype, int(training),
+            check(lib().tf_detnet_trunk_forward_ctx(_trunk_arg(self.trunk), self._ctx(x.device), int(self.single_stream), self.compute_dtype, mode,
                                                     ptr(x), N, H, W, self.num_out, self._param_ptrs, float(bn.eps), float(bn.momentum), ptr(out), ptr(ws),
                                                     ws.numel(), flags, stream()),
                   "tf_detnet_trunk_forward_ctx")
-        if training:
+        if mode == 1:                                                     # (frozen BatchNorm: the counters are not written either)
             if getattr(self, "_flat_nbt", None) is not None:
                 self._flat_nbt += 1                                      # all 94 counters in one launch
             else:
@@ -591,10 +625,12 @@ class DetectionModel(nn.Module):
         hooks.fn = C.cast(cb, C.c_void_p) if cb is not None else None
         hooks.user = getattr(self, "_grad_callback_user", None) if cb is not None else None
         hooks.single_stream = int(self.single_stream)
+        frozen = self._ws_mode == _hip.TF_DETNET_FROZEN_BN                # the graph the forward ran decides, not the flag at backward time
+        entry = lib().tf_detnet_trunk_backward_frozen_ctx if frozen else lib().tf_detnet_trunk_backward_ctx
         with torch.cuda.device(x.device):
-            check(lib().tf_detnet_trunk_backward_ctx(_trunk_arg(self.trunk), self._ctx(x.device), C.byref(hooks), self.compute_dtype, ptr(x), N, H, W,
-                                                     self.num_out, self._param_ptrs, table, ptr(gout), ptr(gflat), gflat.numel() * 4, ptr(self._ws),
-                                                     self._ws.numel(), stream()), "tf_detnet_trunk_backward_ctx")
+            check(entry(_trunk_arg(self.trunk), self._ctx(x.device), C.byref(hooks), self.compute_dtype, ptr(x), N, H, W,
+                        self.num_out, self._param_ptrs, table, ptr(gout), ptr(gflat), gflat.numel() * 4, ptr(self._ws),
+                        self._ws.numel(), stream()), "tf_detnet_trunk_backward_frozen_ctx" if frozen else "tf_detnet_trunk_backward_ctx")
         self._last_grad_flat = gflat
         if persistent:
             return gflat

@@ -317,6 +317,28 @@ def sgd_step(param, grad, momentum_buf, lr, momentum, weight_decay, grad_scale=1
                                 float(weight_decay), float(grad_scale), stream()), "tf_sgd_step")
 
 
+def sgd_step_segments(param, grad, momentum_buf, segments, lr, momentum, weight_decay, grad_scale=1.0):
+    """torch.optim.SGD.step over the element ranges `segments` ([(start, end)], ascending, disjoint) of three flat fp32 buffers;
+    everything outside the ranges is left untouched (tf_sgd_step_segments: parameters without a gradient, e.g. frozen BatchNorm vectors)."""
+    require_gpu(param, "sgd_step_segments")
+    assert param.dtype == grad.dtype == momentum_buf.dtype == torch.float32
+    assert param.is_contiguous() and grad.is_contiguous() and momentum_buf.is_contiguous()
+    n = param.numel()
+    assert grad.numel() == n and momentum_buf.numel() == n
+    segments = [(int(s), int(e)) for s, e in segments if e > s]
+    prev = 0
+    for s, e in segments:
+        if s < prev or e > n:
+            raise ValueError(f"sgd_step_segments: range ({s}, {e}) is out of order or outside the {n} elements of the buffers")
+        prev = e
+    if not segments:
+        return
+    table = (C.c_int64 * (2 * len(segments)))(*[v for se in segments for v in se])
+    with torch.cuda.device(param.device):
+        check(lib().tf_sgd_step_segments(ptr(param), ptr(grad), ptr(momentum_buf), table, len(segments), float(lr), float(momentum),
+                                         float(weight_decay), float(grad_scale), stream()), "tf_sgd_step_segments")
+
+
 # --------------------------------------------------------------------------- conv engine (used directly by the parity tests)
 def pack_weight(w_oihw, dtype, transpose=False, cols_pad=None):
     require_gpu(w_oihw, "pack_weight")
