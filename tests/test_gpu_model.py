@@ -592,6 +592,8 @@ img, cm, rm = (torch.from_numpy(g["b0_img"]).cuda(), torch.from_numpy(g["b0_cm"]
 m = DetectionModel(num_templates=25)
 m.load_state_dict(tame_init_(OracleDetectionModel(num_templates=25), 0).state_dict())
 m.set_compute_dtype(torch.bfloat16)
+if int(sys.argv[2]):
+    m.freeze_batchnorm()
 c = DetectionCriterion(25)
 keep = torch.ones(2, 25 * 16 * 16, dtype=torch.uint8); keep[:, 128:] = 0
 c.inject_sampling(keep, keep)
@@ -606,20 +608,22 @@ np.savez(sys.argv[1], g1=out[0], g2=out[1], lo=o, n=n)
 '''
 
 
+@pytest.mark.parametrize("frozen", [0, 1])
 @pytest.mark.parametrize("refuse", [0, 1])
-def test_refused_wgrad_group_falls_back_into_zeroed_gradients(tmp_path, refuse):
+def test_refused_wgrad_group_falls_back_into_zeroed_gradients(tmp_path, refuse, frozen):
     """when tf_conv2d_wgrad_group refuses a group (layer-3 width the all-taps plan does not take), the per-problem
     fallback accumulates with fp32 atomics -- into tensors the split flat-gradient memset skipped.  On the engine's PERSISTENT gradient the
     second step would then carry step one's values on top.  TINYFACES_DBG_GROUP_REFUSE=1 forces the refusal at any size (the knob is read
-    once per process, hence the subprocess): with lr = 0 the two steps' gradients must agree, and must equal the grouped kernels'."""
+    once per process, hence the subprocess): with lr = 0 the two steps' gradients must agree, and must equal the grouped kernels'.
+    frozen = 1: the same through the frozen-BatchNorm backward, which shares the group flush with the batch-statistics one."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = str(tmp_path / f"g{refuse}.npz")
+    out = str(tmp_path / f"g{refuse}{frozen}.npz")
     env = dict(os.environ)
     env.pop("TINYFACES_DBG_GROUP_REFUSE", None)
     if refuse:
         env["TINYFACES_DBG_GROUP_REFUSE"] = "1"
-    r = subprocess.run([sys.executable, "-c", f"ROOT = {root!r}\n" + _REFUSED_GROUP_SCRIPT, out], capture_output=True, text=True, timeout=600, env=env)
+    r = subprocess.run([sys.executable, "-c", f"ROOT = {root!r}\n" + _REFUSED_GROUP_SCRIPT, out, str(frozen)], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     z = np.load(out)
     g1, g2, lo, n = z["g1"], z["g2"], int(z["lo"]), int(z["n"])
@@ -628,7 +632,7 @@ def test_refused_wgrad_group_falls_back_into_zeroed_gradients(tmp_path, refuse):
     cos = float(np.dot(a, b) / (np.linalg.norm(a) * np.linalg.norm(b)))
     ratio = float(np.linalg.norm(b) / np.linalg.norm(a))
     cos_all = float(np.dot(g1, g2) / (np.linalg.norm(g1) * np.linalg.norm(g2)))
-    report(f"refused_group[refuse={refuse}]", cos_layer3_conv2=cos, norm_ratio=ratio, cos_flat=cos_all)
+    report(f"refused_group[refuse={refuse},frozen={frozen}]", cos_layer3_conv2=cos, norm_ratio=ratio, cos_flat=cos_all)
     # the same function twice.  Not bit-equal: the fp32 atomics of the BN statistic rows land in another order, and on this 2-image
     # fixture (batch statistics over <= 512 pixels) that flips bf16 roundings all the way up -- a layer-3 3x3 gradient repeats itself to
     # cosine 0.978 with or without the refusal.  A gradient accumulated onto the previous step's would have norm ratio 2.

@@ -161,11 +161,7 @@ const Arch* find_arch(const int* blocks) {
 // r4: the weight gradients of the identity bottlenecks of layer 3 (22 blocks of identical shape) are differentiated in GROUPS of up to
 // this many bottlenecks per launch (tf_conv2d_wgrad_group: full-K tiles, no split-K / atomics / partial tiles); their dY operands then
 // live in per-block buffers instead of the two parity sets.  TINYFACES_WGRAD_GROUP=0: the per-block launches of rounds 1-3.
-inline int wgrad_group_size() {
-  const int g = tf::tuning().wgrad_group;
-  return g;
-}
-inline bool wgrad_group_mode(int dtype, int training) { return training && dtype == TF_BF16 && wgrad_group_size() > 0; }
+inline bool wgrad_group_mode(int dtype, int training) { return training && dtype == TF_BF16 && tf::tuning().wgrad_group > 0; }
 
 inline int down2(int n) { return (n - 1) / 2 + 1; }   // every stride-2 stage of the trunk: ceil(n/2)
 inline size_t esize(int dtype) { return dtype == TF_F32 ? 4 : 2; }
@@ -376,9 +372,6 @@ struct Ctx {
   std::vector<tf_pack_job> jobs;
   std::vector<tf_pack2_job> jobs2;
   hipStream_t side = nullptr;                 // weight gradients run here, concurrently with the data-gradient chain
-  hipStream_t gside = nullptr;                // r4: the GROUPED weight gradients of layer 3 (two launches of 150-300 us per group): a queue of their own, so that the
-                                              // per-block gradients of layer 3.0 / layers 1-2 -- whose completion the chain waits for two blocks later (parity buffers) --
-                                              // do not queue up behind a group
   std::vector<hipEvent_t>* events = nullptr; size_t ev_next = 0;
   hipEvent_t next_event() {
     if (ev_next == events->size()) { hipEvent_t e; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { chk(TF_ERR_LAUNCH); return nullptr; } events->push_back(e); }
@@ -391,15 +384,12 @@ struct Ctx {
   hipEvent_t pending = nullptr;
   static bool kernel_events() { return !tf::tuning().fork_by_record; }
   void arm_fork() { if (!side || !kernel_events()) return; pending = next_event(); if (pending) tf::set_next_stop_event(pending); }
-  void fork_armed(hipStream_t to = nullptr) {
+  void fork_armed() {
     if (!side) return;
-    if (!to) to = side;
     if (tf::take_next_stop_event()) pending = nullptr;     // armed but no kernel took it (the producer refused its arguments): plain fork
-    if (pending) { (void)hipStreamWaitEvent(to, pending, 0); pending = nullptr; }
-    else { hipEvent_t e = next_event(); if (e) { (void)hipEventRecord(e, stream); (void)hipStreamWaitEvent(to, e, 0); } }
+    if (pending) { (void)hipStreamWaitEvent(side, pending, 0); pending = nullptr; }
+    else fork();
   }
-  hipStream_t gstream() const { return gside ? gside : wstream(); }
-  hipEvent_t mark(hipStream_t s) { if (!side || !s) return nullptr; hipEvent_t e = next_event(); if (e) (void)hipEventRecord(e, s); return e; }
   // everything enqueued on `stream` so far becomes a dependency of what is enqueued on `side` next
   void fork() { if (!side) return; hipEvent_t e = next_event(); if (e) { (void)hipEventRecord(e, stream); (void)hipStreamWaitEvent(side, e, 0); } }
   hipEvent_t mark_side() { if (!side) return nullptr; hipEvent_t e = next_event(); if (e) (void)hipEventRecord(e, side); return e; }
@@ -445,15 +435,15 @@ void pack2(Ctx& c, const ConvUnit& u, int cout, void* out, void* out_t, int cin_
   c.jobs2.push_back(j);
 }
 
-// BN after a conv: eval -> fold running stats; train -> finalize batch partials (+ running update)
-void bn_forward(Ctx& c, const ConvUnit& u, int C, BnBuf& b, bool training, const tf_conv_args* conv, float* partial, float count, float eps,
-                float mom) {
-  if (!training) {
-    if (!c.skip_fold) c.chk(tf_bn_fold(c.P(u.gamma), c.P(u.beta), c.P(u.rmean), c.P(u.rvar), eps, C, b.scale, b.shift, c.stream));
-  } else {
-    c.chk(tf_bn_finalize(partial, tf_conv_mtiles(conv), conv->ldy, C, count, c.P(u.gamma), c.P(u.beta), eps, mom, b.scale, b.shift, b.mean,
-                         b.invstd, (float*)c.params[u.rmean], (float*)c.params[u.rvar], 1, c.stream));
-  }
+// BN as a constant affine (evaluation and frozen BN): fold the running statistics into scale / shift, unless the arena already holds them
+void bn_fold(Ctx& c, const ConvUnit& u, int C, BnBuf& b, float eps) {
+  if (!c.skip_fold) c.chk(tf_bn_fold(c.P(u.gamma), c.P(u.beta), c.P(u.rmean), c.P(u.rvar), eps, C, b.scale, b.shift, c.stream));
+}
+// BN over batch statistics where no consumer finalizes in-kernel (the stem; every BN of the unfolded flow): finalize the `rows` partial
+// rows (leading dimension ld) its producer left (+ running update)
+void bn_finalize(Ctx& c, const ConvUnit& u, int C, BnBuf& b, const float* partial, int rows, int ld, float count, float eps, float mom) {
+  c.chk(tf_bn_finalize(partial, rows, ld, C, count, c.P(u.gamma), c.P(u.beta), eps, mom, b.scale, b.shift, b.mean, b.invstd,
+                       (float*)c.params[u.rmean], (float*)c.params[u.rvar], 1, c.stream));
 }
 
 // r3: the conv that produces a BN's statistics subtracts the BN's running mean before summing (sum (x - s), sum (x - s)^2) and records
@@ -543,45 +533,27 @@ extern "C" size_t tf_detnet_trunk_param_region_bytes(const int* blocks, int dtyp
 }
 extern "C" size_t tf_detnet_param_region_bytes(int dtype, int nout, int training) { return tf_detnet_trunk_param_region_bytes(nullptr, dtype, nout, training); }
 
-// The executor's second stream (weight gradients of the backward pass; r3: the packing of the layer-3 weights beside the start of the
-// forward pass), one per device, created on first use at the DEFAULT priority.
-// Rounds 1-2 created it at the LOWEST priority ("the weight gradients are off the critical chain"; +0.4 % on the step, A/B r3: 1135.7 vs
-// 1131.6 img/s).  r3 found what that costs as soon as the process has a few more busy queues: with three more streams carrying a token
-// kernel per step -- or with RCCL in the process and its collectives overlapping the backward pass, i.e. the data-parallel path -- the
-// kernels of BOTH queues stretch ~1.6x and the step takes 16.7-17.6 ms instead of 10.6 (profiles/r03_stream_priority.txt; GPU_MAX_HW_QUEUES,
-// creation order and the number of streams of our own made no difference, the priority does).  The round-2 CU-mask experiment
-// (hipExtStreamCreateWithCUMask: 603 img/s whatever the mask) looked the same.  TINYFACES_SIDE_PRIO_LOW=1 brings the low priority back.
-// ---- r4: the executor's own state lives in an explicit CONTEXT (tf_detnet_ctx): the second stream of the device it was created on (weight
-// gradients of the backward pass; the packing of the layer-3 weights beside the start of the forward pass), the optional group stream, the
-// pool of fork / join events, and -- per backward call -- the caller's gradient-ready hooks (tf_detnet_hooks).  Rounds 1-3 kept all of this in
-// process-wide statics behind an ABI documented as stateless (events created on whichever device ran
-// first).  The entry points without a context (tf_detnet_forward / tf_detnet_backward / tf_detnet_set_*) remain as wrappers over ONE
-// default context per device and thread-unsafe process-wide hooks, for callers that drive one model from one thread.
-// The second stream is created at the DEFAULT priority.  Rounds 1-2 created it at the LOWEST priority ("the weight gradients are off the
-// critical chain"; +0.4 % on the step); r3 found what that costs as soon as the process has a few more busy queues -- RCCL with its
-// collectives overlapping the backward pass, i.e. the data-parallel path -- the kernels of BOTH queues stretch ~1.6x
-// (profiles/r03_stream_priority.txt).  TINYFACES_SIDE_PRIO_LOW=1 brings the low priority back.
+// The executor's own state lives in an explicit CONTEXT (tf_detnet_ctx): the second stream of the device it was created on (weight
+// gradients of the backward pass; the packing of the layer-3 weights beside the start of the forward pass), the pool of fork / join
+// events, and -- per backward call -- the caller's gradient-ready hooks (tf_detnet_hooks).  The entry points without a context
+// (tf_detnet_forward / tf_detnet_backward / tf_detnet_set_*) remain as wrappers over ONE default context per device and thread-unsafe
+// process-wide hooks, for callers that drive one model from one thread.
+// The second stream is created at the DEFAULT priority: at the lowest one the kernels of BOTH queues stretch ~1.6x as soon as the process
+// has a few more busy queues -- RCCL with its collectives overlapping the backward pass, i.e. the data-parallel path
+// (profiles/r03_stream_priority.txt).
 struct tf_detnet_ctx {
   int device = -1;
-  hipStream_t side = nullptr, gside = nullptr;
-  hipEvent_t pack_fork = nullptr, pack_join = nullptr, pack_join0 = nullptr;
+  hipStream_t side = nullptr;
+  hipEvent_t pack_fork = nullptr, pack_join = nullptr;
   std::vector<hipEvent_t> events;
 };
 namespace {
-hipStream_t make_stream() {
-  hipStream_t s = nullptr;
-  int least = 0, greatest = 0;
-  const bool low_prio = tf::tuning().side_prio_low;      // A/B knob (the default of rounds 1-2)
-  if (!low_prio || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
-      hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least) != hipSuccess) {
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) s = nullptr;
-  }
-  return s;
+// the stream and the events are created lazily, on the device the context belongs to (the caller has made it current: the binding wraps
+// every call in torch.cuda.device(x.device))
+hipStream_t ctx_side(tf_detnet_ctx* x) {
+  if (x && !x->side && hipStreamCreateWithFlags(&x->side, hipStreamNonBlocking) != hipSuccess) x->side = nullptr;
+  return x ? x->side : nullptr;
 }
-// streams and events are created lazily, on the device the context belongs to (the caller has made it current: the binding wraps every
-// call in torch.cuda.device(x.device))
-hipStream_t ctx_side(tf_detnet_ctx* x) { if (x && !x->side) x->side = make_stream(); return x ? x->side : nullptr; }
-hipStream_t ctx_gside(tf_detnet_ctx* x) { if (x && !x->gside) x->gside = make_stream(); return x ? x->gside : nullptr; }
 tf_detnet_ctx* default_ctx() {            // one per device: what the context-free entry points use
   static tf_detnet_ctx* per_dev[64] = {};
   int dev = 0;
@@ -601,13 +573,10 @@ extern "C" int tf_detnet_ctx_create(tf_detnet_ctx** out) {
 extern "C" int tf_detnet_ctx_destroy(tf_detnet_ctx* x) {
   if (!x) return TF_OK;
   if (x->side) (void)hipStreamSynchronize(x->side);
-  if (x->gside) (void)hipStreamSynchronize(x->gside);
   for (hipEvent_t e : x->events) (void)hipEventDestroy(e);
   if (x->pack_fork) (void)hipEventDestroy(x->pack_fork);
   if (x->pack_join) (void)hipEventDestroy(x->pack_join);
-  if (x->pack_join0) (void)hipEventDestroy(x->pack_join0);
   if (x->side) (void)hipStreamDestroy(x->side);
-  if (x->gside) (void)hipStreamDestroy(x->gside);
   delete x;
   return TF_OK;
 }
@@ -645,47 +614,34 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
   if (tr && hipMemsetAsync(P.stat_fwd, 0, (size_t)((char*)P.partial - (char*)P.stat_fwd) + (size_t)TF_STAT_ROWS * 3 * 1024 * 4, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
   // ---- stem: conv1 (direct, or im2col + GEMM) (+BN+ReLU) + maxpool
   const int M1 = N * P.H1 * P.W1;
-  // r3 experiment, NEGATIVE, kept behind TINYFACES_PACK_SIDE=1: the weight re-packing of a training step (three launches, ~170 us: 111 MB
-  // of masters read, 2 x 55 MB written) on a second stream BESIDE the stem's im2col (~130 us) -- both are HBM-bound, side by side they
-  // take as long as back to back and the fork / join events cost a little: 1153 / 1153 img/s against 1161 / 1159 inline (A/B on one box).
-  bool pack_joined = false;
-  hipStream_t g_pack_stream = nullptr;             // = the context's second stream: idle during the forward pass, no further hardware queue
-  const bool pack_side_env = tf::tuning().pack_side;
-  // r3, second form: only the weights of layer 3 and of the heads (62 % of the bytes) go to the second stream, forked at the top of the step
-  // and joined in front of the first layer-3 bottleneck: they are packed beside the stem and layers 1-2, whose launches are latency-bound
-  // at bs = 12, instead of in front of them.  TINYFACES_PACK_SPLIT_OFF=1: everything inline.
-  const bool pack_split_off = tf::tuning().pack_split_off;
-  const bool single_env = tf::tuning().single_stream;
-  const bool pack_split = step && !ready && !pack_side_env && !pack_split_off && !single_env && !single_stream && xctx;
-  bool pack_side = step && !ready && (pack_side_env || pack_split);
-  if (pack_side) {
-    g_pack_stream = ctx_side(xctx);
-    if (g_pack_stream && !xctx->pack_fork && (hipEventCreateWithFlags(&xctx->pack_fork, hipEventDisableTiming) != hipSuccess ||
-                                              hipEventCreateWithFlags(&xctx->pack_join, hipEventDisableTiming) != hipSuccess ||
-                                              hipEventCreateWithFlags(&xctx->pack_join0, hipEventDisableTiming) != hipSuccess)) g_pack_stream = nullptr;
+  // r3: the weights of layer 3 and of the heads (62 % of the bytes) are packed on the context's second stream (idle during the forward pass:
+  // no further hardware queue), forked at the top of the step and joined in front of the first layer-3 bottleneck: beside the stem and
+  // layers 1-2, whose launches are latency-bound at bs = 12, instead of in front of them.  TINYFACES_PACK_SPLIT_OFF=1, TINYFACES_SINGLE_STREAM=1
+  // or `single_stream`: everything inline.
+  hipStream_t pack_stream = nullptr;
+  if (step && !ready && !tf::tuning().pack_split_off && !tf::tuning().single_stream && !single_stream && xctx) {
+    pack_stream = ctx_side(xctx);
+    if (pack_stream && !xctx->pack_fork && (hipEventCreateWithFlags(&xctx->pack_fork, hipEventDisableTiming) != hipSuccess ||
+                                            hipEventCreateWithFlags(&xctx->pack_join, hipEventDisableTiming) != hipSuccess)) pack_stream = nullptr;
   }
-  if (!g_pack_stream) pack_side = false;
+  const bool pack_side = pack_stream != nullptr;
+  bool pack_joined = false;
   const bool stem_direct = stem_direct_mode(dtype, tr, fused);
-  // r4 experiment, NEGATIVE, opt-in (TINYFACES_PACK_FORK_LATE=1): the layer-3 packing forked BEHIND the stem conv instead of at the top of the
-  // step (beside it the conv takes 99 instead of 56 us): 1273.0 / 1274.2 against 1276.1 / 1276.1 img/s -- the packing then overlaps layer 1
-  const bool fork_late_env = tf::tuning().pack_fork_late;
-  const bool pack_late = pack_side && pack_split && stem_direct && fork_late_env;
   if (fz) {
     // frozen BN: every fold first -- the scales of bn3 / the downsample BN ride in the transposed operands packed below (possibly on the
     // second stream), and the backward pass reads all of them.  Same kernel, same values as the evaluation graph's folds.
-    auto fold = [&](const ConvUnit& u, int C, BnBuf& b) { c.chk(tf_bn_fold(c.P(u.gamma), c.P(u.beta), c.P(u.rmean), c.P(u.rvar), eps, C, b.scale, b.shift, c.stream)); };
-    fold(A.stem, 64, P.bn_stem);
+    bn_fold(c, A.stem, 64, P.bn_stem, eps);
     for (size_t i = 0; i < A.blocks.size(); ++i) {
       const Block& B = A.blocks[i];
       Plan::Blk& b = P.blk[i];
-      fold(B.c1, B.planes, b.b1); fold(B.c2, B.planes, b.b2); fold(B.c3, B.planes * 4, b.b3);
-      if (B.has_ds) fold(B.ds, B.planes * 4, b.bd);
+      bn_fold(c, B.c1, B.planes, b.b1, eps); bn_fold(c, B.c2, B.planes, b.b2, eps); bn_fold(c, B.c3, B.planes * 4, b.b3, eps);
+      if (B.has_ds) bn_fold(c, B.ds, B.planes * 4, b.bd, eps);
     }
     c.skip_fold = true;
     hipLaunchKernelGGL(fill_const_kernel, dim3((2 * kConstC + 255) / 256), dim3(256), 0, c.stream, P.c_one, P.c_zero, kConstC);
   }
-  if (pack_side && !pack_late) {           // everything enqueued so far (the previous step's SGD: the masters) precedes the packing
-    if (hipEventRecord(xctx->pack_fork, c.stream) != hipSuccess || hipStreamWaitEvent(g_pack_stream, xctx->pack_fork, 0) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+  if (pack_side) {                         // everything enqueued so far (the previous step's SGD: the masters) precedes the packing
+    if (hipEventRecord(xctx->pack_fork, c.stream) != hipSuccess || hipStreamWaitEvent(pack_stream, xctx->pack_fork, 0) != hipSuccess) c.chk(TF_ERR_LAUNCH);
   }
   if (!stem_direct) c.chk(tf_stem_im2col(x, N, H, W, dtype, P.col, kStemK, c.stream));
   // ---- every weight of the pass re-packed from the fp32 master copy in two launches
@@ -695,17 +651,7 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
   for (size_t i = 0; i < A.blocks.size(); ++i) {
     const Block& B = A.blocks[i];
     Plan::Blk& b = P.blk[i];
-    // stem + layers 1-2 are needed first: inline, behind the im2col.  r4 experiment, NEUTRAL (1277 / 1281 against 1279 / 1275 img/s), opt-in
-    // (TINYFACES_PACK_FIRST_SIDE=1): packed on the second stream as well, first in its order, beside the stem's im2col, the caller's
-    // stream waiting for them in front of the stem conv
-    if (pack_side && pack_split && (int)i == A.layer_end[1] + 1) {
-      const bool first_inline = !tf::tuning().pack_first_side;
-      if (first_inline) c.flush_packs();
-      else {
-        c.flush_packs(g_pack_stream);
-        if (hipEventRecord(xctx->pack_join0, g_pack_stream) != hipSuccess || hipStreamWaitEvent(c.stream, xctx->pack_join0, 0) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-      }
-    }
+    if (pack_side && (int)i == A.layer_end[1] + 1) c.flush_packs();       // stem + layers 1-2 are needed first: inline, behind the im2col
     pack2(c, B.c1, B.planes, b.w1, b.w1t); pack2(c, B.c2, B.planes, b.w2, b.w2t);
     pack2(c, B.c3, B.planes * 4, b.w3, b.w3t, 0, 0, 0, fz ? b.b3.scale : nullptr);       // frozen BN: (W3 diag(s3))^T
     if (B.has_ds) pack2(c, B.ds, B.planes * 4, b.wd, b.wdt, 0, 0, 0, fz ? b.bd.scale : nullptr);
@@ -718,22 +664,16 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
     j.src = c.P(A.head4.w); j.dst = P.w_h4; j.dst_t = P.w_h4t; j.cin = 1024; j.cols_pad = 1024; j.rows_pad_t = 1024;
     c.jobs2.push_back(j);
   }
-  if (!pack_late) {
-    c.flush_packs(pack_side ? g_pack_stream : nullptr);
-    if (pack_side) {
-      if (hipEventRecord(xctx->pack_join, g_pack_stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-      if (!pack_split && hipStreamWaitEvent(c.stream, xctx->pack_join, 0) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-    }
-  }
+  c.flush_packs(pack_stream);
+  if (pack_side && hipEventRecord(xctx->pack_join, pack_stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
   }
   if (stem_direct) {
     if (tr) {
       int rows = 0;
       c.chk(tf_stem_conv(dtype, x, N, H, W, P.wstem, kStemK, P.cstem, TF_EPI_STATS, nullptr, nullptr, P.partial, &rows, c.stream));
-      c.chk(tf_bn_finalize(P.partial, rows, 64, 64, (float)M1, c.P(A.stem.gamma), c.P(A.stem.beta), eps, mom, P.bn_stem.scale, P.bn_stem.shift,
-                           P.bn_stem.mean, P.bn_stem.invstd, (float*)c.params[A.stem.rmean], (float*)c.params[A.stem.rvar], 1, c.stream));
+      bn_finalize(c, A.stem, 64, P.bn_stem, P.partial, rows, 64, (float)M1, eps, mom);
     } else {
-      bn_forward(c, A.stem, 64, P.bn_stem, false, nullptr, nullptr, 0, eps, mom);
+      bn_fold(c, A.stem, 64, P.bn_stem, eps);
       c.chk(tf_stem_conv(dtype, x, N, H, W, P.wstem, kStemK, P.cstem, TF_EPI_AFFINE | TF_EPI_RELU, P.bn_stem.scale, P.bn_stem.shift, nullptr, nullptr,
                          c.stream));
     }
@@ -742,16 +682,11 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
     a.alg_k = 147;                                  // 7 x 7 x 3 taps*channels, zero-padded to kStemK for the 64-deep K stages
     if (tr) { a.epi = TF_EPI_STATS; a.stat_out = P.partial; }
     else {
-      bn_forward(c, A.stem, 64, P.bn_stem, false, nullptr, nullptr, 0, eps, mom);
+      bn_fold(c, A.stem, 64, P.bn_stem, eps);
       a.epi = TF_EPI_AFFINE | TF_EPI_RELU; a.epi_scale = P.bn_stem.scale; a.epi_shift = P.bn_stem.shift;
     }
     c.chk(tf_conv2d(&a, c.stream));
-    if (tr) bn_forward(c, A.stem, 64, P.bn_stem, true, &a, P.partial, (float)M1, eps, mom);
-  }
-  if (pack_late && !ready) {               // the layer-3 + head packing: forked behind the stem conv, joined in front of layer 3
-    if (hipEventRecord(xctx->pack_fork, c.stream) != hipSuccess || hipStreamWaitEvent(g_pack_stream, xctx->pack_fork, 0) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-    c.flush_packs(g_pack_stream);
-    if (hipEventRecord(xctx->pack_join, g_pack_stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+    if (tr) bn_finalize(c, A.stem, 64, P.bn_stem, P.partial, tf_conv_mtiles(&a), a.ldy, (float)M1, eps, mom);
   }
   c.chk(tf_maxpool_fwd(dtype, P.cstem, N, P.H1, P.W1, 64, tr ? P.bn_stem.scale : nullptr, tr ? P.bn_stem.shift : nullptr, P.pool,
                        step ? P.pool_idx : nullptr, c.stream));
@@ -764,11 +699,11 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
     Plan::Blk& b = P.blk[i];
     const int pl = B.planes, c4 = pl * 4;
     const int Min = N * b.Hin * b.Win, Mout = N * b.Hout * b.Wout;
-    if (pack_side && pack_split && (int)i == A.layer_end[1] + 1) { pack_joined = true; if (hipStreamWaitEvent(c.stream, xctx->pack_join, 0) != hipSuccess) c.chk(TF_ERR_LAUNCH); }
+    if (pack_side && (int)i == A.layer_end[1] + 1) { pack_joined = true; if (hipStreamWaitEvent(c.stream, xctx->pack_join, 0) != hipSuccess) c.chk(TF_ERR_LAUNCH); }
     // conv1 1x1
     conv_fill(a, dtype, 0, N, b.Hin, b.Win, B.cin, b.Hin, b.Win, pl, 1, 1, 0, pl, yin, b.w1, b.c1);
     if (tr) { a.epi = TF_EPI_STATS; a.stat_out = fused ? b.b1.fst : P.partial; stat_shift(a, c, B.c1, b.b1, fused); }
-    else { bn_forward(c, B.c1, pl, b.b1, false, nullptr, nullptr, 0, eps, mom); a.epi = TF_EPI_AFFINE | TF_EPI_RELU; a.epi_scale = b.b1.scale; a.epi_shift = b.b1.shift; }
+    else { bn_fold(c, B.c1, pl, b.b1, eps); a.epi = TF_EPI_AFFINE | TF_EPI_RELU; a.epi_scale = b.b1.scale; a.epi_shift = b.b1.shift; }
     if (tail_deferred) {
       // r5: the PREVIOUS bottleneck's  y = relu(bn3(c3) + residual)  rides on this conv's operand path (tf_conv2d_bnfwd, conv_pwx.hip): the
       // pixel stages are transformed once in LDS on their way to the MFMAs and y (= yin: three more readers) is the launch's side output
@@ -791,22 +726,22 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
       const tf_bn_fwd_desc d = fwd_desc(c, B.c1, b.b1);
       c.chk(tf_bn_relu_fused(dtype, b.c1, &d, srows, Min, pl, (float)Min, eps, mom, b.a1, c.stream));
     } else if (tr) {
-      bn_forward(c, B.c1, pl, b.b1, true, &a, P.partial, (float)Min, eps, mom);
+      bn_finalize(c, B.c1, pl, b.b1, P.partial, tf_conv_mtiles(&a), a.ldy, (float)Min, eps, mom);
       c.chk(tf_bn_relu(dtype, b.c1, b.b1.scale, b.b1.shift, Min, pl, b.a1, c.stream));
     }
     // conv2 3x3 (stride here)
     conv_fill(a, dtype, 0, N, b.Hin, b.Win, pl, b.Hout, b.Wout, pl, 3, B.stride, 1, pl, tr ? b.a1 : b.c1, b.w2, b.c2);
     if (tr) { a.epi = TF_EPI_STATS; a.stat_out = fused ? b.b2.fst : P.partial; stat_shift(a, c, B.c2, b.b2, fused); }
-    else { bn_forward(c, B.c2, pl, b.b2, false, nullptr, nullptr, 0, eps, mom); a.epi = TF_EPI_AFFINE | TF_EPI_RELU; a.epi_scale = b.b2.scale; a.epi_shift = b.b2.shift; }
+    else { bn_fold(c, B.c2, pl, b.b2, eps); a.epi = TF_EPI_AFFINE | TF_EPI_RELU; a.epi_scale = b.b2.scale; a.epi_shift = b.b2.shift; }
     c.chk(tf_conv2d(&a, c.stream));
-    if (tr && !fused) bn_forward(c, B.c2, pl, b.b2, true, &a, P.partial, (float)Mout, eps, mom);
+    if (tr && !fused) bn_finalize(c, B.c2, pl, b.b2, P.partial, tf_conv_mtiles(&a), a.ldy, (float)Mout, eps, mom);
     // downsample 1x1 (stride)
     if (B.has_ds) {
       conv_fill(a, dtype, 0, N, b.Hin, b.Win, B.cin, b.Hout, b.Wout, c4, 1, B.stride, 0, c4, yin, b.wd, b.d);
       if (tr) { a.epi = TF_EPI_STATS; a.stat_out = fused ? b.bd.fst : P.partial; stat_shift(a, c, B.ds, b.bd, fused); }
-      else { bn_forward(c, B.ds, c4, b.bd, false, nullptr, nullptr, 0, eps, mom); a.epi = TF_EPI_AFFINE; a.epi_scale = b.bd.scale; a.epi_shift = b.bd.shift; }
+      else { bn_fold(c, B.ds, c4, b.bd, eps); a.epi = TF_EPI_AFFINE; a.epi_scale = b.bd.scale; a.epi_shift = b.bd.shift; }
       c.chk(tf_conv2d(&a, c.stream));
-      if (tr && !fused) bn_forward(c, B.ds, c4, b.bd, true, &a, P.partial, (float)Mout, eps, mom);
+      if (tr && !fused) bn_finalize(c, B.ds, c4, b.bd, P.partial, tf_conv_mtiles(&a), a.ldy, (float)Mout, eps, mom);
     }
     // a2 = relu(bn2(c2)): a launch of its own.  Folding it into conv3 (r3, tf_conv_args.bnf: the ring-less pointwise kernel activates its
     // pixel tile in LDS and writes a2 for the weight gradient; bit-identical, tests/test_gpu_conv.py) removes 33 launches from the
@@ -827,7 +762,7 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
     if (bnf) { a.bnf = &d2; a.bnf_out = b.a2; a.bnf_rows = srows; a.bnf_count = (float)Mout; a.bnf_eps = eps; a.bnf_momentum = mom; }
     if (tr) { a.epi = TF_EPI_STATS; a.stat_out = fused ? b.b3.fst : P.partial; stat_shift(a, c, B.c3, b.b3, fused); }
     else {
-      bn_forward(c, B.c3, c4, b.b3, false, nullptr, nullptr, 0, eps, mom);
+      bn_fold(c, B.c3, c4, b.b3, eps);
       a.epi = TF_EPI_AFFINE | TF_EPI_RES | TF_EPI_RELU; a.epi_scale = b.b3.scale; a.epi_shift = b.b3.shift; a.aux = B.has_ds ? b.d : yin;
     }
     c.chk(tf_conv2d(&a, c.stream));
@@ -848,7 +783,7 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
       c.chk(tf_bn_add_relu_fused(dtype, b.c3, &d3, B.has_ds ? b.d : yin, B.has_ds ? &dd : nullptr, srows, Mout, c4, (float)Mout, eps, mom, b.y,
                                  c.stream));
     } else if (tr) {
-      bn_forward(c, B.c3, c4, b.b3, true, &a, P.partial, (float)Mout, eps, mom);
+      bn_finalize(c, B.c3, c4, b.b3, P.partial, tf_conv_mtiles(&a), a.ldy, (float)Mout, eps, mom);
       c.chk(tf_bn_add_relu(dtype, b.c3, b.b3.scale, b.b3.shift, B.has_ds ? b.d : yin, B.has_ds ? b.bd.scale : nullptr,
                            B.has_ds ? b.bd.shift : nullptr, Mout, c4, b.y, c.stream));
     }
@@ -868,7 +803,7 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
   a.epi = TF_EPI_AFFINE; a.epi_scale = P.ones; a.epi_shift = P.hbias4; a.alg_n = nout;
   c.chk(tf_conv2d(&a, c.stream));
   c.chk(tf_upsample_add_crop(dtype, P.s3, P.s4, P.wup_diag, N, nout, kHeadLd, P.H3, P.W3, P.H4, P.W4, out, c.stream));
-  if (pack_side && pack_split && !pack_joined) (void)hipStreamWaitEvent(c.stream, xctx->pack_join, 0);      // (never leave the caller's stream un-joined)
+  if (pack_side && !pack_joined) (void)hipStreamWaitEvent(c.stream, xctx->pack_join, 0);      // (never leave the caller's stream un-joined)
   if (hipGetLastError() != hipSuccess && c.rc == TF_OK) c.rc = TF_ERR_LAUNCH;
   return c.rc;
 }
@@ -903,14 +838,16 @@ tf_wgrad_args wgrad_args(const Ctx& c, const ConvUnit& u, int cout, int N, int H
   return w;
 }
 
+// one weight gradient on the weight-gradient stream.  row_scale (frozen BN, pointwise convs): dW[co] *= the folded scale of the BN behind the conv
 void wgrad(Ctx& c, const ConvUnit& u, int cout, int N, int H, int W, int OH, int OW, const void* x, int ldx, const void* dy, int lddy,
-           const BnBuf* pro, int cin_override = 0, int k_override = 0, int dw_ld = 0, float* packed_scratch = nullptr, size_t scratch_floats = 0) {
+           const float* row_scale = nullptr, int cin_override = 0, int k_override = 0, int dw_ld = 0, float* packed_scratch = nullptr,
+           size_t scratch_floats = 0) {
   // timing-ablation knob (RESULTS INVALID): the step without any weight gradient = what the data-gradient chain costs when it owns the GPU
   const bool skip = tf::tuning().dbg_skip_wgrad;
   if (skip) return;
   const int cin = cin_override ? cin_override : u.cin, k = k_override ? k_override : u.k;
   tf_wgrad_args w = wgrad_args(c, u, cout, N, H, W, OH, OW, x, ldx, dy, lddy, cin_override, k_override, dw_ld);
-  if (pro) { w.pro_scale = pro->scale; w.pro_shift = pro->shift; w.pro_relu = 1; }
+  w.row_scale = row_scale;
   if (k > 1 && packed_scratch && c.grads_zeroed) {
     // 3x3 / stride 1: the all-taps kernel sums its split-K slices through the scratch straight into the (already zeroed) OIHW
     // gradient: no memset, no atomics, no transposing copy
@@ -960,42 +897,240 @@ static void record_grad_events(const tf_detnet_hooks* h, int block, hipStream_t 
     }
   if (registered && h->fn) h->fn(block, (void*)s, h->user);
 }
-static bool grad_event_registered(const tf_detnet_hooks* h, int block) {
-  if (!h) return false;
-  for (int k = 0; k < h->n; ++k) if (h->blocks[k] == block) return true;
-  return false;
-}
 // 1 = weight gradients on a second stream (default), 0 = everything on the caller's stream (A/B + race tests)
 extern "C" int tf_detnet_set_dual_stream(int on) { g_force_single = !on; return TF_OK; }
 
-extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x, int N,
-                                            int H, int W, int nout, void* const* params, void* const* grads, const float* gout, void* grad_flat,
-                                            size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream_) {
-  const Arch* Ap = find_arch(blocks);
-  if (!Ap) return TF_ERR_UNSUPPORTED;
+// ---- the stages the two backward passes (batch statistics below, frozen BN behind it) share: everything that is not BN mathematics
+namespace {
+
+// entry: the trunk, the plan of the forward that ran (`training` = 1 or TF_DETNET_FROZEN_BN) and the launch context with its second stream
+int open_backward(const int* blocks, tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x, int N, int H, int W, int nout,
+                  void* const* params, void* const* grads, const float* gout, void* ws, size_t ws_bytes, void* stream_, int training,
+                  const Arch*& A, Plan& P, Ctx& c) {
+  A = find_arch(blocks);
+  if (!A) return TF_ERR_UNSUPPORTED;
   if (!x || !params || !grads || !gout || !ws) return TF_ERR_ARG;
   if (hooks && (hooks->n < 0 || (hooks->n > 0 && !hooks->blocks))) return TF_ERR_ARG;
   if (!xctx) xctx = default_ctx();
   if (dtype != TF_BF16 && dtype != TF_F32) return TF_ERR_UNSUPPORTED;
-  const Arch& A = *Ap;
-  Plan P; Arena ar(ws, ws_bytes);
-  build_plan(A, P, ar, dtype, N, H, W, nout, 1);
+  Arena ar(ws, ws_bytes);
+  build_plan(*A, P, ar, dtype, N, H, W, nout, training);
   if (!ar.ok) return TF_ERR_WORKSPACE;
-  Ctx c{dtype, (hipStream_t)stream_, params, grads, TF_OK};   // (grads_zeroed / jobs default-initialised)
-  const bool g_single_env = tf::tuning().single_stream;
-  if (!g_single_env && !(hooks && hooks->single_stream) && xctx) {
-    hipStream_t g_side = ctx_side(xctx);
-    c.side = g_side; c.events = &xctx->events;
-    // r4, measured NEGATIVE, opt-in (TINYFACES_GROUP_STREAM=1): the grouped launches on a third queue, so that the per-block gradients of
-    // layer 3.0 / layers 1-2 do not queue up behind a group: 1170 / 1164 img/s against 1177 / 1181 on the second stream (A/B on one box,
-    // main-queue idle time of the backward pass 508 instead of 379 us): a third busy queue costs more than the queueing it removes.
-    const bool gstream_on = tf::tuning().group_stream;
-    if (g_side && gstream_on) c.gside = ctx_gside(xctx);
+  c = Ctx{dtype, (hipStream_t)stream_, params, grads, TF_OK};   // (grads_zeroed / jobs default-initialised)
+  if (!tf::tuning().single_stream && !(hooks && hooks->single_stream) && xctx) { c.side = ctx_side(xctx); c.events = &xctx->events; }
+  return TF_OK;
+}
+
+// exit: the caller's stream sees every weight gradient, then the hook of the very end
+int close_backward(Ctx& c, const tf_detnet_hooks* hooks) {
+  // (r5, measured and removed: returning WITHOUT joining the last kernel, conv1's weight gradient, and running the SGD update of every other
+  //  parameter beside it -- 1282.2 / 1284.0 against 1282.1 / 1281.2 img/s joined: both are HBM-bound, side by side they take as long as back
+  //  to back)
+  c.wait_on_main(c.mark_side());
+  record_grad_events(hooks, -1, c.stream, c.rc);
+  if (hipGetLastError() != hipSuccess && c.rc == TF_OK) c.rc = TF_ERR_LAUNCH;
+  return c.rc;
+}
+
+// is parameter q a trained tensor (conv weight, BN gamma / beta) of the identity bottleneck B?
+bool block_owns(const Block& B, int q) {
+  for (const ConvUnit* u : {&B.c1, &B.c2, &B.c3})
+    if (q == u->w || q == u->gamma || q == u->beta) return true;
+  return false;
+}
+
+// One memset for every weight gradient (atomics accumulate into them) ...
+// r4: ... except where nothing accumulates: the grouped weight gradients OVERWRITE theirs, and the BatchNorm gradients in between are
+// published with plain stores (bn_fused.hip) -- the 22 identity bottlenecks of layer 3 are 98 of the 111 MB of the flat gradient.
+// With the table in executor order (DetectionModel.flatten_parameters) they are ONE range: [layer3.1.conv1.weight, score_res3.weight),
+// skipped when every trained tensor of these blocks lies inside it and nothing else does (TINYFACES_GRAD_MEMSET_FULL=1: never).
+// zero_bn_slices (frozen BN): the BN segments inside that range have NO writer: zero_ranges_kernel clears them, so that the optimizer, the
+// all-reduce buckets and a checkpoint never see what an earlier (batch-statistics) step left there.
+void zero_flat_gradient(Ctx& c, const Arch& A, void* grad_flat, size_t grad_flat_bytes, bool group_on, bool zero_bn_slices) {
+  if (!grad_flat || !grad_flat_bytes) return;
+  const int first_id = A.layer_end[1] + 2, last_id = A.layer_end[2];           // the identity bottlenecks of layer 3 (ResNet-101: blocks 8 .. 29)
+  char* lo = group_on ? (char*)c.G(A.blocks[first_id].c1.w) : nullptr;
+  char* hi = group_on ? (char*)c.G(A.head3.w) : nullptr;
+  char* g0 = (char*)grad_flat; char* g1 = g0 + grad_flat_bytes;
+  bool split = lo && hi && lo >= g0 && hi <= g1 && lo < hi;
+  std::vector<std::pair<float*, int>> zr;           // the BN slices inside the range, adjacent ones (gamma | beta of one BN) merged
+  for (int i = first_id; split && i <= last_id; ++i)                // every trained tensor of these blocks must lie inside the range
+    for (const ConvUnit* u : {&A.blocks[i].c1, &A.blocks[i].c2, &A.blocks[i].c3}) {
+      char* w = (char*)c.G(u->w);
+      split = split && w >= lo && w < hi;
+      for (int q : {u->gamma, u->beta}) {
+        char* t = (char*)c.G(q);
+        if (!t && zero_bn_slices) continue;                 // (a table without BN gradient slots: nothing to zero)
+        split = split && t >= lo && t + (size_t)u->cout * 4 <= hi;
+        if (!zero_bn_slices) continue;
+        if (!zr.empty() && zr.back().first + zr.back().second == (float*)t) zr.back().second += u->cout;
+        else zr.emplace_back((float*)t, u->cout);
+      }
+    }
+  for (int q = 0; split && q < (int)A.names.size(); ++q) {          // ... and nothing else may
+    char* t = (char*)c.G(q);
+    if (!t || t < lo || t >= hi) continue;
+    bool mine = false;
+    for (int i = first_id; i <= last_id && !mine; ++i) mine = block_owns(A.blocks[i], q);
+    split = split && mine;
+  }
+  const bool split_off = tf::tuning().grad_memset_full;     // A/B + safety knob
+  if (split && !split_off) {
+    if (lo > g0 && hipMemsetAsync(g0, 0, (size_t)(lo - g0), c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+    if (g1 > hi && hipMemsetAsync(hi, 0, (size_t)(g1 - hi), c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+    // one launch per kZeroRanges ranges (ResNet-101: 66 ranges, ResNet-152: 105 -- one launch; the table travels as kernel arguments)
+    for (size_t at = 0; at < zr.size(); at += kZeroRanges) {
+      ZeroRanges tab;
+      const int nz = (int)(zr.size() - at < (size_t)kZeroRanges ? zr.size() - at : (size_t)kZeroRanges);
+      for (int q = 0; q < kZeroRanges; ++q) { tab.p[q] = q < nz ? zr[at + q].first : nullptr; tab.n[q] = q < nz ? zr[at + q].second : 0; }
+      hipLaunchKernelGGL(zero_ranges_kernel, dim3(1, nz), dim3(256), 0, c.stream, tab);
+    }
+  } else if (hipMemsetAsync(grad_flat, 0, grad_flat_bytes, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+  c.grads_zeroed = true;
+}
+
+// The heads: the gradients of the two score maps, their bias and weight gradients, and the data gradients into the trunk -- res3's into
+// P.R3, the last block's output gradient into `gtop` with the epilogue `top` gives it (the one thing the two graphs do differently here).
+// (the transposed weight operands w*t were packed by the training forward, together with the forward operands)
+template <class F>
+void heads_backward(Ctx& c, const Arch& A, const Plan& P, const float* gout, void* grad_flat, size_t grad_flat_bytes, void* gtop, F&& top) {
+  const int dtype = P.dtype, N = P.N, nout = P.nout;
+  const int M3 = N * P.H3 * P.W3, M4 = N * P.H4 * P.W4;
+  c.chk(tf_upsample_add_crop_bwd(dtype, gout, P.wup_diag, N, nout, kHeadLd, P.H3, P.W3, P.H4, P.W4, P.g3, P.g4, c.stream));
+  const int nb3 = tf_colstats_blocks(M3, kHeadLd, dtype), nb4 = tf_colstats_blocks(M4, kHeadLd, dtype);
+  c.chk(tf_colstats(dtype, P.g3, nullptr, nullptr, nullptr, M3, kHeadLd, kHeadLd, P.partial_b, c.stream));
+  c.chk(tf_reduce_partials(P.partial_b, nb3, 1, 0, kHeadLd, nout, c.G(A.head3.bias), 1, c.stream));
+  c.chk(tf_colstats(dtype, P.g4, nullptr, nullptr, nullptr, M4, kHeadLd, kHeadLd, P.partial_b, c.stream));
+  c.chk(tf_reduce_partials(P.partial_b, nb4, 1, 0, kHeadLd, nout, c.G(A.head4.bias), 1, c.stream));
+  c.fork();
+  wgrad(c, A.head3, nout, N, P.H3, P.W3, P.H3, P.W3, P.blk[A.layer_end[1]].y, 512, P.g3, kHeadLd);
+  wgrad(c, A.head4, nout, N, P.H4, P.W4, P.H4, P.W4, P.blk[A.layer_end[2]].y, 1024, P.g4, kHeadLd);
+  // score4_upsample.weight has lr 0 (model.py:84): its gradient is defined as zero here
+  {
+    char* u = (char*)c.G(A.upsample_w);
+    const bool covered = c.grads_zeroed && u >= (char*)grad_flat && u + (size_t)nout * nout * 16 * 4 <= (char*)grad_flat + grad_flat_bytes;     // (the flat buffer's memset)
+    if (u && !covered && hipMemsetAsync(u, 0, (size_t)nout * nout * 16 * 4, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
   }
   tf_conv_args a;
-  const int M3 = N * P.H3 * P.W3, M4 = N * P.H4 * P.W4;
-  const void* res3 = P.blk[A.layer_end[1]].y;
-  const void* res4 = P.blk[A.layer_end[2]].y;
+  conv_fill(a, dtype, 1, N, P.H4, P.W4, kHeadLd, P.H4, P.W4, 1024, 1, 1, 0, 1024, P.g4, P.w_h4t, gtop);
+  a.alg_k = nout;
+  top(a);
+  c.chk(tf_conv2d(&a, c.stream));
+  conv_fill(a, dtype, 1, N, P.H3, P.W3, kHeadLd, P.H3, P.W3, 512, 1, 1, 0, 512, P.g3, P.w_h3t, P.R3);
+  a.alg_k = nout;
+  c.chk(tf_conv2d(&a, c.stream));
+}
+
+// r4: GROUPED weight gradients of the identity bottlenecks of layer 3.  Their three gradients are not launched
+// per block any more: the block's dY operands go to buffers of its own (Plan::Blk::gT1 / gT2 / gU1), the problems are queued, and when
+// a group is complete -- behind the kernel that produces the last operand of its LAST (lowest) block -- ONE fork hands the second stream
+// two launches (tf_conv2d_wgrad_group): the 2 x n pointwise problems (128 x 128 tiles, each reduced over all 12 288 pixels in-block) and
+// the n 3x3 problems (all-taps kernel, splitk = 1).  No split-K, no atomics, no partial tiles, no reduce kernel, 3 forks instead of 22
+// for these blocks; the gradient-ready events of the group's blocks fire behind the group.
+struct WgradGroups {
+  int first_id = 0, last_id = -1;                     // the identity bottlenecks of layer 3 (ResNet-101: blocks 8 .. 29); empty when grouping is off
+  std::vector<int> group_close;                       // block index that closes each group (descending)
+  std::vector<tf_wgrad_args> pend_pw, pend_c3;
+  std::vector<int> pend_blocks;
+  WgradGroups(const Arch& A, bool on) {
+    if (!on) return;
+    first_id = A.layer_end[1] + 2; last_id = A.layer_end[2];
+    const int nid = last_id - first_id + 1, gs = tf::tuning().wgrad_group, ng = (nid + gs - 1) / gs;
+    for (int g = 1; g <= ng; ++g) group_close.push_back(last_id + 1 - (int)(((long long)nid * g + ng - 1) / ng));      // balanced: 8 + 7 + 7 (ResNet-101)
+  }
+  bool grouped(int i) const { return i >= first_id && i <= last_id; }
+  bool closes(int i) const { for (int gc : group_close) if (gc == i) return true; return false; }
+  void push(int block, const tf_wgrad_args& w3, const tf_wgrad_args& w2, const tf_wgrad_args& w1) {
+    pend_pw.push_back(w3); pend_pw.push_back(w1); pend_c3.push_back(w2); pend_blocks.push_back(block);
+  }
+  void flush(Ctx& c, const tf_detnet_hooks* hooks) {
+    if (pend_blocks.empty()) return;
+    const bool skip = tf::tuning().dbg_skip_wgrad;
+    if (!skip) {
+      // the 3x3 group first: 16 tiles per problem = half a machine for a group of eight; the pointwise launch behind it fills the CUs its
+      // tail leaves (both are enqueued behind the same fork)
+      // A refused group (e.g. a layer-3 width the all-taps plan does not take: inputs wider than ~2000 px) falls back to the per-problem
+      // split-K kernels, which ACCUMULATE with fp32 atomics -- and the split memset skipped exactly these tensors, so on a persistent
+      // flat gradient they would be added onto the previous step's (all-reduced) values: zero each one here, on the stream the
+      // fallback launches run on (tests/test_gpu_model.py::test_refused_wgrad_group_falls_back_into_zeroed_gradients)
+      auto fallback = [&](const std::vector<tf_wgrad_args>& v) {
+        for (const tf_wgrad_args& w : v) {
+          if (hipMemsetAsync(w.dw_oihw, 0, (size_t)w.Cout * w.dw_ld * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+          c.chk(tf_conv2d_wgrad(&w, c.wstream()));
+        }
+      };
+      const bool force_refuse = tf::tuning().dbg_group_refuse;      // test knob: exercise the fallback at any size
+      int rc = force_refuse ? TF_ERR_UNSUPPORTED : tf_conv2d_wgrad_group(pend_c3.data(), (int)pend_c3.size(), c.wstream());
+      if (rc == TF_ERR_UNSUPPORTED) fallback(pend_c3);
+      else c.chk(rc);
+      // r5: the pointwise group in `pw_split` launches (default 1).  A group of eight bottlenecks is 256 tiles = one block on EVERY CU for
+      // ~150 us, and beside it the chain's kernels crawl (profiles/r05_step_timeline.txt: the data gradient that normally takes 22 us
+      // takes 118-130 us while the group runs); split, each launch leaves CUs to the chain.  TINYFACES_WGRADG_SPLIT=n.
+      const int pw_split = tf::tuning().wgradg_split;
+      const int npw = (int)pend_pw.size(), per = (npw + pw_split - 1) / pw_split;
+      rc = TF_OK;
+      for (int at = 0; at < npw && rc == TF_OK; at += per)
+        rc = force_refuse ? TF_ERR_UNSUPPORTED : tf_conv2d_wgrad_group(pend_pw.data() + at, npw - at < per ? npw - at : per, c.wstream());
+      if (rc == TF_ERR_UNSUPPORTED) fallback(pend_pw);        // (the first launch already refuses: all problems of a group have the same kind of shape)
+      else c.chk(rc);
+    }
+    // a gradient-ready event of a grouped block promises "every gradient of the blocks >= it, and of the heads": all of them are on this stream
+    for (int blk : pend_blocks) record_grad_events(hooks, blk, c.wstream(), c.rc);
+    pend_pw.clear(); pend_c3.clear(); pend_blocks.clear();
+  }
+};
+
+// The gradient w.r.t. a block's input -> dst:  W1^T g1 + the skip branch (+ `extra`: the head's gradient w.r.t. res3, where the input is
+// res3).  gskip is the skip branch's operand: the identity residual, or dY of the downsample conv where the block has one.  hand_over
+// decorates the launch(es) that complete dst -- the one place the two graphs differ (ReLU mask of the previous block, its BN3 sums, tile).
+// r6: the stride-2 downsample gradient is nonzero on the even-even pixels of the block's input raster only.  Rounds 3-5 zeroed (or, with
+// the res3 head gradient, copied) a raster of that size, scattered into it, and the hand-over conv read it back as its residual: a
+// 96 MB fill + 49 MB copy by blit kernels at 2.6 TB/s and two more passes over those rasters.  Now the hand-over writes the raster first
+// (residual = the head gradient where there is one) and the scattered gradient ACCUMULATES IN PLACE (tf_conv2d: aux == y), applying the
+// same ReLU mask and adding its own share to the same BN-backward sums.  TINYFACES_DS_INPLACE_OFF=1, or a caller whose hand-over does not
+// mask (!inplace_ok): the old order, through P.T4.
+template <class F>
+void input_gradient(Ctx& c, const Plan& P, const Block& B, const Plan::Blk& b, const void* g1, const void* gskip, const void* extra, void* dst,
+                    bool inplace_ok, F&& hand_over) {
+  const int dtype = P.dtype, N = P.N, pl = B.planes, c4 = pl * 4;
+  tf_conv_args a;
+  if (!B.has_ds) {
+    conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, g1, b.w1t, dst);
+    a.epi = TF_EPI_RES; a.aux = gskip;
+    hand_over(a);
+    c.chk(tf_conv2d(&a, c.stream));
+  } else if (inplace_ok && B.stride == 2 && !tf::tuning().ds_inplace_off) {
+    conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, g1, b.w1t, dst);
+    if (extra) { a.epi = TF_EPI_RES; a.aux = extra; }
+    hand_over(a);
+    c.chk(tf_conv2d(&a, c.stream));
+    conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hin, b.Win, B.cin, 1, B.stride, 0, B.cin, gskip, b.wdt, dst);
+    a.epi = TF_EPI_RES; a.aux = dst;
+    hand_over(a);
+    a.tile = 0;                                          // (a hand-over tile choice is about the pointwise conv above)
+    c.chk(tf_conv2d(&a, c.stream));
+  } else {
+    conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hin, b.Win, B.cin, 1, B.stride, 0, B.cin, gskip, b.wdt, P.T4);
+    if (extra) { a.epi = TF_EPI_RES; a.aux = extra; }
+    c.chk(tf_conv2d(&a, c.stream));
+    conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, g1, b.w1t, dst);
+    a.epi = TF_EPI_RES; a.aux = P.T4;
+    hand_over(a);
+    c.chk(tf_conv2d(&a, c.stream));
+  }
+}
+
+}  // namespace
+
+// backward through the BATCH-STATISTICS graph (forward with training = 1)
+extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x, int N,
+                                            int H, int W, int nout, void* const* params, void* const* grads, const float* gout, void* grad_flat,
+                                            size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream_) {
+  const Arch* Ap; Plan P; Ctx c{};
+  const int rc0 = open_backward(blocks, xctx, hooks, dtype, x, N, H, W, nout, params, grads, gout, ws, ws_bytes, stream_, 1, Ap, P, c);
+  if (rc0 != TF_OK) return rc0;
+  const Arch& A = *Ap;
+  tf_conv_args a;
 
   const int srows = tf_get_stat_rows();
   const bool g_unfused_env = tf::tuning().unfused_bn;
@@ -1011,136 +1146,27 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
     else c.chk(tf_stem_im2col(x, N, H, W, dtype, P.col, kStemK, c.stream));
   }
   const bool group_on = wgrad_group_mode(dtype, 1) && fused;
-  const int first_id = A.layer_end[1] + 2, last_id = A.layer_end[2];           // the identity bottlenecks of layer 3 (ResNet-101: blocks 8 .. 29)
-  if (grad_flat && grad_flat_bytes) {                     // one memset for every weight gradient (atomics accumulate into them) ...
-    // r4: ... except where nothing accumulates: the grouped weight gradients OVERWRITE theirs, and the BatchNorm gradients in between are
-    // published with plain stores (bn_fused.hip) -- the 22 identity bottlenecks of layer 3 are 98 of the 111 MB of the flat gradient.
-    // With the table in executor order (DetectionModel.flatten_parameters) they are ONE range: [layer3.1.conv1.weight, score_res3.weight).
-    char* lo = group_on ? (char*)c.G(A.blocks[first_id].c1.w) : nullptr;
-    char* hi = group_on ? (char*)c.G(A.head3.w) : nullptr;
-    char* g0 = (char*)grad_flat; char* g1 = g0 + grad_flat_bytes;
-    bool split = lo && hi && lo >= g0 && hi <= g1 && lo < hi;
-    for (int i = first_id; split && i <= last_id; ++i) {          // every trained tensor of these blocks must lie inside the range
-      const Block& B = A.blocks[i];
-      const int idx[9] = {B.c1.w, B.c1.gamma, B.c1.beta, B.c2.w, B.c2.gamma, B.c2.beta, B.c3.w, B.c3.gamma, B.c3.beta};
-      for (int q : idx) { char* t = (char*)c.G(q); split = split && t >= lo && t < hi; }
-    }
-    for (int q = 0; split && q < (int)A.names.size(); ++q) {       // ... and nothing else may
-      char* t = (char*)c.G(q);
-      if (!t || t < lo || t >= hi) continue;
-      bool mine = false;
-      for (int i = first_id; i <= last_id && !mine; ++i) {
-        const Block& B = A.blocks[i];
-        mine = q == B.c1.w || q == B.c1.gamma || q == B.c1.beta || q == B.c2.w || q == B.c2.gamma || q == B.c2.beta || q == B.c3.w || q == B.c3.gamma || q == B.c3.beta;
-      }
-      split = split && mine;
-    }
-    const bool split_off = tf::tuning().grad_memset_full;     // A/B + safety knob
-    if (split && !split_off) {
-      if (lo > g0 && hipMemsetAsync(g0, 0, (size_t)(lo - g0), c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-      if (g1 > hi && hipMemsetAsync(hi, 0, (size_t)(g1 - hi), c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-    } else if (hipMemsetAsync(grad_flat, 0, grad_flat_bytes, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-    c.grads_zeroed = true;
-  }
-  // (the transposed weight operands w*t were packed by the training forward, together with the forward operands)
-
-  // ---- heads
-  c.chk(tf_upsample_add_crop_bwd(dtype, gout, P.wup_diag, N, nout, kHeadLd, P.H3, P.W3, P.H4, P.W4, P.g3, P.g4, c.stream));
-  {
-    const int nb3 = tf_colstats_blocks(M3, kHeadLd, dtype), nb4 = tf_colstats_blocks(M4, kHeadLd, dtype);
-    c.chk(tf_colstats(dtype, P.g3, nullptr, nullptr, nullptr, M3, kHeadLd, kHeadLd, P.partial_b, c.stream));
-    c.chk(tf_reduce_partials(P.partial_b, nb3, 1, 0, kHeadLd, nout, c.G(A.head3.bias), 1, c.stream));
-    c.chk(tf_colstats(dtype, P.g4, nullptr, nullptr, nullptr, M4, kHeadLd, kHeadLd, P.partial_b, c.stream));
-    c.chk(tf_reduce_partials(P.partial_b, nb4, 1, 0, kHeadLd, nout, c.G(A.head4.bias), 1, c.stream));
-  }
-  {
-    ConvUnit h3 = A.head3, h4 = A.head4;
-    c.fork();
-    wgrad(c, h3, nout, N, P.H3, P.W3, P.H3, P.W3, res3, 512, P.g3, kHeadLd, nullptr);
-    wgrad(c, h4, nout, N, P.H4, P.W4, P.H4, P.W4, res4, 1024, P.g4, kHeadLd, nullptr);
-  }
-  // score4_upsample.weight has lr 0 (model.py:84): its gradient is defined as zero here
-  {
-    char* u = (char*)c.G(A.upsample_w);
-    const bool covered = c.grads_zeroed && u >= (char*)grad_flat && u + (size_t)nout * nout * 16 * 4 <= (char*)grad_flat + grad_flat_bytes;     // (the flat buffer's memset)
-    if (u && !covered && hipMemsetAsync(u, 0, (size_t)nout * nout * 16 * 4, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-  }
+  zero_flat_gradient(c, A, grad_flat, grad_flat_bytes, group_on, false);
 
   // Buffer roles: Gcur/Gnext ping-pong the gradient w.r.t. a block output / input; T1 = g_c3 then g_c1;
   // T2 = gz2 -> g_c2; T3 = g_d; T4 = downsample-branch input gradient; R3 = gradient w.r.t. res3 from the head.
   void *Gcur = P.G0, *Gnext = P.G1;
-  conv_fill(a, dtype, 1, N, P.H4, P.W4, kHeadLd, P.H4, P.W4, 1024, 1, 1, 0, 1024, P.g4, P.w_h4t, Gcur);
-  a.alg_k = nout;
-  if (fused) {
+  heads_backward(c, A, P, gout, grad_flat, grad_flat_bytes, Gcur, [&](tf_conv_args& q) {
+    if (!fused) return;
     // fused flow: Gcur always carries gz = g_y * (y > 0) of the block about to be processed, and (unless that block has a
     // downsample branch) its BN3-backward sums are accumulated by the conv that produces it (MASK2 | STATS3)
     const size_t last = A.blocks.size() - 1;
-    a.epi = TF_EPI_MASK2; a.aux2 = P.blk[last].y;
-    if (!A.blocks[last].has_ds) { a.epi |= TF_EPI_STATS3; a.aux3 = P.blk[last].c3; a.stat_out = P.blk[last].b3.bst; }
-  }
-  c.chk(tf_conv2d(&a, c.stream));
-  conv_fill(a, dtype, 1, N, P.H3, P.W3, kHeadLd, P.H3, P.W3, 512, 1, 1, 0, 512, P.g3, P.w_h3t, P.R3);
-  a.alg_k = nout;
-  c.chk(tf_conv2d(&a, c.stream));
+    q.epi = TF_EPI_MASK2; q.aux2 = P.blk[last].y;
+    if (!A.blocks[last].has_ds) { q.epi |= TF_EPI_STATS3; q.aux3 = P.blk[last].c3; q.stat_out = P.blk[last].b3.bst; }
+  });
 
-  // one fork per weight gradient (default) or, TINYFACES_FORK_PER_BLOCK=1, one per block: measured 948 vs 943 img/s
-  const bool fork_each = !tf::tuning().fork_per_block;
   // Every fork makes its producer kernel carry a completion signal, which costs ~6 us of main-queue bubble behind that kernel
-  // (profiles/r02b_step_timeline.txt: 90 x 5.9 us).  The 22 identity bottlenecks of layer 3 therefore fork ONCE, behind the
+  // (profiles/r02b_step_timeline.txt: 90 x 5.9 us).  The ungrouped identity bottlenecks of layer 3 therefore fork ONCE, behind the
   // BN1-backward apply, when the dY operands of all three weight gradients exist: conv3's and conv2's gradients start ~100 us
   // later and overlap the next bottleneck instead, far from the end of the pass (layer 1 / 2 and the stem keep one fork per
   // gradient so that the tail of the weight-gradient stream stays short).  TINYFACES_L3_FORK_PER_WGRAD=1: the old schedule.
   const bool l3_single_fork = !tf::tuning().l3_fork_per_wgrad;
-  // r4: GROUPED weight gradients of the identity bottlenecks of layer 3.  Their three gradients are not launched
-  // per block any more: the block's dY operands go to buffers of its own (Plan::Blk::gT1 / gT2 / gU1), the problems are queued, and when
-  // a group is complete -- behind the BN1-backward apply of its LAST (lowest) block, the kernel that produces the group's last operand --
-  // ONE fork hands the second stream two launches (tf_conv2d_wgrad_group): the 2 x n pointwise problems (128 x 128 tiles, each reduced
-  // over all 12 288 pixels in-block) and the n 3x3 problems (all-taps kernel, splitk = 1).  No split-K, no atomics, no partial tiles, no
-  // reduce kernel, 3 forks instead of 22 for these blocks; the gradient-ready events of the group's blocks fire behind the group.
-  std::vector<int> group_close;                                                 // block index that closes each group (descending)
-  if (group_on) {
-    const int nid = last_id - first_id + 1, gs = wgrad_group_size(), ng = (nid + gs - 1) / gs;
-    for (int g = 1; g <= ng; ++g) group_close.push_back(last_id + 1 - (int)(((long long)nid * g + ng - 1) / ng));      // balanced: 8 + 7 + 7 (ResNet-101)
-  }
-  std::vector<tf_wgrad_args> pend_pw, pend_c3;
-  std::vector<int> pend_blocks;
-  auto flush_group = [&]() {
-    if (pend_blocks.empty()) return;
-    const bool skip = tf::tuning().dbg_skip_wgrad;
-    if (!skip) {
-      // the 3x3 group first: 16 tiles per problem = half a machine for a group of eight; the pointwise launch behind it fills the CUs its
-      // tail leaves (both are enqueued behind the same fork)
-      // A refused group (e.g. a layer-3 width the all-taps plan does not take: inputs wider than ~2000 px) falls back to the per-problem
-      // split-K kernels, which ACCUMULATE with fp32 atomics -- and the split memset above skipped exactly these tensors, so on a
-      // persistent flat gradient they would be added onto the previous step's (all-reduced) values: zero each one here, on the stream
-      // the fallback launches run on (tests/test_gpu_model.py::test_refused_wgrad_group_falls_back_into_zeroed_gradients)
-      auto fallback = [&](const std::vector<tf_wgrad_args>& v) {
-        for (const tf_wgrad_args& w : v) {
-          if (hipMemsetAsync(w.dw_oihw, 0, (size_t)w.Cout * w.dw_ld * 4, c.gstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-          c.chk(tf_conv2d_wgrad(&w, c.gstream()));
-        }
-      };
-      const bool force_refuse = tf::tuning().dbg_group_refuse;      // test knob: exercise the fallback at any size
-      int rc = force_refuse ? TF_ERR_UNSUPPORTED : tf_conv2d_wgrad_group(pend_c3.data(), (int)pend_c3.size(), c.gstream());
-      if (rc == TF_ERR_UNSUPPORTED) fallback(pend_c3);
-      else c.chk(rc);
-      // r5: the pointwise group in `pw_split` launches (default 1).  A group of eight bottlenecks is 256 tiles = one block on EVERY CU for
-      // ~150 us, and beside it the chain's kernels crawl (profiles/r05_step_timeline.txt: the data gradient that normally takes 22 us
-      // takes 118-130 us while the group runs); split, each launch leaves CUs to the chain.  TINYFACES_WGRADG_SPLIT=n.
-      const int pw_split = tf::tuning().wgradg_split;
-      const int npw = (int)pend_pw.size(), per = (npw + pw_split - 1) / pw_split;
-      rc = TF_OK;
-      for (int at = 0; at < npw && rc == TF_OK; at += per)
-        rc = force_refuse ? TF_ERR_UNSUPPORTED : tf_conv2d_wgrad_group(pend_pw.data() + at, npw - at < per ? npw - at : per, c.gstream());
-      if (rc == TF_ERR_UNSUPPORTED) fallback(pend_pw);        // (the first launch already refuses: all problems of a group have the same kind of shape)
-      else c.chk(rc);
-    }
-    // a gradient-ready event of a grouped block promises "every gradient of the blocks >= it, and of the heads": the heads and layer3.x
-    // per-block launches live on the second stream, so the group's stream first orders itself behind that stream's position
-    if (c.gside && !pend_blocks.empty()) { hipEvent_t e = c.mark(c.side); if (e) (void)hipStreamWaitEvent(c.gside, e, 0); }
-    for (int blk : pend_blocks) record_grad_events(hooks, blk, c.gstream(), c.rc);
-    pend_pw.clear(); pend_c3.clear(); pend_blocks.clear();
-  };
+  WgradGroups groups(A, group_on);        // a group closes behind the BN1-backward apply of its lowest block
   // ---- bottlenecks in reverse
   for (int i = (int)A.blocks.size() - 1; i >= 0; --i) {
     const Block& B = A.blocks[i];
@@ -1149,10 +1175,8 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
     const int Min = N * b.Hin * b.Win, Mout = N * b.Hout * b.Wout;
     const void* yin = i == 0 ? P.pool : P.blk[i - 1].y;
     const void* extra = (i == A.layer_end[1] + 1) ? P.R3 : nullptr;     // the block whose INPUT is res3
-    const bool grouped = group_on && i >= first_id && i <= last_id;
-    bool closes_group = false;
-    if (grouped) for (int gc : group_close) closes_group |= gc == i;
-    const bool late = !grouped && fused && fork_each && l3_single_fork && i > A.layer_end[1] && !B.has_ds;    // the three gradients behind ONE fork
+    const bool grouped = groups.grouped(i), closes_group = groups.closes(i);
+    const bool late = !grouped && fused && l3_single_fork && i > A.layer_end[1] && !B.has_ds;    // the three gradients behind ONE fork
     void *T1 = b.gT1, *T2 = b.gT2, *U1 = b.gU1, *T3 = b.gT3;      // the block's own buffers: nothing on this stream ever waits for a weight gradient
     // (1) per-channel sums for bn3 (and the downsample BN) with gz = g_y * (y > 0)
     const int nb = tf_colstats_blocks(Mout, c4, dtype);
@@ -1175,7 +1199,7 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
       const tf_bn_bwd_desc d = bwd_desc(c, B.c3, b.b3, b.b3.bst, nk, 1);
       conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hout, b.Wout, pl, 1, 1, 0, pl, Gcur, b.w3t, T2);
       a.epi = TF_EPI_MASK | TF_EPI_STATS2; a.aux = b.c2; a.mask_scale = b.b2.scale; a.mask_shift = b.b2.shift; a.stat_out = b.b2.bst;
-      if (fork_each && !late && !grouped) c.arm_fork();
+      if (!late && !grouped) c.arm_fork();
       const int rc = tf_conv_pwx_launch(&a, &d, b.c3, T1, srows, (float)Mout, c.stream);
       if (rc == TF_OK) fused24 = true;
       else if (rc != TF_ERR_UNSUPPORTED) c.chk(rc);
@@ -1185,7 +1209,7 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
       // nothing: T1 and T2 are on their way
     } else if (fused) {
       const tf_bn_bwd_desc d = bwd_desc(c, B.c3, b.b3, b.b3.bst, nk, 1);
-      if (fork_each && !late && !grouped) c.arm_fork();
+      if (!late && !grouped) c.arm_fork();
       c.chk(tf_bn_bwd_apply_fused(dtype, Gcur, nullptr, b.c3, &d, srows, Mout, c4, (float)Mout, T1, c.stream));
     } else {
       bn_backward_coefs(c, B.c3, c4, b.b3, P.partial_b, nb, nk, 1, c4, (float)Mout, B.has_ds ? 0 : 1);   // the last reader clears the partial rows
@@ -1193,9 +1217,8 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
       c.chk(tf_bn_bwd_apply(dtype, Gcur, b.y, b.c3, b.b3.cA, b.b3.cB, b.b3.cD, Mout, c4, T1, c.stream));
     }
     // (3) wgrad conv3 (its input is relu(bn2(c2)), materialised in the forward)
-    auto wg3 = [&]() { wgrad(c, B.c3, c4, N, b.Hout, b.Wout, b.Hout, b.Wout, b.a2, pl, T1, c4, nullptr); };
-    if (grouped) pend_pw.push_back(wgrad_args(c, B.c3, c4, N, b.Hout, b.Wout, b.Hout, b.Wout, b.a2, pl, T1, c4));
-    else if (fork_each && !late) { c.fork_armed(); wg3(); }
+    auto wg3 = [&]() { wgrad(c, B.c3, c4, N, b.Hout, b.Wout, b.Hout, b.Wout, b.a2, pl, T1, c4); };
+    if (!grouped && !late) { c.fork_armed(); wg3(); }
     // (4) dgrad conv3 -> gz2 in T2 (masked by relu(bn2(c2))) + BN-backward sums
     if (!fused24) {
       conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hout, b.Wout, pl, 1, 1, 0, pl, T1, b.w3t, T2);
@@ -1206,7 +1229,7 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
     // (5) g_c2 in place
     if (fused) {
       const tf_bn_bwd_desc d = bwd_desc(c, B.c2, b.b2, b.b2.bst, 2, 1);
-      if (fork_each && !late && !grouped) c.arm_fork();
+      if (!late && !grouped) c.arm_fork();
       c.chk(tf_bn_bwd_apply_fused(dtype, T2, nullptr, b.c2, &d, srows, Mout, pl, (float)Mout, T2, c.stream));
     } else {
       bn_backward_coefs(c, B.c2, pl, b.b2, P.partial_b, tf_conv_mtiles(&a), 2, 1, pl, (float)Mout);
@@ -1214,8 +1237,7 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
     }
     // (6) wgrad conv2 (input relu(bn1(c1)))
     auto wg2 = [&]() { wgrad(c, B.c2, pl, N, b.Hin, b.Win, b.Hout, b.Wout, b.a1, pl, T2, pl, nullptr, 0, 0, 0, P.dwp, P.dwp_floats); };
-    if (grouped) pend_c3.push_back(wgrad_args(c, B.c2, pl, N, b.Hin, b.Win, b.Hout, b.Wout, b.a1, pl, T2, pl));
-    else if (fork_each && !late) { c.fork_armed(); wg2(); }
+    if (!grouped && !late) { c.fork_armed(); wg2(); }
     // (7) dgrad conv2 -> gz1 in U1 (+ sums); output spatial = conv2's input
     conv_fill(a, dtype, 1, N, b.Hout, b.Wout, pl, b.Hin, b.Win, pl, 3, B.stride, 1, pl, T2, b.w2t, U1);
     a.epi = TF_EPI_MASK | TF_EPI_STATS2; a.aux = b.c1; a.mask_scale = b.b1.scale; a.mask_shift = b.b1.shift;
@@ -1224,19 +1246,23 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
     // (8) g_c1 in place
     if (fused) {
       const tf_bn_bwd_desc d = bwd_desc(c, B.c1, b.b1, b.b1.bst, 2, 1);
-      if (grouped ? closes_group : fork_each) c.arm_fork();       // grouped: only the kernel that completes a GROUP's operands carries a fork
+      if (!grouped || closes_group) c.arm_fork();                 // grouped: only the kernel that completes a GROUP's operands carries a fork
       c.chk(tf_bn_bwd_apply_fused(dtype, U1, nullptr, b.c1, &d, srows, Min, pl, (float)Min, U1, c.stream));
     } else {
       bn_backward_coefs(c, B.c1, pl, b.b1, P.partial_b, tf_conv_mtiles(&a), 2, 1, pl, (float)Min);
       c.chk(tf_bn_bwd_apply(dtype, U1, nullptr, b.c1, b.b1.cA, b.b1.cB, b.b1.cD, Min, pl, U1, c.stream));
     }
-    // (9) wgrad conv1 (input = block input, already activated)
-    auto wg1 = [&]() { wgrad(c, B.c1, pl, N, b.Hin, b.Win, b.Hin, b.Win, yin, B.cin, U1, pl, nullptr); };
+    // (9) wgrad conv1 (input = block input, already activated); a grouped block queues its three problems instead
     if (grouped) {
-      pend_pw.push_back(wgrad_args(c, B.c1, pl, N, b.Hin, b.Win, b.Hin, b.Win, yin, B.cin, U1, pl));
-      pend_blocks.push_back(i);
-      if (closes_group) { c.fork_armed(c.gstream()); flush_group(); }
-    } else if (fork_each) { c.fork_armed(); if (late) { wg3(); wg2(); } wg1(); }
+      groups.push(i, wgrad_args(c, B.c3, c4, N, b.Hout, b.Wout, b.Hout, b.Wout, b.a2, pl, T1, c4),
+                  wgrad_args(c, B.c2, pl, N, b.Hin, b.Win, b.Hout, b.Wout, b.a1, pl, T2, pl),
+                  wgrad_args(c, B.c1, pl, N, b.Hin, b.Win, b.Hin, b.Win, yin, B.cin, U1, pl));
+      if (closes_group) { c.fork_armed(); groups.flush(c, hooks); }
+    } else {
+      c.fork_armed();
+      if (late) { wg3(); wg2(); }
+      wgrad(c, B.c1, pl, N, b.Hin, b.Win, b.Hin, b.Win, yin, B.cin, U1, pl);
+    }
     // (10) gradient w.r.t. the block input -> Gnext.  Fused flow: the conv that completes it also applies the ReLU mask of
     //      the previous block's output (MASK2 with aux2 = yin) and, unless that block has a downsample branch, accumulates
     //      its BN3-backward sums (STATS3 with aux3 = its c3), so the next iteration starts at step (2).
@@ -1247,64 +1273,25 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
       q.epi |= TF_EPI_MASK2; q.aux2 = yin;
       if (!A.blocks[i - 1].has_ds) { q.epi |= TF_EPI_STATS3; q.aux3 = P.blk[i - 1].c3; q.stat_out = P.blk[i - 1].b3.bst; }
     };
-    if (B.has_ds) {
+    if (B.has_ds) {                                        // the downsample BN's backward -> T3, and the weight gradient of its conv
       if (fused) {
         const tf_bn_bwd_desc d = bwd_desc(c, B.ds, b.bd, b.b3.bst, 3, 2);      // the downsample BN's sums are row 2 of bn3's region
-        if (fork_each) c.arm_fork();
+        c.arm_fork();
         c.chk(tf_bn_bwd_apply_fused(dtype, Gcur, nullptr, b.d, &d, srows, Mout, c4, (float)Mout, T3, c.stream));
       } else {
         c.chk(tf_bn_bwd_apply(dtype, Gcur, b.y, b.d, b.bd.cA, b.bd.cB, b.bd.cD, Mout, c4, T3, c.stream));
       }
-      if (fork_each) { c.fork_armed(); wgrad(c, B.ds, c4, N, b.Hin, b.Win, b.Hout, b.Wout, yin, B.cin, T3, c4, nullptr); }
-      // r6: the stride-2 downsample gradient is nonzero on the even-even pixels of the block's input raster only.  Rounds 3-5 zeroed (or, with
-      // the res3 head gradient, copied) a raster of that size, scattered into it, and the hand-over conv read it back as its residual: a
-      // 96 MB fill + 49 MB copy by blit kernels at 2.6 TB/s and two more passes over those rasters.  Now the hand-over writes the raster first
-      // (residual = the head gradient where there is one) and the scattered gradient ACCUMULATES IN PLACE (tf_conv2d: aux == y), applying the
-      // same ReLU mask and adding its own share to the same BN-backward sums.  TINYFACES_DS_INPLACE_OFF=1: the old order.
-      const bool ds_inplace = fused && i > 0 && B.stride == 2 && !tf::tuning().ds_inplace_off;
-      if (ds_inplace) {
-        conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, U1, b.w1t, Gnext);
-        if (extra) { a.epi = TF_EPI_RES; a.aux = extra; }
-        hand_over(a);
-        c.chk(tf_conv2d(&a, c.stream));
-        conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hin, b.Win, B.cin, 1, B.stride, 0, B.cin, T3, b.wdt, Gnext);
-        a.epi = TF_EPI_RES; a.aux = Gnext;
-        hand_over(a);
-        a.tile = 0;                                          // (the hand-over tile knob is about the pointwise conv above)
-        c.chk(tf_conv2d(&a, c.stream));
-      } else {
-      conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hin, b.Win, B.cin, 1, B.stride, 0, B.cin, T3, b.wdt, P.T4);
-      if (extra) { a.epi = TF_EPI_RES; a.aux = extra; }
-      c.chk(tf_conv2d(&a, c.stream));
+      c.fork_armed();
+      wgrad(c, B.ds, c4, N, b.Hin, b.Win, b.Hout, b.Wout, yin, B.cin, T3, c4);
+    }
+    if (fused || B.has_ds) input_gradient(c, P, B, b, U1, B.has_ds ? T3 : Gcur, extra, Gnext, fused && i > 0, hand_over);   // identity branch: Gcur is already g_y * (y > 0)
+    else {                                                 // unfolded flow, identity branch: + g_y * (y > 0)
       conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, U1, b.w1t, Gnext);
-      a.epi = TF_EPI_RES; a.aux = P.T4;
-      hand_over(a);
-      c.chk(tf_conv2d(&a, c.stream));
-      }
-    } else {
-      conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, U1, b.w1t, Gnext);
-      if (fused) { a.epi = TF_EPI_RES; a.aux = Gcur; hand_over(a); }       // identity branch: Gcur is already g_y * (y > 0)
-      else { a.epi = TF_EPI_JOIN; a.aux2 = b.y; a.aux3 = Gcur; }            // identity branch: + g_y * (y > 0)
+      a.epi = TF_EPI_JOIN; a.aux2 = b.y; a.aux3 = Gcur;
       c.chk(tf_conv2d(&a, c.stream));
     }
-    if (!fork_each && !grouped) {
-      // alternative schedule: the block's four weight gradients start together once its data-gradient chain is enqueued
-      // and overlap the NEXT block's chain (their operands live in this parity's buffers until block i-2 reuses them)
-      c.fork();
-      wg3(); wg2(); wg1();
-      if (B.has_ds) wgrad(c, B.ds, c4, N, b.Hin, b.Win, b.Hout, b.Wout, yin, B.cin, T3, c4, nullptr);
-    }
-    if (!grouped) {
-      // everything up to here: the weight / BN gradients of blocks >= i and of the heads.  With a group stream they are spread over two
-      // queues: the event goes to the group stream, ordered behind the second stream's position (never the other way round: the second
-      // stream must not wait for a group)
-      if (c.gside && grad_event_registered(hooks, i)) {
-        hipEvent_t e = c.mark(c.side); if (e) (void)hipStreamWaitEvent(c.gside, e, 0);
-        record_grad_events(hooks, i, c.gside, c.rc);
-      } else {
-        record_grad_events(hooks, i, c.wstream(), c.rc);
-      }
-    }                                                // (grouped blocks: their events fire in flush_group)
+    // everything up to here: the weight / BN gradients of blocks >= i and of the heads (grouped blocks: their events fire behind the group)
+    if (!grouped) record_grad_events(hooks, i, c.wstream(), c.rc);
     void* t = Gcur; Gcur = Gnext; Gnext = t;
   }
 
@@ -1337,13 +1324,7 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
       c.chk(tf_stem_wgrad(dtype, x, N, H, W, gz, stem_apply_fused ? P.cstem : nullptr, P.bn_stem.cA, P.bn_stem.cB, P.bn_stem.cD, c.G(A.stem.w), c.wstream()));
     } else wgrad(c, s, 64, 1, 1, M1, 1, M1, P.col, kStemK, gz, 64, nullptr, 147, 1, 147);
   }
-  // (r5, measured and removed: returning WITHOUT joining this last kernel and running the SGD update of every other parameter beside it --
-  //  1282.2 / 1284.0 against 1282.1 / 1281.2 img/s joined: both are HBM-bound, side by side they take as long as back to back)
-  c.wait_on_main(c.mark_side());           // join: the caller's stream sees every weight gradient
-  if (c.gside) c.wait_on_main(c.mark(c.gside));
-  record_grad_events(hooks, -1, c.stream, c.rc);
-  if (hipGetLastError() != hipSuccess && c.rc == TF_OK) c.rc = TF_ERR_LAUNCH;
-  return c.rc;
+  return close_backward(c, hooks);
 }
 extern "C" int tf_detnet_backward_ctx(tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x, int N, int H, int W, int nout,
                                       void* const* params, void* const* grads, const float* gout, void* grad_flat, size_t grad_flat_bytes,
@@ -1367,133 +1348,21 @@ extern "C" int tf_detnet_backward_ctx(tf_detnet_ctx* xctx, const tf_detnet_hooks
 extern "C" int tf_detnet_trunk_backward_frozen_ctx(const int* blocks, tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x,
                                                    int N, int H, int W, int nout, void* const* params, void* const* grads, const float* gout,
                                                    void* grad_flat, size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream_) {
-  const Arch* Ap = find_arch(blocks);
-  if (!Ap) return TF_ERR_UNSUPPORTED;
-  if (!x || !params || !grads || !gout || !ws) return TF_ERR_ARG;
-  if (hooks && (hooks->n < 0 || (hooks->n > 0 && !hooks->blocks))) return TF_ERR_ARG;
-  if (!xctx) xctx = default_ctx();
-  if (dtype != TF_BF16 && dtype != TF_F32) return TF_ERR_UNSUPPORTED;
+  const Arch* Ap; Plan P; Ctx c{};
+  const int rc0 = open_backward(blocks, xctx, hooks, dtype, x, N, H, W, nout, params, grads, gout, ws, ws_bytes, stream_, kFrozen, Ap, P, c);
+  if (rc0 != TF_OK) return rc0;
   const Arch& A = *Ap;
-  Plan P; Arena ar(ws, ws_bytes);
-  build_plan(A, P, ar, dtype, N, H, W, nout, kFrozen);
-  if (!ar.ok) return TF_ERR_WORKSPACE;
-  Ctx c{dtype, (hipStream_t)stream_, params, grads, TF_OK};
-  if (!tf::tuning().single_stream && !(hooks && hooks->single_stream) && xctx) { c.side = ctx_side(xctx); c.events = &xctx->events; }
   tf_conv_args a;
-  const int M3 = N * P.H3 * P.W3, M4 = N * P.H4 * P.W4;
-  const void* res3 = P.blk[A.layer_end[1]].y;
-  const void* res4 = P.blk[A.layer_end[2]].y;
   const int nblocks = (int)A.blocks.size();
   // the head-bias column sums fold into the head of this pass's partial buffer: zero on entry
   if (hipMemsetAsync(P.partial_b, 0, (size_t)TF_STAT_ROWS * 3 * 1024 * 4, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
   const bool stem_direct = stem_direct_mode(dtype, false, false);      // (what the frozen forward took)
   const bool group_on = wgrad_group_mode(dtype, 1);
-  const int first_id = A.layer_end[1] + 2, last_id = A.layer_end[2];
-  if (grad_flat && grad_flat_bytes) {
-    // the split memset of the batch-statistics graph: [layer3.1.conv1.weight, score_res3.weight) is skipped, the grouped weight gradients
-    // overwrite theirs.  The BN segments inside that range have NO writer here: zero_ranges_kernel clears them, so that the optimizer, the
-    // all-reduce buckets and a checkpoint never see what an earlier (batch-statistics) step left there.
-    char* lo = group_on ? (char*)c.G(A.blocks[first_id].c1.w) : nullptr;
-    char* hi = group_on ? (char*)c.G(A.head3.w) : nullptr;
-    char* g0 = (char*)grad_flat; char* g1 = g0 + grad_flat_bytes;
-    bool split = lo && hi && lo >= g0 && hi <= g1 && lo < hi;
-    std::vector<std::pair<float*, int>> zr;           // the BN slices inside the range, adjacent ones (gamma | beta of one BN) merged
-    for (int i = first_id; split && i <= last_id; ++i) {
-      const Block& B = A.blocks[i];
-      const int widx[3] = {B.c1.w, B.c2.w, B.c3.w};
-      for (int q : widx) { char* t = (char*)c.G(q); split = split && t >= lo && t < hi; }
-      const int bidx[6] = {B.c1.gamma, B.c1.beta, B.c2.gamma, B.c2.beta, B.c3.gamma, B.c3.beta};
-      const int bC[6] = {B.planes, B.planes, B.planes, B.planes, B.planes * 4, B.planes * 4};
-      for (int q = 0; q < 6; ++q) {
-        char* t = (char*)c.G(bidx[q]);
-        if (!t) continue;                                   // (a table without BN gradient slots: nothing to zero)
-        split = split && t >= lo && t + (size_t)bC[q] * 4 <= hi;
-        if (!zr.empty() && zr.back().first + zr.back().second == (float*)t) zr.back().second += bC[q];
-        else zr.emplace_back((float*)t, bC[q]);
-      }
-    }
-    for (int q = 0; split && q < (int)A.names.size(); ++q) {       // nothing else may lie inside the range
-      char* t = (char*)c.G(q);
-      if (!t || t < lo || t >= hi) continue;
-      bool mine = false;
-      for (int i = first_id; i <= last_id && !mine; ++i) {
-        const Block& B = A.blocks[i];
-        mine = q == B.c1.w || q == B.c1.gamma || q == B.c1.beta || q == B.c2.w || q == B.c2.gamma || q == B.c2.beta || q == B.c3.w || q == B.c3.gamma || q == B.c3.beta;
-      }
-      split = split && mine;
-    }
-    if (split && !tf::tuning().grad_memset_full) {
-      if (lo > g0 && hipMemsetAsync(g0, 0, (size_t)(lo - g0), c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-      if (g1 > hi && hipMemsetAsync(hi, 0, (size_t)(g1 - hi), c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-      // one launch per kZeroRanges ranges (ResNet-101: 66 ranges, ResNet-152: 105 -- one launch; the table travels as kernel arguments)
-      for (size_t at = 0; at < zr.size(); at += kZeroRanges) {
-        ZeroRanges tab;
-        const int nz = (int)(zr.size() - at < (size_t)kZeroRanges ? zr.size() - at : (size_t)kZeroRanges);
-        for (int q = 0; q < kZeroRanges; ++q) { tab.p[q] = q < nz ? zr[at + q].first : nullptr; tab.n[q] = q < nz ? zr[at + q].second : 0; }
-        hipLaunchKernelGGL(zero_ranges_kernel, dim3(1, nz), dim3(256), 0, c.stream, tab);
-      }
-    } else if (hipMemsetAsync(grad_flat, 0, grad_flat_bytes, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-    c.grads_zeroed = true;
-  }
-
-  // ---- heads (as in the batch-statistics graph)
-  c.chk(tf_upsample_add_crop_bwd(dtype, gout, P.wup_diag, N, nout, kHeadLd, P.H3, P.W3, P.H4, P.W4, P.g3, P.g4, c.stream));
-  {
-    const int nb3 = tf_colstats_blocks(M3, kHeadLd, dtype), nb4 = tf_colstats_blocks(M4, kHeadLd, dtype);
-    c.chk(tf_colstats(dtype, P.g3, nullptr, nullptr, nullptr, M3, kHeadLd, kHeadLd, P.partial_b, c.stream));
-    c.chk(tf_reduce_partials(P.partial_b, nb3, 1, 0, kHeadLd, nout, c.G(A.head3.bias), 1, c.stream));
-    c.chk(tf_colstats(dtype, P.g4, nullptr, nullptr, nullptr, M4, kHeadLd, kHeadLd, P.partial_b, c.stream));
-    c.chk(tf_reduce_partials(P.partial_b, nb4, 1, 0, kHeadLd, nout, c.G(A.head4.bias), 1, c.stream));
-  }
-  {
-    ConvUnit h3 = A.head3, h4 = A.head4;
-    c.fork();
-    wgrad(c, h3, nout, N, P.H3, P.W3, P.H3, P.W3, res3, 512, P.g3, kHeadLd, nullptr);
-    wgrad(c, h4, nout, N, P.H4, P.W4, P.H4, P.W4, res4, 1024, P.g4, kHeadLd, nullptr);
-  }
-  {   // score4_upsample.weight has lr 0 (model.py:84): its gradient is defined as zero
-    char* u = (char*)c.G(A.upsample_w);
-    const bool covered = c.grads_zeroed && u >= (char*)grad_flat && u + (size_t)nout * nout * 16 * 4 <= (char*)grad_flat + grad_flat_bytes;
-    if (u && !covered && hipMemsetAsync(u, 0, (size_t)nout * nout * 16 * 4, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-  }
+  zero_flat_gradient(c, A, grad_flat, grad_flat_bytes, group_on, true);
   // gm of the last block: the head's data gradient, masked by the block's own output
-  conv_fill(a, dtype, 1, N, P.H4, P.W4, kHeadLd, P.H4, P.W4, 1024, 1, 1, 0, 1024, P.g4, P.w_h4t, P.blk[nblocks - 1].gT1);
-  a.alg_k = nout; a.epi = TF_EPI_MASK2; a.aux2 = P.blk[nblocks - 1].y;
-  c.chk(tf_conv2d(&a, c.stream));
-  conv_fill(a, dtype, 1, N, P.H3, P.W3, kHeadLd, P.H3, P.W3, 512, 1, 1, 0, 512, P.g3, P.w_h3t, P.R3);
-  a.alg_k = nout;
-  c.chk(tf_conv2d(&a, c.stream));
-
-  std::vector<int> group_close;
-  if (group_on) {
-    const int nid = last_id - first_id + 1, gs = wgrad_group_size(), ng = (nid + gs - 1) / gs;
-    for (int g = 1; g <= ng; ++g) group_close.push_back(last_id + 1 - (int)(((long long)nid * g + ng - 1) / ng));
-  }
-  std::vector<tf_wgrad_args> pend_pw, pend_c3;
-  std::vector<int> pend_blocks;
-  auto flush_group = [&]() {
-    if (pend_blocks.empty()) return;
-    if (!tf::tuning().dbg_skip_wgrad) {
-      // a refused group falls back to the per-problem split-K kernels, which ACCUMULATE: the split memset skipped these tensors, zero each one
-      auto fallback = [&](const std::vector<tf_wgrad_args>& v) {
-        for (const tf_wgrad_args& w : v) {
-          if (hipMemsetAsync(w.dw_oihw, 0, (size_t)w.Cout * w.dw_ld * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-          c.chk(tf_conv2d_wgrad(&w, c.wstream()));
-        }
-      };
-      const bool force_refuse = tf::tuning().dbg_group_refuse;
-      int rc = force_refuse ? TF_ERR_UNSUPPORTED : tf_conv2d_wgrad_group(pend_c3.data(), (int)pend_c3.size(), c.wstream());
-      if (rc == TF_ERR_UNSUPPORTED) fallback(pend_c3); else c.chk(rc);
-      const int pw_split = tf::tuning().wgradg_split;
-      const int npw = (int)pend_pw.size(), per = (npw + pw_split - 1) / pw_split;
-      rc = TF_OK;
-      for (int at = 0; at < npw && rc == TF_OK; at += per)
-        rc = force_refuse ? TF_ERR_UNSUPPORTED : tf_conv2d_wgrad_group(pend_pw.data() + at, npw - at < per ? npw - at : per, c.wstream());
-      if (rc == TF_ERR_UNSUPPORTED) fallback(pend_pw); else c.chk(rc);
-    }
-    for (int blk : pend_blocks) record_grad_events(hooks, blk, c.wstream(), c.rc);
-    pend_pw.clear(); pend_c3.clear(); pend_blocks.clear();
-  };
+  heads_backward(c, A, P, gout, grad_flat, grad_flat_bytes, P.blk[nblocks - 1].gT1,
+                 [&](tf_conv_args& q) { q.epi = TF_EPI_MASK2; q.aux2 = P.blk[nblocks - 1].y; });
+  WgradGroups groups(A, group_on);        // a group closes behind the conv2 data gradient of its lowest block
 
   // ---- bottlenecks in reverse
   for (int i = nblocks - 1; i >= 0; --i) {
@@ -1502,9 +1371,7 @@ extern "C" int tf_detnet_trunk_backward_frozen_ctx(const int* blocks, tf_detnet_
     const int pl = B.planes, c4 = pl * 4;
     const void* yin = i == 0 ? P.pool : P.blk[i - 1].y;
     const void* extra = (i == A.layer_end[1] + 1) ? P.R3 : nullptr;     // the block whose INPUT is res3
-    const bool grouped = group_on && i >= first_id && i <= last_id;
-    bool closes_group = false;
-    if (grouped) for (int gc : group_close) closes_group |= gc == i;
+    const bool grouped = groups.grouped(i), closes_group = groups.closes(i);
     void *gm = b.gT1, *T2 = b.gT2, *U1 = b.gU1;
     void* gprev = i > 0 ? P.blk[i - 1].gT1 : P.R3;      // (block 0: the gradient of the max-pool output; R3's last reader is far ahead on this stream)
     // (1) g2 = (W3 diag(s3))^T gm * (a2 > 0) * s2
@@ -1517,60 +1384,24 @@ extern "C" int tf_detnet_trunk_backward_frozen_ctx(const int* blocks, tf_detnet_
     // (a stride-2 3x3 data gradient is four parity-class launches: the first would carry the event away -- a plain fork behind all four)
     if ((!grouped || closes_group) && B.stride == 1) c.arm_fork();
     c.chk(tf_conv2d(&a, c.stream));
-    // (3) weight gradients, on the second stream
-    tf_wgrad_args w3 = wgrad_args(c, B.c3, c4, N, b.Hout, b.Wout, b.Hout, b.Wout, b.c2, pl, gm, c4);
-    w3.row_scale = b.b3.scale;
-    tf_wgrad_args w1 = wgrad_args(c, B.c1, pl, N, b.Hin, b.Win, b.Hin, b.Win, yin, B.cin, U1, pl);
+    // (3) weight gradients, on the second stream; a grouped block queues its three problems instead
     if (grouped) {
-      pend_pw.push_back(w3); pend_pw.push_back(w1);
-      pend_c3.push_back(wgrad_args(c, B.c2, pl, N, b.Hin, b.Win, b.Hout, b.Wout, b.c1, pl, T2, pl));
-      pend_blocks.push_back(i);
-      if (closes_group) { c.fork_armed(); flush_group(); }
+      tf_wgrad_args w3 = wgrad_args(c, B.c3, c4, N, b.Hout, b.Wout, b.Hout, b.Wout, b.c2, pl, gm, c4);
+      w3.row_scale = b.b3.scale;
+      groups.push(i, w3, wgrad_args(c, B.c2, pl, N, b.Hin, b.Win, b.Hout, b.Wout, b.c1, pl, T2, pl),
+                  wgrad_args(c, B.c1, pl, N, b.Hin, b.Win, b.Hin, b.Win, yin, B.cin, U1, pl));
+      if (closes_group) { c.fork_armed(); groups.flush(c, hooks); }
     } else {
       c.fork_armed();
-      if (!tf::tuning().dbg_skip_wgrad) {
-        if (!c.grads_zeroed && hipMemsetAsync(w3.dw_oihw, 0, (size_t)c4 * w3.dw_ld * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-        c.chk(tf_conv2d_wgrad(&w3, c.wstream()));
-      }
+      wgrad(c, B.c3, c4, N, b.Hout, b.Wout, b.Hout, b.Wout, b.c2, pl, gm, c4, b.b3.scale);
       wgrad(c, B.c2, pl, N, b.Hin, b.Win, b.Hout, b.Wout, b.c1, pl, T2, pl, nullptr, 0, 0, 0, P.dwp, P.dwp_floats);
-      wgrad(c, B.c1, pl, N, b.Hin, b.Win, b.Hin, b.Win, yin, B.cin, U1, pl, nullptr);
-      if (B.has_ds && !tf::tuning().dbg_skip_wgrad) {
-        tf_wgrad_args wd = wgrad_args(c, B.ds, c4, N, b.Hin, b.Win, b.Hout, b.Wout, yin, B.cin, gm, c4);
-        wd.row_scale = b.bd.scale;
-        if (!c.grads_zeroed && hipMemsetAsync(wd.dw_oihw, 0, (size_t)c4 * wd.dw_ld * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-        c.chk(tf_conv2d_wgrad(&wd, c.wstream()));
-      }
+      wgrad(c, B.c1, pl, N, b.Hin, b.Win, b.Hin, b.Win, yin, B.cin, U1, pl);
+      if (B.has_ds) wgrad(c, B.ds, c4, N, b.Hin, b.Win, b.Hout, b.Wout, yin, B.cin, gm, c4, b.bd.scale);
       record_grad_events(hooks, i, c.wstream(), c.rc);
     }
-    // (4) gm_prev = (W1^T g1 + skip) * (x > 0) -> the previous block's gT1 (block 0: no ReLU between the max-pool and its input)
-    auto hand_over = [&](tf_conv_args& q) { if (i > 0) { q.epi |= TF_EPI_MASK2; q.aux2 = yin; } };
-    if (B.has_ds) {
-      const bool ds_inplace = i > 0 && B.stride == 2 && !tf::tuning().ds_inplace_off;
-      if (ds_inplace) {
-        // the raster first (residual = the head gradient where there is one), then the stride-2 downsample gradient accumulates IN PLACE
-        conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, U1, b.w1t, gprev);
-        if (extra) { a.epi = TF_EPI_RES; a.aux = extra; }
-        hand_over(a);
-        c.chk(tf_conv2d(&a, c.stream));
-        conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hin, b.Win, B.cin, 1, B.stride, 0, B.cin, gm, b.wdt, gprev);
-        a.epi = TF_EPI_RES; a.aux = gprev;
-        hand_over(a);
-        c.chk(tf_conv2d(&a, c.stream));
-      } else {
-        conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hin, b.Win, B.cin, 1, B.stride, 0, B.cin, gm, b.wdt, P.T4);
-        if (extra) { a.epi = TF_EPI_RES; a.aux = extra; }
-        c.chk(tf_conv2d(&a, c.stream));
-        conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, U1, b.w1t, gprev);
-        a.epi = TF_EPI_RES; a.aux = P.T4;
-        hand_over(a);
-        c.chk(tf_conv2d(&a, c.stream));
-      }
-    } else {
-      conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, U1, b.w1t, gprev);
-      a.epi = TF_EPI_RES; a.aux = gm;                       // identity branch: gm is already g_y * (y > 0)
-      hand_over(a);
-      c.chk(tf_conv2d(&a, c.stream));
-    }
+    // (4) gm_prev = (W1^T g1 + skip) * (x > 0) -> the previous block's gT1 (block 0: no ReLU between the max-pool and its input); gm is the
+    //     skip branch's operand either way: the identity residual (already g_y * (y > 0)), or dY of the scaled downsample conv
+    input_gradient(c, P, B, b, U1, gm, extra, gprev, i > 0, [&](tf_conv_args& q) { if (i > 0) { q.epi |= TF_EPI_MASK2; q.aux2 = yin; } });
   }
 
   // ---- stem: max-pool backward masks through relu (the stored cstem is post-ReLU: scale 1, shift 0), the BN scale rides in the weight gradient
@@ -1584,18 +1415,9 @@ extern "C" int tf_detnet_trunk_backward_frozen_ctx(const int* blocks, tf_detnet_
       if (!c.grads_zeroed && hipMemsetAsync(c.G(A.stem.w), 0, (size_t)64 * 147 * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
       // operand = cA * g + cB * x_conv + cD with cA = the folded scale, cB = cD = 0
       c.chk(tf_stem_wgrad(dtype, x, N, H, W, gz, P.cstem, P.bn_stem.scale, P.c_zero, P.c_zero, c.G(A.stem.w), c.wstream()));
-    } else if (!tf::tuning().dbg_skip_wgrad) {
-      // (P.col still holds the im2col matrix of this forward)
-      tf_wgrad_args w = wgrad_args(c, s, 64, 1, 1, M1, 1, M1, P.col, kStemK, gz, 64, 147, 1, 147);
-      w.row_scale = P.bn_stem.scale;
-      if (!c.grads_zeroed && hipMemsetAsync(w.dw_oihw, 0, (size_t)64 * 147 * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-      c.chk(tf_conv2d_wgrad(&w, c.wstream()));
-    }
+    } else wgrad(c, s, 64, 1, 1, M1, 1, M1, P.col, kStemK, gz, 64, P.bn_stem.scale, 147, 1, 147);      // (P.col still holds the im2col matrix of this forward)
   }
-  c.wait_on_main(c.mark_side());           // join: the caller's stream sees every weight gradient
-  record_grad_events(hooks, -1, c.stream, c.rc);
-  if (hipGetLastError() != hipSuccess && c.rc == TF_OK) c.rc = TF_ERR_LAUNCH;
-  return c.rc;
+  return close_backward(c, hooks);
 }
 extern "C" int tf_detnet_backward_frozen_ctx(tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x, int N, int H, int W, int nout,
                                              void* const* params, void* const* grads, const float* gout, void* grad_flat, size_t grad_flat_bytes,

@@ -28,20 +28,14 @@ struct Tuning {
   int wgrad_group = 8;                   // TINYFACES_WGRAD_GROUP
   bool fork_by_record = false;           // TINYFACES_FORK_BY_RECORD
   bool stat_shift_off = false;           // TINYFACES_STAT_SHIFT_OFF
-  bool side_prio_low = false;            // TINYFACES_SIDE_PRIO_LOW
   bool unfused_bn = false;               // TINYFACES_UNFUSED_BN
-  bool pack_side = false;                // TINYFACES_PACK_SIDE
   bool pack_split_off = false;           // TINYFACES_PACK_SPLIT_OFF
   bool single_stream = false;            // TINYFACES_SINGLE_STREAM
-  bool pack_fork_late = false;           // TINYFACES_PACK_FORK_LATE
-  bool pack_first_side = false;          // TINYFACES_PACK_FIRST_SIDE
   bool bnf = false;                      // TINYFACES_BNF
   bool dbg_skip_wgrad = false;           // TINYFACES_DBG_SKIP_WGRAD
   bool wgrad3_off = false;               // TINYFACES_WGRAD3_OFF
-  bool group_stream = false;             // TINYFACES_GROUP_STREAM
   bool stem_wgrad_im2col = false;        // TINYFACES_STEM_WGRAD_IM2COL
   bool grad_memset_full = false;         // TINYFACES_GRAD_MEMSET_FULL
-  bool fork_per_block = false;           // TINYFACES_FORK_PER_BLOCK
   bool l3_fork_per_wgrad = false;        // TINYFACES_L3_FORK_PER_WGRAD
   bool dbg_group_refuse = false;         // TINYFACES_DBG_GROUP_REFUSE
   int wgradg_split = 1;                  // TINYFACES_WGRADG_SPLIT

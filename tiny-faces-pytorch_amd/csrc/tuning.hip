@@ -33,20 +33,14 @@ Tuning parse() {
   t.wgrad_group = (int)num("TINYFACES_WGRAD_GROUP", 8);
   t.fork_by_record = flag("TINYFACES_FORK_BY_RECORD");
   t.stat_shift_off = flag("TINYFACES_STAT_SHIFT_OFF");
-  t.side_prio_low = flag("TINYFACES_SIDE_PRIO_LOW");
   t.unfused_bn = flag("TINYFACES_UNFUSED_BN");
-  t.pack_side = flag("TINYFACES_PACK_SIDE");
   t.pack_split_off = flag("TINYFACES_PACK_SPLIT_OFF");
   t.single_stream = flag("TINYFACES_SINGLE_STREAM");
-  t.pack_fork_late = flag("TINYFACES_PACK_FORK_LATE");
-  t.pack_first_side = flag("TINYFACES_PACK_FIRST_SIDE");
   t.bnf = flag("TINYFACES_BNF");
   t.dbg_skip_wgrad = flag("TINYFACES_DBG_SKIP_WGRAD");
   t.wgrad3_off = flag("TINYFACES_WGRAD3_OFF");
-  t.group_stream = flag("TINYFACES_GROUP_STREAM");
   t.stem_wgrad_im2col = flag("TINYFACES_STEM_WGRAD_IM2COL");
   t.grad_memset_full = flag("TINYFACES_GRAD_MEMSET_FULL");
-  t.fork_per_block = flag("TINYFACES_FORK_PER_BLOCK");
   t.l3_fork_per_wgrad = flag("TINYFACES_L3_FORK_PER_WGRAD");
   t.dbg_group_refuse = flag("TINYFACES_DBG_GROUP_REFUSE");
   t.wgradg_split = (int)num("TINYFACES_WGRADG_SPLIT", 1);
