@@ -144,7 +144,11 @@ int tf_sgd_step_segments(float* param, const float* grad, float* momentum_buf, c
  * Replaces every nn.Conv2d on the path (tinyfaces/models/model.py:25-32,90-106 and the
  * torchvision Bottleneck convs) plus the BN / ReLU / residual passes fused around them.
  *   x  [N][H][W][Cin]  (dtype), w packed [CoutPad][KH*KW][Cin] K-contiguous (tf_pack_weight),
- *   y  [M][ldy] with M = N*OH*OW, ldy >= Cout, multiple of 4.
+ *   y  [M][ldy] with M = N*OH*OW, ldy >= Cout, multiple of 4 (fp32) / 8 (bf16, fp16): rows are moved in 16-byte chunks.  Another ldy is
+ *      TF_ERR_ARG from tf_conv2d and tf_conv_mtiles (and tf_conv2d_bnfwd / tf_conv2d_bnbwd); nothing is launched.
+ *   Write contract: rows [0, M) of y, ALL ldy columns of each (the pad columns [Cout, ldy) included: zero-padded weights make them the
+ *      epilogue of zero), rows [0, tf_conv_mtiles()) of stat_out, stat_shift_out[0, ldy); nothing else.  aux / aux2 / aux3 are read over the
+ *      same rows and columns, the per-channel vectors (epi_scale, epi_shift, mask_scale, mask_shift, stat_shift) over [0, ldy).
  * mode 0: y[p,co] = sum x[gather(p,tap),ci] w[co,tap,ci]            (forward conv)
  * mode 1: transposed gather: "x" is dY [N][H][W][Cin'=Cout_fwd] of a conv with (stride,pad)
  *         and y is dX [N][OH][OW][Cout'=Cin_fwd]  (data gradient)
@@ -205,14 +209,14 @@ typedef struct tf_conv_args {
                          removed in r4: TF_ERR_UNSUPPORTED, like a prologue (pro_scale != NULL) -- tf_conv2d_wgrad keeps its prologue. */
   /* TF_EPI_STATS only (r3): per-channel value subtracted from every output BEFORE it enters the two sums, so that the consumer computes
    * var = E[(x-s)^2] - E[x-s]^2 around a shift s close to the mean instead of E[x^2] - mean^2 (which loses (mean/std)^2 of the
-   * significant bits in fp32).  The executor passes the BN's running mean.  stat_shift_out [Cout] receives the shift that was used
+   * significant bits in fp32).  The executor passes the BN's running mean.  stat_shift [ldy] is read and stat_shift_out [ldy] receives the shift that was used
    * (written by the launch's first pixel tile) -- the consumer reads it from there, never from a buffer that is updated meanwhile.
    * NULL: no shift (sums of x and x^2 as before). */
   const float* stat_shift; float* stat_shift_out;
   /* r3: training-mode BatchNorm + ReLU of the conv's INPUT applied inside the conv (x := relu(bn(x)) with the batch statistics of `bnf`
    * finalized in-kernel, exactly tf_bn_relu_fused followed by this conv): bf16, 1x1 / stride 1 with Cin <= 256 only (the ring-less
    * LDS-DMA kernel fixes its pixel tile up in LDS after the DMA landed); bnf_out [M][Cin] receives the activated tensor (the weight
-   * gradient's operand; may be NULL).  TF_ERR_UNSUPPORTED for other shapes: run tf_bn_relu_fused + tf_conv2d.  NULL: off. */
+   * gradient's operand, row stride Cin; may be NULL).  TF_ERR_UNSUPPORTED for other shapes: run tf_bn_relu_fused + tf_conv2d.  NULL: off. */
   const struct tf_bn_fwd_desc* bnf; void* bnf_out; int bnf_rows; float bnf_count, bnf_eps, bnf_momentum;
   int alg_k, alg_n;   /* measurement hooks only: the UNPADDED reduction length (taps * channels) and output-channel count when the
                          operands are zero-padded (stem: 147 of 192, heads: 125 of 128); 0 = Cin*KH*KW / Cout */
@@ -246,7 +250,7 @@ int tf_pack_weights_tiled(int dtype, const tf_pack2_job* host_jobs, int njobs, v
 typedef struct tf_wgrad_args {
   int dtype;
   int N, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad;
-  int ldx, lddy;      /* row strides of x and dy */
+  int ldx, lddy;      /* row strides (elements) of x and dy: >= Cin / Cout, multiples of 4 (fp32) / 8 (bf16) -- 16-byte chunks; else TF_ERR_ARG */
   int pro_relu;
   const void* x; const void* dy; float* dw_oihw;
   const float* pro_scale; const float* pro_shift;
@@ -278,7 +282,7 @@ int tf_unpack_dw(const float* packed, int Cout, int Cin, int taps, float* dw_oih
 
 /* ---- HBM-bound companions of the conv engine (NHWC, dtype TF_F32 | TF_BF16) ---------- */
 /* conv1 (7x7 s2 p3, 3->64; model.py:90): x NCHW fp32 -> im2col [N*OH*OW][ldc], k = c*49+kh*7+kw
- * (the OIHW order of conv1.weight), zero padded to ldc (>= 147, multiple of 8). */
+ * (the OIHW order of conv1.weight), zero padded to ldc (>= 147, multiple of 8 for every dtype; else TF_ERR_ARG); all ldc columns of every row are written. */
 int tf_stem_im2col(const float* x_nchw, int N, int H, int W, int dtype, void* col, int ldc, void* stream);
 /* r4: conv1 straight from the NCHW fp32 image, no im2col matrix (dtype TF_BF16 | TF_F16; TF_F32 keeps tf_stem_im2col + tf_conv2d):
  * y [N*OH*OW][64] = conv(x, W) with w_packed = conv1.weight as tf_pack_weight* writes it for the im2col GEMM ([>= 64 rows][ldw],
@@ -374,7 +378,9 @@ int tf_conv2d_bnfwd(const tf_conv_args* a, const tf_bn_fwd_desc* bn, const void*
                     float eps, float momentum, void* stream);
 #endif /* TF_EXPERIMENTAL */
 /* score4_upsample (frozen bilinear ConvTranspose2d k4 s2 p1, model.py:34-40,107) + crop (:110-124)
- * + add (:126); wup_diag [C][4][4] = the channel diagonal of the (C,C,4,4) weight; output NCHW fp32. */
+ * + add (:126); wup_diag [C][4][4] = the channel diagonal of the (C,C,4,4) weight; output NCHW fp32.
+ * ldc = row stride (elements) of s3 / s4 / g3 / g4: >= C, a multiple of 4 (fp32) / 8 (bf16, fp16) forward and of 32 backward (TF_ERR_ARG /
+ * TF_ERR_UNSUPPORTED otherwise, nothing launched); the backward writes all ldc columns of g3 and g4 (zeros in [C, ldc)). */
 int tf_upsample_add_crop(int dtype, const void* s3, const void* s4, const float* wup_diag, int B, int C, int ldc,
                          int H3, int W3, int H4, int W4, float* out_nchw, void* stream);
 int tf_upsample_add_crop_bwd(int dtype, const float* g_nchw, const float* wup_diag, int B, int C, int ldc,

@@ -73,10 +73,17 @@ int pick_tile(const tf_conv_args* a) {
   }
 }
 int tile_bm(int t) { return ((t % 10) == 3 || (t % 10) == 6) ? 64 : 128; }
+// every epilogue moves 16-byte chunks of a row of y / aux / aux2 / aux3 (4 fp32, 8 bf16 / fp16 channels) guarded by c0 < ldy alone, and reads the
+// per-channel vectors [ldy] the same way: a row pitch that is no multiple of 16 bytes would let the last chunk of a row run into the next one
+bool ldy_ok(const tf_conv_args* a) {
+  const int eps = a->dtype == TF_F32 ? 4 : 8;
+  return a->ldy >= a->Cout && a->ldy % eps == 0;
+}
 
 }  // namespace
 
 extern "C" int tf_conv_mtiles(const tf_conv_args* a) {
+  if (!a || !ldy_ok(a)) return TF_ERR_ARG;
   const long M = (long)a->N * a->OH * a->OW;
   const int t = pick_tile(a);
   if (t == 50) { const int mt = tf_conv3x3h_mtiles(a); return mt > tf_get_stat_rows() ? tf_get_stat_rows() : mt; }
@@ -96,7 +103,7 @@ extern "C" int tf_conv2d(const tf_conv_args* a, void* stream_) {
   const int kch = a->dtype == TF_F32 ? 32 : 64;
   if (a->dtype != TF_BF16 && a->dtype != TF_F32 && a->dtype != TF_F16) return TF_ERR_UNSUPPORTED;
   if (a->pro_scale) return TF_ERR_UNSUPPORTED;    // the producer-BN prologue went with the register-staged kernel (r4)
-  if (a->Cin % kch != 0 || a->ldy % 4 != 0 || a->ldy < a->Cout) return TF_ERR_ARG;
+  if (a->Cin % kch != 0 || !ldy_ok(a)) return TF_ERR_ARG;
   if (a->stride != 1 && a->stride != 2) return TF_ERR_UNSUPPORTED;
   if ((a->epi & (TF_EPI_STATS | TF_EPI_STATS2 | TF_EPI_STATS3)) && !a->stat_out) return TF_ERR_ARG;
   {
@@ -127,6 +134,7 @@ extern "C" int tf_conv2d(const tf_conv_args* a, void* stream_) {
 #if TF_EXP
 extern "C" int tf_conv2d_bnbwd(const tf_conv_args* a, const tf_bn_bwd_desc* bn, const void* x2, void* applied_out, int rows, float count, void* stream_) {
   if (!a || !a->x || !a->w || !a->y || !bn || !x2) return TF_ERR_ARG;
+  if (!ldy_ok(a)) return TF_ERR_ARG;
   if ((a->epi & (TF_EPI_STATS | TF_EPI_STATS2 | TF_EPI_STATS3)) && !a->stat_out) return TF_ERR_ARG;
   if ((a->epi & (TF_EPI_RES | TF_EPI_MASK | TF_EPI_STATS2)) && !a->aux) return TF_ERR_ARG;
   if ((a->epi & TF_EPI_MASK) && (!a->mask_scale || !a->mask_shift)) return TF_ERR_ARG;
@@ -143,6 +151,7 @@ extern "C" int tf_conv2d_bnbwd(const tf_conv_args* a, const tf_bn_bwd_desc* bn, 
 extern "C" int tf_conv2d_bnfwd(const tf_conv_args* a, const tf_bn_fwd_desc* bn, const void* res, const tf_bn_fwd_desc* bn_res, void* y_out, int rows,
                                float count, float eps, float momentum, void* stream_) {
   if (!a || !a->x || !a->w || !a->y || !bn || !res || !y_out) return TF_ERR_ARG;
+  if (!ldy_ok(a)) return TF_ERR_ARG;
   if (!bn->stat || !bn->gamma || !bn->beta || !bn->scale || !bn->shift || !bn->mean || !bn->invstd) return TF_ERR_ARG;
   if (bn_res && (!bn_res->stat || !bn_res->gamma || !bn_res->beta || !bn_res->scale || !bn_res->shift || !bn_res->mean || !bn_res->invstd)) return TF_ERR_ARG;
   if ((a->epi & (TF_EPI_STATS | TF_EPI_STATS2 | TF_EPI_STATS3)) && !a->stat_out) return TF_ERR_ARG;

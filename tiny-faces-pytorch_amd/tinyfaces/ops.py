@@ -247,9 +247,10 @@ def decode_compact(score, templates_d, valid_x, valid_t, prob_thresh, scale, det
 
 # --------------------------------------------------------------------------- criterion
 def criterion_fwd_bwd(output, class_map, regression_map, n_templates=25, reg_weight=1.0, ohem_thresh=0.03, max_pos=128,
-                      max_neg=128, pos_keep=None, neg_keep=None, seed=0, want_labels=False):
+                      max_neg=128, pos_keep=None, neg_keep=None, seed=0, want_labels=False, grad=None):
     """DetectionCriterion.forward + backward (tinyfaces/models/loss.py:59-93).  class_map is mined in place.
-    Returns (loss[2] f64 device tensor = [sum cls, sum reg], grad wrt output, labels or None)."""
+    Returns (loss[2] f64 device tensor = [sum cls, sum reg], grad wrt output, labels or None).
+    grad: write the gradient into this contiguous fp32 tensor of output's shape (every element is written exactly once, no memset needed)."""
     require_gpu(output, "criterion")
     assert output.dtype == torch.float32 and class_map.dtype == torch.float32 and regression_map.dtype == torch.float32
     output, regression_map = output.contiguous(), regression_map.contiguous()
@@ -258,7 +259,9 @@ def criterion_fwd_bwd(output, class_map, regression_map, n_templates=25, reg_wei
     nt = n_templates
     assert C5 == 5 * nt and class_map.shape == (B, nt, H, W) and regression_map.shape == (B, 4 * nt, H, W)
     dev = output.device
-    grad = torch.empty_like(output)
+    if grad is None:
+        grad = torch.empty_like(output)
+    assert grad.shape == output.shape and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == dev
     loss = torch.empty(2, dtype=torch.float64, device=dev)
     labels = torch.empty_like(class_map) if want_labels else None
     wsb = lib().tf_criterion_workspace_bytes(B, nt, H, W)
@@ -387,6 +390,8 @@ def stem_wgrad(x_nchw, g_nhwc, x_conv=None, cA=None, cB=None, cD=None):
 def conv2d_nhwc(x, w_packed, Cout, KH, KW, stride, pad, mode=0, out_hw=None, ldy=None, pro=None, epi=0, epi_scale=None,
                 epi_shift=None, aux=None, aux2=None, aux3=None, mask=None, want_stats=False, tile=0, out=None, stats_into=None):
     """x (N,H,W,Cin) dtype bf16|f32 contiguous; returns y (N,OH,OW,ldy) [, stat partials (mtiles,2,ldy)].
+    ldy: row stride of y / aux / aux2 / aux3 and length of the per-channel vectors, >= Cout and a multiple of 4 (fp32) / 8 (bf16, fp16) -- the
+    rule of include/tinyfaces_hip.h (tf_conv2d returns TF_ERR_ARG otherwise); default: Cout rounded up to it.
     out: write into this (N,OH,OW,ldy) tensor (with aux=out and TF_EPI_RES the scattered stride-2 data gradient accumulates in place);
     stats_into: add the statistic sums into these existing rows instead of fresh zeros."""
     require_gpu(x, "conv2d_nhwc")
@@ -395,7 +400,8 @@ def conv2d_nhwc(x, w_packed, Cout, KH, KW, stride, pad, mode=0, out_hw=None, ldy
         assert mode == 0
         out_hw = ((H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1)
     OH, OW = out_hw
-    ldy = ldy or (Cout + 3) // 4 * 4
+    eps = 16 // x.element_size()                             # elements per 16-byte chunk of a row
+    ldy = ldy or (Cout + eps - 1) // eps * eps
     a = _hip.ConvArgs()
     a.dtype, a.mode = _hip.tf_dtype(x.dtype), mode
     a.N, a.H, a.W, a.Cin, a.OH, a.OW, a.Cout, a.KH, a.KW, a.stride, a.pad = N, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad
@@ -451,17 +457,18 @@ def conv2d_wgrad(x, dy, Cin, Cout, KH, KW, stride, pad, pro=None, splitk=0, tile
     return dw
 
 
-def conv2d_wgrad_group(problems, K, pad):
+def conv2d_wgrad_group(problems, K, pad, out=None):
     """The weight gradients of a GROUP of convolutions in one launch (tf_conv2d_wgrad_group: every output tile reduced over all pixels
     in-block, dW overwritten).  problems: [(x (N,H,W,ldx), dy (N,H,W,lddy), Cin, Cout)] bf16, stride 1; K = 1 (pad 0; any channel counts,
     one pixel count) or K = 3 (pad 1; identical shapes).  Returns the list of dW (Cout,Cin,K,K) fp32, allocated with NaN so that an
-    element the launch does not write is seen."""
+    element the launch does not write is seen.  out: write into these (Cout,Cin,K,K) fp32 tensors instead, one per problem."""
     args = (_hip.WgradArgs * len(problems))()
     outs = []
-    for a, (x, dy, Cin, Cout) in zip(args, problems):
+    for i, (a, (x, dy, Cin, Cout)) in enumerate(zip(args, problems)):
         require_gpu(x, "conv2d_wgrad_group")
         N, H, W, ldx = x.shape
-        dw = torch.full((Cout, Cin, K, K), float("nan"), dtype=torch.float32, device=x.device)
+        dw = torch.full((Cout, Cin, K, K), float("nan"), dtype=torch.float32, device=x.device) if out is None else out[i]
+        assert dw.shape == (Cout, Cin, K, K) and dw.dtype == torch.float32 and dw.is_contiguous()
         a.dtype = _hip.tf_dtype(x.dtype)
         a.N, a.H, a.W, a.Cin, a.OH, a.OW, a.Cout, a.KH, a.KW, a.stride, a.pad = N, H, W, Cin, H, W, Cout, K, K, 1, pad
         a.ldx, a.lddy, a.x, a.dy, a.dw_oihw, a.dw_ld = ldx, dy.shape[3], ptr(x), ptr(dy), ptr(dw), Cin * K * K
