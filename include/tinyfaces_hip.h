@@ -145,7 +145,7 @@ int tf_sgd_step_segments(float* param, const float* grad, float* momentum_buf, c
  * torchvision Bottleneck convs) plus the BN / ReLU / residual passes fused around them.
  *   x  [N][H][W][Cin]  (dtype), w packed [CoutPad][KH*KW][Cin] K-contiguous (tf_pack_weight),
  *   y  [M][ldy] with M = N*OH*OW, ldy >= Cout, multiple of 4 (fp32) / 8 (bf16, fp16): rows are moved in 16-byte chunks.  Another ldy is
- *      TF_ERR_ARG from tf_conv2d and tf_conv_mtiles (and tf_conv2d_bnfwd / tf_conv2d_bnbwd); nothing is launched.
+ *      TF_ERR_ARG from tf_conv2d and tf_conv_mtiles; nothing is launched.
  *   Write contract: rows [0, M) of y, ALL ldy columns of each (the pad columns [Cout, ldy) included: zero-padded weights make them the
  *      epilogue of zero), rows [0, tf_conv_mtiles()) of stat_out, stat_shift_out[0, ldy); nothing else.  aux / aux2 / aux3 are read over the
  *      same rows and columns, the per-channel vectors (epi_scale, epi_shift, mask_scale, mask_shift, stat_shift) over [0, ldy).
@@ -199,24 +199,24 @@ typedef struct tf_conv_args {
   float* stat_out;    /* [mtiles][2][ldy] fp32 partial sums, mtiles = tf_conv_mtiles() */
   int tile;           /* 0 = auto (recommended).  Else a kernel / tile code, pixels x channels: 11 128x128, 12 128x64, 13 64x64 on the LDS-DMA
                          kernel (3-deep ring; 2x = 4-deep, 3x = ring-less, 4x = 2-deep; x4 / x5 / x6 = 128x128 / 128x64 / 64x128 on 32x32x16
-                         fragments), 50 = halo-resident 3x3 kernel, 60 = conv_pwx, 70 = conv_pws (r5: wave-streaming pointwise kernel with resident weights).
+                         fragments), 50 = halo-resident 3x3 kernel, 70 = conv_pws (r5: wave-streaming pointwise kernel with resident weights).
                          conv_pws takes EXACTLY: 1x1 / stride 1 / pad 0, bf16 or fp16, no prologue, ldy == Cout, M >= 16 384 pixels,
                          (Cin, Cout) in {(64, 256), (256, 64), (64, 64), (256, 128)}, epilogue sets AFFINE[+RELU], AFFINE+RES+RELU (both types) and, bf16
                          only, none, STATS, MASK+STATS2, RES[+MASK2[+STATS3]]; statistic epilogues only with folded rows (tf_get_stat_rows() <=
                          TF_STAT_ROWS).  0 picks it for those launches (TINYFACES_PWS_OFF=1: never); tile = 70 on anything else is TF_ERR_UNSUPPORTED from
-                         tf_conv2d and from tf_conv_mtiles (negative return).  Output-channel slices (Cout > 256) exist in the TF_EXPERIMENTAL build only.
-                         Codes 1-3 (the register-staged kernel of round 1) were
-                         removed in r4: TF_ERR_UNSUPPORTED, like a prologue (pro_scale != NULL) -- tf_conv2d_wgrad keeps its prologue. */
+                         tf_conv2d and from tf_conv_mtiles (negative return).
+                         Codes 1-3 (the register-staged kernel of round 1, removed in r4) and code 60 (a register-staged pointwise kernel with
+                         BatchNorm prologues, measured slower on every layer and removed) are TF_ERR_UNSUPPORTED from tf_conv2d and from
+                         tf_conv_mtiles, like a prologue (pro_scale != NULL) -- tf_conv2d_wgrad keeps its prologue. */
   /* TF_EPI_STATS only (r3): per-channel value subtracted from every output BEFORE it enters the two sums, so that the consumer computes
    * var = E[(x-s)^2] - E[x-s]^2 around a shift s close to the mean instead of E[x^2] - mean^2 (which loses (mean/std)^2 of the
    * significant bits in fp32).  The executor passes the BN's running mean.  stat_shift [ldy] is read and stat_shift_out [ldy] receives the shift that was used
    * (written by the launch's first pixel tile) -- the consumer reads it from there, never from a buffer that is updated meanwhile.
    * NULL: no shift (sums of x and x^2 as before). */
   const float* stat_shift; float* stat_shift_out;
-  /* r3: training-mode BatchNorm + ReLU of the conv's INPUT applied inside the conv (x := relu(bn(x)) with the batch statistics of `bnf`
-   * finalized in-kernel, exactly tf_bn_relu_fused followed by this conv): bf16, 1x1 / stride 1 with Cin <= 256 only (the ring-less
-   * LDS-DMA kernel fixes its pixel tile up in LDS after the DMA landed); bnf_out [M][Cin] receives the activated tensor (the weight
-   * gradient's operand, row stride Cin; may be NULL).  TF_ERR_UNSUPPORTED for other shapes: run tf_bn_relu_fused + tf_conv2d.  NULL: off. */
+  /* RESERVED (the layout is ABI): an in-LDS BatchNorm + ReLU prologue of the ring-less pointwise kernel lived here in r3-r6; it was measured
+   * slower than tf_bn_relu_fused + tf_conv2d and removed.  bnf must be NULL: tf_conv2d returns TF_ERR_UNSUPPORTED otherwise, before anything
+   * is launched; the other five fields are ignored. */
   const struct tf_bn_fwd_desc* bnf; void* bnf_out; int bnf_rows; float bnf_count, bnf_eps, bnf_momentum;
   int alg_k, alg_n;   /* measurement hooks only: the UNPADDED reduction length (taps * channels) and output-channel count when the
                          operands are zero-padded (stem: 147 of 192, heads: 125 of 128); 0 = Cin*KH*KW / Cout */
@@ -358,25 +358,6 @@ int tf_bn_add_relu_fused(int dtype, const void* x, const tf_bn_fwd_desc* bn, con
                          int rows, int64_t M, int C, float count, float eps, float momentum, void* y, void* stream);
 int tf_bn_bwd_apply_fused(int dtype, const void* g, const void* y /* NULL: no ReLU mask */, const void* x, const tf_bn_bwd_desc* bn,
                           int rows, int64_t M, int C, float count, void* out, void* stream);
-#ifdef TF_EXPERIMENTAL
-/* EXPERIMENTAL BUILD ONLY (build.py --experimental): parity-green, measured slower than the two launches on every layer,
- * not part of the default library.
- * r3: tf_bn_bwd_apply_fused + the pointwise tf_conv2d that consumes its output, in ONE launch (csrc/conv_pwx.hip): the conv's pixel
- * operand is A*x + B*x2 + D (a->x = the incoming gradient g, x2 = the BatchNorm's input, coefficients from `bn`'s statistic rows as in
- * tf_bn_bwd_apply_fused, dgamma / dbeta published), the applied tensor is also written to applied_out [M][Cin] (NULL: not kept).
- * Replaces the backward of BatchNorm2d followed by the data gradient of the 1x1 conv in front of it (torchvision Bottleneck.bn3 / conv3
- * under autograd, tinyfaces/trainer.py:86).  bf16, 1x1 / stride 1, Cin a multiple of 64 in [128, 1024], Cout a multiple of 128 with
- * ldy == Cout; TF_ERR_UNSUPPORTED otherwise (run the two calls). */
-int tf_conv2d_bnbwd(const tf_conv_args* a, const tf_bn_bwd_desc* bn, const void* x2, void* applied_out, int rows, float count, void* stream);
-/* r5: tf_bn_add_relu_fused + the pointwise tf_conv2d that consumes its output, in ONE launch (csrc/conv_pwx.hip): the conv's pixel operand
- * is y = relu(bn(a->x) + (bn_res(res) | res)) -- a->x = the raw output of the previous bottleneck's conv3, `bn` its bn3 (batch statistics
- * finalized in-kernel: scale / shift / mean / invstd published, running statistics updated, exactly like tf_bn_add_relu_fused), res = the
- * residual (bn_res != NULL: the raw downsample conv output and its BatchNorm) -- and y is also written to y_out [M][Cin]: the block output.
- * Replaces bn3 -> += identity -> relu of a torchvision Bottleneck followed by conv1 of the NEXT one (tinyfaces/models/model.py:90-101).
- * Same shape limits and error codes as tf_conv2d_bnbwd. */
-int tf_conv2d_bnfwd(const tf_conv_args* a, const tf_bn_fwd_desc* bn, const void* res, const tf_bn_fwd_desc* bn_res, void* y_out, int rows, float count,
-                    float eps, float momentum, void* stream);
-#endif /* TF_EXPERIMENTAL */
 /* score4_upsample (frozen bilinear ConvTranspose2d k4 s2 p1, model.py:34-40,107) + crop (:110-124)
  * + add (:126); wup_diag [C][4][4] = the channel diagonal of the (C,C,4,4) weight; output NCHW fp32.
  * ldc = row stride (elements) of s3 / s4 / g3 / g4: >= C, a multiple of 4 (fp32) / 8 (bf16, fp16) forward and of 32 backward (TF_ERR_ARG /
@@ -543,7 +524,7 @@ int tf_image_prepare(const tf_image_prepare_args* a, void* stream);
  * forward convolution the launch belongs to, unpadded channels: a stride-2 data gradient counts the
  * forward conv's MACs, not the zero-inserted gather it executes), algorithmic bytes, EXECUTED flops
  * (2*M*N*K of the GEMM the kernel ran, padding and zero taps included).  kind 0..5 = conv_igemm (dtype*3 + tile-1), 8..11 = wgrad (8 + dtype*2 + (tile==128)),
- * 12/13/15 = conv_dma f32/bf16/f16, 14 = wgrad_dma bf16, 6/7 = conv3x3h bf16/f16, 16 = wgrad3x3 bf16 (both launches of its two-phase form), 17 = conv_pwx,
+ * 12/13/15 = conv_dma f32/bf16/f16, 14 = wgrad_dma bf16, 6/7 = conv3x3h bf16/f16, 16 = wgrad3x3 bf16 (both launches of its two-phase form), 17 = retired (conv_pwx, a removed kernel: not reused),
  * 18 / 19 = the grouped pointwise / 3x3 weight gradients (tf_conv2d_wgrad_group: flops and bytes of the whole group). */
 int tf_profile_enable(int every);   /* 0 = off, 1 = bracket every launch, n = every n-th launch (sampling keeps the timed region undisturbed) */
 int tf_profile_collect(double* host_out, int max_rows);

@@ -17,10 +17,12 @@ def built():
     return mod.build(verbose=False)
 
 
-def _declared(experimental=False):
+REMOVED = ("tf_conv2d_bnbwd", "tf_conv2d_bnfwd")     # entry points of a kernel that was measured, lost and removed
+
+
+def _declared():
     src = open(os.path.join(ROOT, "include", "tinyfaces_hip.h")).read()
-    if not experimental:       # the default library does not carry the `#ifdef TF_EXPERIMENTAL` entry points (measured-and-lost kernels)
-        src = re.sub(r"#ifdef TF_EXPERIMENTAL.*?#endif /\* TF_EXPERIMENTAL \*/", "", src, flags=re.S)
+    assert not [n for n in REMOVED if re.search(r"\b%s\s*\(" % n, src)]
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"\b(tf_[a-z0-9_]+)\s*\(", src)))
 
@@ -28,11 +30,9 @@ def _declared(experimental=False):
 def test_library_exports_every_declared_symbol(built, hip):
     import ctypes
     l = ctypes.CDLL(built)
-    declared = _declared(hip.experimental())
+    declared = _declared()
     assert len(declared) >= 35
-    if not hip.experimental():      # r6: the default library is WITHOUT the kernels that lost (conv_pwx: tf_conv2d_bnbwd / tf_conv2d_bnfwd)
-        assert not hasattr(l, "tf_conv2d_bnfwd") and not hasattr(l, "tf_conv2d_bnbwd")
-        assert set(_declared(True)) - set(declared) == {"tf_conv2d_bnbwd", "tf_conv2d_bnfwd"}
+    assert not [n for n in REMOVED if hasattr(l, n) or n in declared]
     for name in declared:
         assert hasattr(l, name), f"{name} declared in include/tinyfaces_hip.h but not exported"
     listed = hip.symbols()
@@ -48,11 +48,8 @@ def test_library_exports_only_the_c_abi(built):
     names = [ln.split()[-1] for ln in out.splitlines() if ln.strip()]
     assert names and not [n for n in names if n.startswith("_Z")], [n for n in names if n.startswith("_Z")][:5]
     dbg = set(re.findall(r"\b(tf_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "tiny-faces-pytorch_amd", "csrc", "debug_api.h")).read()))
-    import ctypes
-    fn = ctypes.CDLL(built).tf_build_id
-    fn.restype = ctypes.c_char_p
-    exp = fn().decode().endswith("+x")
-    assert set(names) == set(_declared(exp)) | dbg
+    assert set(names) == set(_declared()) | dbg
+    assert not [n for n in REMOVED if n in names]
 
 
 def test_binding_signatures_cover_the_abi(hip):
@@ -137,53 +134,6 @@ def test_kernel_selection_queries_host_side(hip):
     assert wgrad_ws(12, 63, 63, 128, 128, 3, stride=2) == 0       # strided 3x3: the per-tap kernel
 
 
-def test_conv_pwx_k_loop_holds_only_the_hand_counted_waits(tmp_path):
-    """csrc/conv_pwx.hip (r5 rewrite) streams its raw pixel stages through a 4-10 deep LDS-DMA ring issued by waves 4-7 and transforms them in
-    place.  Two things hipcc does on its own would flatten that ring to one stage, and both were seen in the ISA of the first build: a
-    `s_waitcnt vmcnt(0)` in front of the first ds_write behind a DMA it knows about (the builtin is modelled as a pending LDS write), and
-    `s_waitcnt vmcnt(0) lgkmcnt(0)` in front of every __syncthreads().  ISA audit of every instantiation: every DMA is issued from inline
-    asm, and in the basic blocks of the K loop every wait on the VM counter is a hand-written one; no scratch."""
-    import re
-    import subprocess
-    src = os.path.join(ROOT, "tiny-faces-pytorch_amd", "csrc", "conv_pwx.hip")
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-DTF_EXPERIMENTAL", "-save-temps", "-c", src, "-o", str(tmp_path / "pwx.o")],      # (r6: an experimental-build kernel)
-                       cwd=tmp_path, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = open(tmp_path / "conv_pwx-hip-amdgcn-amd-amdhsa-gfx950.s").read()
-    names = re.findall(r"^(_ZN12_GLOBAL__N_115conv_pwx_kernel\w+):", asm, re.M)
-    assert len(names) >= 10           # {128, 256} x {plain, bn-bwd (2 epilogue forms), bn-fwd identity / downsample (2 each)}
-    for name in names:
-        body = re.search(re.escape(name) + r":(.*?)\.Lfunc_end", asm, re.S).group(1)
-        assert "scratch_" not in body, name
-        lines = [l.strip() for l in body.split("\n")]
-        in_asm, hand = False, set()
-        for i, l in enumerate(lines):
-            if l.startswith(";;#ASMSTART"):
-                in_asm = True
-            elif l.startswith(";;#ASMEND"):
-                in_asm = False
-            elif in_asm:
-                hand.add(i)
-        dmas = [i for i, l in enumerate(lines) if l.startswith("global_load_lds")]
-        assert dmas and all(i in hand for i in dmas), name
-        # basic blocks of the K loop = the blocks hipcc annotates with the loop header of the block that holds the MFMAs
-        owner, cur = {}, None
-        for i, l in enumerate(lines):
-            m = re.match(r"\.L(BB\d+_\d+):\s*;(.*)", l)
-            if m:
-                h = re.search(r"Header=(BB\d+_\d+)", m.group(2))
-                cur = h.group(1) if h else (m.group(1) if "Loop Header" in m.group(2) else None)
-            elif re.match(r"\.L(BB\d+_\d+):", l):
-                cur = None
-            owner[i] = cur
-        kloops = {owner[i] for i, l in enumerate(lines) if l.startswith("v_mfma")}
-        assert len(kloops) == 1 and None not in kloops, (name, kloops)
-        loop = [i for i in range(len(lines)) if owner[i] in kloops]
-        waits = [i for i in loop if lines[i].startswith("s_waitcnt") and "vmcnt" in lines[i]]
-        assert waits, name
-        assert all(i in hand for i in waits), (name, [lines[i] for i in waits if i not in hand])
-
-
 def _barriers_with_lds_in_flight(asm):
     """{kernel: [(lds ops in flight at the barrier, a DMA is issued behind it before the next barrier)]} from hipcc's gfx950 assembly: a
     linear walk that counts ds_* instructions up and applies every `s_waitcnt lgkmcnt(n)`."""
@@ -214,7 +164,7 @@ def _barriers_with_lds_in_flight(asm):
     return out
 
 
-@pytest.mark.parametrize("src", ["conv3x3h.hip", "conv_dma_bf16.hip", "wgrad_dma.hip", "wgrad3x3.hip", "conv_pwx.hip"])
+@pytest.mark.parametrize("src", ["conv3x3h.hip", "conv_dma_bf16.hip", "wgrad_dma.hip", "wgrad3x3.hip"])
 def test_no_lds_read_is_in_flight_across_a_barrier_that_frees_its_ring_slot(tmp_path, src):
     """r5, the race behind `get_detections` returning different boxes from run to run (csrc/conv3x3h.hip): hipcc sank the last MFMAs of a K
     stage, and the wait for the fragment reads that feed them, below the NEXT stage's counted vmcnt wait + raw s_barrier; a wave then
@@ -226,8 +176,7 @@ def test_no_lds_read_is_in_flight_across_a_barrier_that_frees_its_ring_slot(tmp_
     import subprocess
     path = os.path.join(ROOT, "tiny-faces-pytorch_amd", "csrc", src)
     out = tmp_path / "k.s"
-    exp = ["-DTF_EXPERIMENTAL"] if src == "conv_pwx.hip" else []        # (r6: conv_pwx is an experimental-build kernel; the others are audited as shipped)
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17"] + exp + ["-S", "--cuda-device-only", path, "-o", str(out)],
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", path, "-o", str(out)],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     found = _barriers_with_lds_in_flight(open(out).read())
@@ -284,3 +233,10 @@ def test_round4_entry_points_refuse_bad_arguments_without_launching(hip):
     # the executor context and the communicator: NULL handles are refused, not dereferenced
     assert l.tf_comm_rank(None) == -1 and l.tf_comm_world(None) == 0          # "no communicator": rank -1 of a world of 0
     assert l.tf_allreduce_bucket(None, p, 4, None) == ERR_ARG
+    # removed kernels stay refused: tile code 60 (like codes 1-3) from tf_conv2d AND from tf_conv_mtiles (no buffer is ever sized from it), and
+    # the reserved in-LDS BatchNorm prologue field of tf_conv_args
+    a = hip.ConvArgs(dtype=1, mode=0, N=1, H=8, W=8, Cin=256, OH=8, OW=8, Cout=128, KH=1, KW=1, stride=1, pad=0, ldy=128, x=p, w=p, y=p, tile=60)
+    assert l.tf_conv2d(C.byref(a), None) == ERR_UNSUPPORTED
+    assert l.tf_conv_mtiles(C.byref(a)) == ERR_UNSUPPORTED
+    a.tile, a.bnf = 0, p
+    assert l.tf_conv2d(C.byref(a), None) == ERR_UNSUPPORTED

@@ -20,7 +20,6 @@ pytestmark = pytest.mark.gpu
 F32, BF16, F16 = torch.float32, torch.bfloat16, torch.float16
 DEV = "cuda"
 DMA_TILES = [0, 11, 12, 13, 22, 23, 32]                    # the tile codes tests/test_gpu_conv.py names for the 16x16x32-fragment kernel
-# (tile code 60 = conv_pwx exists in the experimental build only: no shape qualifies in the library under test)
 
 
 def _tol(dtype):
@@ -326,10 +325,8 @@ def test_default_ldy_is_the_smallest_the_header_allows_and_stays_inside_its_rows
 
 
 def test_in_lds_bn_prologue_and_its_side_output_are_refused_by_this_build(hip):
-    """tf_conv_args.bnf / bnf_out (a second [M][Cin] output of the ring-less tile) exist in the experimental build only: the library
-    under test refuses the launch, y and bnf_out stay untouched."""
-    if hip.experimental():
-        pytest.skip("the experimental build implements the in-LDS prologue (tests/test_gpu_conv.py runs it there); bnf_out has no guarded case in that build")
+    """tf_conv_args.bnf / bnf_out (once a second [M][Cin] output of the ring-less tile) are reserved fields of a removed prologue: the
+    library refuses the launch, y and bnf_out stay untouched."""
     lib = hip.lib()
     g, x, wp, _, _ = _conv_problem(BF16, 0, 1, 1, 5, 13, 64, 64, 64, seed=3)
     y, side = guarded((1, 5, 13, 64), BF16, DEV), guarded((1, 5, 13, 64), BF16, DEV)
@@ -340,34 +337,6 @@ def test_in_lds_bn_prologue_and_its_side_output_are_refused_by_this_build(hip):
     a.x, a.w, a.y = x.data_ptr(), wp.data_ptr(), y.data_ptr()
     a.bnf, a.bnf_out, a.bnf_rows, a.bnf_count, a.bnf_eps, a.bnf_momentum = C.addressof(desc), side.data_ptr(), 8, 65.0, 1e-5, 0.1
     assert lib.tf_conv2d(C.byref(a), hip.stream()) == -3     # TF_ERR_UNSUPPORTED
-    _sync_ok()
-    for t in (y, side):
-        assert_guards(t, "refused launch")
-        assert unwritten(t)[0] == t.numel()
-
-
-def test_conv_pwx_writes_its_rows_and_nothing_else(hip):
-    """Tile code 60 (csrc/conv_pwx.hip), plain form: 256 -> 128 over 9 x 22 = 198 pixels (no multiple of its 64-pixel tile), STATS."""
-    if not hip.experimental():
-        pytest.skip("conv_pwx is compiled into the experimental build only (build.py --experimental)")
-    _run_conv(hip, "bf16,t60,9x22,c128/128,m0,stats", BF16, 60, 0, 1, 1, 9, 22, 256, 128, 128, "stats", seed=60)
-
-
-def test_fused_bn_conv_entries_refuse_a_two_byte_ldy_that_is_no_multiple_of_8(hip):
-    """tf_conv2d_bnfwd / tf_conv2d_bnbwd (experimental build only) take the same tf_conv_args: ldy = Cout = 100 in bf16 is TF_ERR_ARG before
-    anything is launched.  The library under test does not export them at all."""
-    lib = hip.lib()
-    fwd, bwd = getattr(lib, "tf_conv2d_bnfwd", None), getattr(lib, "tf_conv2d_bnbwd", None)
-    if not hip.experimental():
-        assert fwd is None and bwd is None
-        return
-    _, x, wp, _, _ = _conv_problem(BF16, 0, 1, 1, 5, 13, 64, 100, 100, seed=3)
-    y, side = guarded((1, 5, 13, 100), BF16, DEV), guarded((1, 5, 13, 100), BF16, DEV)
-    other = gin(torch.zeros(1, 5, 13, 100), BF16)
-    a = _conv_args(hip, BF16, 0, 1, 5, 13, 64, 5, 13, 100, 1, 1, 0, 100, 0, 0)
-    a.x, a.w, a.y = x.data_ptr(), wp.data_ptr(), y.data_ptr()
-    assert fwd(C.byref(a), C.byref(hip.BnFwdDesc()), other.data_ptr(), None, side.data_ptr(), 8, 65.0, 1e-5, 0.1, hip.stream()) == -1
-    assert bwd(C.byref(a), C.byref(hip.BnBwdDesc()), other.data_ptr(), side.data_ptr(), 8, 65.0, hip.stream()) == -1
     _sync_ok()
     for t in (y, side):
         assert_guards(t, "refused launch")

@@ -18,16 +18,13 @@
 // block and channel.
 // Epilogue sets (compile-time, as in conv_dma): STATS | AFFINE+RELU | AFFINE | AFFINE+RES+RELU | MASK+STATS2 | none, and the hand-over sets of the
 // data gradient of conv1 (RES+MASK2+STATS3, RES+MASK2, RES: three operand rings per wave -> two waves per block).
-// Output-channel slices (N > 256: 256 -> 512 / 1024, 128 -> 512): a block keeps a 128-channel slice resident and the nsl blocks that walk the
-// same pixel tiles sit on one XCD.  Parity-green and slower than the tiled kernel (64 KiB of weights leave room for two waves x one tile in
-// flight): on request (tile = 70) or with TINYFACES_PWS_SLICED=1 only.
+// nsl is ALWAYS 1: output-channel slices (N > 256) were measured slower than the tiled kernel and are no longer dispatched; the kernel keeps their arithmetic.
 // Replaces nn.Conv2d (1x1) + BN statistics / folded BN (+ residual + ReLU) of the torchvision Bottleneck (tinyfaces/models/model.py:90-101)
 // and the data gradient of conv3 for those shapes.  bf16 and fp16 operands.
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
-#include "tuning.h"
 #include "lds_dma.h"
 #include "profile.h"
 
@@ -360,13 +357,6 @@ int launch(const tf_conv_args* A, hipStream_t stream) {
   k.M = A->N * A->OH * A->OW; k.K = A->Cin; k.ntiles = (k.M + 15) / 16; k.srows = tf_get_stat_rows(); k.ldy = A->ldy;
   k.nsl = 1; k.nb = 1;
   const int ks = A->Cin / 64, nf = A->Cout / 16;
-  if (nf > 16) {                                                            // sliced: 128 output channels per block (experimental build only)
-#if TF_EXP
-    if (ks == 4) return launch_epi<T, 4, 8>(A, k, stream);                  // 256 -> 1024: conv3 of layer 3 and the data gradient of its conv1
-    if (ks == 2) return launch_epi<T, 2, 8>(A, k, stream);                  // 128 -> 512: the same of layer 2
-#endif
-    return TF_ERR_UNSUPPORTED;
-  }
   if (ks == 1 && nf == 16) return launch_epi<T, 1, 16>(A, k, stream);     // 64 -> 256: conv3 / downsample of layer 1
   if (ks == 4 && nf == 4) return launch_epi<T, 4, 4>(A, k, stream);       // 256 -> 64: conv1 of layer 1, the data gradient of its conv3
   if (ks == 1 && nf == 4) return launch_epi<T, 1, 4>(A, k, stream);       // 64 -> 64: conv1 of layer1.0
@@ -386,12 +376,11 @@ bool epi_ok(const tf_conv_args* a) {
 
 }  // namespace
 
-// pointwise (1x1, stride 1, pad 0) conv / data gradient with 2-byte operands, (Cin, Cout) in {(64, 256), (256, 64), (64, 64), (256, 128)} or
-// (256 | 128, a multiple of 128 above 256: sliced),
+// pointwise (1x1, stride 1, pad 0) conv / data gradient with 2-byte operands, (Cin, Cout) in {(64, 256), (256, 64), (64, 64), (256, 128)},
 // ldy == Cout, one of the epilogue sets above, and enough pixels that the launch is a stream (M >= 16 384)
 bool tf_conv_pws_applicable(const tf_conv_args* a) {
   if (a->dtype != TF_BF16 && a->dtype != TF_F16) return false;
-  if (a->pro_scale || a->bnf) return false;
+  if (a->pro_scale) return false;
   if (a->KH != 1 || a->KW != 1 || a->stride != 1 || a->pad != 0 || a->H != a->OH || a->W != a->OW) return false;
   if (a->ldy != a->Cout || !epi_ok(a)) return false;
   // statistic sums are folded into <= TF_STAT_ROWS rows by atomics: the bit-reproducible flow (tf_set_stat_rows(0): one row per tile) keeps conv_dma
@@ -399,14 +388,6 @@ bool tf_conv_pws_applicable(const tf_conv_args* a) {
   const int ks = a->Cin / 64, nf = a->Cout / 16;
   if (a->Cin % 64 || a->Cout % 16) return false;
   const long M = (long)a->N * a->OH * a->OW;
-  if (nf > 16) {
-    // sliced: 256 -> 512 / 1024, 128 -> 512 in slices of 128 output channels.  Built, parity-green (tile = 70 on request), and SLOWER than the
-    // tiled kernel on every layer-2/3 shape (alone: 39.8 vs 24.9 us on the layer-3 hand-over gradient; in the step: -5 %, profiles/r05_conv_pws.txt):
-    // two waves per CU hold one 24 KiB tile in flight each.  The dispatcher takes it only with TINYFACES_PWS_SLICED=1.
-    const bool sliced = tf::tuning().pws_sliced;
-    if (!TF_EXP || !(ks == 4 || ks == 2) || a->Cout % 128 != 0 || M < 8192) return false;
-    return sliced || a->tile == 70;
-  }
   if (!((ks == 1 && nf == 16) || (ks == 4 && nf == 4) || (ks == 1 && nf == 4) || (ks == 4 && nf == 8))) return false;
   return M >= 16384;
 }

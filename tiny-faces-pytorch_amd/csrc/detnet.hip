@@ -60,9 +60,6 @@ int tf_upsample_add_crop_bwd(int, const float*, const float*, int, int, int, int
 int tf_reduce_partials(const float*, int, int, int, int, int, float*, int, void*);
 int tf_conv2d_wgrad_group(const tf_wgrad_args*, int, void*);
 }
-// (conv_pwx.hip; TF_ERR_UNSUPPORTED in the default build: the C entry points tf_conv2d_bnbwd / tf_conv2d_bnfwd exist in the experimental build only)
-int tf_conv_pwx_launch(const tf_conv_args*, const tf_bn_bwd_desc*, const void*, void*, int, float, hipStream_t);
-int tf_conv_pwx_launch_fwd(const tf_conv_args*, const tf_bn_fwd_desc*, const void*, const tf_bn_fwd_desc*, void*, int, float, float, float, hipStream_t);
 
 namespace {
 
@@ -693,7 +690,6 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
 
   // ---- bottlenecks
   const void* yin = P.pool;
-  bool tail_deferred = false;             // the previous bottleneck left c3 raw: this one's conv1 produces y on its way in
   for (size_t i = 0; i < A.blocks.size(); ++i) {
     const Block& B = A.blocks[i];
     Plan::Blk& b = P.blk[i];
@@ -704,23 +700,7 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
     conv_fill(a, dtype, 0, N, b.Hin, b.Win, B.cin, b.Hin, b.Win, pl, 1, 1, 0, pl, yin, b.w1, b.c1);
     if (tr) { a.epi = TF_EPI_STATS; a.stat_out = fused ? b.b1.fst : P.partial; stat_shift(a, c, B.c1, b.b1, fused); }
     else { bn_fold(c, B.c1, pl, b.b1, eps); a.epi = TF_EPI_AFFINE | TF_EPI_RELU; a.epi_scale = b.b1.scale; a.epi_shift = b.b1.shift; }
-    if (tail_deferred) {
-      // r5: the PREVIOUS bottleneck's  y = relu(bn3(c3) + residual)  rides on this conv's operand path (tf_conv2d_bnfwd, conv_pwx.hip): the
-      // pixel stages are transformed once in LDS on their way to the MFMAs and y (= yin: three more readers) is the launch's side output
-      const Block& Bp = A.blocks[i - 1];
-      Plan::Blk& bp = P.blk[i - 1];
-      const tf_bn_fwd_desc d3 = fwd_desc(c, Bp.c3, bp.b3);
-      tf_bn_fwd_desc dd; if (Bp.has_ds) dd = fwd_desc(c, Bp.ds, bp.bd);
-      const void* resid = Bp.has_ds ? bp.d : (i >= 2 ? P.blk[i - 2].y : P.pool);
-      a.x = bp.c3;
-      const int rc = tf_conv_pwx_launch_fwd(&a, &d3, resid, Bp.has_ds ? &dd : nullptr, bp.y, srows, (float)Min, eps, mom, c.stream);
-      if (rc == TF_ERR_UNSUPPORTED) {              // a shape the fused kernel does not take after all: the two launches it stands for
-        c.chk(tf_bn_add_relu_fused(dtype, bp.c3, &d3, resid, Bp.has_ds ? &dd : nullptr, srows, Min, B.cin, (float)Min, eps, mom, bp.y, c.stream));
-        a.x = yin;
-        c.chk(tf_conv2d(&a, c.stream));
-      } else c.chk(rc);
-      tail_deferred = false;
-    } else c.chk(tf_conv2d(&a, c.stream));
+    c.chk(tf_conv2d(&a, c.stream));
     // a1 = relu(bn1(c1)), materialised on purpose: every consumer (conv2, its weight gradient) uses the LDS-DMA pipeline
     if (fused) {
       const tf_bn_fwd_desc d = fwd_desc(c, B.c1, b.b1);
@@ -743,41 +723,22 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
       c.chk(tf_conv2d(&a, c.stream));
       if (tr && !fused) bn_finalize(c, B.ds, c4, b.bd, P.partial, tf_conv_mtiles(&a), a.ldy, (float)Mout, eps, mom);
     }
-    // a2 = relu(bn2(c2)): a launch of its own.  Folding it into conv3 (r3, tf_conv_args.bnf: the ring-less pointwise kernel activates its
-    // pixel tile in LDS and writes a2 for the weight gradient; bit-identical, tests/test_gpu_conv.py) removes 33 launches from the
-    // forward chain but LOSES 1.3 % on the step (A/B 1101 vs 1116 img/s): each of the 4-16 channel tiles of a pixel tile repeats the
-    // activation and the table derivation, and the extra barrier per stage sits in a launch that is latency-bound already.
-    // TINYFACES_BNF=1 turns it on (kept for the eval-sized shapes where pixel tiles >> channel tiles).
-    const bool bnf_on = TF_EXP && tf::tuning().bnf;
-    const bool bnf = fused && bnf_on && dtype != TF_F32 && pl <= 256;
-    tf_bn_fwd_desc d2;
-    if (fused) d2 = fwd_desc(c, B.c2, b.b2);
-    if (fused && !bnf) {
+    // a2 = relu(bn2(c2)): a launch of its own (folding it into conv3's LDS stage lost 1.3 % on the step: DESIGN_HISTORY.md)
+    if (fused) {
+      const tf_bn_fwd_desc d2 = fwd_desc(c, B.c2, b.b2);
       c.chk(tf_bn_relu_fused(dtype, b.c2, &d2, srows, Mout, pl, (float)Mout, eps, mom, b.a2, c.stream));
-    } else if (tr && !fused) {
+    } else if (tr) {
       c.chk(tf_bn_relu(dtype, b.c2, b.b2.scale, b.b2.shift, Mout, pl, b.a2, c.stream));
     }
     // conv3 1x1 (+ BN + residual + ReLU)
-    conv_fill(a, dtype, 0, N, b.Hout, b.Wout, pl, b.Hout, b.Wout, c4, 1, 1, 0, c4, bnf ? b.c2 : (tr ? b.a2 : b.c2), b.w3, tr ? b.c3 : b.y);
-    if (bnf) { a.bnf = &d2; a.bnf_out = b.a2; a.bnf_rows = srows; a.bnf_count = (float)Mout; a.bnf_eps = eps; a.bnf_momentum = mom; }
+    conv_fill(a, dtype, 0, N, b.Hout, b.Wout, pl, b.Hout, b.Wout, c4, 1, 1, 0, c4, tr ? b.a2 : b.c2, b.w3, tr ? b.c3 : b.y);
     if (tr) { a.epi = TF_EPI_STATS; a.stat_out = fused ? b.b3.fst : P.partial; stat_shift(a, c, B.c3, b.b3, fused); }
     else {
       bn_fold(c, B.c3, c4, b.b3, eps);
       a.epi = TF_EPI_AFFINE | TF_EPI_RES | TF_EPI_RELU; a.epi_scale = b.b3.scale; a.epi_shift = b.b3.shift; a.aux = B.has_ds ? b.d : yin;
     }
     c.chk(tf_conv2d(&a, c.stream));
-    // r5: the block's tail (bn3 + residual + ReLU) is NOT launched when the next bottleneck's conv1 can apply it on its operand path
-    // (bf16 training, conv1 with 128 / 256 output channels and 128 ... 1024 input channels: layers 2 and 3).  OPT-IN (TINYFACES_PWX_FWD=1): measured
-    // r5, it LOSES -- alone 37.4 us against 29.1 for the two launches at layer 3, 45.5 against 40.7 at layer 2 (profiles/r05_conv_pwx.txt); in the
-    // step 1238-1240 img/s against 1277-1279 without it (same box).  DESIGN.md 7.
-    const bool pwx_fwd_off = !(TF_EXP && tf::tuning().pwx_fwd);
-    if (fused && !pwx_fwd_off && dtype == TF_BF16 && i + 1 < A.blocks.size()) {
-      const Block& Bn = A.blocks[i + 1];
-      tail_deferred = Bn.cin == c4 && Bn.planes % 128 == 0 && Bn.cin % 64 == 0 && Bn.cin >= 128 && Bn.cin <= 1024;
-    }
-    if (tail_deferred) {
-      // nothing here
-    } else if (fused) {
+    if (fused) {
       const tf_bn_fwd_desc d3 = fwd_desc(c, B.c3, b.b3);
       tf_bn_fwd_desc dd; if (B.has_ds) dd = fwd_desc(c, B.ds, b.bd);
       c.chk(tf_bn_add_relu_fused(dtype, b.c3, &d3, B.has_ds ? b.d : yin, B.has_ds ? &dd : nullptr, srows, Mout, c4, (float)Mout, eps, mom, b.y,
@@ -1183,31 +1144,8 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
     const int nk = B.has_ds ? 3 : 2;
     if (!fused) c.chk(tf_colstats(dtype, Gcur, b.y, b.c3, b.d, Mout, c4, c4, P.partial_b, c.stream));
     else if (B.has_ds) c.chk(tf_colstats(dtype, Gcur, nullptr, b.c3, b.d, Mout, c4, c4, b.b3.bst, c.stream));   // Gcur is already masked
-    // (2) g_c3 -> T1.  r3: in bf16 the apply can ride on the operand path of the data gradient that consumes it (tf_conv2d_bnbwd,
-    //     conv_pwx.hip): steps (2) and (4) in ONE launch, T1 its side output for the weight gradient.  Measured (scripts/microbench_pwx.py,
-    //     profiles/r03_conv_pwx.txt): layer 2 (M = 47 628, K = 512 -> 128) 37.2 us against 43.1 for the two launches; layer 3 (M = 12 288,
-    //     K = 1024 -> 256) 31.6 against 29.8 -- 192 one-per-CU blocks pay the coefficient table and the register-staged operand where the
-    //     elementwise kernel has thousands of threads in flight.  So: the identity bottlenecks of layer 2 only (TINYFACES_PWX_ALL=1: every
-    //     eligible one, TINYFACES_PWX_OFF=1: none; the step is the same within noise either way, 1160 img/s).
-    // Measured r5 (profiles/r05_conv_pwx.txt): alone 27.8 us against 29.9 for the two launches at layer 3 but 46.8 against 40.9 at layer 2 (one block
-    // per CU with the deep rings); in the step: off 1287-1294, layer 2 only 1280-1287, layers 2 + 3 1277-1279 img/s.  So the fused form is
-    // OPT-IN now: TINYFACES_PWX_BWD=1 (layer 2) / TINYFACES_PWX_ALL=1 (layers 2 and 3).
-    const bool pwx_all = TF_EXP && tf::tuning().pwx_all;
-    const bool pwx_off = !TF_EXP || tf::tuning().pwx_off || (!tf::tuning().pwx_bwd && !pwx_all);
-    bool fused24 = false;
-    if (fused && !pwx_off && dtype == TF_BF16 && !B.has_ds && pl % 128 == 0 && (pl == 128 || pwx_all)) {
-      const tf_bn_bwd_desc d = bwd_desc(c, B.c3, b.b3, b.b3.bst, nk, 1);
-      conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hout, b.Wout, pl, 1, 1, 0, pl, Gcur, b.w3t, T2);
-      a.epi = TF_EPI_MASK | TF_EPI_STATS2; a.aux = b.c2; a.mask_scale = b.b2.scale; a.mask_shift = b.b2.shift; a.stat_out = b.b2.bst;
-      if (!late && !grouped) c.arm_fork();
-      const int rc = tf_conv_pwx_launch(&a, &d, b.c3, T1, srows, (float)Mout, c.stream);
-      if (rc == TF_OK) fused24 = true;
-      else if (rc != TF_ERR_UNSUPPORTED) c.chk(rc);
-      else if (tf::take_next_stop_event()) c.pending = nullptr;       // the armed event was not consumed: arm again below
-    }
-    if (fused24) {
-      // nothing: T1 and T2 are on their way
-    } else if (fused) {
+    // (2) g_c3 -> T1
+    if (fused) {
       const tf_bn_bwd_desc d = bwd_desc(c, B.c3, b.b3, b.b3.bst, nk, 1);
       if (!late && !grouped) c.arm_fork();
       c.chk(tf_bn_bwd_apply_fused(dtype, Gcur, nullptr, b.c3, &d, srows, Mout, c4, (float)Mout, T1, c.stream));
@@ -1220,12 +1158,10 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
     auto wg3 = [&]() { wgrad(c, B.c3, c4, N, b.Hout, b.Wout, b.Hout, b.Wout, b.a2, pl, T1, c4); };
     if (!grouped && !late) { c.fork_armed(); wg3(); }
     // (4) dgrad conv3 -> gz2 in T2 (masked by relu(bn2(c2))) + BN-backward sums
-    if (!fused24) {
-      conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hout, b.Wout, pl, 1, 1, 0, pl, T1, b.w3t, T2);
-      a.epi = TF_EPI_MASK | TF_EPI_STATS2; a.aux = b.c2; a.mask_scale = b.b2.scale; a.mask_shift = b.b2.shift;
-      a.stat_out = fused ? b.b2.bst : P.partial_b;
-      c.chk(tf_conv2d(&a, c.stream));
-    }
+    conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hout, b.Wout, pl, 1, 1, 0, pl, T1, b.w3t, T2);
+    a.epi = TF_EPI_MASK | TF_EPI_STATS2; a.aux = b.c2; a.mask_scale = b.b2.scale; a.mask_shift = b.b2.shift;
+    a.stat_out = fused ? b.b2.bst : P.partial_b;
+    c.chk(tf_conv2d(&a, c.stream));
     // (5) g_c2 in place
     if (fused) {
       const tf_bn_bwd_desc d = bwd_desc(c, B.c2, b.b2, b.b2.bst, 2, 1);

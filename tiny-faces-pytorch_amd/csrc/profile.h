@@ -10,8 +10,9 @@ namespace tf {
 //    inter-packet latency of the queue are inside the interval, and the two event packets perturb the stream;
 //  * kernel (r3, `kernel_mode = true` + TF_LAUNCH_TIMED at the launch site): the launch itself carries both events
 //    (hipExtLaunchKernelGGL startEvent / stopEvent), the interval is the dispatch's own begin / end time stamp -- what rocprofv3 reports
-//    for the same kernel -- and no packet is added to the stream.  A launch that also carries a fork's completion event (conv_pwx) falls
+//    for the same kernel -- and no packet is added to the stream.  A launch that also carries a fork's completion event falls
 //    back to the bracket.  TINYFACES_PROFILE_BRACKET=1 forces the bracket everywhere (A/B of the two clocks).
+// (kind numbers: include/tinyfaces_hip.h at tf_profile_enable.  17 is RETIRED -- it was conv_pwx, a removed kernel -- and is not reused.)
 struct ProfScope {
   int slot;
   hipStream_t stream;

@@ -10,7 +10,6 @@ struct Tuning {
   bool comm_fail_init = false;           // TINYFACES_COMM_FAIL_INIT
   int comm_fail_bucket = -1;             // TINYFACES_COMM_FAIL_BUCKET
   bool pws_off = false;                  // TINYFACES_PWS_OFF
-  bool pwx_fwd = false;                  // TINYFACES_PWX_FWD
   bool t12_shortk_off = false;           // TINYFACES_T12_SHORTK_OFF
   bool t46_shortk_off = false;           // TINYFACES_T46_SHORTK_OFF
   int shortk_big_tile = 46;              // TINYFACES_SHORTK_BIG_TILE
@@ -23,7 +22,6 @@ struct Tuning {
   bool conv3h_off = false;               // TINYFACES_CONV3H_OFF
   int conv3h_mincin = 256;               // TINYFACES_CONV3H_MINCIN
   bool conv3h_tr6 = true;                // TINYFACES_CONV3H_TR6 (0: evaluation launches never take the 6-row tile)
-  bool pws_sliced = false;               // TINYFACES_PWS_SLICED
   bool stem_direct_off = false;          // TINYFACES_STEM_DIRECT_OFF
   int wgrad_group = 8;                   // TINYFACES_WGRAD_GROUP
   bool fork_by_record = false;           // TINYFACES_FORK_BY_RECORD
@@ -31,7 +29,6 @@ struct Tuning {
   bool unfused_bn = false;               // TINYFACES_UNFUSED_BN
   bool pack_split_off = false;           // TINYFACES_PACK_SPLIT_OFF
   bool single_stream = false;            // TINYFACES_SINGLE_STREAM
-  bool bnf = false;                      // TINYFACES_BNF
   bool dbg_skip_wgrad = false;           // TINYFACES_DBG_SKIP_WGRAD
   bool wgrad3_off = false;               // TINYFACES_WGRAD3_OFF
   bool stem_wgrad_im2col = false;        // TINYFACES_STEM_WGRAD_IM2COL
@@ -39,9 +36,6 @@ struct Tuning {
   bool l3_fork_per_wgrad = false;        // TINYFACES_L3_FORK_PER_WGRAD
   bool dbg_group_refuse = false;         // TINYFACES_DBG_GROUP_REFUSE
   int wgradg_split = 1;                  // TINYFACES_WGRADG_SPLIT
-  bool pwx_all = false;                  // TINYFACES_PWX_ALL
-  bool pwx_off = false;                  // TINYFACES_PWX_OFF
-  bool pwx_bwd = false;                  // TINYFACES_PWX_BWD
   int handover_tile = 0;                 // TINYFACES_HANDOVER_TILE
   bool pool_stats_off = false;           // TINYFACES_POOL_STATS_OFF
   bool stem_apply_separate = false;      // TINYFACES_STEM_APPLY_SEPARATE

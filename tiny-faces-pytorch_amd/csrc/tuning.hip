@@ -15,7 +15,6 @@ Tuning parse() {
   t.comm_fail_init = flag("TINYFACES_COMM_FAIL_INIT");
   t.comm_fail_bucket = (int)num("TINYFACES_COMM_FAIL_BUCKET", -1);
   t.pws_off = flag("TINYFACES_PWS_OFF");
-  t.pwx_fwd = flag("TINYFACES_PWX_FWD");
   t.t12_shortk_off = flag("TINYFACES_T12_SHORTK_OFF");
   t.t46_shortk_off = flag("TINYFACES_T46_SHORTK_OFF");
   t.shortk_big_tile = (int)num("TINYFACES_SHORTK_BIG_TILE", 46);
@@ -28,7 +27,6 @@ Tuning parse() {
   t.conv3h_off = flag("TINYFACES_CONV3H_OFF");
   t.conv3h_mincin = (int)num("TINYFACES_CONV3H_MINCIN", 256);
   t.conv3h_tr6 = num("TINYFACES_CONV3H_TR6", 1) != 0;
-  t.pws_sliced = flag("TINYFACES_PWS_SLICED");
   t.stem_direct_off = flag("TINYFACES_STEM_DIRECT_OFF");
   t.wgrad_group = (int)num("TINYFACES_WGRAD_GROUP", 8);
   t.fork_by_record = flag("TINYFACES_FORK_BY_RECORD");
@@ -36,7 +34,6 @@ Tuning parse() {
   t.unfused_bn = flag("TINYFACES_UNFUSED_BN");
   t.pack_split_off = flag("TINYFACES_PACK_SPLIT_OFF");
   t.single_stream = flag("TINYFACES_SINGLE_STREAM");
-  t.bnf = flag("TINYFACES_BNF");
   t.dbg_skip_wgrad = flag("TINYFACES_DBG_SKIP_WGRAD");
   t.wgrad3_off = flag("TINYFACES_WGRAD3_OFF");
   t.stem_wgrad_im2col = flag("TINYFACES_STEM_WGRAD_IM2COL");
@@ -44,9 +41,6 @@ Tuning parse() {
   t.l3_fork_per_wgrad = flag("TINYFACES_L3_FORK_PER_WGRAD");
   t.dbg_group_refuse = flag("TINYFACES_DBG_GROUP_REFUSE");
   t.wgradg_split = (int)num("TINYFACES_WGRADG_SPLIT", 1);
-  t.pwx_all = flag("TINYFACES_PWX_ALL");
-  t.pwx_off = flag("TINYFACES_PWX_OFF");
-  t.pwx_bwd = flag("TINYFACES_PWX_BWD");
   t.handover_tile = (int)num("TINYFACES_HANDOVER_TILE", 0);
   t.pool_stats_off = flag("TINYFACES_POOL_STATS_OFF");
   t.stem_apply_separate = flag("TINYFACES_STEM_APPLY_SEPARATE");

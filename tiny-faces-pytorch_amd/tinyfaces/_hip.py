@@ -184,18 +184,6 @@ _DEBUG_SIGNATURES = {
 _lib = None
 
 
-# entry points of the EXPERIMENTAL build only (build.py --experimental; include/tinyfaces_hip.h `#ifdef TF_EXPERIMENTAL`): bound when the library has them
-_EXPERIMENTAL_SIGNATURES = {
-    "tf_conv2d_bnbwd": (i32, [C.POINTER(ConvArgs), C.POINTER(BnBwdDesc), vp, vp, i32, f32, vp]),
-    "tf_conv2d_bnfwd": (i32, [C.POINTER(ConvArgs), C.POINTER(BnFwdDesc), vp, C.POINTER(BnFwdDesc), vp, i32, f32, f32, f32, vp]),
-}
-
-
-def experimental():
-    """True when the loaded library was built with TF_EXPERIMENTAL (the measured-and-lost kernels compiled in)."""
-    return lib().tf_build_id().decode().endswith("+x")
-
-
 def lib():
     """The loaded library (raises HipLibraryMissing with build instructions if absent)."""
     global _lib
@@ -208,7 +196,7 @@ def lib():
         for name, (res, args) in _SIGNATURES.items():
             fn = getattr(l, name)          # AttributeError here == ABI mismatch with include/tinyfaces_hip.h
             fn.restype, fn.argtypes = res, args
-        for name, (res, args) in list(_DEBUG_SIGNATURES.items()) + list(_EXPERIMENTAL_SIGNATURES.items()):
+        for name, (res, args) in _DEBUG_SIGNATURES.items():
             fn = getattr(l, name, None)
             if fn is not None:
                 fn.restype, fn.argtypes = res, args
