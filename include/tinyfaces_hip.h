@@ -203,7 +203,7 @@ typedef struct tf_conv_args {
                          conv_pws takes EXACTLY: 1x1 / stride 1 / pad 0, bf16 or fp16, no prologue, ldy == Cout, M >= 16 384 pixels,
                          (Cin, Cout) in {(64, 256), (256, 64), (64, 64), (256, 128)}, epilogue sets AFFINE[+RELU], AFFINE+RES+RELU (both types) and, bf16
                          only, none, STATS, MASK+STATS2, RES[+MASK2[+STATS3]]; statistic epilogues only with folded rows (tf_get_stat_rows() <=
-                         TF_STAT_ROWS).  0 picks it for those launches (TINYFACES_PWS_OFF=1: never); tile = 70 on anything else is TF_ERR_UNSUPPORTED from
+                         TF_STAT_ROWS).  0 picks it for those launches (an explicit tile code reaches the tiled kernel there); tile = 70 on anything else is TF_ERR_UNSUPPORTED from
                          tf_conv2d and from tf_conv_mtiles (negative return).
                          Codes 1-3 (the register-staged kernel of round 1, removed in r4) and code 60 (a register-staged pointwise kernel with
                          BatchNorm prologues, measured slower on every layer and removed) are TF_ERR_UNSUPPORTED from tf_conv2d and from

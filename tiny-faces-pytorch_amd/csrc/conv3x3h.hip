@@ -436,10 +436,6 @@ __global__ void __launch_bounds__(NT, 2) conv3x3h_kernel(const HK a) {
 
 unsigned long long* g_trace = nullptr;
 int g_last_tile_rows = 0;          // tile height of the most recent launch (tf_debug_conv3x3h_tile_rows: which instantiation a test just ran)
-int dbg_flags() { return tf::tuning().conv3h_dbg; }
-int min_blocks() {
-  return tf::tuning().conv3h_minblocks;
-}
 
 template <typename T, bool TRACE, int EPIC = -1, int TR_ = 4>
 void launch_var(const HK& k, hipStream_t stream) {
@@ -462,10 +458,10 @@ int launch(const tf_conv_args* A, hipStream_t stream) {
   k.ntiles = A->Cout / BN; k.epi = A->epi; k.srows = tf_get_stat_rows();
   // tile height (r6): evaluation launches (folded BN + ReLU) whose 4-row tiles leave a mostly empty last round of blocks take 6-row tiles when
   // that makes rounds x rows smaller -- 1 x 120 x 160 (the 1920 x 2560 level): 300 blocks = 2 rounds x 4 rows against 200 blocks = 1 round x 6 rows.
-  // The statistic epilogues of the training step keep TR = 4 (tf_conv3x3h_mtiles sizes their partial rows).  TINYFACES_CONV3H_TR6=0: never.
+  // The statistic epilogues of the training step keep TR = 4 (tf_conv3x3h_mtiles sizes their partial rows).
   k.ctiles = (A->OW + TC - 1) / TC;
   bool tall = false;
-  if (A->epi == (TF_EPI_AFFINE | TF_EPI_RELU) && !g_trace && !tf::tuning().epi_spec_off && tf::tuning().conv3h_tr6) {
+  if (A->epi == (TF_EPI_AFFINE | TF_EPI_RELU) && !g_trace) {
     const long cus = tf::device_cus();
     auto cost = [&](int tr) { const long blocks = (long)A->N * ((A->OH + tr - 1) / tr) * k.ctiles * k.ntiles; return ((blocks + cus - 1) / cus) * tr; };
     tall = cost(6) < cost(4);
@@ -474,7 +470,7 @@ int launch(const tf_conv_args* A, hipStream_t stream) {
   g_last_tile_rows = tr;
   k.rtiles = (A->OH + tr - 1) / tr; k.mtiles = A->N * k.rtiles * k.ctiles;
   k.sign = A->mode == 0 ? 1 : -1;                    // forward reads pixel + (kh-1, kw-1); the data gradient reads pixel - (kh-1, kw-1)
-  k.dbg = dbg_flags(); k.trace = g_trace;
+  k.dbg = tf::tuning().conv3h_dbg; k.trace = g_trace;
   const double es = sizeof(T), M = (double)A->N * A->OH * A->OW, Kt = k.Ktot;
   double bytes = (M * A->Cin + (double)A->Cout * Kt + M * A->Cout) * es;
   if (A->epi & (TF_EPI_RES | TF_EPI_MASK | TF_EPI_STATS2)) bytes += M * A->Cout * es;
@@ -482,14 +478,18 @@ int launch(const tf_conv_args* A, hipStream_t stream) {
   if (A->epi & TF_EPI_MASK2) bytes += M * A->Cout * es;
   if (A->epi & TF_EPI_STATS3) bytes += M * A->Cout * es;
   tf::ProfScope prof(A->dtype == TF_BF16 ? 6 : 7, 2.0 * M * A->Cout * Kt, bytes, stream, (int)M, A->Cout, k.Ktot, 9, A->mode, A->epi, -1.0, true);   // 6 = conv3x3h bf16, 7 = f16
-  const bool spec_off = tf::tuning().epi_spec_off;       // A/B knob (shared with conv_dma)
+  // Three flag sets have a specialised epilogue; every other one takes the run-time flags.  That generic arm is really the `else` of the
+  // chain.  It stands second, behind a negated test, for ONE reason: hipcc emits the instantiations in the order the chain names them, and
+  // this order keeps the code object byte-identical to the one the step A/Bs were taken on.  Whoever next changes this file's device code
+  // anyway should move it to the end as a plain `else`.
+  const int e = A->epi;
+  const bool specialised = e == TF_EPI_STATS || e == (TF_EPI_MASK | TF_EPI_STATS2) || e == (TF_EPI_AFFINE | TF_EPI_RELU);
   if (g_trace) launch_var<T, true>(k, stream);
-  else if (spec_off) launch_var<T, false>(k, stream);
-  else if (A->epi == TF_EPI_STATS) launch_var<T, false, TF_EPI_STATS>(k, stream);                                           // training forward
-  else if (A->epi == (TF_EPI_MASK | TF_EPI_STATS2)) launch_var<T, false, TF_EPI_MASK | TF_EPI_STATS2>(k, stream);           // training data gradient
-  else if (A->epi == (TF_EPI_AFFINE | TF_EPI_RELU) && tall) launch_var<T, false, TF_EPI_AFFINE | TF_EPI_RELU, 6>(k, stream);
-  else if (A->epi == (TF_EPI_AFFINE | TF_EPI_RELU)) launch_var<T, false, TF_EPI_AFFINE | TF_EPI_RELU>(k, stream);           // evaluation (folded BN + ReLU)
-  else launch_var<T, false>(k, stream);
+  else if (!specialised) launch_var<T, false>(k, stream);                                                      // run-time epilogue flags
+  else if (e == TF_EPI_STATS) launch_var<T, false, TF_EPI_STATS>(k, stream);                                   // training forward
+  else if (e == (TF_EPI_MASK | TF_EPI_STATS2)) launch_var<T, false, TF_EPI_MASK | TF_EPI_STATS2>(k, stream);   // training data gradient
+  else if (tall) launch_var<T, false, TF_EPI_AFFINE | TF_EPI_RELU, 6>(k, stream);                              // evaluation (folded BN + ReLU), 6-row tiles
+  else launch_var<T, false, TF_EPI_AFFINE | TF_EPI_RELU>(k, stream);                                           // evaluation, 4-row tiles
   return hipGetLastError() == hipSuccess ? TF_OK : TF_ERR_LAUNCH;
 }
 
@@ -502,14 +502,11 @@ bool tf_conv3x3h_applicable(const tf_conv_args* a, bool forced) {
   if (a->KH != 3 || a->KW != 3 || a->stride != 1 || a->pad != 1 || a->H != a->OH || a->W != a->OW) return false;
   if (a->Cin % 64 != 0 || a->Cout % BN != 0 || a->pro_scale) return false;
   if (forced) return true;
-  const bool off = tf::tuning().conv3h_off;
-  if (off) return false;
   // >= 4 channel chunks (36 stages): with the 18 stages of layer 2 (128 channels) the prologue / epilogue weigh too much and the
   // 64 x 128 im2col tile wins (A/B on one box: 1116 / 1114 img/s without layer 2, 1107 / 1111 with)
-  const int min_cin = tf::tuning().conv3h_mincin;
-  if (a->Cin < min_cin) return false;
+  if (a->Cin < 256) return false;
   const long blocks = (long)a->N * ((a->OH + TR - 1) / TR) * ((a->OW + TC - 1) / TC) * (a->Cout / BN);
-  return blocks >= min_blocks();
+  return blocks >= 160;      // fewer blocks leave CUs idle: the im2col tiles take the launch
 }
 // debugging: register (or clear, nullptr) a device buffer of 8 blocks x 8 waves x 64 stages x 8 u64 for the stage stamps of the
 // NEXT launches (scripts/trace_conv3x3h.py); not part of the product path

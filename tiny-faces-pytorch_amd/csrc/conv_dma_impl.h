@@ -246,7 +246,7 @@ __global__ void __launch_bounds__(256, MMA == 32 ? 2 : (NS <= 2 && BM == 128 && 
   // mask / statistic operands (up to three tensors as large as the output) used to be requested only after the K loop, with the
   // whole HBM latency exposed once per block.  Request them NOW: they travel while the K stages are DMA-ed and multiplied.
   // (Older loads retire first, so the counted vmcnt waits of the K loop are unaffected.)
-  // (r4: also the 2-deep form of the 128 x 64 tile for the hand-over class: TINYFACES_HANDOVER_TILE=42)
+  // (r4: also the 2-deep form of the 128 x 64 tile for the hand-over class: tile code 42)
   constexpr bool PREF = (NS == 1 && KIND == 1) || (NS == 2 && KIND == 1 && BM == 128 && BN == 64 && MMA == 16 && EPIC == (TF_EPI_RES | TF_EPI_MASK2 | TF_EPI_STATS3));
   // r4, hand-over instantiation (RES | MASK2 | STATS3 known at compile time): two of its three epilogue operands are COLD -- aux2 (the
   // previous block's output y) and aux3 (its conv3 output) were written in the forward pass -- and the third, the residual gradient, was
@@ -595,28 +595,25 @@ int launch_kind(const tf_conv_args* A, hipStream_t stream, int pcls = -1) {
     constexpr bool SPEC = sizeof(T) == 2 && ((MMA == 32 && BM == 64 && BN == 128 && NS == 2) || (MMA == 16 && BM == 128 && BN == 64 && NS == 1 && KIND != 2) || (MMA == 16 && BM == 128 && BN == 64 && NS == 2 && KIND == 1) ||
                                              (MMA == 16 && BM == 64 && BN == 64 && NS <= 3));
     constexpr bool TRAIN = std::is_same<T, tf::bf16_t>::value;          // the training flag sets: bf16 only (fp16 is inference only)
-    const bool spec_off = tf::tuning().epi_spec_off;       // A/B knob
     const dim3 grid(mtiles * k.ntiles);
     bool done = false;
     if constexpr (SPEC) {
-      if (!spec_off) {
-        auto go = [&](auto epic) {
-          constexpr int E = decltype(epic)::value;
-          static tf::PerDevice set;
-          if (set.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_kernel<T, BM, BN, NS, KIND, MMA, E>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          TF_LAUNCH_TIMED((conv_dma_kernel<T, BM, BN, NS, KIND, MMA, E>), grid, dim3(256), lds, stream, k);
-          done = true;
-        };
-        if constexpr (TRAIN) {
-          if (A->epi == TF_EPI_STATS) go(std::integral_constant<int, TF_EPI_STATS>{});
-          else if (A->epi == (TF_EPI_MASK | TF_EPI_STATS2)) go(std::integral_constant<int, TF_EPI_MASK | TF_EPI_STATS2>{});
-          else if (KIND == 1 && A->epi == (TF_EPI_RES | TF_EPI_MASK2 | TF_EPI_STATS3)) go(std::integral_constant<int, TF_EPI_RES | TF_EPI_MASK2 | TF_EPI_STATS3>{});
-          else if (KIND == 1 && A->epi == (TF_EPI_MASK2 | TF_EPI_STATS3)) go(std::integral_constant<int, TF_EPI_MASK2 | TF_EPI_STATS3>{});      // r6: the hand-over of layer2.0 (its residual arrives in place, behind it)
-        }
-        if (!done && KIND != 2) {                      // the folded-BN epilogues of the evaluation graph (forward convs only)
-          if (A->epi == (TF_EPI_AFFINE | TF_EPI_RELU)) go(std::integral_constant<int, TF_EPI_AFFINE | TF_EPI_RELU>{});
-          else if (KIND == 1 && A->epi == (TF_EPI_AFFINE | TF_EPI_RES | TF_EPI_RELU)) go(std::integral_constant<int, TF_EPI_AFFINE | TF_EPI_RES | TF_EPI_RELU>{});
-        }
+      auto go = [&](auto epic) {
+        constexpr int E = decltype(epic)::value;
+        static tf::PerDevice set;
+        if (set.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_kernel<T, BM, BN, NS, KIND, MMA, E>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        TF_LAUNCH_TIMED((conv_dma_kernel<T, BM, BN, NS, KIND, MMA, E>), grid, dim3(256), lds, stream, k);
+        done = true;
+      };
+      if constexpr (TRAIN) {
+        if (A->epi == TF_EPI_STATS) go(std::integral_constant<int, TF_EPI_STATS>{});
+        else if (A->epi == (TF_EPI_MASK | TF_EPI_STATS2)) go(std::integral_constant<int, TF_EPI_MASK | TF_EPI_STATS2>{});
+        else if (KIND == 1 && A->epi == (TF_EPI_RES | TF_EPI_MASK2 | TF_EPI_STATS3)) go(std::integral_constant<int, TF_EPI_RES | TF_EPI_MASK2 | TF_EPI_STATS3>{});
+        else if (KIND == 1 && A->epi == (TF_EPI_MASK2 | TF_EPI_STATS3)) go(std::integral_constant<int, TF_EPI_MASK2 | TF_EPI_STATS3>{});      // r6: the hand-over of layer2.0 (its residual arrives in place, behind it)
+      }
+      if (!done && KIND != 2) {                      // the folded-BN epilogues of the evaluation graph (forward convs only)
+        if (A->epi == (TF_EPI_AFFINE | TF_EPI_RELU)) go(std::integral_constant<int, TF_EPI_AFFINE | TF_EPI_RELU>{});
+        else if (KIND == 1 && A->epi == (TF_EPI_AFFINE | TF_EPI_RES | TF_EPI_RELU)) go(std::integral_constant<int, TF_EPI_AFFINE | TF_EPI_RES | TF_EPI_RELU>{});
       }
     }
     if (!done) TF_LAUNCH_TIMED((conv_dma_kernel<T, BM, BN, NS, KIND, MMA>), grid, dim3(256), lds, stream, k);
@@ -631,9 +628,8 @@ int launch(const tf_conv_args* A, hipStream_t stream) {
   // r3: the data gradient of a 1x1 / stride-2 / pad-0 conv (the downsample branches of layer2.0 and layer3.0) is the pointwise GEMM over the
   // gradient's own pixels, scattered to the even-even positions of the 2x larger output raster (the rest is zero, or the residual
   // operand): the pointwise kernel with a row map instead of the transposed gather over all four parities.  Epilogues that reduce over
-  // the output raster (statistics) or read a mask there keep the generic kernel; TINYFACES_SCATTER_DGRAD_OFF=1: A/B knob.
-  const bool scat_off = tf::tuning().scatter_dgrad_off;
-  if (!scat_off && A->mode == 1 && A->KH == 1 && A->KW == 1 && A->stride == 2 && A->pad == 0 && A->OH >= 2 * A->H - 1 && A->OW >= 2 * A->W - 1 &&
+  // the output raster (statistics) or read a mask there keep the generic kernel.
+  if (A->mode == 1 && A->KH == 1 && A->KW == 1 && A->stride == 2 && A->pad == 0 && A->OH >= 2 * A->H - 1 && A->OW >= 2 * A->W - 1 &&
       A->ldy == A->Cout &&
       (!(A->epi & ~(TF_EPI_RES | TF_EPI_AFFINE)) ||
        // r6: IN PLACE (aux == y): the raster already holds another launch's result and the scattered rows are added to it -- then the ReLU mask
@@ -646,8 +642,7 @@ int launch(const tf_conv_args* A, hipStream_t stream) {
   // walks all 9 for every pixel and reads the zero page for the rest (4x the stages, DMAs and MFMAs: 134 and 113 us per launch at
   // bs = 12, 8-13x over their roofline, profiles/r02_layer_table.md).  Four launches, each a gather over its class's half-resolution
   // raster with its own tap list; rows scatter back to (2h + ph, 2w + pw); statistic sums fold into the same rows by atomics.
-  const bool par_off = tf::tuning().parity_dgrad_off;
-  if (!par_off && A->mode == 1 && A->stride == 2 && A->KH == 3 && A->KW == 3 && A->pad == 1 && A->OH >= 2 && A->OW >= 2 &&
+  if (A->mode == 1 && A->stride == 2 && A->KH == 3 && A->KW == 3 && A->pad == 1 && A->OH >= 2 && A->OW >= 2 &&
       (tf_get_stat_rows() <= TF_STAT_ROWS || !(A->epi & (TF_EPI_STATS | TF_EPI_STATS2 | TF_EPI_STATS3)))) {
     for (int pc = 0; pc < 4; ++pc) {
       const int rc = launch_kind<T, BM, BN, NS, 2, MMA>(A, stream, pc);
@@ -668,19 +663,17 @@ int launch_half(const tf_conv_args* a, int tile, int depth, hipStream_t stream) 
   if (tile == 1) return launch<T, 128, 128, 3>(a, stream);
   if (tile == 2) {
     if (depth == 1) return launch<T, 128, 64, 1>(a, stream);       // tile code 32: ring-less, short K (see pick_tile)
-    if (depth == 2) return launch<T, 128, 64, 2>(a, stream);       // tile code 42 (r4: A/B form of the hand-over data gradient)
+    if (depth == 2) return launch<T, 128, 64, 2>(a, stream);       // tile code 42 (explicit requests only)
     return depth == 4 ? launch<T, 128, 64, 4>(a, stream) : launch<T, 128, 64, 3>(a, stream);
   }
   if (depth == 3) {
     // convs of up to 16 K-stages (every 1x1 of the trunk, K <= 1024) are dispatch + prologue + epilogue bound rather than
     // K-loop bound: a 2-deep ring is 32 KiB of LDS, so five blocks fit a CU instead of three and more of those phases
     // overlap.  A/B on one box, img/s: 956 (3-deep everywhere), 989 (<= 4 stages), 996 (<= 8), 1008 (<= 16), 1001 (all).
-    const int ns2_max = tf::tuning().ns2_maxstages;
     const int nst = a->KH * a->KW * (a->Cin / 64);
     // ... and no ring at all up to 4 stages (17 KiB of LDS, 8 blocks/CU): 1007 -> 1013 img/s
-    const int ns1_max = tf::tuning().ns1_maxstages;
-    if (nst <= ns1_max) return launch<T, 64, 64, 1>(a, stream);
-    if (nst <= ns2_max) return launch<T, 64, 64, 2>(a, stream);
+    if (nst <= 4) return launch<T, 64, 64, 1>(a, stream);
+    if (nst <= 16) return launch<T, 64, 64, 2>(a, stream);
     return launch<T, 64, 64, 3>(a, stream);
   }
   return launch<T, 64, 64, 4>(a, stream);

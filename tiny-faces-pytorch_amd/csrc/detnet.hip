@@ -66,12 +66,7 @@ namespace {
 constexpr int kStemK = 192;     // 147 taps*channels padded to 3 x 64
 // r4: conv1 AND its weight gradient straight from the image (csrc/stem_conv.hip: tf_stem_conv, tf_stem_wgrad) for the 2-byte operand types:
 // no 288 MB im2col matrix in a training step or an evaluation forward.  fp32 and the unfolded-statistics mode keep im2col + GEMM.
-// TINYFACES_STEM_DIRECT_OFF=1: the path of rounds 1-3; TINYFACES_STEM_WGRAD_IM2COL=1: only the weight gradient over the im2col matrix (built on
-// the second stream at the top of the backward pass).
-bool stem_direct_mode(int dtype, bool training, bool fused) {
-  const bool off = tf::tuning().stem_direct_off;
-  return !off && dtype != TF_F32 && (!training || fused);
-}
+bool stem_direct_mode(int dtype, bool training, bool fused) { return dtype != TF_F32 && (!training || fused); }
 constexpr int kHeadLd = 128;    // 125 outputs padded
 constexpr int kConstC = 1024;   // widest channel count of the trunk (layer 3 output)
 constexpr int kFrozen = TF_DETNET_FROZEN_BN;     // `training` = 2: the evaluation forward + a backward through the folded BN
@@ -156,9 +151,10 @@ const Arch* find_arch(const int* blocks) {
 }
 
 // r4: the weight gradients of the identity bottlenecks of layer 3 (22 blocks of identical shape) are differentiated in GROUPS of up to
-// this many bottlenecks per launch (tf_conv2d_wgrad_group: full-K tiles, no split-K / atomics / partial tiles); their dY operands then
-// live in per-block buffers instead of the two parity sets.  TINYFACES_WGRAD_GROUP=0: the per-block launches of rounds 1-3.
-inline bool wgrad_group_mode(int dtype, int training) { return training && dtype == TF_BF16 && tf::tuning().wgrad_group > 0; }
+// kWgradGroup bottlenecks per launch (tf_conv2d_wgrad_group: full-K tiles, no split-K / atomics / partial tiles); their dY operands then
+// live in per-block buffers instead of the two parity sets.
+constexpr int kWgradGroup = 8;
+inline bool wgrad_group_mode(int dtype, int training) { return training && dtype == TF_BF16; }
 
 inline int down2(int n) { return (n - 1) / 2 + 1; }   // every stride-2 stage of the trunk: ceil(n/2)
 inline size_t esize(int dtype) { return dtype == TF_F32 ? 4 : 2; }
@@ -379,8 +375,7 @@ struct Ctx {
   // weight-gradient stream wait for it.  hipEventRecord costs a barrier packet = an ~8 us bubble on the data-gradient chain
   // (profiles/r02_step_timeline.txt), three to four times per bottleneck.
   hipEvent_t pending = nullptr;
-  static bool kernel_events() { return !tf::tuning().fork_by_record; }
-  void arm_fork() { if (!side || !kernel_events()) return; pending = next_event(); if (pending) tf::set_next_stop_event(pending); }
+  void arm_fork() { if (!side) return; pending = next_event(); if (pending) tf::set_next_stop_event(pending); }
   void fork_armed() {
     if (!side) return;
     if (tf::take_next_stop_event()) pending = nullptr;     // armed but no kernel took it (the producer refused its arguments): plain fork
@@ -447,8 +442,7 @@ void bn_finalize(Ctx& c, const ConvUnit& u, int C, BnBuf& b, const float* partia
 // s in the extra row of the BN's statistic region, where the consumer's table picks it up (fused flow only; bn_fused.hip fwd_table).
 // E[x^2] - mean^2 from fp32 sums loses (mean / std)^2 of the significant bits; around the running mean it loses ((mean - s) / std)^2.
 void stat_shift(tf_conv_args& a, const Ctx& c, const ConvUnit& u, const BnBuf& b, bool fused) {
-  const bool off = tf::tuning().stat_shift_off;       // A/B + parity knob
-  if (!fused || off || !b.fst || u.rmean < 0) return;
+  if (!fused || !b.fst || u.rmean < 0) return;
   a.stat_shift = (const float*)c.params[u.rmean];
   a.stat_shift_out = b.fst + (size_t)TF_STAT_ROWS * 2 * b.C;
 }
@@ -605,18 +599,17 @@ extern "C" int tf_detnet_trunk_forward_ctx(const int* blocks, tf_detnet_ctx* xct
   // statistics folded into <= TF_STAT_ROWS rows: the elementwise consumers finalize them in-kernel (bn_fused.hip);
   // unfolded (tf_set_stat_rows(0), bit-reproducible sums): separate finalize kernels on the shared partial buffer
   const int srows = tf_get_stat_rows();
-  const bool g_unfused_env = tf::tuning().unfused_bn;     // A/B knob
-  const bool fused = tr && srows <= TF_STAT_ROWS && !g_unfused_env;
+  const bool fused = tr && srows <= TF_STAT_ROWS;
   // statistic rows start at zero: the per-BN regions and, right behind them in the arena, the head of the shared partial buffer -- ONE memset
   if (tr && hipMemsetAsync(P.stat_fwd, 0, (size_t)((char*)P.partial - (char*)P.stat_fwd) + (size_t)TF_STAT_ROWS * 3 * 1024 * 4, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
   // ---- stem: conv1 (direct, or im2col + GEMM) (+BN+ReLU) + maxpool
   const int M1 = N * P.H1 * P.W1;
   // r3: the weights of layer 3 and of the heads (62 % of the bytes) are packed on the context's second stream (idle during the forward pass:
   // no further hardware queue), forked at the top of the step and joined in front of the first layer-3 bottleneck: beside the stem and
-  // layers 1-2, whose launches are latency-bound at bs = 12, instead of in front of them.  TINYFACES_PACK_SPLIT_OFF=1, TINYFACES_SINGLE_STREAM=1
-  // or `single_stream`: everything inline.
+  // layers 1-2, whose launches are latency-bound at bs = 12, instead of in front of them.  TINYFACES_SINGLE_STREAM=1 or `single_stream`:
+  // everything inline.
   hipStream_t pack_stream = nullptr;
-  if (step && !ready && !tf::tuning().pack_split_off && !tf::tuning().single_stream && !single_stream && xctx) {
+  if (step && !ready && !tf::tuning().single_stream && !single_stream && xctx) {
     pack_stream = ctx_side(xctx);
     if (pack_stream && !xctx->pack_fork && (hipEventCreateWithFlags(&xctx->pack_fork, hipEventDisableTiming) != hipSuccess ||
                                             hipEventCreateWithFlags(&xctx->pack_join, hipEventDisableTiming) != hipSuccess)) pack_stream = nullptr;
@@ -813,10 +806,7 @@ void wgrad(Ctx& c, const ConvUnit& u, int cout, int N, int H, int W, int OH, int
     // 3x3 / stride 1: the all-taps kernel sums its split-K slices through the scratch straight into the (already zeroed) OIHW
     // gradient: no memset, no atomics, no transposing copy
     w.partial_ws = packed_scratch; w.partial_ws_bytes = scratch_floats * 4;
-    if (tf_wgrad_workspace_bytes(&w) != 0 && tf_wgrad_workspace_bytes(&w) <= w.partial_ws_bytes) {
-      const bool w3_off = tf::tuning().wgrad3_off;
-      if (!w3_off) { c.chk(tf_conv2d_wgrad(&w, c.wstream())); return; }
-    }
+    if (tf_wgrad_workspace_bytes(&w) != 0 && tf_wgrad_workspace_bytes(&w) <= w.partial_ws_bytes) { c.chk(tf_conv2d_wgrad(&w, c.wstream())); return; }
     w.partial_ws = nullptr; w.partial_ws_bytes = 0;
   }
   if (k > 1 && packed_scratch) {          // 3x3 (stride 2): coalesced atomics into [Cout][tap][Cin], then one transposing copy to OIHW
@@ -996,7 +986,7 @@ struct WgradGroups {
   WgradGroups(const Arch& A, bool on) {
     if (!on) return;
     first_id = A.layer_end[1] + 2; last_id = A.layer_end[2];
-    const int nid = last_id - first_id + 1, gs = tf::tuning().wgrad_group, ng = (nid + gs - 1) / gs;
+    const int nid = last_id - first_id + 1, gs = kWgradGroup, ng = (nid + gs - 1) / gs;
     for (int g = 1; g <= ng; ++g) group_close.push_back(last_id + 1 - (int)(((long long)nid * g + ng - 1) / ng));      // balanced: 8 + 7 + 7 (ResNet-101)
   }
   bool grouped(int i) const { return i >= first_id && i <= last_id; }
@@ -1024,15 +1014,11 @@ struct WgradGroups {
       int rc = force_refuse ? TF_ERR_UNSUPPORTED : tf_conv2d_wgrad_group(pend_c3.data(), (int)pend_c3.size(), c.wstream());
       if (rc == TF_ERR_UNSUPPORTED) fallback(pend_c3);
       else c.chk(rc);
-      // r5: the pointwise group in `pw_split` launches (default 1).  A group of eight bottlenecks is 256 tiles = one block on EVERY CU for
-      // ~150 us, and beside it the chain's kernels crawl (profiles/r05_step_timeline.txt: the data gradient that normally takes 22 us
-      // takes 118-130 us while the group runs); split, each launch leaves CUs to the chain.  TINYFACES_WGRADG_SPLIT=n.
-      const int pw_split = tf::tuning().wgradg_split;
-      const int npw = (int)pend_pw.size(), per = (npw + pw_split - 1) / pw_split;
-      rc = TF_OK;
-      for (int at = 0; at < npw && rc == TF_OK; at += per)
-        rc = force_refuse ? TF_ERR_UNSUPPORTED : tf_conv2d_wgrad_group(pend_pw.data() + at, npw - at < per ? npw - at : per, c.wstream());
-      if (rc == TF_ERR_UNSUPPORTED) fallback(pend_pw);        // (the first launch already refuses: all problems of a group have the same kind of shape)
+      // The pointwise group is ONE launch.  A group of eight bottlenecks is 256 tiles = one block on EVERY CU for ~150 us, and beside it the
+      // chain's kernels crawl (profiles/r05_step_timeline.txt: the data gradient that normally takes 22 us takes 118-130 us while the group
+      // runs); split into several launches that leave CUs to the chain, the step measured no faster (DESIGN_HISTORY.md section 7, row 46).
+      rc = force_refuse ? TF_ERR_UNSUPPORTED : tf_conv2d_wgrad_group(pend_pw.data(), (int)pend_pw.size(), c.wstream());
+      if (rc == TF_ERR_UNSUPPORTED) fallback(pend_pw);
       else c.chk(rc);
     }
     // a gradient-ready event of a grouped block promises "every gradient of the blocks >= it, and of the heads": all of them are on this stream
@@ -1048,8 +1034,8 @@ struct WgradGroups {
 // the res3 head gradient, copied) a raster of that size, scattered into it, and the hand-over conv read it back as its residual: a
 // 96 MB fill + 49 MB copy by blit kernels at 2.6 TB/s and two more passes over those rasters.  Now the hand-over writes the raster first
 // (residual = the head gradient where there is one) and the scattered gradient ACCUMULATES IN PLACE (tf_conv2d: aux == y), applying the
-// same ReLU mask and adding its own share to the same BN-backward sums.  TINYFACES_DS_INPLACE_OFF=1, or a caller whose hand-over does not
-// mask (!inplace_ok): the old order, through P.T4.
+// same ReLU mask and adding its own share to the same BN-backward sums.  A caller whose hand-over does not mask (!inplace_ok):
+// the old order, through P.T4.
 template <class F>
 void input_gradient(Ctx& c, const Plan& P, const Block& B, const Plan::Blk& b, const void* g1, const void* gskip, const void* extra, void* dst,
                     bool inplace_ok, F&& hand_over) {
@@ -1060,7 +1046,7 @@ void input_gradient(Ctx& c, const Plan& P, const Block& B, const Plan::Blk& b, c
     a.epi = TF_EPI_RES; a.aux = gskip;
     hand_over(a);
     c.chk(tf_conv2d(&a, c.stream));
-  } else if (inplace_ok && B.stride == 2 && !tf::tuning().ds_inplace_off) {
+  } else if (inplace_ok && B.stride == 2) {
     conv_fill(a, dtype, 1, N, b.Hin, b.Win, pl, b.Hin, b.Win, B.cin, 1, 1, 0, B.cin, g1, b.w1t, dst);
     if (extra) { a.epi = TF_EPI_RES; a.aux = extra; }
     hand_over(a);
@@ -1068,7 +1054,6 @@ void input_gradient(Ctx& c, const Plan& P, const Block& B, const Plan::Blk& b, c
     conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hin, b.Win, B.cin, 1, B.stride, 0, B.cin, gskip, b.wdt, dst);
     a.epi = TF_EPI_RES; a.aux = dst;
     hand_over(a);
-    a.tile = 0;                                          // (a hand-over tile choice is about the pointwise conv above)
     c.chk(tf_conv2d(&a, c.stream));
   } else {
     conv_fill(a, dtype, 1, N, b.Hout, b.Wout, c4, b.Hin, b.Win, B.cin, 1, B.stride, 0, B.cin, gskip, b.wdt, P.T4);
@@ -1094,18 +1079,11 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
   tf_conv_args a;
 
   const int srows = tf_get_stat_rows();
-  const bool g_unfused_env = tf::tuning().unfused_bn;
-  const bool fused = srows <= TF_STAT_ROWS && !g_unfused_env;   // see tf_detnet_forward
+  const bool fused = srows <= TF_STAT_ROWS;   // see tf_detnet_forward
   // statistic rows start at zero: the per-BN backward regions + the head of this pass's partial buffer right behind them, ONE memset
   if (hipMemsetAsync(P.stat_bwd, 0, (size_t)((char*)P.partial_b - (char*)P.stat_bwd) + (size_t)TF_STAT_ROWS * 3 * 1024 * 4, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-  // the forward pass took conv1 straight from the image.  Its weight gradient does too (tf_stem_wgrad); with TINYFACES_STEM_WGRAD_IM2COL=1 it
-  // reduces over the im2col matrix as in rounds 1-3, built here on the second stream (beside the head's backward)
-  const bool stem_wgrad_im2col = tf::tuning().stem_wgrad_im2col;
+  // the forward pass took conv1 straight from the image; its weight gradient does too (tf_stem_wgrad)
   const bool stem_direct = stem_direct_mode(dtype, true, fused);
-  if (stem_direct && stem_wgrad_im2col) {
-    if (c.side) { c.fork(); c.chk(tf_stem_im2col(x, N, H, W, dtype, P.col, kStemK, c.side)); }
-    else c.chk(tf_stem_im2col(x, N, H, W, dtype, P.col, kStemK, c.stream));
-  }
   const bool group_on = wgrad_group_mode(dtype, 1) && fused;
   zero_flat_gradient(c, A, grad_flat, grad_flat_bytes, group_on, false);
 
@@ -1125,8 +1103,7 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
   // (profiles/r02b_step_timeline.txt: 90 x 5.9 us).  The ungrouped identity bottlenecks of layer 3 therefore fork ONCE, behind the
   // BN1-backward apply, when the dY operands of all three weight gradients exist: conv3's and conv2's gradients start ~100 us
   // later and overlap the next bottleneck instead, far from the end of the pass (layer 1 / 2 and the stem keep one fork per
-  // gradient so that the tail of the weight-gradient stream stays short).  TINYFACES_L3_FORK_PER_WGRAD=1: the old schedule.
-  const bool l3_single_fork = !tf::tuning().l3_fork_per_wgrad;
+  // gradient so that the tail of the weight-gradient stream stays short).
   WgradGroups groups(A, group_on);        // a group closes behind the BN1-backward apply of its lowest block
   // ---- bottlenecks in reverse
   for (int i = (int)A.blocks.size() - 1; i >= 0; --i) {
@@ -1137,7 +1114,7 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
     const void* yin = i == 0 ? P.pool : P.blk[i - 1].y;
     const void* extra = (i == A.layer_end[1] + 1) ? P.R3 : nullptr;     // the block whose INPUT is res3
     const bool grouped = groups.grouped(i), closes_group = groups.closes(i);
-    const bool late = !grouped && fused && l3_single_fork && i > A.layer_end[1] && !B.has_ds;    // the three gradients behind ONE fork
+    const bool late = !grouped && fused && i > A.layer_end[1] && !B.has_ds;    // the three gradients behind ONE fork
     void *T1 = b.gT1, *T2 = b.gT2, *U1 = b.gU1, *T3 = b.gT3;      // the block's own buffers: nothing on this stream ever waits for a weight gradient
     // (1) per-channel sums for bn3 (and the downsample BN) with gz = g_y * (y > 0)
     const int nb = tf_colstats_blocks(Mout, c4, dtype);
@@ -1204,8 +1181,6 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
     //      its BN3-backward sums (STATS3 with aux3 = its c3), so the next iteration starts at step (2).
     auto hand_over = [&](tf_conv_args& q) {
       if (!fused || i == 0) return;                        // block 0's input is the max-pool output: no ReLU in between
-      const int ho_tile = tf::tuning().handover_tile;     // A/B knob: tile code of the hand-over data gradients
-      if (ho_tile) q.tile = ho_tile;
       q.epi |= TF_EPI_MASK2; q.aux2 = yin;
       if (!A.blocks[i - 1].has_ds) { q.epi |= TF_EPI_STATS3; q.aux3 = P.blk[i - 1].c3; q.stat_out = P.blk[i - 1].b3.bst; }
     };
@@ -1235,10 +1210,9 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
   const int M1 = N * P.H1 * P.W1;
   void* gz = P.T4;                          // main-stream scratch (its last reader, block 0's conv1 dgrad, is ahead on this stream)
   // r4: the statistic sums of the stem's BN backward ride in the max-pool backward (gz and x are in its registers): one pass over two 96 MB
-  // tensors and one launch fewer at the very end of the chain (TINYFACES_POOL_STATS_OFF=1: the two-pass form)
-  const bool pool_stats_off = tf::tuning().pool_stats_off;
+  // tensors and one launch fewer at the very end of the chain (the unfolded flow keeps the two-pass form)
   int nb = 0;
-  if (fused && !pool_stats_off) {
+  if (fused) {
     c.chk(tf_maxpool_bwd_stats(dtype, Gcur, P.pool_idx, P.cstem, P.bn_stem.scale, P.bn_stem.shift, N, P.H1, P.W1, 64, gz, P.partial_b, &nb, c.stream));
   } else {
     c.chk(tf_maxpool_bwd(dtype, Gcur, P.pool_idx, P.cstem, P.bn_stem.scale, P.bn_stem.shift, N, P.H1, P.W1, 64, gz, c.stream));
@@ -1247,17 +1221,14 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
   }
   bn_backward_coefs(c, A.stem, 64, P.bn_stem, P.partial_b, nb, 2, 1, 64, (float)M1);
   // (r4: with the direct weight gradient the apply rides in that kernel's staging -- its output has no other reader)
-  const bool stem_wgrad_direct = stem_direct && !stem_wgrad_im2col;
-  const bool stem_apply_off = tf::tuning().stem_apply_separate;
-  const bool stem_apply_fused = stem_wgrad_direct && !stem_apply_off;
-  if (!stem_apply_fused) c.chk(tf_bn_bwd_apply(dtype, gz, nullptr, P.cstem, P.bn_stem.cA, P.bn_stem.cB, P.bn_stem.cD, M1, 64, gz, c.stream));
+  if (!stem_direct) c.chk(tf_bn_bwd_apply(dtype, gz, nullptr, P.cstem, P.bn_stem.cA, P.bn_stem.cB, P.bn_stem.cD, M1, 64, gz, c.stream));
   // P.col still holds the im2col matrix of this forward (nothing else is carved from that range)
   {
     ConvUnit s = A.stem; s.stride = 1; s.pad = 0;
     c.fork();
-    if (stem_wgrad_direct) {
+    if (stem_direct) {
       if (!c.grads_zeroed && hipMemsetAsync(c.G(A.stem.w), 0, (size_t)64 * 147 * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-      c.chk(tf_stem_wgrad(dtype, x, N, H, W, gz, stem_apply_fused ? P.cstem : nullptr, P.bn_stem.cA, P.bn_stem.cB, P.bn_stem.cD, c.G(A.stem.w), c.wstream()));
+      c.chk(tf_stem_wgrad(dtype, x, N, H, W, gz, P.cstem, P.bn_stem.cA, P.bn_stem.cB, P.bn_stem.cD, c.G(A.stem.w), c.wstream()));
     } else wgrad(c, s, 64, 1, 1, M1, 1, M1, P.col, kStemK, gz, 64, nullptr, 147, 1, 147);
   }
   return close_backward(c, hooks);

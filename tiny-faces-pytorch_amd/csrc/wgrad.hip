@@ -14,7 +14,6 @@
 // Split-K partial tiles are combined with fp32 atomics straight into the OIHW gradient
 // (coalesced 64-byte runs along ci for 1x1 convs).
 #include "common.h"
-#include "tuning.h"
 #include "profile.h"
 
 int tf_wgrad_dma_launch(const tf_wgrad_args* a, hipStream_t stream);
@@ -239,9 +238,8 @@ extern "C" int tf_conv2d_wgrad(const tf_wgrad_args* a, void* stream_) {
   // tile: 0 = auto (bf16, no prologue: the all-taps kernel for 3x3 / stride 1 / pad 1, else the per-tap LDS-DMA pipeline),
   //       1 = force the per-tap DMA kernel, 3 = force the all-taps kernel, 64 / 128 = register-staged kernel
   if ((a->tile == 0 || a->tile == 3) && a->dtype == TF_BF16 && !a->pro_scale) {
-    const bool w3_off = tf::tuning().wgrad3_off;          // A/B knob
     // (the all-taps kernel has no row scale: such a problem keeps the per-tap kernel)
-    const int rc = ((w3_off && a->tile == 0) || a->row_scale) ? TF_ERR_UNSUPPORTED : tf_wgrad3x3_launch(a, stream);
+    const int rc = a->row_scale ? TF_ERR_UNSUPPORTED : tf_wgrad3x3_launch(a, stream);
     if (rc != TF_ERR_UNSUPPORTED || a->tile == 3) return rc;
   }
   if ((a->tile == 0 || a->tile == 1) && a->dtype == TF_BF16 && !a->pro_scale) return tf_wgrad_dma_launch(a, stream);

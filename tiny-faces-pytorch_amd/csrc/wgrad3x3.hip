@@ -375,8 +375,7 @@ int tf_wgrad3x3_launch(const tf_wgrad_args* A, hipStream_t stream) {
   W3K k;
   if (!w3_plan(A, k)) return TF_ERR_UNSUPPORTED;
   const size_t need = (size_t)k.splitk * k.nco * k.nci * TILE_FLOATS * sizeof(float);
-  const bool atomics_only = tf::tuning().wgrad3_atomics;      // A/B knob
-  if (A->partial_ws && A->partial_ws_bytes >= need && !atomics_only) k.partial = (float*)A->partial_ws;
+  if (A->partial_ws && A->partial_ws_bytes >= need) k.partial = (float*)A->partial_ws;
   const int dbg = tf::tuning().wgrad3_dbg;     // timing ablation: 1 = no MFMA loop body, 2 = no partial stores (results invalid)
   k.dbg = dbg;
   const size_t lds = (size_t)NS * YT + XBYTES;

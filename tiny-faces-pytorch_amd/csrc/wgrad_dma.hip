@@ -26,23 +26,14 @@ struct WdK {
   int nco, nci, splitk, chunk;
 };
 
-constexpr int PK = 64, TILEB = PK * 128, BUF = 2 * TILEB, L = 4;     // ring depth NS: template parameter (3 default; 2 = 32 KiB of LDS per block)
+constexpr int PK = 64, TILEB = PK * 128, BUF = 2 * TILEB, L = 4, NS = 3;     // NS: ring depth (NS * BUF = 96 KiB of LDS per block)
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // r4: issued from inline asm (lds_dma.h).  Through __builtin_amdgcn_global_load_lds hipcc saw a pending LDS write and put an
 // `s_waitcnt vmcnt(0)` in front of the first ds_read_b64_tr_b16 of EVERY stage (the transposing read carries no memory operand the
 // wait-count pass could disambiguate): the ring was drained once per stage, each stage paid the full latency of the DMA issued just
 // before it.  The counted vmcnt + barrier of the loop is what orders the fragment reads behind the DMA.
-// HIDDEN = false keeps the builtin form of rounds 1-3 for the A/B (TINYFACES_DMA_BUILTIN=1).
-template <bool HIDDEN> __device__ __forceinline__ void dma16(const void* gsrc, void* lds_wave_base) {
-  if constexpr (HIDDEN) {
-    tf::dma16_hidden(gsrc, tf::lds_addr_uniform(lds_wave_base));
-  } else {
-    typedef __attribute__((address_space(3))) void lds_void;
-    typedef __attribute__((address_space(1))) const void glb_void;
-    __builtin_amdgcn_global_load_lds((glb_void*)gsrc, (lds_void*)lds_wave_base, 16, 0, 0);
-  }
-}
+__device__ __forceinline__ void dma16(const void* gsrc, void* lds_wave_base) { tf::dma16_hidden(gsrc, tf::lds_addr_uniform(lds_wave_base)); }
 __device__ __forceinline__ int fsw(int row) { return ((row >> 1) & 3) << 1; }
 
 // 16 channels (c0 multiple of 16) x 32 pixels (one MFMA k-step) from a pixel-major swizzled tile; k <-> pixel = h*16 + g*4 + j
@@ -59,7 +50,7 @@ __device__ __forceinline__ bf16x8 frag_tr(const char* tile, int pk0, int c0) {
 
 // KIND 1: pointwise (1x1, stride 1, pad 0): X row of pixel p is row p.  KIND 0: generic tap gather.
 // RS: tf_wgrad_args.row_scale (frozen-BN graph) -- a compile-time form of its own, so that the default instantiation is the kernel it always was
-template <int KIND, int NS = 3, bool HIDDEN = true, bool RS = false>
+template <int KIND, bool RS = false>
 __global__ void __launch_bounds__(256) wgrad_dma_kernel(const WdK a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int b = blockIdx.x;
@@ -103,7 +94,7 @@ __global__ void __launch_bounds__(256) wgrad_dma_kernel(const WdK a) {
     for (int i = 0; i < 2; ++i) {
       const bool in = prow[i] < pend;
       const uintptr_t ysrc = (in && ycol[i]) ? reinterpret_cast<uintptr_t>(yptr[i]) : reinterpret_cast<uintptr_t>(zero);
-      dma16<HIDDEN>(reinterpret_cast<const void*>(ysrc), ys + i * 4096 + wave_byte);
+      dma16(reinterpret_cast<const void*>(ysrc), ys + i * 4096 + wave_byte);
       uintptr_t xsrc;
       if (KIND == 1) {
         xsrc = (in && xcol[i]) ? reinterpret_cast<uintptr_t>(xptr[i]) : reinterpret_cast<uintptr_t>(zero);
@@ -117,7 +108,7 @@ __global__ void __launch_bounds__(256) wgrad_dma_kernel(const WdK a) {
         row_[i] += PK;
         while (row_[i] >= a.OW) { row_[i] -= a.OW; if (++roh[i] == a.OH) { roh[i] = 0; ++rn[i]; } }
       }
-      dma16<HIDDEN>(reinterpret_cast<const void*>(xsrc), xs + i * 4096 + wave_byte);
+      dma16(reinterpret_cast<const void*>(xsrc), xs + i * 4096 + wave_byte);
       yptr[i] += (size_t)PK * a.lddy * 2;
       prow[i] += PK;
     }
@@ -199,29 +190,21 @@ int tf_wgrad_dma_launch(const tf_wgrad_args* A, hipStream_t stream) {
   k.chunk = (((k.M + sk - 1) / sk) + PK - 1) / PK * PK;
   k.splitk = (k.M + k.chunk - 1) / k.chunk;
   // ring depth: the weight gradients share every CU's 160 KiB of LDS with the data-gradient chain on the other stream
-  // (profiles/r03_contention.txt); TINYFACES_WGRAD_NS=2 trades a shallower ring for a third less LDS per block
-  const int ns = tf::tuning().wgrad_ns;
-  const size_t lds = (size_t)ns * BUF;
-  auto lds3 = [] { return (size_t)3 * BUF; };
+  // (profiles/r03_contention.txt); a 2-deep ring (a third less LDS per block) measured no faster
+  const size_t lds = (size_t)NS * BUF;
   const bool pointwise = ntaps == 1 && A->stride == 1 && A->pad == 0 && A->H == A->OH && A->W == A->OW;
   const double Md = k.M;
   tf::ProfScope prof(14, 2.0 * Md * A->Cout * A->Cin * ntaps,
                      (Md * A->Cout + (double)A->N * A->H * A->W * A->Cin) * 2 + (double)A->Cout * A->Cin * ntaps * 4, stream, k.M, A->Cout,
                      A->Cin * ntaps, ntaps, 2, 0, -1.0, true);
-  const bool builtin_dma = tf::tuning().dma_builtin;       // A/B: the compiler-visible DMA of rounds 1-3 (drained every stage)
   const dim3 grid(tiles * k.splitk);
   if (A->row_scale) {
-    if (pointwise) TF_LAUNCH_TIMED((wgrad_dma_kernel<1, 3, true, true>), grid, dim3(256), lds3(), stream, k);
-    else TF_LAUNCH_TIMED((wgrad_dma_kernel<0, 3, true, true>), grid, dim3(256), lds3(), stream, k);
-  } else if (builtin_dma) {
-    if (pointwise) TF_LAUNCH_TIMED((wgrad_dma_kernel<1, 3, false>), grid, dim3(256), lds3(), stream, k);
-    else TF_LAUNCH_TIMED((wgrad_dma_kernel<0, 3, false>), grid, dim3(256), lds3(), stream, k);
+    if (pointwise) TF_LAUNCH_TIMED((wgrad_dma_kernel<1, true>), grid, dim3(256), lds, stream, k);
+    else TF_LAUNCH_TIMED((wgrad_dma_kernel<0, true>), grid, dim3(256), lds, stream, k);
   } else if (pointwise) {
-    if (ns == 2) TF_LAUNCH_TIMED((wgrad_dma_kernel<1, 2>), grid, dim3(256), lds, stream, k);
-    else TF_LAUNCH_TIMED((wgrad_dma_kernel<1, 3>), grid, dim3(256), lds, stream, k);
+    TF_LAUNCH_TIMED((wgrad_dma_kernel<1>), grid, dim3(256), lds, stream, k);
   } else {
-    if (ns == 2) TF_LAUNCH_TIMED((wgrad_dma_kernel<0, 2>), grid, dim3(256), lds, stream, k);
-    else TF_LAUNCH_TIMED((wgrad_dma_kernel<0, 3>), grid, dim3(256), lds, stream, k);
+    TF_LAUNCH_TIMED((wgrad_dma_kernel<0>), grid, dim3(256), lds, stream, k);
   }
   return hipGetLastError() == hipSuccess ? TF_OK : TF_ERR_LAUNCH;
 }

@@ -24,7 +24,6 @@
 // torchvision's Bottleneck); bf16 only (the fp32 parity path keeps wgrad.hip).
 #include <cstdlib>
 #include "common.h"
-#include "tuning.h"
 #include "profile.h"
 #include "lds_dma.h"
 
@@ -354,15 +353,11 @@ int tf_wgrad_pw_group_launch(const tf_wgrad_args* A, int n, hipStream_t stream) 
   static tf::PerDevice attr_set;
   if (attr_set.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_group_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_group_fast_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_group_fast_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
   // kind 18 = grouped pointwise weight gradient (bench.py tables); the GEMM view is the SUM over the group
   tf::ProfScope prof(18, flops, bytes, stream, k.M, A[0].Cout, A[0].Cin, 1, 2, 0, -1.0, true);
-  const int fast_ns = tf::tuning().wgradg_fast;      // 0: the generic kernel (A/B); 4 / 8: ring depth of the fast one
-  if (full && fast_ns == 4 && (k.M / GP_PK) % 4 == 0) {
-    TF_LAUNCH_TIMED((wgrad_group_fast_kernel<4>), dim3(tiles), dim3(256), (size_t)4 * GP_STAGE, stream, k);
-  } else if (full && fast_ns == 8 && (k.M / GP_PK) % 8 == 0) {
+  if (full && (k.M / GP_PK) % 8 == 0) {
     TF_LAUNCH_TIMED((wgrad_group_fast_kernel<8>), dim3(tiles), dim3(256), (size_t)8 * GP_STAGE, stream, k);
   } else {
     TF_LAUNCH_TIMED((wgrad_group_kernel<4>), dim3(tiles), dim3(256), lds, stream, k);       // ragged shapes: zero-page selects, 64 KiB ring
