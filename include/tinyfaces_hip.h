@@ -464,6 +464,25 @@ int tf_detnet_trunk_backward_frozen_ctx(const int* blocks, tf_detnet_ctx* ctx, c
 int tf_detnet_backward_frozen_ctx(tf_detnet_ctx* ctx, const tf_detnet_hooks* hooks, int dtype, const float* x_nchw, int N, int H, int W,
                                   int num_out, void* const* params, void* const* grads, const float* gout_nchw,
                                   void* grad_flat, size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream);
+/* ---- partial freeze (version 630): the frozen-BN backward cut at a stage boundary ------------------------------------------------------
+ * tf_detnet_trunk_backward_frozen_ctx with the stem and the lowest stages of the trunk frozen as well (torchvision's
+ * trainable_backbone_layers, Detectron's FREEZE_AT): autograd as above with, in addition, requires_grad = False on every parameter below
+ * the cut.  first_block = the index of the lowest bottleneck that receives weight gradients:
+ *   -1 the stem too (the call above, launch for launch) | 0 layer 1 and up | n1 layer 2 and up | n1 + n2 layer 3 and up |
+ *   n1 + n2 + n3 the two heads only        (blocks = {n1, n2, n3}; ResNet-101: -1, 0, 3, 7, 30)
+ * Any other value is TF_ERR_ARG before anything is launched (a cut inside a stage is not taken).  The forward is the same
+ * training = TF_DETNET_FROZEN_BN forward with the same workspace; the pass launches a strict subset of the full pass: nothing below block
+ * first_block, no input gradient of that block, no max-pool backward or stem weight gradient, and no head data gradient without a reader.
+ * Writes: the conv weights of the blocks >= first_block, the head weights and biases and score4_upsample.weight (zero) receive their
+ * gradients.  The tensors below the cut have NO writer, like BN gamma / beta: inside grad_flat their slots are zero after the call (the
+ * memset covers them; the split memset is only taken while layer 3 is trained), entries of `grads` outside grad_flat are left untouched
+ * and may be NULL there.
+ * Hooks: every registered hook still fires exactly once.  Those of the blocks >= first_block fire where they always do; those of the
+ * blocks below the cut, in the order they were registered, and then the -1 hook fire at the end of the shortened pass on the caller's
+ * stream, behind the join with the weight-gradient stream and behind the memset of their (all-zero) ranges. */
+int tf_detnet_trunk_backward_frozen_from_ctx(const int* blocks, tf_detnet_ctx* ctx, const tf_detnet_hooks* hooks, int dtype, const float* x_nchw,
+                                             int N, int H, int W, int num_out, void* const* params, void* const* grads, const float* gout_nchw,
+                                             void* grad_flat, size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream, int first_block);
 
 /* ---- gradient exchange of the data-parallel path over RCCL (the reference has no distributed code) -------------
  * One process per GPU; the gradients are SUMMED over the ranks bucket by bucket while the backward pass runs, the 1/world goes into

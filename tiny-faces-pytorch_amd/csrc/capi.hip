@@ -19,7 +19,7 @@ static const char* const kSymbols[] = {
     "tf_detnet_set_dual_stream", "tf_detnet_set_grad_events", "tf_detnet_set_grad_callback",
     "tf_detnet_trunk_num_params", "tf_detnet_trunk_param_name", "tf_detnet_trunk_param_numel", "tf_detnet_trunk_workspace_bytes",
     "tf_detnet_trunk_param_region_bytes", "tf_detnet_trunk_forward_ctx", "tf_detnet_trunk_backward_ctx",
-    "tf_detnet_trunk_backward_frozen_ctx", "tf_detnet_backward_frozen_ctx",
+    "tf_detnet_trunk_backward_frozen_ctx", "tf_detnet_backward_frozen_ctx", "tf_detnet_trunk_backward_frozen_from_ctx",
     "tf_set_stat_rows", "tf_get_stat_rows", "tf_profile_enable", "tf_profile_collect", "tf_profile_shapes",
 };
 
@@ -29,7 +29,7 @@ void set_next_stop_event(hipEvent_t e) { g_next_stop_event = e; }
 hipEvent_t take_next_stop_event() { hipEvent_t e = g_next_stop_event; g_next_stop_event = nullptr; return e; }
 }  // namespace tf
 
-extern "C" int tf_version(void) { return 620; }   // 620: frozen BatchNorm (training = 2, tf_detnet_*backward_frozen_ctx, tf_sgd_step_segments); 610: tf_detnet_trunk_* (ResNet-50 / -152 trunks); r6: tf_build_id; r4: context + hooks + communicator entry points
+extern "C" int tf_version(void) { return 630; }   // 630: partial freeze (tf_detnet_trunk_backward_frozen_from_ctx); 620: frozen BatchNorm (training = 2, tf_detnet_*backward_frozen_ctx, tf_sgd_step_segments); 610: tf_detnet_trunk_* (ResNet-50 / -152 trunks); r6: tf_build_id; r4: context + hooks + communicator entry points
 #ifndef TF_BUILD_ID
 #define TF_BUILD_ID "unstamped"
 #endif

@@ -872,12 +872,20 @@ int open_backward(const int* blocks, tf_detnet_ctx* xctx, const tf_detnet_hooks*
   return TF_OK;
 }
 
-// exit: the caller's stream sees every weight gradient, then the hook of the very end
-int close_backward(Ctx& c, const tf_detnet_hooks* hooks) {
+// exit: the caller's stream sees every weight gradient, then the hook of the very end.  first_block > 0 (a backward cut at a stage boundary,
+// tf_detnet_trunk_backward_frozen_from_ctx): the hooks of the blocks below the cut, whose ranges hold nothing but the memset's zeros, fire here
+// too, in the registered order, each block once, ahead of the -1 hook.
+int close_backward(Ctx& c, const tf_detnet_hooks* hooks, int first_block = -1) {
   // (r5, measured and removed: returning WITHOUT joining the last kernel, conv1's weight gradient, and running the SGD update of every other
   //  parameter beside it -- 1282.2 / 1284.0 against 1282.1 / 1281.2 img/s joined: both are HBM-bound, side by side they take as long as back
   //  to back)
   c.wait_on_main(c.mark_side());
+  for (int k = 0; hooks && first_block > 0 && k < hooks->n; ++k) {
+    const int blk = hooks->blocks[k];
+    bool seen = false;
+    for (int j = 0; j < k && !seen; ++j) seen = hooks->blocks[j] == blk;
+    if (blk >= 0 && blk < first_block && !seen) record_grad_events(hooks, blk, c.stream, c.rc);
+  }
   record_grad_events(hooks, -1, c.stream, c.rc);
   if (hipGetLastError() != hipSuccess && c.rc == TF_OK) c.rc = TF_ERR_LAUNCH;
   return c.rc;
@@ -943,8 +951,10 @@ void zero_flat_gradient(Ctx& c, const Arch& A, void* grad_flat, size_t grad_flat
 // The heads: the gradients of the two score maps, their bias and weight gradients, and the data gradients into the trunk -- res3's into
 // P.R3, the last block's output gradient into `gtop` with the epilogue `top` gives it (the one thing the two graphs do differently here).
 // (the transposed weight operands w*t were packed by the training forward, together with the forward operands)
+// want_top / want_r3 = false (a frozen-BN backward cut above layer 3 / above layer 2): that data gradient has no reader and is not launched.
 template <class F>
-void heads_backward(Ctx& c, const Arch& A, const Plan& P, const float* gout, void* grad_flat, size_t grad_flat_bytes, void* gtop, F&& top) {
+void heads_backward(Ctx& c, const Arch& A, const Plan& P, const float* gout, void* grad_flat, size_t grad_flat_bytes, void* gtop, F&& top,
+                    bool want_top = true, bool want_r3 = true) {
   const int dtype = P.dtype, N = P.N, nout = P.nout;
   const int M3 = N * P.H3 * P.W3, M4 = N * P.H4 * P.W4;
   c.chk(tf_upsample_add_crop_bwd(dtype, gout, P.wup_diag, N, nout, kHeadLd, P.H3, P.W3, P.H4, P.W4, P.g3, P.g4, c.stream));
@@ -963,13 +973,17 @@ void heads_backward(Ctx& c, const Arch& A, const Plan& P, const float* gout, voi
     if (u && !covered && hipMemsetAsync(u, 0, (size_t)nout * nout * 16 * 4, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
   }
   tf_conv_args a;
-  conv_fill(a, dtype, 1, N, P.H4, P.W4, kHeadLd, P.H4, P.W4, 1024, 1, 1, 0, 1024, P.g4, P.w_h4t, gtop);
-  a.alg_k = nout;
-  top(a);
-  c.chk(tf_conv2d(&a, c.stream));
-  conv_fill(a, dtype, 1, N, P.H3, P.W3, kHeadLd, P.H3, P.W3, 512, 1, 1, 0, 512, P.g3, P.w_h3t, P.R3);
-  a.alg_k = nout;
-  c.chk(tf_conv2d(&a, c.stream));
+  if (want_top) {
+    conv_fill(a, dtype, 1, N, P.H4, P.W4, kHeadLd, P.H4, P.W4, 1024, 1, 1, 0, 1024, P.g4, P.w_h4t, gtop);
+    a.alg_k = nout;
+    top(a);
+    c.chk(tf_conv2d(&a, c.stream));
+  }
+  if (want_r3) {
+    conv_fill(a, dtype, 1, N, P.H3, P.W3, kHeadLd, P.H3, P.W3, 512, 1, 1, 0, 512, P.g3, P.w_h3t, P.R3);
+    a.alg_k = nout;
+    c.chk(tf_conv2d(&a, c.stream));
+  }
 }
 
 // r4: GROUPED weight gradients of the identity bottlenecks of layer 3.  Their three gradients are not launched
@@ -1252,9 +1266,20 @@ extern "C" int tf_detnet_backward_ctx(tf_detnet_ctx* xctx, const tf_detnet_hooks
 // gradients of conv3 / the downsample conv read it on the second stream), g2 in gT2, g1 in gU1: the chain never waits for a weight gradient.
 // Forks: ONE per block, carried by the conv2 data gradient (the kernel that produces the block's last weight-gradient operand); the grouped
 // identity bottlenecks of layer 3 fork once per group, as in the batch-statistics graph.
-extern "C" int tf_detnet_trunk_backward_frozen_ctx(const int* blocks, tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x,
-                                                   int N, int H, int W, int nout, void* const* params, void* const* grads, const float* gout,
-                                                   void* grad_flat, size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream_) {
+//
+// first_block (partial freeze: the stem and the lowest stages keep their weights) = the lowest bottleneck that receives weight gradients; -1 =
+// the stem too, the whole graph.  Only stage boundaries are taken: a cut inside layer 3 would have to flush a half-filled weight-gradient group.
+// The chain stops where the trained part begins: block first_block runs its two data gradients and its weight gradients (dW1 / dWd read the
+// frozen prefix's output) but no input gradient, nothing below it is launched, and a head data gradient that has lost its reader is skipped.
+extern "C" int tf_detnet_trunk_backward_frozen_from_ctx(const int* blocks, tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype,
+                                                        const float* x, int N, int H, int W, int nout, void* const* params, void* const* grads,
+                                                        const float* gout, void* grad_flat, size_t grad_flat_bytes, void* ws, size_t ws_bytes,
+                                                        void* stream_, int first_block) {
+  if (const Arch* a0 = find_arch(blocks)) {
+    const int nb = (int)a0->blocks.size();
+    if (first_block != -1 && first_block != 0 && first_block != a0->layer_end[0] + 1 && first_block != a0->layer_end[1] + 1 && first_block != nb)
+      return TF_ERR_ARG;
+  }
   const Arch* Ap; Plan P; Ctx c{};
   const int rc0 = open_backward(blocks, xctx, hooks, dtype, x, N, H, W, nout, params, grads, gout, ws, ws_bytes, stream_, kFrozen, Ap, P, c);
   if (rc0 != TF_OK) return rc0;
@@ -1265,14 +1290,16 @@ extern "C" int tf_detnet_trunk_backward_frozen_ctx(const int* blocks, tf_detnet_
   if (hipMemsetAsync(P.partial_b, 0, (size_t)TF_STAT_ROWS * 3 * 1024 * 4, c.stream) != hipSuccess) c.chk(TF_ERR_LAUNCH);
   const bool stem_direct = stem_direct_mode(dtype, false, false);      // (what the frozen forward took)
   const bool group_on = wgrad_group_mode(dtype, 1);
-  zero_flat_gradient(c, A, grad_flat, grad_flat_bytes, group_on, true);
+  // (the tensors of the frozen stages have no writer: the memset covers them; the split memset only where layer 3 is trained)
+  zero_flat_gradient(c, A, grad_flat, grad_flat_bytes, group_on && first_block < nblocks, true);
   // gm of the last block: the head's data gradient, masked by the block's own output
   heads_backward(c, A, P, gout, grad_flat, grad_flat_bytes, P.blk[nblocks - 1].gT1,
-                 [&](tf_conv_args& q) { q.epi = TF_EPI_MASK2; q.aux2 = P.blk[nblocks - 1].y; });
+                 [&](tf_conv_args& q) { q.epi = TF_EPI_MASK2; q.aux2 = P.blk[nblocks - 1].y; },
+                 first_block < nblocks, first_block <= A.layer_end[1]);      // (R3's only reader is the input gradient of layer 3's first block)
   WgradGroups groups(A, group_on);        // a group closes behind the conv2 data gradient of its lowest block
 
-  // ---- bottlenecks in reverse
-  for (int i = nblocks - 1; i >= 0; --i) {
+  // ---- bottlenecks in reverse, down to the lowest trained one
+  for (int i = nblocks - 1; i >= (first_block > 0 ? first_block : 0); --i) {
     const Block& B = A.blocks[i];
     Plan::Blk& b = P.blk[i];
     const int pl = B.planes, c4 = pl * 4;
@@ -1308,8 +1335,10 @@ extern "C" int tf_detnet_trunk_backward_frozen_ctx(const int* blocks, tf_detnet_
     }
     // (4) gm_prev = (W1^T g1 + skip) * (x > 0) -> the previous block's gT1 (block 0: no ReLU between the max-pool and its input); gm is the
     //     skip branch's operand either way: the identity residual (already g_y * (y > 0)), or dY of the scaled downsample conv
+    if (i == first_block) break;          // what lies below is frozen: nobody reads the gradient of this block's input
     input_gradient(c, P, B, b, U1, gm, extra, gprev, i > 0, [&](tf_conv_args& q) { if (i > 0) { q.epi |= TF_EPI_MASK2; q.aux2 = yin; } });
   }
+  if (first_block >= 0) return close_backward(c, hooks, first_block);      // the stem is frozen too: no max-pool backward, no fork, no weight gradient
 
   // ---- stem: max-pool backward masks through relu (the stored cstem is post-ReLU: scale 1, shift 0), the BN scale rides in the weight gradient
   const int M1 = N * P.H1 * P.W1;
@@ -1326,11 +1355,17 @@ extern "C" int tf_detnet_trunk_backward_frozen_ctx(const int* blocks, tf_detnet_
   }
   return close_backward(c, hooks);
 }
+extern "C" int tf_detnet_trunk_backward_frozen_ctx(const int* blocks, tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x,
+                                                   int N, int H, int W, int nout, void* const* params, void* const* grads, const float* gout,
+                                                   void* grad_flat, size_t grad_flat_bytes, void* ws, size_t ws_bytes, void* stream_) {
+  return tf_detnet_trunk_backward_frozen_from_ctx(blocks, xctx, hooks, dtype, x, N, H, W, nout, params, grads, gout, grad_flat, grad_flat_bytes, ws,
+                                                  ws_bytes, stream_, -1);
+}
 extern "C" int tf_detnet_backward_frozen_ctx(tf_detnet_ctx* xctx, const tf_detnet_hooks* hooks, int dtype, const float* x, int N, int H, int W, int nout,
                                              void* const* params, void* const* grads, const float* gout, void* grad_flat, size_t grad_flat_bytes,
                                              void* ws, size_t ws_bytes, void* stream_) {
-  return tf_detnet_trunk_backward_frozen_ctx(nullptr, xctx, hooks, dtype, x, N, H, W, nout, params, grads, gout, grad_flat, grad_flat_bytes, ws,
-                                             ws_bytes, stream_);
+  return tf_detnet_trunk_backward_frozen_from_ctx(nullptr, xctx, hooks, dtype, x, N, H, W, nout, params, grads, gout, grad_flat, grad_flat_bytes,
+                                                  ws, ws_bytes, stream_, -1);
 }
 
 // context-free form (rounds 1-3): the default context of the current device + the process-wide hooks registered with tf_detnet_set_*

@@ -70,23 +70,31 @@ FREEZE_HELP = ("--freeze-bn: fine-tune with every BatchNorm of the trunk frozen 
                "(DetectionModel.freeze_batchnorm: torchvision's FrozenBatchNorm2d), default off")
 
 
+TRAINABLE_HELP = ("--trainable-layers {0,1,2,3,4}: train the heads and the top K of the trunk's stages layer3, layer2, layer1, stem "
+                  "(DetectionModel.set_trainable_layers: torchvision's trainable_backbone_layers), default 4 = everything; K < 4 needs --freeze-bn")
+
+
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog=TRUNK_HELP + "; " + FREEZE_HELP)
+    parser = argparse.ArgumentParser(epilog=TRUNK_HELP + "; " + FREEZE_HELP + "; " + TRAINABLE_HELP)
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
 
 
 def trunk_arguments(argv=None):
-    """`arguments` plus `base_model` from --base-model and `freeze_bn` from --freeze-bn.  Parsed apart, so that `arguments` keeps resolving exactly the reference's options
-    and the additions above."""
+    """`arguments` plus `base_model` from --base-model, `freeze_bn` from --freeze-bn and `trainable_layers` from --trainable-layers.  Parsed apart, so that
+    `arguments` keeps resolving exactly the reference's options and the additions above."""
     parser = argparse.ArgumentParser(add_help=False)
     parser.add_argument("--base-model", dest="base_model", default="resnet101", choices=list(model_zoo.TRUNKS), help=TRUNK_HELP)
     parser.add_argument("--freeze-bn", dest="freeze_bn", action="store_true", help=FREEZE_HELP)
+    parser.add_argument("--trainable-layers", dest="trainable_layers", default=4, type=int, choices=range(5), help=TRAINABLE_HELP)
     known, rest = parser.parse_known_args(argv)
+    if known.trainable_layers < 4 and not known.freeze_bn:
+        parser.error(f"--trainable-layers {known.trainable_layers} freezes stages of the trunk, which is defined on frozen BatchNorm only: add --freeze-bn")
     args = arguments(rest)
     args.base_model = known.base_model
     args.freeze_bn = known.freeze_bn
+    args.trainable_layers = known.trainable_layers
     return args
 
 
@@ -134,7 +142,10 @@ def main():
     preprocess = transforms.Compose([transforms.ToTensor(), transforms.Normalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225])])
     train_loader, _ = get_dataloader(args.traindata, args, NUM_TEMPLATES, img_transforms=preprocess)
     model = DetectionModel(base_model=getattr(model_zoo, args.base_model), num_objects=1, num_templates=NUM_TEMPLATES).set_compute_dtype(args.dtype)
-    model.freeze_batchnorm(args.freeze_bn)
+    model.freeze_batchnorm(args.freeze_bn).set_trainable_layers(args.trainable_layers)
+    if parallel.rank() == 0:
+        print(f"trunk {args.base_model}, {args.dtype}, BatchNorm {'frozen' if args.freeze_bn else 'on batch statistics'}, trainable layers "
+              f"{args.trainable_layers} of 4 ({len(model.trainable_parameter_names())} trained tensors)")
     loss_fn = DetectionCriterion(NUM_TEMPLATES, seed=args.seed * parallel.world_size() + parallel.rank(), lazy_meters=True)
     loss_fn.ohem_thresh = args.ohem_thresh
 

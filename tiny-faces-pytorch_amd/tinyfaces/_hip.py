@@ -162,6 +162,7 @@ _SIGNATURES = {
     "tf_detnet_trunk_backward_ctx": (i32, [vp, vp, C.POINTER(DetnetHooks), i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, sz, vp]),
     "tf_detnet_trunk_backward_frozen_ctx": (i32, [vp, vp, C.POINTER(DetnetHooks), i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, sz, vp]),
     "tf_detnet_backward_frozen_ctx": (i32, [vp, C.POINTER(DetnetHooks), i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, sz, vp]),
+    "tf_detnet_trunk_backward_frozen_from_ctx": (i32, [vp, vp, C.POINTER(DetnetHooks), i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, sz, vp, i32]),
     "tf_pack_weights_batched": (i32, [i32, vp, i32, vp]),
     "tf_pack_weights_tiled": (i32, [i32, vp, i32, vp]),
     "tf_detnet_set_dual_stream": (i32, [i32]),

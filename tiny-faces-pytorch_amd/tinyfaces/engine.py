@@ -441,13 +441,14 @@ class TrainEngine:
         cur.wait_stream(comm)
 
     def _trained_segments(self):
-        """Frozen BatchNorm: [(start, end)] of the flat buffer that the optimizer touches -- every segment that is not a BatchNorm weight /
-        bias, ascending.  The BN vectors sit in between (the trunk group is ONE range): a plain tf_sgd_step over the group would decay them
-        through weight decay although their gradient is zero."""
-        key = id(self.model._segments)
+        """Frozen BatchNorm: [(start, end)] of the flat buffer that the optimizer touches, ascending -- the segments of
+        DetectionModel.trainable_parameter_names(): every tensor that is neither a BatchNorm weight / bias nor a conv weight of a stage
+        set_trainable_layers() froze.  The frozen vectors sit in between (the trunk group is ONE range): a plain tf_sgd_step over the group
+        would decay them through weight decay although their gradient is zero."""
+        key = (id(self.model._segments), self.model.batchnorm_frozen, self.model.trainable_layers)
         if getattr(self, "_trained_key", None) != key:
-            bn = self.model._bn_param_names
-            self._trained = sorted((o, o + n) for k, (o, n) in self.model._segments.items() if k not in bn)
+            seg = self.model._segments
+            self._trained = sorted((seg[k][0], seg[k][0] + seg[k][1]) for k in self.model.trainable_parameter_names())
             self._trained_key = key
         return self._trained
 
@@ -464,8 +465,11 @@ class TrainEngine:
         """x (B,3,H,W) f32, class_map (B,nt,h,w) f32 (mined in place), regression_map (B,4nt,h,w) f32: all on the device.
         Returns the device tensor [sum cls loss, sum reg loss] (float64) without synchronising.
         The step follows the model's BatchNorm mode (DetectionModel.freeze_batchnorm): frozen, the forward and backward run the folded-BN
-        graph, and the update skips the BatchNorm vectors (no weight decay, no momentum: their momentum buffers stay zero)."""
+        graph, and the update skips the BatchNorm vectors (no weight decay, no momentum: their momentum buffers stay zero) and, with
+        DetectionModel.set_trainable_layers(k < 4), the conv weights of the frozen stages; the bucket plan of the gradient exchange stays
+        as it is (frozen ranges are reduced as zeros)."""
         m, c = self.model, self.criterion
+        m._check_partial_freeze()
         m._sync_tables(x.device)
         out = m._run_forward(x, training=True)
         loss2, grad, _ = ops.criterion_fwd_bwd(out, class_map, regression_map, c.n_templates, c.reg_weight, c.ohem_thresh, c.max_pos,

@@ -179,10 +179,16 @@ class _DetNetFunction(torch.autograd.Function):
             raise RuntimeError("DetectionModel: the activation arena was reused by a later forward before this "
                                "backward ran (one in-flight training step per model)")
         grads = owner._run_backward(x, gout.contiguous().float())
-        if owner._ws_mode == _hip.TF_DETNET_FROZEN_BN:         # frozen BatchNorm: weight / bias have NO gradient (FrozenBatchNorm2d)
-            bn = owner._bn_param_names
-            grads = [None if k in bn else g for k, g in zip(owner._grad_names, grads)]
+        if owner._ws_mode == _hip.TF_DETNET_FROZEN_BN:         # frozen BatchNorm: weight / bias have NO gradient (FrozenBatchNorm2d) ...
+            keep = owner._trainable_set(True, owner._ws_trainable)      # ... and neither has a conv weight of a frozen stage (set_trainable_layers)
+            grads = [g if k in keep or k == _UPSAMPLE else None for k, g in zip(owner._grad_names, grads)]
         return (None, None) + tuple(grads)
+
+
+# The trunk's stages from the top, as set_trainable_layers counts them: torchvision's ["layer4", "layer3", "layer2", "layer1", "conv1"] without
+# the deleted layer4; `trainable_layers = k` trains the heads and the first k of these
+_STAGES = ("model.layer3.", "model.layer2.", "model.layer1.", "model.conv1.")
+_UPSAMPLE = "score4_upsample.weight"     # lr 0 (model.py:84): not trained, its gradient is DEFINED as zero in every mode
 
 
 # Every register_parameter / register_buffer of ANY module in the process (Module.__setattr__ goes through them too) bumps this counter: a frozen
@@ -224,6 +230,8 @@ class DetectionModel(nn.Module):
         self._table_key = None
         self._frozen_tensors, self._frozen_version = (), -1
         self._bn_frozen = False          # freeze_batchnorm(): a mode like train() / eval(), not part of the state_dict
+        self._trainable_layers = 4       # set_trainable_layers(): a mode too
+        self._ws_trainable = 4           # ... and its value at the forward whose activations sit in the workspace
         self._ws_mode = 0                # the executor mode (0 eval, 1 batch statistics, 2 frozen BN) of the forward whose activations sit in the workspace
         self._session_depth = 0          # constant_weights() nesting
         self._ready_key = None           # (workspace ptr, dtype, table key) whose packed eval weights sit in the workspace
@@ -292,7 +300,8 @@ class DetectionModel(nn.Module):
         * eval() is unchanged.
 
         Per-module modes are NOT honoured: the executor looks at the model's own flags only, `model.model.layer1[0].bn1.eval()` is
-        ignored exactly as without this switch.  fp16 stays an inference-only operand type.  Returns self."""
+        ignored exactly as without this switch.  fp16 stays an inference-only operand type.  set_trainable_layers(k) freezes the stem
+        and the lowest stages of the trunk on top of this mode.  Returns self."""
         self._bn_frozen = bool(on)
         return self
 
@@ -300,6 +309,73 @@ class DetectionModel(nn.Module):
     def batchnorm_frozen(self):
         """True while freeze_batchnorm() is on."""
         return self._bn_frozen
+
+    def set_trainable_layers(self, k):
+        """Fine-tune the heads and the top `k` of the trunk's four stages -- from the top: layer3, layer2, layer1, stem (conv1 + bn1) -- and
+        keep the rest on their pretrained weights: torchvision's `trainable_backbone_layers` (its list without the deleted layer4), Detectron's
+        FREEZE_AT.  4 (the default) trains everything, 0 the two score heads only.  A mode like freeze_batchnorm(): not part of the
+        state_dict, it survives train(), eval(), .to() and pickling and does not travel with load_state_dict.
+
+        Partial freezing is defined on the frozen-BN graph only (in torchvision frozen stages always sit on frozen BatchNorm): with k < 4
+        and batchnorm_frozen False a train() forward with gradients enabled raises RuntimeError (call freeze_batchnorm(); the order of the
+        two setters does not matter); eval() and no_grad forwards never look at k.  While k < 4 and BatchNorm is frozen
+
+        * the training forward is the frozen (= evaluation) forward, bit for bit;
+        * the backward pass stops where the trained part begins: no data or weight gradient of a frozen stage is launched;
+        * the conv weights of the frozen stages get no gradient (`.grad` stays None like a BN weight's, so torch.optim.SGD skips them: no
+          update, no weight decay, no momentum; TrainEngine does the same); every trained tensor gets the gradient autograd gives the
+          reference model with its BatchNorm2d in eval() and requires_grad_(False) on every parameter of the frozen stages;
+        * `requires_grad` flags are not touched and learnable_parameters() stays the reference's four groups.
+
+        Per-module flags are still NOT honoured (see freeze_batchnorm): the executor looks at the model's own modes only.  Returns self."""
+        if type(k) is not int or not 0 <= k <= 4:
+            raise ValueError(f"set_trainable_layers: k must be one of the ints 0, 1, 2, 3, 4 (got {k!r})")
+        self._trainable_layers = k
+        return self
+
+    @property
+    def trainable_layers(self):
+        """How many of the trunk's stages (layer3, layer2, layer1, stem) are trained: set_trainable_layers()."""
+        return getattr(self, "_trainable_layers", 4)
+
+    def _executor_names(self):
+        names = getattr(self, "_names", None)
+        if not names:
+            tr = _trunk_arg(self.trunk)
+            names = [lib().tf_detnet_trunk_param_name(tr, i).decode() for i in range(lib().tf_detnet_trunk_num_params(tr))]
+        return names
+
+    def trainable_parameter_names(self):
+        """The names of the tensors that receive a gradient under the current two modes (freeze_batchnorm, set_trainable_layers), in
+        executor order: the head weights and biases, the conv weights of the trained stages and, unless BatchNorm is frozen, the BN weights
+        and biases.  score4_upsample.weight is never among them: it is not trained (lr 0) and its gradient is defined as zero."""
+        return self._trainable_names(self._bn_frozen, self.trainable_layers)
+
+    def _trainable_names(self, bn_frozen, k):
+        cache = self.__dict__.setdefault("_trainable_cache", {})
+        if (bn_frozen, k) not in cache:
+            params = dict(self.named_parameters())
+            bn = frozenset(f"{n}.{w}" for n, m in self.named_modules() if isinstance(m, nn.BatchNorm2d) for w in ("weight", "bias"))
+            cut = _STAGES[k:] if bn_frozen else ()            # (partial freezing exists on the frozen-BN graph only)
+            cache[(bn_frozen, k)] = tuple(n for n in self._executor_names() if n in params and n != _UPSAMPLE and not (bn_frozen and n in bn)
+                                          and not n.startswith(cut))
+        return list(cache[(bn_frozen, k)])
+
+    def _trainable_set(self, bn_frozen, k):
+        cache = self.__dict__.setdefault("_trainable_set_cache", {})
+        if (bn_frozen, k) not in cache:
+            cache[(bn_frozen, k)] = frozenset(self._trainable_names(bn_frozen, k))
+        return cache[(bn_frozen, k)]
+
+    def _first_block(self, k):
+        """tf_detnet_trunk_backward_frozen_from_ctx's first_block for `k` trainable stages: the lowest bottleneck with weight gradients."""
+        n1, n2, n3 = self.trunk
+        return (n1 + n2 + n3, n1 + n2, n1, 0, -1)[k]
+
+    def _check_partial_freeze(self):
+        if self.trainable_layers < 4 and not self._bn_frozen:
+            raise RuntimeError(f"DetectionModel: set_trainable_layers({self.trainable_layers}) freezes stages of the trunk, which is defined on the "
+                               "frozen-BatchNorm graph only: call freeze_batchnorm() as well (or set_trainable_layers(4))")
 
     def set_compute_dtype(self, dtype):
         """torch.float32 (exact-fp32 MFMA, parity path), torch.bfloat16 (fast path, training and inference) or torch.float16
@@ -314,6 +390,7 @@ class DetectionModel(nn.Module):
         x = x.contiguous().float()
         self._sync_tables(x.device)
         if self.training and torch.is_grad_enabled():
+            self._check_partial_freeze()                 # (before anything is launched or written)
             params = [p for p in self._grad_params]
             return _DetNetFunction.apply(x, self, *params)
         # (frozen BatchNorm under no_grad: the folded forward, nothing written -- not the statistics update of a plain train() forward)
@@ -407,7 +484,7 @@ class DetectionModel(nn.Module):
         d = dict(self.__dict__)
         d.update(_table_key=None, _tables_frozen=False, _frozen_tensors=(), _frozen_version=-1, _ws=None, _ready_key=None, _lanes=[], _session_depth=0,
                  _ws_mode=0)
-        for k in ("_param_ptrs", "_grad_params", "_bn_modules", "_bn_param_names"):
+        for k in ("_param_ptrs", "_grad_params", "_bn_modules", "_bn_param_names", "_trainable_cache", "_trainable_set_cache"):
             d.pop(k, None)
         return d
 
@@ -565,6 +642,7 @@ class DetectionModel(nn.Module):
         ws = self._workspace(x.device, nbytes)
         self._ws_generation += 1
         self._ws_mode = mode
+        self._ws_trainable = self.trainable_layers if mode == _hip.TF_DETNET_FROZEN_BN else 4
         self._ws_shape = (N, H, W)
         out = torch.empty(N, self.num_out, H3.value, W3.value, dtype=torch.float32, device=x.device)
         bn = self.model.bn1
@@ -626,11 +704,12 @@ class DetectionModel(nn.Module):
         hooks.user = getattr(self, "_grad_callback_user", None) if cb is not None else None
         hooks.single_stream = int(self.single_stream)
         frozen = self._ws_mode == _hip.TF_DETNET_FROZEN_BN                # the graph the forward ran decides, not the flag at backward time
-        entry = lib().tf_detnet_trunk_backward_frozen_ctx if frozen else lib().tf_detnet_trunk_backward_ctx
+        entry = lib().tf_detnet_trunk_backward_frozen_from_ctx if frozen else lib().tf_detnet_trunk_backward_ctx
+        cut = (self._first_block(getattr(self, "_ws_trainable", 4)),) if frozen else ()       # (what was set when the forward ran)
         with torch.cuda.device(x.device):
             check(entry(_trunk_arg(self.trunk), self._ctx(x.device), C.byref(hooks), self.compute_dtype, ptr(x), N, H, W,
                         self.num_out, self._param_ptrs, table, ptr(gout), ptr(gflat), gflat.numel() * 4, ptr(self._ws),
-                        self._ws.numel(), stream()), "tf_detnet_trunk_backward_frozen_ctx" if frozen else "tf_detnet_trunk_backward_ctx")
+                        self._ws.numel(), stream(), *cut), "tf_detnet_trunk_backward_frozen_from_ctx" if frozen else "tf_detnet_trunk_backward_ctx")
         self._last_grad_flat = gflat
         if persistent:
             return gflat
