@@ -140,6 +140,38 @@ int tf_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n,
 int tf_sgd_step_segments(float* param, const float* grad, float* momentum_buf, const int64_t* host_segments, int nseg,
                          float lr, float momentum, float weight_decay, float grad_scale, void* stream);
 
+/* ---- gradient-norm clipping and the non-finite-step guard ------------------------------
+ * Replaces torch.nn.utils.clip_grad_norm_ at the spot between loss.backward() and optimizer.step() (tinyfaces/trainer.py:86-87), which the
+ * reference leaves empty: the global L2 norm of the gradient, the clip coefficient and the skip verdict stay in DEVICE memory (one
+ * tf_clip_state, 32 bytes), and the SGD entry points below read them from there -- the step stays free of host syncs.
+ *   sumsq    sum of squares of the gradient elements inside the ranges (fp64, unscaled)
+ *   norm     |grad_scale| * sqrt(sumsq)
+ *   coef     min(1, max_norm / (norm + 1e-6)) as torch defines it (fp64 arithmetic, stored as float); 1 when max_norm <= 0 or +inf
+ *   skip     1: norm is not finite and TF_CLIP_SKIP_NONFINITE was given (coef = 0 then); else 0
+ *   skipped  how many times skip was set since the caller zeroed the state (a plain counter, advanced by tf_grad_clip_coef alone) */
+typedef struct tf_clip_state { double sumsq; double norm; float coef; int32_t skip; int64_t skipped; } tf_clip_state;
+#define TF_CLIP_SKIP_NONFINITE 1
+/* tf_grad_clip_coef: one deterministic pass over the ranges host_segments[nseg][2] (as tf_sgd_step_segments: HOST memory, ascending and
+ * disjoint, TF_SGD_MAX_SEGMENTS per launch) of the flat fp32 gradient.  Every element is squared and summed in fp64; each block stores ONE
+ * partial sum into ws (no atomics: the result is bit-identical from run to run), a one-block launch adds the partials in index order and
+ * writes *state.  Elements outside the ranges are never read; grad is never written.  ws: tf_grad_norm_workspace_bytes(nseg) bytes (exact:
+ * one double per block of every launch at their capped grid; less is TF_ERR_ARG), 8-byte aligned, written in full or in part, never read
+ * beyond what this call wrote.  nseg == 0: norm 0, coef 1 (grad and ws may be NULL). */
+size_t tf_grad_norm_workspace_bytes(int nseg);
+int tf_grad_clip_coef(const float* grad, const int64_t* host_segments, int nseg, float grad_scale, float max_norm, int flags,
+                      void* ws, size_t ws_bytes, tf_clip_state* state /*device*/, void* stream);
+/* tf_sgd_step / tf_sgd_step_segments with the verdict of a tf_grad_clip_coef enqueued earlier on the same stream (replaces optimizer.step()
+ * behind clip_grad_norm_, tinyfaces/trainer.py:86-87): grad_scale * state->coef (one fp32 product) takes the place of grad_scale, and with
+ * state->skip set neither param nor momentum_buf is touched.  state == NULL is TF_ERR_ARG (call the plain entry points instead). */
+int tf_sgd_step_clipped(float* param, const float* grad, float* momentum_buf, int64_t n,
+                        float lr, float momentum, float weight_decay, float grad_scale, const tf_clip_state* state, void* stream);
+int tf_sgd_step_segments_clipped(float* param, const float* grad, float* momentum_buf, const int64_t* host_segments, int nseg,
+                                 float lr, float momentum, float weight_decay, float grad_scale, const tf_clip_state* state, void* stream);
+/* grad[i] *= state->coef over the ranges; with state->skip set nothing is read and ZEROS are stored (coef is 0 then, but NaN * 0 is NaN:
+ * the gradient an optimizer sees behind a skipped step is the zero it was scaled to).  Elements outside the ranges are neither read nor
+ * written.  The in-place scaling clip_grad_norm_ does at tinyfaces/trainer.py:86-87 when torch.optim.SGD applies the update (the autograd path). */
+int tf_scale_segments(float* grad, const int64_t* host_segments, int nseg, const tf_clip_state* state, void* stream);
+
 /* ---- convolution as MFMA implicit GEMM (NHWC) --------------------------------------
  * Replaces every nn.Conv2d on the path (tinyfaces/models/model.py:25-32,90-106 and the
  * torchvision Bottleneck convs) plus the BN / ReLU / residual passes fused around them.

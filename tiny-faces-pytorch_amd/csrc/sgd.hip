@@ -2,11 +2,27 @@
 // Replaces torch.optim.SGD.step as configured at main.py:67-70 (dampening 0, no nesterov):
 //   d = grad*grad_scale + wd*p ;  buf = mu*buf + d  (buf starts at 0, so step 1 gives buf = d) ;  p -= lr*buf
 // HBM bound: 3 reads + 2 writes of 4 B per element, float4-vectorised, grid-stride.
+//
+// Gradient-norm clipping and the non-finite-step guard (the spot between loss.backward() and optimizer.step(), tinyfaces/trainer.py:86-87):
+//   grad_sqnorm_kernel         sum of squares over a range table, fp64, one plain store per block (no atomics: bit-identical run to run)
+//   grad_norm_finalize_kernel  one block: the partials in a fixed order -> tf_clip_state {sumsq, norm, coef, skip, skipped} in device memory
+//   sgd_kernel<true> / sgd_segments_kernel<true>   the update with grad_scale * coef, nothing at all when skip is set
+//   scale_segments_kernel      g *= coef for the autograd path (torch.optim.SGD applies the update)
+// The norm pass reads 4 B per trained element and nothing else: HBM bound.
+#include <math.h>
+
 #include "common.h"
 
 namespace {
+// CLIP: `st` is the verdict of a tf_grad_clip_coef enqueued earlier on the stream -- a skipped step returns before it touches p or m, a
+// clipped one uses gs * coef (one fp32 product).  CLIP = false never looks at `st`: the code of the plain entry points.
+template <bool CLIP>
 __global__ void __launch_bounds__(256) sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  int64_t n, float lr, float mu, float wd, float gs, int vec) {
+                                                  int64_t n, float lr, float mu, float wd, float gs, int vec, const tf_clip_state* __restrict__ st) {
+  if constexpr (CLIP) {
+    if (st->skip) return;
+    gs = gs * st->coef;
+  }
   const int64_t n4 = vec ? (n >> 2) : 0;
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
@@ -37,8 +53,14 @@ __device__ __forceinline__ int seg_of(const SgdSegs& t, int nseg, int64_t j) {
   while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (t.cum[mid] <= j) lo = mid; else hi = mid - 1; }
   return lo;
 }
+template <bool CLIP>
 __global__ void __launch_bounds__(256) sgd_segments_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                           const SgdSegs t, int nseg, float lr, float mu, float wd, float gs, int vec) {
+                                                           const SgdSegs t, int nseg, float lr, float mu, float wd, float gs, int vec,
+                                                           const tf_clip_state* __restrict__ st) {
+  if constexpr (CLIP) {
+    if (st->skip) return;
+    gs = gs * st->coef;
+  }
   const int64_t total = t.cum[nseg];
   const int64_t stride = (int64_t)gridDim.x * 256 * 4;
   for (int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; j < total; j += stride) {
@@ -65,54 +87,229 @@ __global__ void __launch_bounds__(256) sgd_segments_kernel(float* __restrict__ p
     }
   }
 }
-}  // namespace
+// g *= coef over a range table (the index space of sgd_segments_kernel).  A skipped step stores zeros without reading: coef is 0 then, and
+// NaN * 0 would stay NaN.
+__global__ void __launch_bounds__(256) scale_segments_kernel(float* __restrict__ g, const SgdSegs t, int nseg, int vec,
+                                                             const tf_clip_state* __restrict__ st) {
+  const int skip = st->skip;
+  const float coef = st->coef;
+  const int64_t total = t.cum[nseg];
+  const int64_t stride = (int64_t)gridDim.x * 256 * 4;
+  for (int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; j < total; j += stride) {
+    const int k = seg_of(t, nseg, j);
+    const int64_t i = t.start[k] + (j - t.cum[k]);
+    if (vec) {
+      float4 gv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (!skip) {
+        gv = *reinterpret_cast<const float4*>(g + i);
+        gv.x *= coef; gv.y *= coef; gv.z *= coef; gv.w *= coef;
+      }
+      *reinterpret_cast<float4*>(g + i) = gv;
+    } else {
+      for (int e = 0; e < 4 && j + e < total; ++e) {
+        const int ke = seg_of(t, nseg, j + e);
+        const int64_t ie = t.start[ke] + (j + e - t.cum[ke]);
+        g[ie] = skip ? 0.f : g[ie] * coef;
+      }
+    }
+  }
+}
 
-extern "C" int tf_sgd_step_segments(float* param, const float* grad, float* momentum_buf, const int64_t* host_segments, int nseg,
-                                    float lr, float momentum, float weight_decay, float grad_scale, void* stream) {
-  if (nseg < 0 || (nseg > 0 && (!param || !grad || !momentum_buf || !host_segments))) return TF_ERR_ARG;
-  if (nseg == 0) return TF_OK;
+// Sum of squares over a range table: every element widened to fp64 (the square of an fp32 value is exact there), a private sum per
+// thread over its grid-stride walk, then wave (xor butterfly) -> block (LDS, waves in order) -> ONE plain store per block.  Nothing
+// outside the ranges is read; the order of every addition is a function of the launch geometry alone.
+__global__ void __launch_bounds__(256) grad_sqnorm_kernel(const float* __restrict__ g, const SgdSegs t, int nseg, int vec,
+                                                          double* __restrict__ partials) {
+  __shared__ double wsum[4];
+  const int64_t total = t.cum[nseg];
+  const int64_t stride = (int64_t)gridDim.x * 256 * 4;
+  double acc = 0.0;
+  for (int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; j < total; j += stride) {
+    const int k = seg_of(t, nseg, j);
+    const int64_t i = t.start[k] + (j - t.cum[k]);
+    if (vec) {
+      const float4 gv = *reinterpret_cast<const float4*>(g + i);
+      const double x = gv.x, y = gv.y, z = gv.z, w = gv.w;
+      acc += (x * x + y * y) + (z * z + w * w);
+    } else {
+      for (int e = 0; e < 4 && j + e < total; ++e) {
+        const int ke = seg_of(t, nseg, j + e);
+        const double x = g[t.start[ke] + (j + e - t.cum[ke])];
+        acc += x * x;
+      }
+    }
+  }
+  acc = tf::wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// One block: thread t adds partials t, t + 256, ... in index order, then the same wave -> LDS order as above; thread 0 writes the state.
+// It is the only writer of *st while it runs, so `skipped` advances with a plain read-modify-write.
+__global__ void __launch_bounds__(256) grad_norm_finalize_kernel(const double* __restrict__ partials, int count, float grad_scale,
+                                                                 float max_norm, int flags, tf_clip_state* __restrict__ st) {
+  __shared__ double wsum[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < count; i += 256) acc += partials[i];
+  acc = tf::wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double sumsq = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+  const double norm = fabs((double)grad_scale) * sqrt(sumsq);
+  double coef = 1.0;
+  if (max_norm > 0.f && !isinf(max_norm)) {
+    const double c = (double)max_norm / (norm + 1e-6);
+    coef = c > 1.0 ? 1.0 : c;                      // a NaN stays a NaN, as torch.clamp(max=1) leaves it
+  }
+  int skip = 0;
+  if ((flags & TF_CLIP_SKIP_NONFINITE) && !isfinite(norm)) { skip = 1; coef = 0.0; }
+  st->sumsq = sumsq;
+  st->norm = norm;
+  st->coef = (float)coef;
+  st->skip = skip;
+  if (skip) st->skipped = st->skipped + 1;
+}
+
+bool table_ok(const int64_t* host_segments, int nseg) {          // ascending, disjoint
   int64_t prev = 0;
   for (int k = 0; k < nseg; ++k) {
     const int64_t s = host_segments[2 * k], e = host_segments[2 * k + 1];
-    if (s < prev || e < s) return TF_ERR_ARG;                  // ascending, disjoint
+    if (s < prev || e < s) return false;
     prev = e;
   }
+  return true;
+}
+// The table of the launch that starts at range k0 (empty ranges dropped).  Returns the ranges used; *vec is cleared by a range that is not
+// 4-aligned, *blocks is the capped grid (<= 2048 blocks of 256 threads, four compact elements per thread and trip).
+int fill_table(const int64_t* host_segments, int nseg, int k0, SgdSegs* t, int* vec, int64_t* blocks) {
+  const int n = nseg - k0 < TF_SGD_MAX_SEGMENTS ? nseg - k0 : TF_SGD_MAX_SEGMENTS;
+  int64_t cum = 0;
+  int used = 0;
+  for (int k = 0; k < n; ++k) {
+    const int64_t s = host_segments[2 * (k0 + k)], e = host_segments[2 * (k0 + k) + 1];
+    if (e == s) continue;
+    if ((s & 3) || (e & 3)) *vec = 0;
+    t->start[used] = s; t->cum[used] = cum; cum += e - s; ++used;
+  }
+  if (used == 0) return 0;
+  t->cum[used] = cum;
+  for (int k = used; k < TF_SGD_MAX_SEGMENTS; ++k) { t->start[k] = 0; t->cum[k + 1] = cum; }
+  int64_t b = ((cum + 3) / 4 + 255) / 256;
+  if (b < 1) b = 1;
+  if (b > 2048) b = 2048;
+  *blocks = b;
+  return used;
+}
+
+int sgd_segments(float* param, const float* grad, float* momentum_buf, const int64_t* host_segments, int nseg, float lr, float momentum,
+                 float weight_decay, float grad_scale, const tf_clip_state* state, void* stream) {
+  if (nseg < 0 || (nseg > 0 && (!param || !grad || !momentum_buf || !host_segments))) return TF_ERR_ARG;
+  if (nseg == 0) return TF_OK;
+  if (!table_ok(host_segments, nseg)) return TF_ERR_ARG;
   const bool aligned = (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)momentum_buf) & 15) == 0;
   for (int k0 = 0; k0 < nseg; k0 += TF_SGD_MAX_SEGMENTS) {
-    const int n = nseg - k0 < TF_SGD_MAX_SEGMENTS ? nseg - k0 : TF_SGD_MAX_SEGMENTS;
     SgdSegs t;
     int vec = aligned ? 1 : 0;
-    int64_t cum = 0;
-    int used = 0;
-    for (int k = 0; k < n; ++k) {
-      const int64_t s = host_segments[2 * (k0 + k)], e = host_segments[2 * (k0 + k) + 1];
-      if (e == s) continue;
-      if ((s & 3) || (e & 3)) vec = 0;
-      t.start[used] = s; t.cum[used] = cum; cum += e - s; ++used;
-    }
+    int64_t blocks = 0;
+    const int used = fill_table(host_segments, nseg, k0, &t, &vec, &blocks);
     if (used == 0) continue;
-    t.cum[used] = cum;
-    for (int k = used; k < TF_SGD_MAX_SEGMENTS; ++k) { t.start[k] = 0; t.cum[k + 1] = cum; }
-    int64_t blocks = ((cum + 3) / 4 + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(sgd_segments_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, t, used, lr,
-                       momentum, weight_decay, grad_scale, vec);
+    if (state)
+      hipLaunchKernelGGL(sgd_segments_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, t,
+                         used, lr, momentum, weight_decay, grad_scale, vec, state);
+    else
+      hipLaunchKernelGGL(sgd_segments_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, t,
+                         used, lr, momentum, weight_decay, grad_scale, vec, (const tf_clip_state*)nullptr);
   }
   TF_CHECK_LAUNCH();
   return TF_OK;
 }
 
-extern "C" int tf_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n,
-                           float lr, float momentum, float weight_decay, float grad_scale, void* stream) {
+int sgd_flat(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum, float weight_decay, float grad_scale,
+             const tf_clip_state* state, void* stream) {
   if (n < 0 || (n > 0 && (!param || !grad || !momentum_buf))) return TF_ERR_ARG;
   if (n == 0) return TF_OK;
   const int vec = (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)momentum_buf) & 15) == 0;   // float4 path needs 16-byte alignment
   int64_t blocks = ((vec ? (n >> 2) : n) + 255) / 256;
   if (blocks < 1) blocks = 1;
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, n, lr,
-                     momentum, weight_decay, grad_scale, vec);
+  if (state)
+    hipLaunchKernelGGL(sgd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, n, lr,
+                       momentum, weight_decay, grad_scale, vec, state);
+  else
+    hipLaunchKernelGGL(sgd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, n, lr,
+                       momentum, weight_decay, grad_scale, vec, (const tf_clip_state*)nullptr);
+  TF_CHECK_LAUNCH();
+  return TF_OK;
+}
+}  // namespace
+
+extern "C" int tf_sgd_step_segments(float* param, const float* grad, float* momentum_buf, const int64_t* host_segments, int nseg,
+                                    float lr, float momentum, float weight_decay, float grad_scale, void* stream) {
+  return sgd_segments(param, grad, momentum_buf, host_segments, nseg, lr, momentum, weight_decay, grad_scale, nullptr, stream);
+}
+
+extern "C" int tf_sgd_step_segments_clipped(float* param, const float* grad, float* momentum_buf, const int64_t* host_segments, int nseg,
+                                            float lr, float momentum, float weight_decay, float grad_scale, const tf_clip_state* state,
+                                            void* stream) {
+  if (!state) return TF_ERR_ARG;
+  return sgd_segments(param, grad, momentum_buf, host_segments, nseg, lr, momentum, weight_decay, grad_scale, state, stream);
+}
+
+extern "C" int tf_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n,
+                           float lr, float momentum, float weight_decay, float grad_scale, void* stream) {
+  return sgd_flat(param, grad, momentum_buf, n, lr, momentum, weight_decay, grad_scale, nullptr, stream);
+}
+
+extern "C" int tf_sgd_step_clipped(float* param, const float* grad, float* momentum_buf, int64_t n,
+                                   float lr, float momentum, float weight_decay, float grad_scale, const tf_clip_state* state, void* stream) {
+  if (!state) return TF_ERR_ARG;
+  return sgd_flat(param, grad, momentum_buf, n, lr, momentum, weight_decay, grad_scale, state, stream);
+}
+
+// One double per block of every launch, at the capped grid: the caller sizes the workspace from the table length alone.
+extern "C" size_t tf_grad_norm_workspace_bytes(int nseg) {
+  if (nseg <= 0) return 0;
+  const size_t launches = ((size_t)nseg + TF_SGD_MAX_SEGMENTS - 1) / TF_SGD_MAX_SEGMENTS;
+  return launches * 2048 * sizeof(double);
+}
+
+extern "C" int tf_grad_clip_coef(const float* grad, const int64_t* host_segments, int nseg, float grad_scale, float max_norm, int flags,
+                                 void* ws, size_t ws_bytes, tf_clip_state* state, void* stream) {
+  if (!state || nseg < 0 || (nseg > 0 && (!grad || !host_segments || !ws))) return TF_ERR_ARG;
+  if (nseg > 0 && (!table_ok(host_segments, nseg) || ws_bytes < tf_grad_norm_workspace_bytes(nseg) || ((uintptr_t)ws & 7))) return TF_ERR_ARG;
+  double* partials = (double*)ws;
+  const bool aligned = ((uintptr_t)grad & 15) == 0;
+  int64_t base = 0;                                             // partials written so far: launch k stores [base, base + its blocks)
+  for (int k0 = 0; k0 < nseg; k0 += TF_SGD_MAX_SEGMENTS) {
+    SgdSegs t;
+    int vec = aligned ? 1 : 0;
+    int64_t blocks = 0;
+    const int used = fill_table(host_segments, nseg, k0, &t, &vec, &blocks);
+    if (used == 0) continue;
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, grad, t, used, vec, partials + base);
+    base += blocks;
+  }
+  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, (int)base, grad_scale,
+                     max_norm, flags, state);
+  TF_CHECK_LAUNCH();
+  return TF_OK;
+}
+
+extern "C" int tf_scale_segments(float* grad, const int64_t* host_segments, int nseg, const tf_clip_state* state, void* stream) {
+  if (!state || nseg < 0 || (nseg > 0 && (!grad || !host_segments))) return TF_ERR_ARG;
+  if (nseg == 0) return TF_OK;
+  if (!table_ok(host_segments, nseg)) return TF_ERR_ARG;
+  const bool aligned = ((uintptr_t)grad & 15) == 0;
+  for (int k0 = 0; k0 < nseg; k0 += TF_SGD_MAX_SEGMENTS) {
+    SgdSegs t;
+    int vec = aligned ? 1 : 0;
+    int64_t blocks = 0;
+    const int used = fill_table(host_segments, nseg, k0, &t, &vec, &blocks);
+    if (used == 0) continue;
+    hipLaunchKernelGGL(scale_segments_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, grad, t, used, vec, state);
+  }
   TF_CHECK_LAUNCH();
   return TF_OK;
 }

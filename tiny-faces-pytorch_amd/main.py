@@ -14,7 +14,7 @@ from pathlib import Path
 import torch
 from torch import optim
 
-from tinyfaces import parallel, trainer, transforms
+from tinyfaces import ops, parallel, trainer, transforms
 from tinyfaces.datasets import get_dataloader
 from tinyfaces.engine import TrainEngine
 from tinyfaces.models.loss import DetectionCriterion
@@ -74,20 +74,38 @@ TRAINABLE_HELP = ("--trainable-layers {0,1,2,3,4}: train the heads and the top K
                   "(DetectionModel.set_trainable_layers: torchvision's trainable_backbone_layers), default 4 = everything; K < 4 needs --freeze-bn")
 
 
+CLIP_HELP = ("--clip-grad-norm FLOAT: clip the global L2 norm of the gradient to FLOAT before every update (torch.nn.utils.clip_grad_norm_ "
+             "between backward() and optimizer.step(); computed and applied on the device), default off")
+
+
+SKIP_HELP = ("--skip-nonfinite: a step whose gradient norm is NaN or Inf is not applied (the fused engine leaves parameters and momentum "
+             "untouched; the autograd path zeroes the gradient), default off")
+
+
+def _positive_float(text):
+    value = float(text)
+    if not value > 0.0:
+        raise argparse.ArgumentTypeError(f"must be a positive number, got {text}")
+    return value
+
+
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog=TRUNK_HELP + "; " + FREEZE_HELP + "; " + TRAINABLE_HELP)
+    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP)))
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
 
 
 def trunk_arguments(argv=None):
-    """`arguments` plus `base_model` from --base-model, `freeze_bn` from --freeze-bn and `trainable_layers` from --trainable-layers.  Parsed apart, so that
-    `arguments` keeps resolving exactly the reference's options and the additions above."""
+    """`arguments` plus `base_model` from --base-model, `freeze_bn` from --freeze-bn, `trainable_layers` from --trainable-layers, `clip_grad_norm`
+    from --clip-grad-norm and `skip_nonfinite` from --skip-nonfinite.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
+    options and the additions above."""
     parser = argparse.ArgumentParser(add_help=False)
     parser.add_argument("--base-model", dest="base_model", default="resnet101", choices=list(model_zoo.TRUNKS), help=TRUNK_HELP)
     parser.add_argument("--freeze-bn", dest="freeze_bn", action="store_true", help=FREEZE_HELP)
     parser.add_argument("--trainable-layers", dest="trainable_layers", default=4, type=int, choices=range(5), help=TRAINABLE_HELP)
+    parser.add_argument("--clip-grad-norm", dest="clip_grad_norm", default=None, type=_positive_float, help=CLIP_HELP)
+    parser.add_argument("--skip-nonfinite", dest="skip_nonfinite", action="store_true", help=SKIP_HELP)
     known, rest = parser.parse_known_args(argv)
     if known.trainable_layers < 4 and not known.freeze_bn:
         parser.error(f"--trainable-layers {known.trainable_layers} freezes stages of the trunk, which is defined on frozen BatchNorm only: add --freeze-bn")
@@ -95,6 +113,8 @@ def trunk_arguments(argv=None):
     args.base_model = known.base_model
     args.freeze_bn = known.freeze_bn
     args.trainable_layers = known.trainable_layers
+    args.clip_grad_norm = known.clip_grad_norm
+    args.skip_nonfinite = known.skip_nonfinite
     return args
 
 
@@ -166,7 +186,8 @@ def main():
 
     engine = optimizer = scheduler = None
     if args.fused:
-        engine = TrainEngine(model, loss_fn, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay, device=device)
+        engine = TrainEngine(model, loss_fn, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay, device=device,
+                             max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
         if state is not None:
             engine.load_optimizer_state_dict(state.get("optimizer"))      # momentum buffers (a torch.optim.SGD state_dict)
     else:
@@ -189,6 +210,7 @@ def main():
             g["lr"] = want
         scheduler._last_lr = [g["lr"] for g in optimizer.param_groups]       # what get_last_lr() reports must be what the groups hold
 
+    skipped = 0
     for epoch in range(first_epoch, args.epochs):
         if hasattr(train_loader, "set_epoch"):
             train_loader.set_epoch(epoch)                                 # reshuffle the rank shards
@@ -197,8 +219,14 @@ def main():
         if engine is not None:
             run_fused_epoch(engine, loss_fn, train_loader, epoch, device, args.lr)
         else:
-            trainer.train(model, loss_fn, optimizer, train_loader, epoch, device=device)
+            trainer.train(model, loss_fn, optimizer, train_loader, epoch, device=device, max_grad_norm=args.clip_grad_norm,
+                          skip_nonfinite=args.skip_nonfinite)
             scheduler.step()
+        if args.skip_nonfinite and parallel.rank() == 0:
+            total = engine.skipped_steps if engine is not None else ops.clip_skipped_steps(device)
+            if total != skipped:
+                print(f"Epoch: [{epoch}]\t{total - skipped} step(s) skipped: the gradient norm was not finite ({total} since the start)")
+                skipped = total
         done = epoch + 1
         if done % args.save_every == 0 and parallel.rank() == 0:
             if engine is not None:

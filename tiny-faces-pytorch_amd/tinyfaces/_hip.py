@@ -60,6 +60,14 @@ class CommPlan(C.Structure):
                 ("rc", i32), ("issued", i32), ("status", C.POINTER(i32))]
 
 
+class ClipState(C.Structure):
+    """tf_clip_state (include/tinyfaces_hip.h): what tf_grad_clip_coef leaves in device memory, 32 bytes."""
+    _fields_ = [("sumsq", C.c_double), ("norm", C.c_double), ("coef", f32), ("skip", i32), ("skipped", i64)]
+
+
+TF_CLIP_SKIP_NONFINITE = 1
+
+
 class ConvArgs(C.Structure):
     _fields_ = [("dtype", i32), ("mode", i32),
                 ("N", i32), ("H", i32), ("W", i32), ("Cin", i32), ("OH", i32), ("OW", i32), ("Cout", i32),
@@ -104,6 +112,11 @@ _SIGNATURES = {
     "tf_image_prepare": (i32, [C.POINTER(ImagePrepareArgs), vp]),
     "tf_sgd_step": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, vp]),
     "tf_sgd_step_segments": (i32, [vp, vp, vp, C.POINTER(i64), i32, f32, f32, f32, f32, vp]),
+    "tf_grad_norm_workspace_bytes": (C.c_size_t, [i32]),
+    "tf_grad_clip_coef": (i32, [vp, C.POINTER(i64), i32, f32, f32, i32, vp, C.c_size_t, vp, vp]),
+    "tf_sgd_step_clipped": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, vp, vp]),
+    "tf_sgd_step_segments_clipped": (i32, [vp, vp, vp, C.POINTER(i64), i32, f32, f32, f32, f32, vp, vp]),
+    "tf_scale_segments": (i32, [vp, C.POINTER(i64), i32, vp, vp]),
     "tf_conv_mtiles": (i32, [C.POINTER(ConvArgs)]),
     "tf_conv2d": (i32, [C.POINTER(ConvArgs), vp]),
     "tf_pack_weight": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp]),

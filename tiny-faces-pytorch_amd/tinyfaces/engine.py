@@ -2,7 +2,8 @@
 no per-parameter Python loop and no host sync:
 
     targets (HIP) -> forward (HIP executor) -> criterion fwd+bwd (HIP) -> backward (HIP executor)
-    -> [RCCL all-reduce of the flat gradient, overlapped with the backward pass] -> fused SGD (one launch per group)
+    -> [RCCL all-reduce of the flat gradient, overlapped with the backward pass]
+    -> [global gradient norm -> clip coefficient / non-finite verdict, in device memory] -> fused SGD (one launch per group)
 
 Data-parallel overlap: the flat gradient is cut along the backward order into buckets of ~`bucket_mb` MB (default 10: heads +
 layer3.21-22 first, then THREE layer-3 bottlenecks of 4.46 MB each per bucket (two stay under 10 MB), ..., finally layer1/2 + stem: SURVEY.md 8e asks for
@@ -24,7 +25,14 @@ from ._hip import lib
 
 
 class TrainEngine:
-    def __init__(self, model, criterion, lr=1e-4, momentum=0.9, weight_decay=5e-4, device="cuda", bucket_mb=10, native_exchange=None):
+    def __init__(self, model, criterion, lr=1e-4, momentum=0.9, weight_decay=5e-4, device="cuda", bucket_mb=10, native_exchange=None,
+                 max_grad_norm=None, skip_nonfinite=False):
+        """max_grad_norm: clip the global L2 norm of the (rank-averaged) gradient of the trained tensors to this value before the update, as
+        torch.nn.utils.clip_grad_norm_ between backward() and optimizer.step() would (tinyfaces/trainer.py:86-87).  skip_nonfinite: a step
+        whose gradient norm is NaN or Inf changes neither the parameters nor the momentum (`skipped_steps` counts them; what the FORWARD
+        pass of that step wrote -- the running BatchNorm statistics of a batch-statistics step -- stays written).  Both decisions
+        are taken and applied on the device: the step stays free of host syncs.  With the defaults (None, False) a step launches exactly
+        what it launched before these arguments existed."""
         self.device = torch.device(device)
         self.model = model.to(self.device).train()
         self.criterion = criterion
@@ -52,6 +60,12 @@ class TrainEngine:
         # at the end of the step.  Same numbers bit for bit; 1113-1117 img/s against 1118-1123 at the end (A/B on one box): the update
         # is HBM-bound (850 MB) and takes from the backward pass what it saves at the tail.
         self.sgd_per_bucket = bool(os.environ.get("TINYFACES_SGD_PER_BUCKET"))
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._clip_state = None               # ops.ClipState, allocated by the first step that needs it
+        self.set_max_grad_norm(max_grad_norm)
+        if self._clip_on() and self.sgd_per_bucket:
+            raise ValueError("max_grad_norm / skip_nonfinite cannot be combined with TINYFACES_SGD_PER_BUCKET: a bucket cannot be applied "
+                             "before the global gradient norm exists")
         if parallel.is_distributed() or self.sgd_per_bucket:
             self._setup_overlap()
 
@@ -281,6 +295,63 @@ class TrainEngine:
     def set_lr(self, lr):
         self.lr = lr
 
+    # ---- gradient-norm clipping and the non-finite-step guard ----------------------------------------------------------
+    def set_max_grad_norm(self, max_grad_norm):
+        """None: no clipping.  Otherwise a positive number, the largest global L2 norm the applied gradient may have."""
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:
+                raise ValueError(f"max_grad_norm must be positive or None, got {max_grad_norm}")
+            if getattr(self, "sgd_per_bucket", False):
+                raise ValueError("max_grad_norm cannot be combined with TINYFACES_SGD_PER_BUCKET")
+        self.max_grad_norm = max_grad_norm
+        return self
+
+    def _clip_on(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    @property
+    def last_grad_norm(self):
+        """Global L2 norm of the gradient the last clipped / guarded step saw (after the average over ranks, before clipping): a 0-d
+        float64 DEVICE tensor that shares the state's memory -- reading it synchronises, asking for it does not.  None before such a step."""
+        return None if self._clip_state is None else self._clip_state.norm_tensor()
+
+    @property
+    def last_clip_coef(self):
+        """The coefficient the last clipped step multiplied its gradient with (1: not clipped, 0: skipped).  Synchronises."""
+        return None if self._clip_state is None else self._clip_state.coef()
+
+    @property
+    def skipped_steps(self):
+        """How many steps the non-finite guard has skipped so far (reads the device counter: synchronises)."""
+        return 0 if self._clip_state is None else self._clip_state.skipped()
+
+    def _norm_segments(self):
+        """The ranges the gradient norm is taken over: _trained_segments(), each extended over the alignment pad of its own slot (the
+        backward pass zeroes the pads with the rest of the flat gradient, and the group-wide SGD launch walks them too) and joined where they
+        touch -- a 4-aligned table takes the kernel's 16-byte path, and the batch-statistics step needs a handful of ranges instead of one
+        per tensor.  The frozen slices in between stay outside."""
+        trained = self._trained_segments()
+        if getattr(self, "_norm_key", None) is not trained:
+            out = []
+            for s, e in trained:
+                e = (e + 3) // 4 * 4
+                if out and out[-1][1] == s:
+                    out[-1][1] = e
+                else:
+                    out.append([s, e])
+            self._norm_segs, self._norm_key = [tuple(r) for r in out], trained
+        return self._norm_segs
+
+    def _clip_coef(self, gflat, scale):
+        """Enqueue norm -> coefficient -> verdict behind the (joined) gradient exchange; `scale` = 1 / world makes it the norm of the
+        AVERAGED gradient, what clip_grad_norm_ behind a DDP all-reduce sees.  Every rank computes it from the same summed gradient, so a
+        NaN on one rank makes every rank skip the same step without a further collective."""
+        if self._clip_state is None:
+            self._clip_state = ops.ClipState(gflat.device)
+        return ops.grad_clip_coef(gflat, self._norm_segments(), self._clip_state, grad_scale=scale, max_norm=self.max_grad_norm,
+                                  skip_nonfinite=self.skip_nonfinite)
+
     # ---- checkpoint interop with torch.optim.SGD (main.py:67-76,97-102) ------------------------------------------------
     def _group_params(self):
         """[(lr multiplier, [(state_dict key, nn.Parameter)])] in the order of DetectionModel.learnable_parameters
@@ -452,14 +523,16 @@ class TrainEngine:
             self._trained_key = key
         return self._trained
 
-    def _sgd(self, gflat, a, b, mult, scale):
+    def _sgd(self, gflat, a, b, mult, scale, clip=None):
         """The SGD update of the flat range [a, b) (inside one parameter group, lr multiplier `mult`).  With the model's BatchNorm frozen
-        only the trained segments of the range are touched, in one launch per TF_SGD_MAX_SEGMENTS segments (ops.sgd_step_segments)."""
+        only the trained segments of the range are touched, in one launch per TF_SGD_MAX_SEGMENTS segments (ops.sgd_step_segments).
+        clip: the ClipState of this step (_clip_coef) -- the clipped / guarded forms of the same two launches."""
+        kw = {} if clip is None else {"clip_state": clip}       # (the default step calls the ops exactly as it always did)
         if not self.model.batchnorm_frozen:
-            ops.sgd_step(self.flat_p[a:b], gflat[a:b], self.flat_m[a:b], self.lr * mult, self.momentum, self.weight_decay, scale)
+            ops.sgd_step(self.flat_p[a:b], gflat[a:b], self.flat_m[a:b], self.lr * mult, self.momentum, self.weight_decay, scale, **kw)
             return
         segs = [(max(s, a), min(e, b)) for s, e in self._trained_segments() if e > a and s < b]
-        ops.sgd_step_segments(self.flat_p, gflat, self.flat_m, segs, self.lr * mult, self.momentum, self.weight_decay, scale)
+        ops.sgd_step_segments(self.flat_p, gflat, self.flat_m, segs, self.lr * mult, self.momentum, self.weight_decay, scale, **kw)
 
     def step(self, x, class_map, regression_map):
         """x (B,3,H,W) f32, class_map (B,nt,h,w) f32 (mined in place), regression_map (B,4nt,h,w) f32: all on the device.
@@ -467,7 +540,9 @@ class TrainEngine:
         The step follows the model's BatchNorm mode (DetectionModel.freeze_batchnorm): frozen, the forward and backward run the folded-BN
         graph, and the update skips the BatchNorm vectors (no weight decay, no momentum: their momentum buffers stay zero) and, with
         DetectionModel.set_trainable_layers(k < 4), the conv weights of the frozen stages; the bucket plan of the gradient exchange stays
-        as it is (frozen ranges are reduced as zeros)."""
+        as it is (frozen ranges are reduced as zeros).
+        With max_grad_norm / skip_nonfinite the update is clipped / guarded on the device (see __init__); a skipped step still counts in
+        `steps` and still returns its loss."""
         m, c = self.model, self.criterion
         m._check_partial_freeze()
         m._sync_tables(x.device)
@@ -492,10 +567,11 @@ class TrainEngine:
         else:
             if reduce:
                 self._allreduce(gflat)
+            clip = self._clip_coef(gflat, scale) if self._clip_on() else None      # behind the join: the norm of the summed gradient
             for s, e, mult in self.groups:
                 if mult == 0.0:
                     continue                              # score4_upsample: lr 0 (model.py:84) -> nothing to do
-                self._sgd(gflat, s, e, mult, scale)
+                self._sgd(gflat, s, e, mult, scale, clip)
         self.steps += 1
         if hasattr(c, "_pending") and (parallel.rank() == 0 or not parallel.is_distributed()):
             c._pending.append((loss2, x.shape[0]))       # only the logging rank ever flushes the meters

@@ -310,19 +310,149 @@ def image_prepare(img_u8, resized_hw=None, crop=None, paste=(0, 0), flip=False, 
     return out
 
 
-def sgd_step(param, grad, momentum_buf, lr, momentum, weight_decay, grad_scale=1.0):
-    """torch.optim.SGD.step for one flat fp32 segment (main.py:67-70)."""
+class ClipState:
+    """The 32 bytes of device memory a clipped step keeps its verdict in (tf_clip_state, include/tinyfaces_hip.h): written by
+    `grad_clip_coef`, read by `sgd_step(..., clip_state=)`, `sgd_step_segments(..., clip_state=)` and `scale_segments` on the device.  The
+    readers below copy it to the host, i.e. they synchronise; `norm_tensor()` is a 0-d device view and does not."""
+
+    def __init__(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"ClipState: device {device}; the tiny-faces hot path only exists as HIP kernels for MI355X (gfx950) -- "
+                               "there is no CPU fallback.")
+        self.buf = torch.zeros(C.sizeof(_hip.ClipState), dtype=torch.uint8, device=device)
+
+    def read(self):
+        """The whole state as a host-side _hip.ClipState (synchronises)."""
+        return _hip.ClipState.from_buffer_copy(self.buf.cpu().numpy().tobytes())
+
+    def norm_tensor(self):
+        """The norm as a 0-d float64 device tensor sharing the state's memory (no sync): it shows the latest grad_clip_coef."""
+        return self.buf[8:16].view(torch.float64).view(())
+
+    def sumsq(self):
+        return float(self.read().sumsq)
+
+    def norm(self):
+        return float(self.read().norm)
+
+    def coef(self):
+        return float(self.read().coef)
+
+    def skip(self):
+        return int(self.read().skip)
+
+    def skipped(self):
+        return int(self.read().skipped)
+
+
+def _segment_table(what, segments, n):
+    """[(start, end)] -> the ctypes table of the *_segments entry points (empty ranges dropped); ValueError when out of order or outside n."""
+    segments = [(int(s), int(e)) for s, e in segments if e > s]
+    prev = 0
+    for s, e in segments:
+        if s < prev or e > n:
+            raise ValueError(f"{what}: range ({s}, {e}) is out of order or outside the {n} elements of the buffers")
+        prev = e
+    return (C.c_int64 * (2 * len(segments)))(*[v for se in segments for v in se]), len(segments)
+
+
+def grad_clip_coef(grad_flat, segments, state, grad_scale=1.0, max_norm=None, skip_nonfinite=False):
+    """The first half of torch.nn.utils.clip_grad_norm_ (the spot between loss.backward() and optimizer.step(), tinyfaces/trainer.py:86-87):
+    the global L2 norm of `grad_scale * grad_flat` over the element ranges `segments` ([(start, end)], ascending, disjoint), the clip
+    coefficient min(1, max_norm / (norm + 1e-6)) (max_norm None: 1) and, with skip_nonfinite, the verdict "skip this step" for a norm that
+    is not finite -- all left in `state` (ClipState) on the device, no host sync.  Deterministic: fp64 sums in a fixed order, no atomics."""
+    require_gpu(grad_flat, "grad_clip_coef")
+    assert grad_flat.dtype == torch.float32 and grad_flat.is_contiguous() and state.buf.device == grad_flat.device
+    table, nseg = _segment_table("grad_clip_coef", segments, grad_flat.numel())
+    need = int(lib().tf_grad_norm_workspace_bytes(nseg))
+    ws = _workspace("grad_norm", need, grad_flat.device)
+    flags = _hip.TF_CLIP_SKIP_NONFINITE if skip_nonfinite else 0
+    with torch.cuda.device(grad_flat.device):
+        check(lib().tf_grad_clip_coef(ptr(grad_flat), table, nseg, float(grad_scale), 0.0 if max_norm is None else float(max_norm), flags,
+                                      ptr(ws), ws.numel(), ptr(state.buf), stream()), "tf_grad_clip_coef")
+    return state
+
+
+def scale_segments(grad_flat, segments, state):
+    """grad_flat[ranges] *= state.coef on the device (zeros behind a skipped step), everything else untouched: the second half of
+    clip_grad_norm_ for the autograd path, where torch.optim.SGD applies the update (tinyfaces/trainer.py:86-87)."""
+    require_gpu(grad_flat, "scale_segments")
+    assert grad_flat.dtype == torch.float32 and grad_flat.is_contiguous() and state.buf.device == grad_flat.device
+    table, nseg = _segment_table("scale_segments", segments, grad_flat.numel())
+    if nseg == 0:
+        return
+    with torch.cuda.device(grad_flat.device):
+        check(lib().tf_scale_segments(ptr(grad_flat), table, nseg, ptr(state.buf), stream()), "tf_scale_segments")
+
+
+_clip_states = {}
+
+
+def clip_grad_norm_(parameters, max_norm, skip_nonfinite=False):
+    """Drop-in for torch.nn.utils.clip_grad_norm_(parameters, max_norm) (L2, error_if_nonfinite=False) on this model's gradients, between
+    loss.backward() and optimizer.step() (tinyfaces/trainer.py:86-87): two launches of the norm pass and one scaling pass instead of a few
+    hundred small kernels, and no host round trip.  The fp32 CUDA `.grad`s are addressed as element ranges from the lowest data_ptr()
+    (views of one flat buffer and separately allocated tensors alike; nothing between the tensors is read or written).  Returns the norm
+    as a 0-d float64 device tensor without synchronising; it is overwritten by the next call on the same device.  With skip_nonfinite a
+    norm that is not finite ZEROES the gradients instead of scaling them: the optimizer then still applies weight decay and momentum."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        raise ValueError("clip_grad_norm_: no parameter has a gradient")
+    for g in grads:
+        require_gpu(g, "clip_grad_norm_")
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            raise ValueError("clip_grad_norm_: gradients must be contiguous fp32 tensors")
+        if g.device != grads[0].device:
+            raise ValueError("clip_grad_norm_: gradients live on more than one device")
+    dev = grads[0].device
+    spans = sorted({(g.data_ptr(), g.numel()) for g in grads if g.numel()})
+    base = spans[0][0] if spans else 0
+    segs = [((a - base) // 4, (a - base) // 4 + n) for a, n in spans]
+    for (_, e0), (s1, _) in zip(segs, segs[1:]):
+        if s1 < e0:
+            raise ValueError("clip_grad_norm_: gradients overlap in memory")
+    state = _clip_states.get(dev)
+    if state is None:
+        state = _clip_states[dev] = ClipState(dev)
+    table = (C.c_int64 * (2 * len(segs)))(*[v for se in segs for v in se])
+    need = int(lib().tf_grad_norm_workspace_bytes(len(segs)))
+    ws = _workspace("grad_norm", need, dev)
+    with torch.cuda.device(dev):
+        check(lib().tf_grad_clip_coef(base, table, len(segs), 1.0, float(max_norm), _hip.TF_CLIP_SKIP_NONFINITE if skip_nonfinite else 0,
+                                      ptr(ws), ws.numel(), ptr(state.buf), stream()), "tf_grad_clip_coef")
+        if segs:
+            check(lib().tf_scale_segments(base, table, len(segs), ptr(state.buf), stream()), "tf_scale_segments")
+    return state.norm_tensor()
+
+
+def clip_skipped_steps(device):
+    """How many calls of clip_grad_norm_(..., skip_nonfinite=True) on `device` met a gradient norm that was not finite (synchronises)."""
+    state = _clip_states.get(torch.device(device))
+    return 0 if state is None else state.skipped()
+
+
+def sgd_step(param, grad, momentum_buf, lr, momentum, weight_decay, grad_scale=1.0, clip_state=None):
+    """torch.optim.SGD.step for one flat fp32 segment (main.py:67-70).  clip_state (ClipState, filled by grad_clip_coef on this stream): the
+    step behind clip_grad_norm_ -- grad_scale * coef, nothing at all when the state says skip."""
     require_gpu(param, "sgd_step")
     assert param.dtype == grad.dtype == momentum_buf.dtype == torch.float32
     assert param.is_contiguous() and grad.is_contiguous() and momentum_buf.is_contiguous()
     with torch.cuda.device(param.device):
+        if clip_state is not None:
+            check(lib().tf_sgd_step_clipped(ptr(param), ptr(grad), ptr(momentum_buf), param.numel(), float(lr), float(momentum),
+                                            float(weight_decay), float(grad_scale), ptr(clip_state.buf), stream()), "tf_sgd_step_clipped")
+            return
         check(lib().tf_sgd_step(ptr(param), ptr(grad), ptr(momentum_buf), param.numel(), float(lr), float(momentum),
                                 float(weight_decay), float(grad_scale), stream()), "tf_sgd_step")
 
 
-def sgd_step_segments(param, grad, momentum_buf, segments, lr, momentum, weight_decay, grad_scale=1.0):
+def sgd_step_segments(param, grad, momentum_buf, segments, lr, momentum, weight_decay, grad_scale=1.0, clip_state=None):
     """torch.optim.SGD.step over the element ranges `segments` ([(start, end)], ascending, disjoint) of three flat fp32 buffers;
-    everything outside the ranges is left untouched (tf_sgd_step_segments: parameters without a gradient, e.g. frozen BatchNorm vectors)."""
+    everything outside the ranges is left untouched (tf_sgd_step_segments: parameters without a gradient, e.g. frozen BatchNorm vectors).
+    clip_state: as in sgd_step (tf_sgd_step_segments_clipped)."""
     require_gpu(param, "sgd_step_segments")
     assert param.dtype == grad.dtype == momentum_buf.dtype == torch.float32
     assert param.is_contiguous() and grad.is_contiguous() and momentum_buf.is_contiguous()
@@ -338,6 +468,11 @@ def sgd_step_segments(param, grad, momentum_buf, segments, lr, momentum, weight_
         return
     table = (C.c_int64 * (2 * len(segments)))(*[v for se in segments for v in se])
     with torch.cuda.device(param.device):
+        if clip_state is not None:
+            check(lib().tf_sgd_step_segments_clipped(ptr(param), ptr(grad), ptr(momentum_buf), table, len(segments), float(lr),
+                                                     float(momentum), float(weight_decay), float(grad_scale), ptr(clip_state.buf), stream()),
+                  "tf_sgd_step_segments_clipped")
+            return
         check(lib().tf_sgd_step_segments(ptr(param), ptr(grad), ptr(momentum_buf), table, len(segments), float(lr), float(momentum),
                                          float(weight_decay), float(grad_scale), stream()), "tf_sgd_step_segments")
 

@@ -7,7 +7,7 @@ from pathlib import Path
 
 import torch
 
-from . import parallel
+from . import ops, parallel
 
 _LOSS_FMT = "\tloss_cls: {:.6f}\tloss_reg: {:.6f}"
 
@@ -30,12 +30,22 @@ def _is_logging_rank():
     return parallel.rank() == 0 or not parallel.is_distributed()
 
 
-def train(model, loss_fn, optimizer, dataloader, epoch, device):
+def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=None, skip_nonfinite=False):
     """One epoch with the reference's step order (trainer.py:68-90): forward, criterion, zero_grad, backward, [all-reduce],
-    optimizer step, progress line."""
+    optimizer step, progress line.
+
+    max_grad_norm / skip_nonfinite (keyword additions behind the reference's signature): ops.clip_grad_norm_ over the gradients of the
+    optimizer's parameters between the averaging and optimizer.step(), the spot torch.nn.utils.clip_grad_norm_ takes in a training loop
+    (trainer.py:86-87), without a host round trip.  skip_nonfinite alone (max_grad_norm None) only guards.  On a step the guard skips the
+    gradient is scaled to ZERO, and torch.optim.SGD still applies weight decay and momentum to the parameters: that is what torch's
+    optimizer does with a zero gradient.  Only the fused engine (TrainEngine(skip_nonfinite=True)) leaves a skipped step untouched."""
     net = model.to(device).train()
     reducer = parallel.reducer_for(net)
     n_batches = len(dataloader)
+    clip = max_grad_norm is not None or skip_nonfinite
+    if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+        raise ValueError(f"max_grad_norm must be positive or None, got {max_grad_norm}")
+    clipped = [p for g in optimizer.param_groups for p in g["params"]] if clip else None
     for step, batch in enumerate(dataloader):
         image, cls_target, reg_target = (t.float().to(device, non_blocking=True) for t in batch)
         loss = loss_fn(net(image), cls_target, reg_target)
@@ -43,6 +53,8 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device):
         loss.backward()
         if reducer is not None:
             reducer.average_gradients()
+        if clip:
+            ops.clip_grad_norm_(clipped, float("inf") if max_grad_norm is None else max_grad_norm, skip_nonfinite=skip_nonfinite)
         optimizer.step()
         if _is_logging_rank():
             flush = getattr(loss_fn, "flush_meters", None)
