@@ -172,6 +172,29 @@ int tf_sgd_step_segments_clipped(float* param, const float* grad, float* momentu
  * written.  The in-place scaling clip_grad_norm_ does at tinyfaces/trainer.py:86-87 when torch.optim.SGD applies the update (the autograd path). */
 int tf_scale_segments(float* grad, const int64_t* host_segments, int nseg, const tf_clip_state* state, void* stream);
 
+/* ---- model EMA: an exponential moving average of the weights, kept on the device ------------
+ * Replaces torch.optim.swa_utils.AveragedModel.update_parameters (multi_avg_fn = get_ema_multi_avg_fn(d)) behind optimizer.step() at
+ * tinyfaces/trainer.py:87, which the reference does not have.  One update is  ema[i] = fmaf(ema_weight, param[i] - ema[i], ema[i])  in fp32,
+ * explicitly fused (torch.lerp(ema, param, ema_weight) for ema_weight < 0.5), with ema_weight = (float)(1 - decay_t) rounded once by the
+ * caller; `ema` is a flat fp32 buffer laid out like `param`.  In all three, `state` may be NULL (not clipped, not guarded); a state whose
+ * skip is set (tf_grad_clip_coef earlier on the stream) makes the call a no-op on the device: param, momentum_buf and ema keep their bits.
+ *
+ * tf_sgd_step_ema / tf_sgd_step_segments_ema: tf_sgd_step[_clipped] / tf_sgd_step_segments[_clipped] (param and momentum_buf bit for bit
+ * theirs) with the average taken on the updated parameter while it is still in registers: one more read and one more write of 4 B per
+ * element, 28 B instead of 20 B.  The 16-byte path needs all four bases 16-byte aligned (and a 4-aligned table); element-wise otherwise.
+ * ema NULL with n > 0 / nseg > 0 is TF_ERR_ARG; other argument errors and n == 0 / nseg == 0 as in the plain entries. */
+int tf_sgd_step_ema(float* param, const float* grad, float* momentum_buf, float* ema, int64_t n, float lr, float momentum, float weight_decay,
+                    float grad_scale, float ema_weight, const tf_clip_state* state /*may be NULL*/, void* stream);
+int tf_sgd_step_segments_ema(float* param, const float* grad, float* momentum_buf, float* ema, const int64_t* host_segments, int nseg,
+                             float lr, float momentum, float weight_decay, float grad_scale, float ema_weight,
+                             const tf_clip_state* state /*may be NULL*/, void* stream);
+/* The average alone over the ranges host_segments[nseg][2] (as tf_scale_segments: HOST memory, ascending and disjoint, TF_SGD_MAX_SEGMENTS per
+ * launch), for the autograd path where torch.optim.SGD has applied the update (AveragedModel.update_parameters right behind optimizer.step(),
+ * tinyfaces/trainer.py:87): reads param and ema, writes ema, touches nothing outside the ranges.  16-byte moves on a 4-aligned table and a
+ * 16-byte-aligned pair of bases, element-wise moves otherwise.  A null or unordered table is TF_ERR_ARG; nseg == 0 is TF_OK, no launch. */
+int tf_ema_update_segments(float* ema, const float* param, const int64_t* host_segments, int nseg, float ema_weight,
+                           const tf_clip_state* state /*may be NULL*/, void* stream);
+
 /* ---- convolution as MFMA implicit GEMM (NHWC) --------------------------------------
  * Replaces every nn.Conv2d on the path (tinyfaces/models/model.py:25-32,90-106 and the
  * torchvision Bottleneck convs) plus the BN / ReLU / residual passes fused around them.

@@ -9,6 +9,11 @@
 //   sgd_kernel<true> / sgd_segments_kernel<true>   the update with grad_scale * coef, nothing at all when skip is set
 //   scale_segments_kernel      g *= coef for the autograd path (torch.optim.SGD applies the update)
 // The norm pass reads 4 B per trained element and nothing else: HBM bound.
+//
+// Model EMA (torch.optim.swa_utils.AveragedModel.update_parameters behind optimizer.step(), tinyfaces/trainer.py:87):
+//   sgd_kernel<CLIP, true> / sgd_segments_kernel<CLIP, true>   e = fmaf(w, p - e, e) on the parameter the update just left in registers:
+//                              one more read and one more write of 4 B per element (28 B instead of 20 B)
+//   ema_segments_kernel        the same average alone over a range table, for the autograd path (reads p and e, writes e)
 #include <math.h>
 
 #include "common.h"
@@ -16,12 +21,21 @@
 namespace {
 // CLIP: `st` is the verdict of a tf_grad_clip_coef enqueued earlier on the stream -- a skipped step returns before it touches p or m, a
 // clipped one uses gs * coef (one fp32 product).  CLIP = false never looks at `st`: the code of the plain entry points.
-template <bool CLIP>
+//
+// EMA: `a.e` is the averaged copy of p, updated behind the SGD update of the same element as e = fmaf(w, p_new - e, e), one explicitly
+// fused fp32 operation (torch.lerp(e, p, w) for w < 0.5) that no contraction flag can change.  A skipped step returns before it touches e
+// either.  The last kernel argument is the clip state alone for EMA = false -- the argument block and the code the kernel had before the
+// average existed -- and the state, e and w for EMA = true.
+template <bool EMA> struct StepArgs { const tf_clip_state* st; float* e; float w; };
+template <> struct StepArgs<false> { const tf_clip_state* st; };
+__device__ __forceinline__ float ema_of(float e, float p, float w) { return __fmaf_rn(w, p - e, e); }
+
+template <bool CLIP, bool EMA>
 __global__ void __launch_bounds__(256) sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  int64_t n, float lr, float mu, float wd, float gs, int vec, const tf_clip_state* __restrict__ st) {
+                                                  int64_t n, float lr, float mu, float wd, float gs, int vec, const StepArgs<EMA> a) {
   if constexpr (CLIP) {
-    if (st->skip) return;
-    gs = gs * st->coef;
+    if (a.st->skip) return;
+    gs = gs * a.st->coef;
   }
   const int64_t n4 = vec ? (n >> 2) : 0;
   const int64_t stride = (int64_t)gridDim.x * 256;
@@ -35,11 +49,22 @@ __global__ void __launch_bounds__(256) sgd_kernel(float* __restrict__ p, const f
     mv.w = mu * mv.w + (gv.w * gs + wd * pv.w); pv.w -= lr * mv.w;
     reinterpret_cast<float4*>(m)[i] = mv;
     reinterpret_cast<float4*>(p)[i] = pv;
+    if constexpr (EMA) {
+      float4 ev = reinterpret_cast<float4*>(a.e)[i];
+      ev.x = ema_of(ev.x, pv.x, a.w); ev.y = ema_of(ev.y, pv.y, a.w); ev.z = ema_of(ev.z, pv.z, a.w); ev.w = ema_of(ev.w, pv.w, a.w);
+      reinterpret_cast<float4*>(a.e)[i] = ev;
+    }
   }
   for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     const float mv = mu * m[i] + (g[i] * gs + wd * p[i]);
     m[i] = mv;
-    p[i] -= lr * mv;
+    if constexpr (EMA) {
+      const float pn = p[i] - lr * mv;
+      p[i] = pn;
+      a.e[i] = ema_of(a.e[i], pn, a.w);
+    } else {
+      p[i] -= lr * mv;
+    }
   }
 }
 
@@ -53,13 +78,13 @@ __device__ __forceinline__ int seg_of(const SgdSegs& t, int nseg, int64_t j) {
   while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (t.cum[mid] <= j) lo = mid; else hi = mid - 1; }
   return lo;
 }
-template <bool CLIP>
+template <bool CLIP, bool EMA>
 __global__ void __launch_bounds__(256) sgd_segments_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            const SgdSegs t, int nseg, float lr, float mu, float wd, float gs, int vec,
-                                                           const tf_clip_state* __restrict__ st) {
+                                                           const StepArgs<EMA> a) {
   if constexpr (CLIP) {
-    if (st->skip) return;
-    gs = gs * st->coef;
+    if (a.st->skip) return;
+    gs = gs * a.st->coef;
   }
   const int64_t total = t.cum[nseg];
   const int64_t stride = (int64_t)gridDim.x * 256 * 4;
@@ -76,13 +101,48 @@ __global__ void __launch_bounds__(256) sgd_segments_kernel(float* __restrict__ p
       mv.w = mu * mv.w + (gv.w * gs + wd * pv.w); pv.w -= lr * mv.w;
       *reinterpret_cast<float4*>(m + i) = mv;
       *reinterpret_cast<float4*>(p + i) = pv;
+      if constexpr (EMA) {
+        float4 ev = *reinterpret_cast<float4*>(a.e + i);
+        ev.x = ema_of(ev.x, pv.x, a.w); ev.y = ema_of(ev.y, pv.y, a.w); ev.z = ema_of(ev.z, pv.z, a.w); ev.w = ema_of(ev.w, pv.w, a.w);
+        *reinterpret_cast<float4*>(a.e + i) = ev;
+      }
     } else {
       for (int e = 0; e < 4 && j + e < total; ++e) {
         const int ke = seg_of(t, nseg, j + e);
         const int64_t ie = t.start[ke] + (j + e - t.cum[ke]);
         const float mv = mu * m[ie] + (g[ie] * gs + wd * p[ie]);
         m[ie] = mv;
-        p[ie] -= lr * mv;
+        if constexpr (EMA) {
+          const float pn = p[ie] - lr * mv;
+          p[ie] = pn;
+          a.e[ie] = ema_of(a.e[ie], pn, a.w);
+        } else {
+          p[ie] -= lr * mv;
+        }
+      }
+    }
+  }
+}
+// e = fmaf(w, p - e, e) over a range table (the index space of scale_segments_kernel), behind an optimizer that is not ours: reads p and
+// e, writes e, nothing outside the ranges.  st may be null; a state that says skip makes the launch a no-op.
+__global__ void __launch_bounds__(256) ema_segments_kernel(float* __restrict__ e, const float* __restrict__ p, const SgdSegs t, int nseg,
+                                                           float w, int vec, const tf_clip_state* __restrict__ st) {
+  if (st != nullptr && st->skip) return;
+  const int64_t total = t.cum[nseg];
+  const int64_t stride = (int64_t)gridDim.x * 256 * 4;
+  for (int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; j < total; j += stride) {
+    const int k = seg_of(t, nseg, j);
+    const int64_t i = t.start[k] + (j - t.cum[k]);
+    if (vec) {
+      const float4 pv = *reinterpret_cast<const float4*>(p + i);
+      float4 ev = *reinterpret_cast<float4*>(e + i);
+      ev.x = ema_of(ev.x, pv.x, w); ev.y = ema_of(ev.y, pv.y, w); ev.z = ema_of(ev.z, pv.z, w); ev.w = ema_of(ev.w, pv.w, w);
+      *reinterpret_cast<float4*>(e + i) = ev;
+    } else {
+      for (int c = 0; c < 4 && j + c < total; ++c) {
+        const int kc = seg_of(t, nseg, j + c);
+        const int64_t ic = t.start[kc] + (j + c - t.cum[kc]);
+        e[ic] = ema_of(e[ic], p[ic], w);
       }
     }
   }
@@ -203,43 +263,60 @@ int fill_table(const int64_t* host_segments, int nseg, int k0, SgdSegs* t, int* 
   return used;
 }
 
-int sgd_segments(float* param, const float* grad, float* momentum_buf, const int64_t* host_segments, int nseg, float lr, float momentum,
-                 float weight_decay, float grad_scale, const tf_clip_state* state, void* stream) {
+// `ema` null: the plain / clipped launches of before.  Otherwise the EMA instantiation, whose 16-byte path also needs `ema` aligned.
+int sgd_segments(float* param, const float* grad, float* momentum_buf, float* ema, const int64_t* host_segments, int nseg, float lr,
+                 float momentum, float weight_decay, float grad_scale, float ema_weight, const tf_clip_state* state, void* stream) {
   if (nseg < 0 || (nseg > 0 && (!param || !grad || !momentum_buf || !host_segments))) return TF_ERR_ARG;
   if (nseg == 0) return TF_OK;
   if (!table_ok(host_segments, nseg)) return TF_ERR_ARG;
-  const bool aligned = (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)momentum_buf) & 15) == 0;
+  const bool aligned = (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)momentum_buf | (uintptr_t)ema) & 15) == 0;
+  const StepArgs<true> ea{state, ema, ema_weight};
+  const StepArgs<false> sa{state};
   for (int k0 = 0; k0 < nseg; k0 += TF_SGD_MAX_SEGMENTS) {
     SgdSegs t;
     int vec = aligned ? 1 : 0;
     int64_t blocks = 0;
     const int used = fill_table(host_segments, nseg, k0, &t, &vec, &blocks);
     if (used == 0) continue;
-    if (state)
-      hipLaunchKernelGGL(sgd_segments_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, t,
-                         used, lr, momentum, weight_decay, grad_scale, vec, state);
+    if (ema && state)
+      hipLaunchKernelGGL((sgd_segments_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad,
+                         momentum_buf, t, used, lr, momentum, weight_decay, grad_scale, vec, ea);
+    else if (ema)
+      hipLaunchKernelGGL((sgd_segments_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad,
+                         momentum_buf, t, used, lr, momentum, weight_decay, grad_scale, vec, ea);
+    else if (state)
+      hipLaunchKernelGGL((sgd_segments_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad,
+                         momentum_buf, t, used, lr, momentum, weight_decay, grad_scale, vec, sa);
     else
-      hipLaunchKernelGGL(sgd_segments_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, t,
-                         used, lr, momentum, weight_decay, grad_scale, vec, (const tf_clip_state*)nullptr);
+      hipLaunchKernelGGL((sgd_segments_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad,
+                         momentum_buf, t, used, lr, momentum, weight_decay, grad_scale, vec, sa);
   }
   TF_CHECK_LAUNCH();
   return TF_OK;
 }
 
-int sgd_flat(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum, float weight_decay, float grad_scale,
-             const tf_clip_state* state, void* stream) {
+int sgd_flat(float* param, const float* grad, float* momentum_buf, float* ema, int64_t n, float lr, float momentum, float weight_decay,
+             float grad_scale, float ema_weight, const tf_clip_state* state, void* stream) {
   if (n < 0 || (n > 0 && (!param || !grad || !momentum_buf))) return TF_ERR_ARG;
   if (n == 0) return TF_OK;
-  const int vec = (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)momentum_buf) & 15) == 0;   // float4 path needs 16-byte alignment
+  const int vec = (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)momentum_buf | (uintptr_t)ema) & 15) == 0;   // float4 path needs 16-byte alignment
   int64_t blocks = ((vec ? (n >> 2) : n) + 255) / 256;
   if (blocks < 1) blocks = 1;
   if (blocks > 2048) blocks = 2048;
-  if (state)
-    hipLaunchKernelGGL(sgd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, n, lr,
-                       momentum, weight_decay, grad_scale, vec, state);
+  const StepArgs<true> ea{state, ema, ema_weight};
+  const StepArgs<false> sa{state};
+  if (ema && state)
+    hipLaunchKernelGGL((sgd_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, n, lr,
+                       momentum, weight_decay, grad_scale, vec, ea);
+  else if (ema)
+    hipLaunchKernelGGL((sgd_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, n, lr,
+                       momentum, weight_decay, grad_scale, vec, ea);
+  else if (state)
+    hipLaunchKernelGGL((sgd_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, n, lr,
+                       momentum, weight_decay, grad_scale, vec, sa);
   else
-    hipLaunchKernelGGL(sgd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, n, lr,
-                       momentum, weight_decay, grad_scale, vec, (const tf_clip_state*)nullptr);
+    hipLaunchKernelGGL((sgd_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, n, lr,
+                       momentum, weight_decay, grad_scale, vec, sa);
   TF_CHECK_LAUNCH();
   return TF_OK;
 }
@@ -247,25 +324,58 @@ int sgd_flat(float* param, const float* grad, float* momentum_buf, int64_t n, fl
 
 extern "C" int tf_sgd_step_segments(float* param, const float* grad, float* momentum_buf, const int64_t* host_segments, int nseg,
                                     float lr, float momentum, float weight_decay, float grad_scale, void* stream) {
-  return sgd_segments(param, grad, momentum_buf, host_segments, nseg, lr, momentum, weight_decay, grad_scale, nullptr, stream);
+  return sgd_segments(param, grad, momentum_buf, nullptr, host_segments, nseg, lr, momentum, weight_decay, grad_scale, 0.f, nullptr, stream);
 }
 
 extern "C" int tf_sgd_step_segments_clipped(float* param, const float* grad, float* momentum_buf, const int64_t* host_segments, int nseg,
                                             float lr, float momentum, float weight_decay, float grad_scale, const tf_clip_state* state,
                                             void* stream) {
   if (!state) return TF_ERR_ARG;
-  return sgd_segments(param, grad, momentum_buf, host_segments, nseg, lr, momentum, weight_decay, grad_scale, state, stream);
+  return sgd_segments(param, grad, momentum_buf, nullptr, host_segments, nseg, lr, momentum, weight_decay, grad_scale, 0.f, state, stream);
 }
 
 extern "C" int tf_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n,
                            float lr, float momentum, float weight_decay, float grad_scale, void* stream) {
-  return sgd_flat(param, grad, momentum_buf, n, lr, momentum, weight_decay, grad_scale, nullptr, stream);
+  return sgd_flat(param, grad, momentum_buf, nullptr, n, lr, momentum, weight_decay, grad_scale, 0.f, nullptr, stream);
 }
 
 extern "C" int tf_sgd_step_clipped(float* param, const float* grad, float* momentum_buf, int64_t n,
                                    float lr, float momentum, float weight_decay, float grad_scale, const tf_clip_state* state, void* stream) {
   if (!state) return TF_ERR_ARG;
-  return sgd_flat(param, grad, momentum_buf, n, lr, momentum, weight_decay, grad_scale, state, stream);
+  return sgd_flat(param, grad, momentum_buf, nullptr, n, lr, momentum, weight_decay, grad_scale, 0.f, state, stream);
+}
+
+// The two updates with the model EMA fused in (state may be null: not clipped, not guarded).
+extern "C" int tf_sgd_step_ema(float* param, const float* grad, float* momentum_buf, float* ema, int64_t n, float lr, float momentum,
+                               float weight_decay, float grad_scale, float ema_weight, const tf_clip_state* state, void* stream) {
+  if (n > 0 && !ema) return TF_ERR_ARG;
+  return sgd_flat(param, grad, momentum_buf, ema, n, lr, momentum, weight_decay, grad_scale, ema_weight, state, stream);
+}
+
+extern "C" int tf_sgd_step_segments_ema(float* param, const float* grad, float* momentum_buf, float* ema, const int64_t* host_segments, int nseg,
+                                        float lr, float momentum, float weight_decay, float grad_scale, float ema_weight,
+                                        const tf_clip_state* state, void* stream) {
+  if (nseg > 0 && !ema) return TF_ERR_ARG;
+  return sgd_segments(param, grad, momentum_buf, ema, host_segments, nseg, lr, momentum, weight_decay, grad_scale, ema_weight, state, stream);
+}
+
+extern "C" int tf_ema_update_segments(float* ema, const float* param, const int64_t* host_segments, int nseg, float ema_weight,
+                                      const tf_clip_state* state, void* stream) {
+  if (nseg < 0 || (nseg > 0 && (!ema || !param || !host_segments))) return TF_ERR_ARG;
+  if (nseg == 0) return TF_OK;
+  if (!table_ok(host_segments, nseg)) return TF_ERR_ARG;
+  const bool aligned = (((uintptr_t)ema | (uintptr_t)param) & 15) == 0;
+  for (int k0 = 0; k0 < nseg; k0 += TF_SGD_MAX_SEGMENTS) {
+    SgdSegs t;
+    int vec = aligned ? 1 : 0;
+    int64_t blocks = 0;
+    const int used = fill_table(host_segments, nseg, k0, &t, &vec, &blocks);
+    if (used == 0) continue;
+    hipLaunchKernelGGL(ema_segments_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ema, param, t, used, ema_weight, vec,
+                       state);
+  }
+  TF_CHECK_LAUNCH();
+  return TF_OK;
 }
 
 // One double per block of every launch, at the capped grid: the caller sizes the workspace from the table length alone.

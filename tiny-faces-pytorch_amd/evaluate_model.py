@@ -29,10 +29,23 @@ FLAGS = [
 
 
 def arguments(argv=None):
-    parser = argparse.ArgumentParser("Model Evaluator")
+    parser = argparse.ArgumentParser("Model Evaluator", epilog=EMA_HELP)
     for name, kw in FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
+
+
+EMA_HELP = "--ema: evaluate the averaged weights of a `main.py --model-ema` run (the checkpoint's \"model_ema\") instead of the last iterate"
+
+
+def ema_arguments(argv=None):
+    """`arguments` plus `ema` from --ema.  Parsed apart, so that `arguments` keeps resolving exactly the reference's options and the additions above."""
+    parser = argparse.ArgumentParser(add_help=False)
+    parser.add_argument("--ema", action="store_true", help=EMA_HELP)
+    known, rest = parser.parse_known_args(argv)
+    args = arguments(rest)
+    args.ema = known.ema
+    return args
 
 
 def dataloader(args):
@@ -57,7 +70,7 @@ def run(model, val_loader, templates, prob_thresh, nms_thresh, device, split, re
 
 
 def main():
-    args = arguments()
+    args = ema_arguments()
     if not torch.cuda.is_available():
         raise SystemExit("this build of the tiny-faces hot path runs on MI355X only (no CPU fallback)")
     # Multi-GPU evaluation = replicas only: under torchrun every rank takes a strided shard of the image list
@@ -70,7 +83,7 @@ def main():
     device = torch.device(f"cuda:{local % torch.cuda.device_count() if share else local}")
     torch.cuda.set_device(device)
     val_loader, templates = dataloader(args)
-    model = get_model(args.checkpoint, num_templates=templates.shape[0])
+    model = get_model(args.checkpoint, num_templates=templates.shape[0], ema=args.ema)
     model = model.to(device).eval()
     with torch.no_grad(), model.constant_weights():          # the checkpoint does not change between images: pack the weights once
         run(model, val_loader, templates, args.prob_thresh, args.nms_thresh, device, args.split, results_dir=args.results_dir,

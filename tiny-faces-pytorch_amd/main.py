@@ -16,6 +16,7 @@ from torch import optim
 
 from tinyfaces import ops, parallel, trainer, transforms
 from tinyfaces.datasets import get_dataloader
+from tinyfaces.ema import ModelEma, ema_decay_at
 from tinyfaces.engine import TrainEngine
 from tinyfaces.models.loss import DetectionCriterion
 from tinyfaces.models import model as model_zoo
@@ -82,6 +83,19 @@ SKIP_HELP = ("--skip-nonfinite: a step whose gradient norm is NaN or Inf is not 
              "untouched; the autograd path zeroes the gradient), default off")
 
 
+EMA_HELP = ("--model-ema DECAY: keep an exponential moving average of the weights with this decay, 0 < DECAY < 1 (torchvision's --model-ema, "
+            "AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(DECAY)); warmed up as min(DECAY, (1 + t) / (10 + t)); updated on the device) and store "
+            "it in every checkpoint as \"model_ema\" (evaluate_model.py --ema), default off")
+
+
+def _ema_decay(text):
+    try:
+        ema_decay_at(float(text), 0)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return float(text)
+
+
 def _positive_float(text):
     value = float(text)
     if not value > 0.0:
@@ -90,7 +104,7 @@ def _positive_float(text):
 
 
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP)))
+    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP)))
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
@@ -98,7 +112,7 @@ def arguments(argv=None):
 
 def trunk_arguments(argv=None):
     """`arguments` plus `base_model` from --base-model, `freeze_bn` from --freeze-bn, `trainable_layers` from --trainable-layers, `clip_grad_norm`
-    from --clip-grad-norm and `skip_nonfinite` from --skip-nonfinite.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
+    from --clip-grad-norm, `skip_nonfinite` from --skip-nonfinite and `model_ema` from --model-ema.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
     options and the additions above."""
     parser = argparse.ArgumentParser(add_help=False)
     parser.add_argument("--base-model", dest="base_model", default="resnet101", choices=list(model_zoo.TRUNKS), help=TRUNK_HELP)
@@ -106,6 +120,7 @@ def trunk_arguments(argv=None):
     parser.add_argument("--trainable-layers", dest="trainable_layers", default=4, type=int, choices=range(5), help=TRAINABLE_HELP)
     parser.add_argument("--clip-grad-norm", dest="clip_grad_norm", default=None, type=_positive_float, help=CLIP_HELP)
     parser.add_argument("--skip-nonfinite", dest="skip_nonfinite", action="store_true", help=SKIP_HELP)
+    parser.add_argument("--model-ema", dest="model_ema", default=None, type=_ema_decay, metavar="DECAY", help=EMA_HELP)
     known, rest = parser.parse_known_args(argv)
     if known.trainable_layers < 4 and not known.freeze_bn:
         parser.error(f"--trainable-layers {known.trainable_layers} freezes stages of the trunk, which is defined on frozen BatchNorm only: add --freeze-bn")
@@ -115,6 +130,7 @@ def trunk_arguments(argv=None):
     args.trainable_layers = known.trainable_layers
     args.clip_grad_norm = known.clip_grad_norm
     args.skip_nonfinite = known.skip_nonfinite
+    args.model_ema = known.model_ema
     return args
 
 
@@ -184,10 +200,11 @@ def main():
             print(f"WARNING: training starts from RANDOM ({args.init}) weights. The reference starts from ImageNet ResNet-101 "
                   "(model.py:13-14); its lr / schedule will not reproduce its results from scratch. Pass --pretrained <resnet101.pth>.")
 
-    engine = optimizer = scheduler = None
+    engine = optimizer = scheduler = ema = None
     if args.fused:
         engine = TrainEngine(model, loss_fn, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay, device=device,
-                             max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
+                             max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, ema_decay=args.model_ema)
+        ema = engine.ema                  # (built from the weights --resume / --pretrained left in the model)
         if state is not None:
             engine.load_optimizer_state_dict(state.get("optimizer"))      # momentum buffers (a torch.optim.SGD state_dict)
     else:
@@ -209,6 +226,19 @@ def main():
                 print(f"WARNING: resumed optimizer group has lr {g['lr']:.3g}; continuing at {want:.3g} (closed form of --lr {args.lr:g} at epoch {first_epoch})")
             g["lr"] = want
         scheduler._last_lr = [g["lr"] for g in optimizer.param_groups]       # what get_last_lr() reports must be what the groups hold
+        if args.model_ema is not None:
+            ema = ModelEma(model, args.model_ema)      # flattens the model; the optimizer's nn.Parameters keep their identity
+    if ema is not None and state is not None:
+        if "model_ema" in state and "ema" in state:
+            ema.load_state_dict(state["model_ema"], state["ema"]["updates"])
+            ema.warmup = bool(state["ema"].get("warmup", ema.warmup))
+            stored = state["ema"].get("decay")
+            if stored is not None and stored != ema.decay and parallel.rank() == 0:
+                print(f"WARNING: {args.resume} was averaged with decay {stored:g}; continuing with --model-ema {ema.decay:g}")
+        elif parallel.rank() == 0:
+            print(f"WARNING: {args.resume} holds no model EMA; the average starts at the loaded weights")
+    elif ema is None and state is not None and "model_ema" in state and parallel.rank() == 0:
+        print(f"WARNING: {args.resume} holds a model EMA, which this run drops: pass --model-ema DECAY to continue it")
 
     skipped = 0
     for epoch in range(first_epoch, args.epochs):
@@ -220,7 +250,7 @@ def main():
             run_fused_epoch(engine, loss_fn, train_loader, epoch, device, args.lr)
         else:
             trainer.train(model, loss_fn, optimizer, train_loader, epoch, device=device, max_grad_norm=args.clip_grad_norm,
-                          skip_nonfinite=args.skip_nonfinite)
+                          skip_nonfinite=args.skip_nonfinite, ema=ema)
             scheduler.step()
         if args.skip_nonfinite and parallel.rank() == 0:
             total = engine.skipped_steps if engine is not None else ops.clip_skipped_steps(device)
@@ -233,6 +263,8 @@ def main():
                 engine.set_lr(lr_at(args.lr, done))                       # what StepLR would have left in the param groups
             snapshot = {"epoch": done, "batch_size": train_loader.batch_size, "model": model.state_dict(),          # main.py:97-102
                         "optimizer": optimizer.state_dict() if optimizer is not None else engine.optimizer_state_dict(base_lr=args.lr)}
+            if ema is not None:
+                snapshot["model_ema"], snapshot["ema"] = ema.state_dict(), ema.settings()
             trainer.save_checkpoint(snapshot, filename=f"checkpoint_{done}.pth", save_path=Path(args.save_path))
 
 

@@ -117,6 +117,9 @@ _SIGNATURES = {
     "tf_sgd_step_clipped": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, vp, vp]),
     "tf_sgd_step_segments_clipped": (i32, [vp, vp, vp, C.POINTER(i64), i32, f32, f32, f32, f32, vp, vp]),
     "tf_scale_segments": (i32, [vp, C.POINTER(i64), i32, vp, vp]),
+    "tf_sgd_step_ema": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, vp]),
+    "tf_sgd_step_segments_ema": (i32, [vp, vp, vp, vp, C.POINTER(i64), i32, f32, f32, f32, f32, f32, vp, vp]),
+    "tf_ema_update_segments": (i32, [vp, vp, C.POINTER(i64), i32, f32, vp, vp]),
     "tf_conv_mtiles": (i32, [C.POINTER(ConvArgs)]),
     "tf_conv2d": (i32, [C.POINTER(ConvArgs), vp]),
     "tf_pack_weight": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp]),

@@ -4,6 +4,7 @@ no per-parameter Python loop and no host sync:
     targets (HIP) -> forward (HIP executor) -> criterion fwd+bwd (HIP) -> backward (HIP executor)
     -> [RCCL all-reduce of the flat gradient, overlapped with the backward pass]
     -> [global gradient norm -> clip coefficient / non-finite verdict, in device memory] -> fused SGD (one launch per group)
+       [+ the model EMA of the updated parameters, inside the same launches]
 
 Data-parallel overlap: the flat gradient is cut along the backward order into buckets of ~`bucket_mb` MB (default 10: heads +
 layer3.21-22 first, then THREE layer-3 bottlenecks of 4.46 MB each per bucket (two stay under 10 MB), ..., finally layer1/2 + stem: SURVEY.md 8e asks for
@@ -22,17 +23,25 @@ import torch.distributed as dist
 
 from . import ops, parallel
 from ._hip import lib
+from .ema import ModelEma
 
 
 class TrainEngine:
     def __init__(self, model, criterion, lr=1e-4, momentum=0.9, weight_decay=5e-4, device="cuda", bucket_mb=10, native_exchange=None,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True):
         """max_grad_norm: clip the global L2 norm of the (rank-averaged) gradient of the trained tensors to this value before the update, as
         torch.nn.utils.clip_grad_norm_ between backward() and optimizer.step() would (tinyfaces/trainer.py:86-87).  skip_nonfinite: a step
         whose gradient norm is NaN or Inf changes neither the parameters nor the momentum (`skipped_steps` counts them; what the FORWARD
         pass of that step wrote -- the running BatchNorm statistics of a batch-statistics step -- stays written).  Both decisions
         are taken and applied on the device: the step stays free of host syncs.  With the defaults (None, False) a step launches exactly
-        what it launched before these arguments existed."""
+        what it launched before these arguments existed.
+        ema_decay: keep an exponential moving average of the weights (`self.ema`, a tinyfaces.ema.ModelEma: torchvision's --model-ema,
+        AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(d))), updated INSIDE the SGD launches of every step from the parameter those launches
+        have just computed: one more flat fp32 buffer, no further launch, no host sync; frozen slices never move.  ema_warmup: the decay of
+        update t is min(ema_decay, (1 + t) / (10 + t)).  `ema.updates` advances on EVERY step, one the non-finite guard drops included (the
+        device leaves the average alone on such a step, but the host cannot know without a sync): the warm-up is indexed by steps taken.
+        Data-parallel runs need no collective for it: every rank applies the same update to the same parameters.  None (the default):
+        `self.ema` is None, no buffer, no new call."""
         self.device = torch.device(device)
         self.model = model.to(self.device).train()
         self.criterion = criterion
@@ -43,6 +52,8 @@ class TrainEngine:
         # anything that moves the module -- .to(), flatten_parameters -- unfreezes it).  TINYFACES_SYNC_TABLES_ALWAYS=1: the walk of rounds 1-3
         self.model._tables_frozen = os.environ.get("TINYFACES_SYNC_TABLES_ALWAYS") is None
         self.flat_m = torch.zeros_like(self.flat_p)
+        self.ema = None if ema_decay is None else ModelEma(self.model, ema_decay, warmup=ema_warmup)     # (behind the broadcast: every rank's clone is rank 0's)
+        self._ema_weight = None               # float32(1 - d_t) of the step under way: taken once per step, not once per group
         self.groups = self.model.group_ranges()
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.bucket_elems = int(bucket_mb * (1 << 20) // 4)
@@ -528,9 +539,15 @@ class TrainEngine:
         only the trained segments of the range are touched, in one launch per TF_SGD_MAX_SEGMENTS segments (ops.sgd_step_segments).
         clip: the ClipState of this step (_clip_coef) -- the clipped / guarded forms of the same two launches."""
         kw = {} if clip is None else {"clip_state": clip}       # (the default step calls the ops exactly as it always did)
+        if self.ema is not None:
+            kw["ema_weight"] = self._ema_weight
         if not self.model.batchnorm_frozen:
+            if self.ema is not None:
+                kw["ema"] = self.ema.flat[a:b]
             ops.sgd_step(self.flat_p[a:b], gflat[a:b], self.flat_m[a:b], self.lr * mult, self.momentum, self.weight_decay, scale, **kw)
             return
+        if self.ema is not None:
+            kw["ema"] = self.ema.flat
         segs = [(max(s, a), min(e, b)) for s, e in self._trained_segments() if e > a and s < b]
         ops.sgd_step_segments(self.flat_p, gflat, self.flat_m, segs, self.lr * mult, self.momentum, self.weight_decay, scale, **kw)
 
@@ -542,7 +559,7 @@ class TrainEngine:
         DetectionModel.set_trainable_layers(k < 4), the conv weights of the frozen stages; the bucket plan of the gradient exchange stays
         as it is (frozen ranges are reduced as zeros).
         With max_grad_norm / skip_nonfinite the update is clipped / guarded on the device (see __init__); a skipped step still counts in
-        `steps` and still returns its loss."""
+        `steps` and still returns its loss.  With ema_decay the same launches also advance `self.ema` (see __init__)."""
         m, c = self.model, self.criterion
         m._check_partial_freeze()
         m._sync_tables(x.device)
@@ -562,6 +579,11 @@ class TrainEngine:
         reduce = parallel.is_distributed() and not self.skip_allreduce
         if reduce:
             scale = 1.0 / parallel.world_size()          # average over ranks, folded into the SGD kernel
+        if self.ema is not None:
+            if self.ema._src is not self.flat_p or m._flat_params is not self.flat_p:
+                raise RuntimeError("TrainEngine.step: the model was flattened again after the engine was built; its model EMA would follow a "
+                                   "buffer the parameters have left: build a new engine")
+            self._ema_weight = self.ema.next_weight()
         if self.sgd_per_bucket and self._overlap is not None:
             self._bucket_updates(gflat, scale, reduce)
         else:

@@ -12,13 +12,20 @@ from . import ops, transforms
 from .models.model import DetectionModel, base_model_of
 
 
-def get_model(checkpoint=None, num_templates=25):
-    """evaluation.py:12-17; the trunk (resnet50 / resnet101 / resnet152) is the one the checkpoint's keys hold."""
+def get_model(checkpoint=None, num_templates=25, ema=False):
+    """evaluation.py:12-17; the trunk (resnet50 / resnet101 / resnet152) is the one the checkpoint's keys hold.  ema=True (an addition):
+    load the averaged weights a `main.py --model-ema` run stored under "model_ema" instead of the last iterate under "model"."""
     if not checkpoint:
+        if ema:
+            raise ValueError("get_model(ema=True) needs a checkpoint: the averaged weights are its \"model_ema\" entry")
         return DetectionModel(num_templates=num_templates)
+    path = checkpoint
     checkpoint = torch.load(checkpoint, map_location="cpu")
-    model = DetectionModel(base_model=base_model_of(checkpoint["model"]), num_templates=num_templates)
-    model.load_state_dict(checkpoint["model"])
+    if ema and "model_ema" not in checkpoint:
+        raise ValueError(f"{path} has no \"model_ema\" entry (keys: {sorted(checkpoint)}): it was not written by a run with --model-ema")
+    weights = checkpoint["model_ema" if ema else "model"]
+    model = DetectionModel(base_model=base_model_of(weights), num_templates=num_templates)
+    model.load_state_dict(weights)
     return model
 
 

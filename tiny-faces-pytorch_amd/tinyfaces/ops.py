@@ -434,13 +434,31 @@ def clip_skipped_steps(device):
     return 0 if state is None else state.skipped()
 
 
-def sgd_step(param, grad, momentum_buf, lr, momentum, weight_decay, grad_scale=1.0, clip_state=None):
+def _ema_pair(what, param, ema, ema_weight):
+    """(ema, weight) checked, or None when neither was given: the fused model EMA of sgd_step / sgd_step_segments."""
+    if ema is None and ema_weight is None:
+        return None
+    if ema is None or ema_weight is None:
+        raise ValueError(f"{what}: ema and ema_weight go together")
+    assert ema.dtype == torch.float32 and ema.is_contiguous() and ema.device == param.device and ema.numel() == param.numel()
+    return ema, float(ema_weight)
+
+
+def sgd_step(param, grad, momentum_buf, lr, momentum, weight_decay, grad_scale=1.0, *, ema=None, ema_weight=None, clip_state=None):
     """torch.optim.SGD.step for one flat fp32 segment (main.py:67-70).  clip_state (ClipState, filled by grad_clip_coef on this stream): the
-    step behind clip_grad_norm_ -- grad_scale * coef, nothing at all when the state says skip."""
+    step behind clip_grad_norm_ -- grad_scale * coef, nothing at all when the state says skip.
+    ema, ema_weight (together): the model EMA in the same launch, ema = fmaf(ema_weight, param_after - ema, ema) (tf_sgd_step_ema; a skipped
+    step leaves ema alone too).  Without them the calls are the ones above, unchanged."""
     require_gpu(param, "sgd_step")
     assert param.dtype == grad.dtype == momentum_buf.dtype == torch.float32
     assert param.is_contiguous() and grad.is_contiguous() and momentum_buf.is_contiguous()
+    avg = _ema_pair("sgd_step", param, ema, ema_weight)
     with torch.cuda.device(param.device):
+        if avg is not None:
+            check(lib().tf_sgd_step_ema(ptr(param), ptr(grad), ptr(momentum_buf), ptr(avg[0]), param.numel(), float(lr), float(momentum),
+                                        float(weight_decay), float(grad_scale), avg[1], None if clip_state is None else ptr(clip_state.buf),
+                                        stream()), "tf_sgd_step_ema")
+            return
         if clip_state is not None:
             check(lib().tf_sgd_step_clipped(ptr(param), ptr(grad), ptr(momentum_buf), param.numel(), float(lr), float(momentum),
                                             float(weight_decay), float(grad_scale), ptr(clip_state.buf), stream()), "tf_sgd_step_clipped")
@@ -449,15 +467,18 @@ def sgd_step(param, grad, momentum_buf, lr, momentum, weight_decay, grad_scale=1
                                 float(weight_decay), float(grad_scale), stream()), "tf_sgd_step")
 
 
-def sgd_step_segments(param, grad, momentum_buf, segments, lr, momentum, weight_decay, grad_scale=1.0, clip_state=None):
+def sgd_step_segments(param, grad, momentum_buf, segments, lr, momentum, weight_decay, grad_scale=1.0, *, ema=None, ema_weight=None,
+                      clip_state=None):
     """torch.optim.SGD.step over the element ranges `segments` ([(start, end)], ascending, disjoint) of three flat fp32 buffers;
     everything outside the ranges is left untouched (tf_sgd_step_segments: parameters without a gradient, e.g. frozen BatchNorm vectors).
-    clip_state: as in sgd_step (tf_sgd_step_segments_clipped)."""
+    clip_state: as in sgd_step (tf_sgd_step_segments_clipped).  ema, ema_weight: as in sgd_step (tf_sgd_step_segments_ema), a fourth flat
+    buffer of the same length whose elements outside the ranges stay untouched as well."""
     require_gpu(param, "sgd_step_segments")
     assert param.dtype == grad.dtype == momentum_buf.dtype == torch.float32
     assert param.is_contiguous() and grad.is_contiguous() and momentum_buf.is_contiguous()
     n = param.numel()
     assert grad.numel() == n and momentum_buf.numel() == n
+    avg = _ema_pair("sgd_step_segments", param, ema, ema_weight)
     segments = [(int(s), int(e)) for s, e in segments if e > s]
     prev = 0
     for s, e in segments:
@@ -468,6 +489,11 @@ def sgd_step_segments(param, grad, momentum_buf, segments, lr, momentum, weight_
         return
     table = (C.c_int64 * (2 * len(segments)))(*[v for se in segments for v in se])
     with torch.cuda.device(param.device):
+        if avg is not None:
+            check(lib().tf_sgd_step_segments_ema(ptr(param), ptr(grad), ptr(momentum_buf), ptr(avg[0]), table, len(segments), float(lr),
+                                                 float(momentum), float(weight_decay), float(grad_scale), avg[1],
+                                                 None if clip_state is None else ptr(clip_state.buf), stream()), "tf_sgd_step_segments_ema")
+            return
         if clip_state is not None:
             check(lib().tf_sgd_step_segments_clipped(ptr(param), ptr(grad), ptr(momentum_buf), table, len(segments), float(lr),
                                                      float(momentum), float(weight_decay), float(grad_scale), ptr(clip_state.buf), stream()),
@@ -475,6 +501,22 @@ def sgd_step_segments(param, grad, momentum_buf, segments, lr, momentum, weight_
             return
         check(lib().tf_sgd_step_segments(ptr(param), ptr(grad), ptr(momentum_buf), table, len(segments), float(lr), float(momentum),
                                          float(weight_decay), float(grad_scale), stream()), "tf_sgd_step_segments")
+
+
+def ema_update_segments(ema, param, segments, weight, clip_state=None):
+    """ema[ranges] = fmaf(weight, param - ema, ema) on the device, everything else untouched (tf_ema_update_segments): what
+    torch.optim.swa_utils.AveragedModel.update_parameters does behind optimizer.step() (tinyfaces/trainer.py:87), in one launch per
+    TF_SGD_MAX_SEGMENTS ranges and without a per-parameter loop.  `ema` and `param` are flat fp32 buffers of one length (or views at the
+    same offset of two such buffers).  clip_state: a state that says skip makes the call a no-op on the device."""
+    require_gpu(ema, "ema_update_segments")
+    assert ema.dtype == param.dtype == torch.float32 and ema.is_contiguous() and param.is_contiguous()
+    assert ema.device == param.device and ema.numel() == param.numel()
+    table, nseg = _segment_table("ema_update_segments", segments, ema.numel())
+    if nseg == 0:
+        return
+    with torch.cuda.device(ema.device):
+        check(lib().tf_ema_update_segments(ptr(ema), ptr(param), table, nseg, float(weight), None if clip_state is None else ptr(clip_state.buf),
+                                           stream()), "tf_ema_update_segments")
 
 
 # --------------------------------------------------------------------------- conv engine (used directly by the parity tests)

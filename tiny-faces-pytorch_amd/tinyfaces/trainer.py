@@ -30,7 +30,7 @@ def _is_logging_rank():
     return parallel.rank() == 0 or not parallel.is_distributed()
 
 
-def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=None, skip_nonfinite=False):
+def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=None, skip_nonfinite=False, ema=None):
     """One epoch with the reference's step order (trainer.py:68-90): forward, criterion, zero_grad, backward, [all-reduce],
     optimizer step, progress line.
 
@@ -38,7 +38,10 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
     optimizer's parameters between the averaging and optimizer.step(), the spot torch.nn.utils.clip_grad_norm_ takes in a training loop
     (trainer.py:86-87), without a host round trip.  skip_nonfinite alone (max_grad_norm None) only guards.  On a step the guard skips the
     gradient is scaled to ZERO, and torch.optim.SGD still applies weight decay and momentum to the parameters: that is what torch's
-    optimizer does with a zero gradient.  Only the fused engine (TrainEngine(skip_nonfinite=True)) leaves a skipped step untouched."""
+    optimizer does with a zero gradient.  Only the fused engine (TrainEngine(skip_nonfinite=True)) leaves a skipped step untouched.
+
+    ema (a tinyfaces.ema.ModelEma of `model`): ema.update() right behind optimizer.step(), the spot of AveragedModel.update_parameters in a
+    torch training loop -- one launch per 128 trained tensors on the device, no host sync."""
     net = model.to(device).train()
     reducer = parallel.reducer_for(net)
     n_batches = len(dataloader)
@@ -56,6 +59,8 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
         if clip:
             ops.clip_grad_norm_(clipped, float("inf") if max_grad_norm is None else max_grad_norm, skip_nonfinite=skip_nonfinite)
         optimizer.step()
+        if ema is not None:
+            ema.update()
         if _is_logging_rank():
             flush = getattr(loss_fn, "flush_meters", None)
             if flush is not None:
