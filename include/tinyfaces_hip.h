@@ -97,6 +97,37 @@ int tf_nms_f64_batched(const double* boxes /*[n][4]*/, const double* scores /*[n
                        int num_segments, double iou_thresh, int64_t* keep_out /*[n]*/, int32_t* num_keep /*[S]*/,
                        void* ws, size_t ws_bytes, void* stream);
 
+/* ---- test-time augmentation: box voting and the un-mirroring of a flipped pyramid level, float64 ----------------
+ * Additions to the reference's evaluation (tinyfaces/evaluation.py:80-87 keeps the NMS survivors as they are): the two test-time
+ * steps WIDER FACE results are usually reported with.
+ *
+ * Box voting (Gidaris & Komodakis, ICCV 2015; Detectron's box_voting with scoring method ID): for segment s and r < num_keep[s],
+ * with k = keep[off[s] + r] (an index into the concatenated input),
+ *     V = { j in [off[s], off[s+1]) : IoU(box_k, box_j) >= vote_thresh }     (`>=`, Detectron's; the NMS suppresses on `>`)
+ *     out[off[s] + r] = (sum_V w_j * box_j / sum_V w_j, score_k)             (the kept box's own score is carried through)
+ * The IoU is tf_nms_f64's expression in the same operation order (areas without +1, inter / (a_k + a_j - inter)), so membership
+ * is decided by the very bits the NMS compared; a NaN IoU (0 / 0: a zero-area box) is not a vote.  Voters whose weight is <= 0 or
+ * NaN are dropped; with no voter left, or a weight sum that is not > 0, the row is (box_k, score_k) unchanged.
+ * votes_out[off[s] + r] (optional) = the number of voters after the weight filter.  Rows r >= num_keep[s] of out / votes_out are
+ * NOT written.  keep / num_keep are tf_nms_f64_batched's keep_out / num_keep as it left them, in DEVICE memory: the call chains
+ * behind the NMS on the same stream with no host synchronisation.  The sums are taken in a fixed order without atomics: the same
+ * bits on every run.  Nothing is launched for n == 0; S outside 1..TF_NMS_MAX_SEGMENTS, descending offsets, an unknown weight_mode
+ * or a vote_thresh outside (0, 1] are TF_ERR_ARG. */
+#define TF_VOTE_WEIGHT_SIGMOID 0   /* w = 1 / (1 + exp(-score)): the scores tf_decode_compact emits are LOGITS (tinyfaces/models/utils.py:37) */
+#define TF_VOTE_WEIGHT_SCORE   1   /* w = score as given (a caller that holds probabilities) */
+int tf_box_vote_f64_batched(const double* boxes /*[n][4]*/, const double* scores /*[n]*/, const int32_t* host_seg_offsets /*[S+1]*/,
+                            int num_segments, const int64_t* keep /*device [n]*/, const int32_t* num_keep /*device [S]*/,
+                            double vote_thresh, int weight_mode, double* out /*[n][5]*/, int32_t* votes_out /*[n] or NULL*/, void* stream);
+/* one segment: the batched form with S = 1, as tf_nms_f64 is of tf_nms_f64_batched */
+int tf_box_vote_f64(const double* boxes /*[n][4]*/, const double* scores /*[n]*/, int n, const int64_t* keep /*device [n]*/,
+                    const int32_t* num_keep /*device [1]*/, double vote_thresh, int weight_mode, double* out /*[n][5]*/,
+                    int32_t* votes_out /*[n] or NULL*/, void* stream);
+/* Rows [*first, *last) of a tf_decode_compact candidate list (first / last: DEVICE int32, copies of its counter taken before and after a
+ * MIRRORED pyramid level) are mirrored back: x1' = c - x2, x2' = c - x1, both read before either is written; y1, y2 and the score
+ * stay, rows outside the range are not written.  c = (W_level - 1) * (1 / scale) is the caller's.  max_rows: a host bound on
+ * *last - *first that sizes the grid (rows beyond it are left alone); 0 launches nothing, < 0 is TF_ERR_ARG. */
+int tf_boxes_unflip_f64(double* dets /*[cap][5]*/, const int32_t* first, const int32_t* last, int max_rows, double c, void* stream);
+
 /* ---- score map -> boxes: sigmoid + threshold + ORDERED compaction + refinement ------
  * Replaces evaluation.py:61-78 + get_bboxes / regression_refinement
  * (tinyfaces/models/utils.py:4-100).  score [5nt][H][W] f32 (one image, NCHW).

@@ -16,6 +16,7 @@
 #   layer-table                bench.py --layer-table (every MFMA launch bracketed)-> gpurun_out/layer_table.{json,md}
 #   eval-table                 the same table for the configs[1] pyramid (per image)-> gpurun_out/eval_layer_table.{json,md}
 #   contention | floor | nms   the round-3 micro-benchmarks (scripts/contention.py, floor.py, nms_bench.py under the tracer)
+#   tta                        cost of the test-time augmentation: vote vs NMS kernels, pyramid with / without flip and voting (scripts/tta_numbers.py) -> $TTA_OUT (default profiles/tta.jsonl)
 #   dist-smoke                 RCCL 1-rank group, 2 gloo ranks on one GPU, 2 nccl ranks on one GPU (expected refusal) -> gpurun_out/dist_smoke.txt
 #   final                      tests + bench + prof + pmc-traffic + layer-table + timeline + eval prof + smoke: the artefacts of a round
 set -u
@@ -84,6 +85,11 @@ print(d['value'], d['ms_per_step'], 'frac', r.get('frac'), 'fwd', r.get('forward
     python scripts/floor.py 2>&1 | grep -v amdgpu.ids | tee "$R/gpurun_out/floor.txt"
     trace_cmd /tmp/fl --stats -- python $R/scripts/floor.py; f=$(find /tmp/fl -name "*kernel_stats.csv" | head -1); head -4 "$f" | cut -c1-160 | tee -a "$R/gpurun_out/floor.txt" ;;
   nms) bash scripts/gpu_nms.sh ;;
+  tta)   # one process and one time limit per step; the second step only behind a clean first one
+    out=${TTA_OUT:-$R/profiles/tta.jsonl}; err=${out%.jsonl}.err
+    timeout -k 10 ${TTA_TIMEOUT:-300} python scripts/tta_numbers.py --step kernels > "$out" 2> "$err" &&
+      timeout -k 10 ${TTA_TIMEOUT:-300} python scripts/tta_numbers.py --step pyramid >> "$out" 2>> "$err"
+    echo "tta exit $?"; cat "$out"; tail -3 "$err" ;;
   dist-smoke) bash scripts/gpu_dist_smoke.sh ;;
   final)
     # the profile passes FIRST: bench.py quotes the committed kernel-stats / PMC files, so they are refreshed in the box's copy of profiles/

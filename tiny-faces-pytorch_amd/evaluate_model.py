@@ -48,6 +48,28 @@ def ema_arguments(argv=None):
     return args
 
 
+TTA_HELP = ("--flip: run every pyramid level mirrored left-right as well and suppress the union of both candidate lists; "
+            "--box-voting T: replace every NMS survivor by the score-weighted mean of all candidates with IoU >= T (0 < T <= 1)")
+
+
+def _vote_thresh(text):
+    t = float(text)
+    if not 0.0 < t <= 1.0:
+        raise argparse.ArgumentTypeError(f"--box-voting {text}: the IoU threshold of the vote lies in (0, 1]")
+    return t
+
+
+def tta_arguments(argv=None):
+    """`ema_arguments` plus `flip` / `box_voting` from --flip / --box-voting T (test-time augmentation), parsed apart in the same way."""
+    parser = argparse.ArgumentParser(add_help=False)
+    parser.add_argument("--flip", action="store_true", help=TTA_HELP)
+    parser.add_argument("--box-voting", dest="box_voting", type=_vote_thresh, default=None, metavar="T", help=TTA_HELP)
+    known, rest = parser.parse_known_args(argv)
+    args = ema_arguments(rest)
+    args.flip, args.box_voting = known.flip, known.box_voting
+    return args
+
+
 def dataloader(args):
     """evaluate_model.py:34-45."""
     tf = transforms.Compose([transforms.ToTensor(), transforms.Normalize([0.485, 0.456, 0.406], [0.229, 0.224, 0.225])])
@@ -56,13 +78,15 @@ def dataloader(args):
     return get_dataloader(args.dataset, largs, train=False, split=args.split, img_transforms=tf)
 
 
-def run(model, val_loader, templates, prob_thresh, nms_thresh, device, split, results_dir=None, debug=False, mask_axis="w"):
+def run(model, val_loader, templates, prob_thresh, nms_thresh, device, split, results_dir=None, debug=False, mask_axis="w",
+        flip=False, box_voting=None):
     """evaluate_model.py:48-68, statement for statement: `img[0]` / `filename[0]` undo the batch axis the loader adds.  The
-    only addition is the keyword that builds the pyramid levels on the GPU (same detections bit for bit)."""
+    only addition is the keyword that builds the pyramid levels on the GPU (same detections bit for bit).
+    flip / box_voting: get_detections' test-time augmentation, off by default."""
     dets = None
     for _, (img, filename) in enumerate(val_loader):
         dets = get_detections(model, img[0], templates, val_loader.dataset.rf, val_loader.dataset.transforms, prob_thresh, nms_thresh,
-                              device=device, pyramid_on_gpu=True, mask_axis=mask_axis)
+                              device=device, pyramid_on_gpu=True, mask_axis=mask_axis, flip=flip, box_voting=box_voting)
         write_results(dets, filename[0], split, results_dir)
         if debug:
             print(f"{filename[0]}: {dets.shape[0]} detections")
@@ -70,7 +94,7 @@ def run(model, val_loader, templates, prob_thresh, nms_thresh, device, split, re
 
 
 def main():
-    args = ema_arguments()
+    args = tta_arguments()
     if not torch.cuda.is_available():
         raise SystemExit("this build of the tiny-faces hot path runs on MI355X only (no CPU fallback)")
     # Multi-GPU evaluation = replicas only: under torchrun every rank takes a strided shard of the image list
@@ -87,7 +111,7 @@ def main():
     model = model.to(device).eval()
     with torch.no_grad(), model.constant_weights():          # the checkpoint does not change between images: pack the weights once
         run(model, val_loader, templates, args.prob_thresh, args.nms_thresh, device, args.split, results_dir=args.results_dir,
-            debug=args.debug or args.dataset == "synthetic", mask_axis=args.mask_axis)
+            debug=args.debug or args.dataset == "synthetic", mask_axis=args.mask_axis, flip=args.flip, box_voting=args.box_voting)
     if distributed:
         torch.distributed.barrier()
         if parallel.rank() == 0:

@@ -47,10 +47,11 @@ def _on_device(model, device):
     return model.to(device)
 
 
-def _pyramid_levels(img, scales, img_transforms, pyramid_on_gpu, device):
-    """evaluation.py:37-53: [(scale, normalised (1,3,H,W) tensor)] for every pyramid level of one image."""
+def _pyramid_levels(img, scales, img_transforms, pyramid_on_gpu, device, flip=False):
+    """evaluation.py:37-53: [(scale, normalised (1,3,H,W) tensor)] for every pyramid level of one image.  flip: the same levels follow
+    once more MIRRORED left-right, in the same order (the second half of the list)."""
     scales_list = [2 ** x for x in scales]
-    levels = []
+    levels, mirrored = [], []
     if pyramid_on_gpu:
         ms = _normalize_of(img_transforms)
         if ms is None:
@@ -66,6 +67,8 @@ def _pyramid_levels(img, scales, img_transforms, pyramid_on_gpu, device):
             new_short, new_long = size, int(size * long / short)
             new_w, new_h = (new_short, new_long) if w <= h else (new_long, new_short)
             levels.append((scale, ops.image_prepare(u8, resized_hw=(new_h, new_w), mean=ms[0], std=ms[1]).unsqueeze(0)))
+            if flip:
+                mirrored.append((scale, ops.image_prepare(u8, resized_hw=(new_h, new_w), mean=ms[0], std=ms[1], flip=True).unsqueeze(0)))
     else:
         image = transforms.to_pil_image(img)                              # :40
         min_side = np.min(image.size)
@@ -74,17 +77,22 @@ def _pyramid_levels(img, scales, img_transforms, pyramid_on_gpu, device):
             scaled = transforms.resize(image, int(min_side * scale))
             x = img_transforms(scaled).unsqueeze(0).float()
             levels.append((scale, x))
-    return levels
+            if flip:
+                mirrored.append((scale, x.flip(-1)))                       # the pixels tf_image_prepare(flip=True) writes, bit for bit
+    return levels + mirrored
 
 
 def _level_capacity(levels, nt):
     return sum(((x.shape[2] + 7) // 8) * ((x.shape[3] + 7) // 8) for _, x in levels) * nt
 
 
-def _decode_levels(model, levels, templates, t_d, rf, prob_thresh, mask_axis, dets, count, device):
+def _decode_levels(model, levels, templates, t_d, rf, prob_thresh, mask_axis, dets, count, device, mirrored=False):
     """Forward + sigmoid / threshold / ordered compaction / refinement of every level, appended to dets[count...].
     The forwards of the levels run side by side on the model's lanes (DetectionModel.forward_levels); the decodes follow in level
-    order on the caller's stream, so the candidate list is the sequential loop's row for row."""
+    order on the caller's stream, so the candidate list is the sequential loop's row for row.
+    mirrored: the levels are left-right mirrors (test-time flip).  They are decoded like any image -- the same template masks, defect D1
+    included --, then the rows each of them appended are mirrored back on the device (tf_boxes_unflip_f64): the row range is the
+    counter before and after the level, kept in device memory."""
     xs = [x.to(device, non_blocking=True) for _, x in levels]
     # any callable nn.Module is accepted, like the reference's get_detections (evaluation.py:56-60): only DetectionModel has lanes (ADVICE r3)
     fl = getattr(model, "forward_levels", None)
@@ -92,19 +100,38 @@ def _decode_levels(model, levels, templates, t_d, rf, prob_thresh, mask_axis, de
     for (scale, x), out in zip(levels, outs):                         # (1, 5nt, H', W')
         _, _, H, W = out.shape
         vx, vt = ops.template_masks(templates, scale, W, mask_axis)
+        first = count.clone() if mirrored else None
         ops.decode_compact(out[0], t_d, torch.from_numpy(vx).to(device), torch.from_numpy(vt).to(device),
                            prob_thresh, scale, dets, count, rf)
+        if mirrored:
+            # a level pixel x' is the image's pixel (W_level - 1 - x') / scale; 1 / scale is the factor of the decode (tf_decode_compact)
+            ops.boxes_unflip_(dets, first, count.clone(), H * W * t_d.shape[0], (x.shape[3] - 1) * (1 / scale))
+
+
+def _decode_image(model, levels, flip, *args):
+    """`_decode_levels` for the levels of one image; with flip the second half of `levels` is the mirrored pyramid, run as a second group
+    behind the first so that the first rows are exactly the candidate list without it."""
+    if not flip:
+        return _decode_levels(model, levels, *args)
+    half = len(levels) // 2
+    _decode_levels(model, levels[:half], *args)
+    _decode_levels(model, levels[half:], *args, mirrored=True)
 
 
 def get_detections(model, img, templates, rf, img_transforms, prob_thresh=0.65, nms_thresh=0.3, scales=(-2, -1, 0, 1),
-                   device=None, mask_axis="w", return_candidates=False, pyramid_on_gpu=False):
+                   device=None, mask_axis="w", return_candidates=False, pyramid_on_gpu=False, flip=False, box_voting=None):
     """evaluation.py:20-87.  Returns (K,5) float64: the reference's (K,4) rows in the same order
     with the score re-attached as column 4 (defect D2: the reference drops it although
     write_results reads x[4], evaluation.py:111).  mask_axis='w' reproduces defect D1
     (tinyfaces/models/utils.py:44); 'template' masks the template axis instead.
     pyramid_on_gpu=True: the uint8 image goes to the device once and every pyramid level is produced there
     by tf_image_prepare (Pillow-exact BILINEAR resize + ToTensor + Normalize in one pass) instead of PIL + torch on the host;
-    needs img_transforms = Compose([ToTensor(), Normalize(mean, std)]); same detections bit for bit."""
+    needs img_transforms = Compose([ToTensor(), Normalize(mean, std)]); same detections bit for bit.
+    Test-time augmentation (additions; with the defaults nothing else is launched and the rows are the same bit for bit):
+    flip=True: every pyramid level is also run mirrored left-right and its candidates, mirrored back, follow those of the unmirrored
+    levels in the candidate list; the one NMS runs over the union.
+    box_voting=t: every NMS survivor is replaced by the sigmoid-weighted mean of all candidates with IoU >= t (`ops.box_voting`:
+    Detectron's box_voting, scoring ID -- the candidates' scores are logits); the rows returned are the voted rows in keep order."""
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
         raise RuntimeError("get_detections: the detector only runs on MI355X (no CPU fallback)")
@@ -112,32 +139,38 @@ def get_detections(model, img, templates, rf, img_transforms, prob_thresh=0.65, 
     model.eval()
     nt = templates.shape[0]
     t_d = torch.as_tensor(np.asarray(templates), dtype=torch.float64).contiguous().to(device)
-    levels = _pyramid_levels(img, scales, img_transforms, pyramid_on_gpu, device)
+    levels = _pyramid_levels(img, scales, img_transforms, pyramid_on_gpu, device, flip)
     dets = torch.empty(max(_level_capacity(levels, nt), 1), 5, dtype=torch.float64, device=device)
     count = torch.zeros(1, dtype=torch.int32, device=device)
     biggest = max(levels, key=lambda l: l[1].shape[2] * l[1].shape[3])[1]
     # weights are constant across the pyramid (and across images when the caller already opened a session): pack once
     with torch.no_grad(), model.constant_weights(reserve=(1, biggest.shape[2], biggest.shape[3])):
-        _decode_levels(model, levels, templates, t_d, rf, prob_thresh, mask_axis, dets, count, device)
+        _decode_image(model, levels, flip, templates, t_d, rf, prob_thresh, mask_axis, dets, count, device)
     n = int(count.item())
     assert n <= dets.shape[0]
     if n > ops.NMS_MAX_BOXES:
         raise RuntimeError(f"get_detections: {n} candidates above prob_thresh={prob_thresh} exceed the {ops.NMS_MAX_BOXES} boxes one NMS call "
                            "takes (64 KiB of LDS for the suppression bitmap); a trained detector keeps a few thousand -- untrained weights?")
     cand = dets[:n]
-    keep = ops.nms(cand[:, :4].contiguous(), cand[:, 4].contiguous(), nms_thresh)      # :80-84
-    result = cand[keep].cpu().numpy()
+    if box_voting is None:
+        keep = ops.nms(cand[:, :4].contiguous(), cand[:, 4].contiguous(), nms_thresh)      # :80-84
+        result = cand[keep].cpu().numpy()
+    else:
+        # the vote chains behind the NMS on its device-side keep count: still one synchronisation
+        keeps, voted = ops.nms_batched(cand[:, :4].contiguous(), cand[:, 4].contiguous(), [0, n], nms_thresh, vote=(box_voting, "sigmoid"))
+        keep, result = keeps[0], voted[0].cpu().numpy()
     if return_candidates:
         return result, cand.cpu().numpy(), keep.cpu().numpy()
     return result
 
 
 def get_detections_batch(model, imgs, templates, rf, img_transforms, prob_thresh=0.65, nms_thresh=0.3, scales=(-2, -1, 0, 1),
-                         device=None, mask_axis="w", pyramid_on_gpu=False):
+                         device=None, mask_axis="w", pyramid_on_gpu=False, flip=False, box_voting=None):
     """`[get_detections(model, img, ...) for img in imgs]` (evaluation.py:20-87 once per image, as evaluate_model.py:60-68 does) with
     the per-image NMS calls batched: every image's multi-scale candidates go into ONE device list, the per-image segments are
     suppressed by ONE tf_nms_f64_batched call (three launches whatever the number of images; BASELINE.json configs[4]) and the
-    only host synchronisation of the whole batch is the read of the candidate counts.  Row for row identical to the loop."""
+    only host synchronisation of the whole batch is the read of the candidate counts.  Row for row identical to the loop.
+    flip / box_voting: as in get_detections; an image's mirrored candidates follow its unmirrored ones, so its segment stays contiguous."""
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
         raise RuntimeError("get_detections_batch: the detector only runs on MI355X (no CPU fallback)")
@@ -148,19 +181,22 @@ def get_detections_batch(model, imgs, templates, rf, img_transforms, prob_thresh
     model.eval()
     nt = templates.shape[0]
     t_d = torch.as_tensor(np.asarray(templates), dtype=torch.float64).contiguous().to(device)
-    per_image = [_pyramid_levels(img, scales, img_transforms, pyramid_on_gpu, device) for img in imgs]
+    per_image = [_pyramid_levels(img, scales, img_transforms, pyramid_on_gpu, device, flip) for img in imgs]
     dets = torch.empty(max(sum(_level_capacity(lv, nt) for lv in per_image), 1), 5, dtype=torch.float64, device=device)
     count = torch.zeros(1, dtype=torch.int32, device=device)
     marks = torch.zeros(len(imgs) + 1, dtype=torch.int32, device=device)
     biggest = max((l[1] for lv in per_image for l in lv), key=lambda x: x.shape[2] * x.shape[3])
     with torch.no_grad(), model.constant_weights(reserve=(1, biggest.shape[2], biggest.shape[3])):
         for i, levels in enumerate(per_image):
-            _decode_levels(model, levels, templates, t_d, rf, prob_thresh, mask_axis, dets, count, device)
+            _decode_image(model, levels, flip, templates, t_d, rf, prob_thresh, mask_axis, dets, count, device)
             marks[i + 1:i + 2].copy_(count, non_blocking=True)        # segment boundary, recorded on the stream
     offs = marks.tolist()                                             # the one sync
     if max(b - a for a, b in zip(offs, offs[1:])) > ops.NMS_MAX_BOXES:
         raise RuntimeError(f"get_detections_batch: an image has more than {ops.NMS_MAX_BOXES} candidates above prob_thresh={prob_thresh}")
     cand = dets[:offs[-1]]
+    if box_voting is not None:
+        _, voted = ops.nms_batched(cand[:, :4].contiguous(), cand[:, 4].contiguous(), offs, nms_thresh, vote=(box_voting, "sigmoid"))
+        return [v.cpu().numpy() for v in voted]
     keeps = ops.nms_batched(cand[:, :4].contiguous(), cand[:, 4].contiguous(), offs, nms_thresh)
     return [cand[k].cpu().numpy() for k in keeps]
 

@@ -159,33 +159,40 @@ def _mask_bytes(n):
     return n * ((n + 63) // 64) * 8
 
 
-def nms_batched(boxes, scores, seg_offsets, iou_threshold, mask_budget_bytes=None):
+def nms_batched(boxes, scores, seg_offsets, iou_threshold, mask_budget_bytes=None, vote=None):
     """`_nms_batched_call` over groups of consecutive segments whose bit matrices fit `mask_budget_bytes` (default 2 GiB): at the
     evaluation default prob_thresh = 0.03 an image can have tens of thousands of candidates (300 MB of matrix each), so a 64-image
-    batch in one call would ask for tens of GB of workspace.  A single segment larger than the budget still goes alone."""
+    batch in one call would ask for tens of GB of workspace.  A single segment larger than the budget still goes alone.
+    vote = (vote_thresh, weight): as in `_nms_batched_call`, returns (keeps, voted rows)."""
     offs = [int(o) for o in seg_offsets]
     budget = NMS_MASK_BUDGET_BYTES if mask_budget_bytes is None else int(mask_budget_bytes)
     S = len(offs) - 1
     sizes = [_mask_bytes(b - a) for a, b in zip(offs, offs[1:])]
+    extra = () if vote is None else (vote,)                   # without a vote the calls are the ones they were
     if S < 1 or sum(sizes) <= budget:
-        return _nms_batched_call(boxes, scores, offs, iou_threshold)
-    out, first, acc = [], 0, 0
+        return _nms_batched_call(boxes, scores, offs, iou_threshold, *extra)
+    out, rows, first, acc = [], [], 0, 0
     for s in range(S + 1):
         if s == S or (s > first and acc + sizes[s] > budget):
             a, b = offs[first], offs[s]
-            keeps = _nms_batched_call(boxes[a:b], scores[a:b], [o - a for o in offs[first:s + 1]], iou_threshold)
+            keeps = _nms_batched_call(boxes[a:b], scores[a:b], [o - a for o in offs[first:s + 1]], iou_threshold, *extra)
+            if vote is not None:
+                keeps, voted = keeps
+                rows += voted
             out += [k + a for k in keeps]                     # indices into the caller's concatenated input
             first, acc = s, 0
         if s < S:
             acc += sizes[s]
-    return out
+    return out if vote is None else (out, rows)
 
 
-def _nms_batched_call(boxes, scores, seg_offsets, iou_threshold):
+def _nms_batched_call(boxes, scores, seg_offsets, iou_threshold, vote=None):
     """S independent NMS problems in one call (BASELINE.json configs[4]: batched multi-scale NMS): segment s = rows
     [seg_offsets[s], seg_offsets[s+1]) of `boxes` / `scores` (float64, device) -- the multi-scale candidate list of image s of an
     evaluation batch (one evaluation.py:80-84 per image), or one list per pyramid level.  Returns a list of S int64 tensors: the kept
-    indices INTO THE CONCATENATED INPUT of each segment, in descending-score order (torchvision.ops.nms semantics per segment)."""
+    indices INTO THE CONCATENATED INPUT of each segment, in descending-score order (torchvision.ops.nms semantics per segment).
+    vote = (vote_thresh, weight): the box vote (`box_voting_batched`) is enqueued behind the NMS on its raw keep list and device-side
+    counts, before the one synchronisation that reads the counts; returns (keeps, [(K_s, 5) voted rows in keep order])."""
     require_gpu(boxes, "nms_batched")
     offs = [int(o) for o in seg_offsets]
     S = len(offs) - 1
@@ -202,8 +209,108 @@ def _nms_batched_call(boxes, scores, seg_offsets, iou_threshold):
     with torch.cuda.device(boxes.device):
         check(lib().tf_nms_f64_batched(ptr(boxes), ptr(scores), host, S, float(iou_threshold), ptr(keep), ptr(cnt), ptr(ws), wsb, stream()),
               "tf_nms_f64_batched")
+    voted = None if vote is None else _box_vote_launch(boxes, scores, host, S, keep, cnt, vote[0], vote[1])[0]
     counts = cnt.tolist()
-    return [keep[offs[s]: offs[s] + counts[s]] for s in range(S)]
+    keeps = [keep[offs[s]: offs[s] + counts[s]] for s in range(S)]
+    if vote is None:
+        return keeps
+    return keeps, [voted[offs[s]: offs[s] + counts[s]] for s in range(S)]
+
+
+# --------------------------------------------------------------------------- test-time augmentation: box voting, un-mirroring
+VOTE_WEIGHTS = {"sigmoid": 0, "score": 1}                 # TF_VOTE_WEIGHT_* (include/tinyfaces_hip.h)
+
+
+def _vote_mode(vote_thresh, weight):
+    if weight not in VOTE_WEIGHTS:
+        raise ValueError(f"box_voting: weight={weight!r}, expected one of {sorted(VOTE_WEIGHTS)}")
+    t = float(vote_thresh)
+    if not 0.0 < t <= 1.0:
+        raise ValueError(f"box_voting: vote_thresh={vote_thresh!r} is outside (0, 1]")
+    return t, VOTE_WEIGHTS[weight]
+
+
+def _box_vote_launch(boxes, scores, host_offs, S, keep, cnt, vote_thresh, weight, want_votes=False):
+    """tf_box_vote_f64_batched on the raw device operands: keep (n,) int64 and cnt (S,) int32 as tf_nms_f64_batched left them.
+    Returns ((n, 5) rows, (n,) int32 votes or None); rows >= cnt[s] of a segment are not written.  No host synchronisation."""
+    t, mode = _vote_mode(vote_thresh, weight)
+    n = boxes.shape[0]
+    out = torch.empty(max(n, 1), 5, dtype=torch.float64, device=boxes.device)
+    votes = torch.empty(max(n, 1), dtype=torch.int32, device=boxes.device) if want_votes else None
+    with torch.cuda.device(boxes.device):
+        check(lib().tf_box_vote_f64_batched(ptr(boxes), ptr(scores), host_offs, S, ptr(keep), ptr(cnt), t, mode, ptr(out), ptr(votes), stream()),
+              "tf_box_vote_f64_batched")
+    return out, votes
+
+
+def box_voting_batched(boxes, scores, seg_offsets, keeps, vote_thresh, weight="sigmoid", num_keep=None, return_votes=False):
+    """Box voting (Gidaris & Komodakis, ICCV 2015; Detectron's box_voting, scoring method ID) behind `nms_batched`, per segment: every
+    kept box is replaced by the weighted mean of all candidates of its segment with IoU >= vote_thresh (the NMS's IoU, bit for bit); its own
+    score stays.  weight: "sigmoid" (w = 1 / (1 + exp(-score)): decode_compact's scores are logits) or "score" (w = score); voters with
+    w <= 0 or NaN are dropped, a kept box without voters stays as it is.  boxes (n, 4) / scores (n,) float64 device tensors.
+    keeps: the list of S int64 index tensors `nms_batched` returns (indices into the concatenated input) -> a list of S (K_s, 5) tensors
+    (x1, y1, x2, y2, score) in keep order [, a list of S (K_s,) int32 vote counts].
+    num_keep (device int32 (S,)): `keeps` is then the RAW (n,) keep buffer of tf_nms_f64_batched and num_keep its device-side counts; nothing
+    is synchronised and the raw (n, 5) rows [, (n,) votes] come back, of which only the first num_keep[s] of each segment are written."""
+    require_gpu(boxes, "box_voting")
+    offs = [int(o) for o in seg_offsets]
+    S = len(offs) - 1
+    if S < 1 or S > NMS_MAX_SEGMENTS or offs[0] != 0 or any(b < a for a, b in zip(offs, offs[1:])) or offs[-1] != boxes.shape[0]:
+        raise ValueError(f"box_voting_batched: bad segment offsets {offs[:4]}... for {boxes.shape[0]} boxes (1..{NMS_MAX_SEGMENTS} segments)")
+    _vote_mode(vote_thresh, weight)
+    boxes = boxes.to(torch.float64).contiguous()
+    scores = scores.to(torch.float64).contiguous()
+    n, dev = offs[-1], boxes.device
+    host = (C.c_int32 * (S + 1))(*offs)
+    if num_keep is not None:
+        require_gpu(num_keep, "box_voting")
+        if num_keep.dtype != torch.int32 or num_keep.numel() != S or keeps.dtype != torch.int64 or keeps.numel() < n:
+            raise ValueError("box_voting_batched: with num_keep, keeps is the raw int64 (n,) keep buffer and num_keep an int32 (S,) device tensor")
+        out, votes = _box_vote_launch(boxes, scores, host, S, keeps.contiguous(), num_keep.contiguous(), vote_thresh, weight, return_votes)
+        return (out, votes) if return_votes else out
+    keeps = list(keeps)
+    if len(keeps) != S:
+        raise ValueError(f"box_voting_batched: {len(keeps)} keep lists for {S} segments")
+    counts = [int(k.numel()) for k in keeps]
+    if any(c > b - a for c, a, b in zip(counts, offs, offs[1:])):
+        raise ValueError("box_voting_batched: a keep list is longer than its segment")
+    keep = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+    for s, k in enumerate(keeps):
+        if counts[s]:
+            keep[offs[s]: offs[s] + counts[s]] = k.to(device=dev, dtype=torch.int64)
+    cnt = torch.tensor(counts, dtype=torch.int32).to(dev)
+    out, votes = _box_vote_launch(boxes, scores, host, S, keep, cnt, vote_thresh, weight, return_votes)
+    rows = [out[offs[s]: offs[s] + counts[s]] for s in range(S)]
+    if return_votes:
+        return rows, [votes[offs[s]: offs[s] + counts[s]] for s in range(S)]
+    return rows
+
+
+def box_voting(boxes, scores, keep, vote_thresh, weight="sigmoid", num_keep=None, return_votes=False):
+    """`box_voting_batched` for one candidate list: keep = the int64 indices `nms` returned -> (K, 5) voted rows in keep order
+    [, (K,) int32 votes]; with num_keep (device int32 (1,)) keep is the raw (n,) keep buffer and the raw (n, 5) rows come back."""
+    require_gpu(boxes, "box_voting")
+    offs = [0, int(boxes.shape[0])]
+    if num_keep is not None:
+        return box_voting_batched(boxes, scores, offs, keep, vote_thresh, weight, num_keep, return_votes)
+    res = box_voting_batched(boxes, scores, offs, [keep], vote_thresh, weight, None, return_votes)
+    return (res[0][0], res[1][0]) if return_votes else res[0]
+
+
+def boxes_unflip_(dets, first, last, max_rows, c):
+    """In place: rows [first, last) of the (cap, 5) float64 candidate list `dets` get x1' = c - x2, x2' = c - x1 (tf_boxes_unflip_f64): the rows a
+    MIRRORED pyramid level appended, mirrored back with c = (W_level - 1) * (1 / scale).  first / last: int32 device tensors of one element
+    (copies of decode_compact's counter before and after the level); max_rows: host bound on last - first.  No host synchronisation."""
+    require_gpu(dets, "boxes_unflip_")
+    require_gpu(first, "boxes_unflip_")
+    require_gpu(last, "boxes_unflip_")
+    if dets.dtype != torch.float64 or dets.dim() != 2 or dets.shape[1] != 5 or not dets.is_contiguous():
+        raise ValueError("boxes_unflip_: expected a contiguous float64 (cap, 5) tensor")
+    if first.dtype != torch.int32 or last.dtype != torch.int32 or first.numel() != 1 or last.numel() != 1:
+        raise ValueError("boxes_unflip_: first and last are int32 device tensors of one element")
+    with torch.cuda.device(dets.device):
+        check(lib().tf_boxes_unflip_f64(ptr(dets), ptr(first), ptr(last), int(max_rows), float(c), stream()), "tf_boxes_unflip_f64")
+    return dets
 
 
 # --------------------------------------------------------------------------- decode
