@@ -226,6 +226,25 @@ int tf_sgd_step_segments_ema(float* param, const float* grad, float* momentum_bu
 int tf_ema_update_segments(float* ema, const float* param, const int64_t* host_segments, int nseg, float ema_weight,
                            const tf_clip_state* state /*may be NULL*/, void* stream);
 
+/* ---- gradient accumulation: several micro-batches per optimizer step ---------------------------
+ * Replaces what autograd does when loss.backward() runs more than once between optimizer.zero_grad() and optimizer.step()
+ * (tinyfaces/trainer.py:85-87): the fused backward pass rewrites the flat gradient on every call, so the sum over a window of micro-batches is
+ * kept in a second flat fp32 buffer `acc`, laid out like `grad`, over the ranges host_segments[nseg][2] (as tf_scale_segments: HOST memory,
+ * ascending and disjoint, TF_SGD_MAX_SEGMENTS per launch).
+ *   TF_ACCUM_STORE   acc = grad          first micro-batch of a window: acc is written without being read or zeroed, so nothing of an
+ *                                        earlier window (a NaN included) survives
+ *   TF_ACCUM_ADD     acc = acc + grad    micro-batches in between; grad is read only
+ *   TF_ACCUM_FINISH  grad = acc + grad   last micro-batch: the sum is written into grad, the buffer the norm, the exchange and the update
+ *                                        read; acc is read only
+ * One plain fp32 add per element with acc as the left operand: a window of N adds as ((g1 + g2) + g3) + ..., the order in which torch
+ * accumulates .grad.  No atomics; elements outside the ranges are neither read nor written.  16-byte moves on a 4-aligned table and a
+ * 16-byte-aligned pair of bases, element-wise moves otherwise.  A null pointer, nseg < 0, an unordered table or an unknown mode is
+ * TF_ERR_ARG; nseg == 0 is TF_OK, no launch. */
+#define TF_ACCUM_STORE 0
+#define TF_ACCUM_ADD 1
+#define TF_ACCUM_FINISH 2
+int tf_grad_accumulate_segments(float* acc, float* grad, const int64_t* host_segments, int nseg, int mode, void* stream);
+
 /* ---- convolution as MFMA implicit GEMM (NHWC) --------------------------------------
  * Replaces every nn.Conv2d on the path (tinyfaces/models/model.py:25-32,90-106 and the
  * torchvision Bottleneck convs) plus the BN / ReLU / residual passes fused around them.

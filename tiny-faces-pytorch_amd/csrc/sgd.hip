@@ -14,6 +14,11 @@
 //   sgd_kernel<CLIP, true> / sgd_segments_kernel<CLIP, true>   e = fmaf(w, p - e, e) on the parameter the update just left in registers:
 //                              one more read and one more write of 4 B per element (28 B instead of 20 B)
 //   ema_segments_kernel        the same average alone over a range table, for the autograd path (reads p and e, writes e)
+//
+// Gradient accumulation (several loss.backward() calls into one .grad before optimizer.step(), tinyfaces/trainer.py:85-87):
+//   grad_accumulate_kernel<MODE>   over a range table: STORE acc = g (first micro-batch; acc is not read), ADD acc = acc + g, FINISH
+//                              g = acc + g (last micro-batch: the sum lands in the buffer every later launch of the step reads).  Plain
+//                              fp32 adds, left to right.  HBM bound: 8 B (STORE) / 12 B (ADD, FINISH) per trained element.
 #include <math.h>
 
 #include "common.h"
@@ -170,6 +175,34 @@ __global__ void __launch_bounds__(256) scale_segments_kernel(float* __restrict__
         const int ke = seg_of(t, nseg, j + e);
         const int64_t ie = t.start[ke] + (j + e - t.cum[ke]);
         g[ie] = skip ? 0.f : g[ie] * coef;
+      }
+    }
+  }
+}
+// Gradient accumulation over a range table (the index space of scale_segments_kernel).  MODE is one of TF_ACCUM_*: STORE writes acc without
+// reading it (whatever an earlier window left there, a NaN included, is gone), ADD writes acc, FINISH writes g and leaves acc alone.  Every
+// element is read and written by the same thread, so FINISH works in place; nothing outside the ranges is touched.
+template <int MODE>
+__global__ void __launch_bounds__(256) grad_accumulate_kernel(float* acc, float* g, const SgdSegs t, int nseg, int vec) {
+  const int64_t total = t.cum[nseg];
+  const int64_t stride = (int64_t)gridDim.x * 256 * 4;
+  for (int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; j < total; j += stride) {
+    const int k = seg_of(t, nseg, j);
+    const int64_t i = t.start[k] + (j - t.cum[k]);
+    if (vec) {
+      float4 gv = *reinterpret_cast<const float4*>(g + i);
+      if constexpr (MODE != TF_ACCUM_STORE) {
+        const float4 av = *reinterpret_cast<const float4*>(acc + i);
+        gv.x = av.x + gv.x; gv.y = av.y + gv.y; gv.z = av.z + gv.z; gv.w = av.w + gv.w;
+      }
+      *reinterpret_cast<float4*>((MODE == TF_ACCUM_FINISH ? g : acc) + i) = gv;
+    } else {
+      for (int e = 0; e < 4 && j + e < total; ++e) {
+        const int ke = seg_of(t, nseg, j + e);
+        const int64_t ie = t.start[ke] + (j + e - t.cum[ke]);
+        if constexpr (MODE == TF_ACCUM_STORE) acc[ie] = g[ie];
+        else if constexpr (MODE == TF_ACCUM_ADD) acc[ie] = acc[ie] + g[ie];
+        else g[ie] = acc[ie] + g[ie];
       }
     }
   }
@@ -419,6 +452,29 @@ extern "C" int tf_scale_segments(float* grad, const int64_t* host_segments, int 
     const int used = fill_table(host_segments, nseg, k0, &t, &vec, &blocks);
     if (used == 0) continue;
     hipLaunchKernelGGL(scale_segments_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, grad, t, used, vec, state);
+  }
+  TF_CHECK_LAUNCH();
+  return TF_OK;
+}
+
+extern "C" int tf_grad_accumulate_segments(float* acc, float* grad, const int64_t* host_segments, int nseg, int mode, void* stream) {
+  if (mode != TF_ACCUM_STORE && mode != TF_ACCUM_ADD && mode != TF_ACCUM_FINISH) return TF_ERR_ARG;
+  if (nseg < 0 || (nseg > 0 && (!acc || !grad || !host_segments))) return TF_ERR_ARG;
+  if (nseg == 0) return TF_OK;
+  if (!table_ok(host_segments, nseg)) return TF_ERR_ARG;
+  const bool aligned = (((uintptr_t)acc | (uintptr_t)grad) & 15) == 0;
+  for (int k0 = 0; k0 < nseg; k0 += TF_SGD_MAX_SEGMENTS) {
+    SgdSegs t;
+    int vec = aligned ? 1 : 0;
+    int64_t blocks = 0;
+    const int used = fill_table(host_segments, nseg, k0, &t, &vec, &blocks);
+    if (used == 0) continue;
+    if (mode == TF_ACCUM_STORE)
+      hipLaunchKernelGGL((grad_accumulate_kernel<TF_ACCUM_STORE>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, acc, grad, t, used, vec);
+    else if (mode == TF_ACCUM_ADD)
+      hipLaunchKernelGGL((grad_accumulate_kernel<TF_ACCUM_ADD>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, acc, grad, t, used, vec);
+    else
+      hipLaunchKernelGGL((grad_accumulate_kernel<TF_ACCUM_FINISH>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, acc, grad, t, used, vec);
   }
   TF_CHECK_LAUNCH();
   return TF_OK;

@@ -88,6 +88,21 @@ EMA_HELP = ("--model-ema DECAY: keep an exponential moving average of the weight
             "it in every checkpoint as \"model_ema\" (evaluate_model.py --ema), default off")
 
 
+ACCUM_HELP = ("--accum-steps N: one optimizer step per N batches (gradient accumulation: the gradients of N micro-batches are summed, as N "
+              "calls of loss.backward() before one optimizer.step() would; the effective batch is batch_size x N x world size), N >= 1, default 1")
+
+
+ACCUM_AVERAGE_HELP = ("--accum-average: apply the MEAN of the accumulated gradients instead of their sum (the `loss / N` of torch loops; the "
+                      "reference's loss is a sum over the batch, so the sum is what a batch N times as large gives), default off")
+
+
+def _accum_steps(text):
+    value = int(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError(f"must be an integer >= 1, got {text}")
+    return value
+
+
 def _ema_decay(text):
     try:
         ema_decay_at(float(text), 0)
@@ -104,7 +119,7 @@ def _positive_float(text):
 
 
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP)))
+    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP)))
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
@@ -112,7 +127,8 @@ def arguments(argv=None):
 
 def trunk_arguments(argv=None):
     """`arguments` plus `base_model` from --base-model, `freeze_bn` from --freeze-bn, `trainable_layers` from --trainable-layers, `clip_grad_norm`
-    from --clip-grad-norm, `skip_nonfinite` from --skip-nonfinite and `model_ema` from --model-ema.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
+    from --clip-grad-norm, `skip_nonfinite` from --skip-nonfinite, `model_ema` from --model-ema, `accum_steps` from --accum-steps and `accum_average`
+    from --accum-average.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
     options and the additions above."""
     parser = argparse.ArgumentParser(add_help=False)
     parser.add_argument("--base-model", dest="base_model", default="resnet101", choices=list(model_zoo.TRUNKS), help=TRUNK_HELP)
@@ -121,6 +137,8 @@ def trunk_arguments(argv=None):
     parser.add_argument("--clip-grad-norm", dest="clip_grad_norm", default=None, type=_positive_float, help=CLIP_HELP)
     parser.add_argument("--skip-nonfinite", dest="skip_nonfinite", action="store_true", help=SKIP_HELP)
     parser.add_argument("--model-ema", dest="model_ema", default=None, type=_ema_decay, metavar="DECAY", help=EMA_HELP)
+    parser.add_argument("--accum-steps", dest="accum_steps", default=1, type=_accum_steps, metavar="N", help=ACCUM_HELP)
+    parser.add_argument("--accum-average", dest="accum_average", action="store_true", help=ACCUM_AVERAGE_HELP)
     known, rest = parser.parse_known_args(argv)
     if known.trainable_layers < 4 and not known.freeze_bn:
         parser.error(f"--trainable-layers {known.trainable_layers} freezes stages of the trunk, which is defined on frozen BatchNorm only: add --freeze-bn")
@@ -131,6 +149,8 @@ def trunk_arguments(argv=None):
     args.clip_grad_norm = known.clip_grad_norm
     args.skip_nonfinite = known.skip_nonfinite
     args.model_ema = known.model_ema
+    args.accum_steps = known.accum_steps
+    args.accum_average = known.accum_average
     return args
 
 
@@ -142,7 +162,8 @@ def run_fused_epoch(engine, loss_fn, loader, epoch, device, base_lr):
     engine.set_lr(lr_at(base_lr, epoch))
     total = len(loader)
     for idx, batch in enumerate(loader):
-        engine.step(*(t.float().to(device, non_blocking=True) for t in batch))
+        # the epoch's last batch ends its window, full or not: no checkpoint is ever written with gradients accumulated and not applied
+        engine.step(*(t.float().to(device, non_blocking=True) for t in batch), apply=True if idx + 1 == total else None)
         if parallel.rank() == 0:
             loss_fn.flush_meters(lag=0 if idx + 1 == total else 1)      # one step behind: the host prepares batch idx + 1 while the GPU runs step idx
             trainer.print_state(idx, epoch, total, loss_fn.class_average.average, loss_fn.reg_average.average)
@@ -182,6 +203,8 @@ def main():
     if parallel.rank() == 0:
         print(f"trunk {args.base_model}, {args.dtype}, BatchNorm {'frozen' if args.freeze_bn else 'on batch statistics'}, trainable layers "
               f"{args.trainable_layers} of 4 ({len(model.trainable_parameter_names())} trained tensors)")
+        print(f"effective batch {args.batch_size * args.accum_steps * parallel.world_size()} = batch_size {args.batch_size} x accum-steps "
+              f"{args.accum_steps} x world {parallel.world_size()}" + (", gradients averaged over the window" if args.accum_average and args.accum_steps > 1 else ""))
     loss_fn = DetectionCriterion(NUM_TEMPLATES, seed=args.seed * parallel.world_size() + parallel.rank(), lazy_meters=True)
     loss_fn.ohem_thresh = args.ohem_thresh
 
@@ -203,7 +226,8 @@ def main():
     engine = optimizer = scheduler = ema = None
     if args.fused:
         engine = TrainEngine(model, loss_fn, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay, device=device,
-                             max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, ema_decay=args.model_ema)
+                             max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, ema_decay=args.model_ema,
+                             accum_steps=args.accum_steps, accum_average=args.accum_average)
         ema = engine.ema                  # (built from the weights --resume / --pretrained left in the model)
         if state is not None:
             engine.load_optimizer_state_dict(state.get("optimizer"))      # momentum buffers (a torch.optim.SGD state_dict)
@@ -250,7 +274,7 @@ def main():
             run_fused_epoch(engine, loss_fn, train_loader, epoch, device, args.lr)
         else:
             trainer.train(model, loss_fn, optimizer, train_loader, epoch, device=device, max_grad_norm=args.clip_grad_norm,
-                          skip_nonfinite=args.skip_nonfinite, ema=ema)
+                          skip_nonfinite=args.skip_nonfinite, ema=ema, accum_steps=args.accum_steps, accum_average=args.accum_average)
             scheduler.step()
         if args.skip_nonfinite and parallel.rank() == 0:
             total = engine.skipped_steps if engine is not None else ops.clip_skipped_steps(device)

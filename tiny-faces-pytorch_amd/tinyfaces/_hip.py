@@ -66,6 +66,7 @@ class ClipState(C.Structure):
 
 
 TF_CLIP_SKIP_NONFINITE = 1
+TF_ACCUM_STORE, TF_ACCUM_ADD, TF_ACCUM_FINISH = 0, 1, 2
 
 
 class ConvArgs(C.Structure):
@@ -123,6 +124,7 @@ _SIGNATURES = {
     "tf_sgd_step_ema": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, vp]),
     "tf_sgd_step_segments_ema": (i32, [vp, vp, vp, vp, C.POINTER(i64), i32, f32, f32, f32, f32, f32, vp, vp]),
     "tf_ema_update_segments": (i32, [vp, vp, C.POINTER(i64), i32, f32, vp, vp]),
+    "tf_grad_accumulate_segments": (i32, [vp, vp, C.POINTER(i64), i32, i32, vp]),
     "tf_conv_mtiles": (i32, [C.POINTER(ConvArgs)]),
     "tf_conv2d": (i32, [C.POINTER(ConvArgs), vp]),
     "tf_pack_weight": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp]),

@@ -6,6 +6,9 @@ no per-parameter Python loop and no host sync:
     -> [global gradient norm -> clip coefficient / non-finite verdict, in device memory] -> fused SGD (one launch per group)
        [+ the model EMA of the updated parameters, inside the same launches]
 
+Gradient accumulation (accum_steps = N > 1): the first N - 1 calls of a window stop behind the backward pass and add their gradient into
+one more flat buffer (ops.grad_accumulate); the N-th adds that buffer into its own gradient and runs the tail above on the sum.
+
 Data-parallel overlap: the flat gradient is cut along the backward order into buckets of ~`bucket_mb` MB (default 10: heads +
 layer3.21-22 first, then THREE layer-3 bottlenecks of 4.46 MB each per bucket (two stay under 10 MB), ..., finally layer1/2 + stem: SURVEY.md 8e asks for
 8-12 buckets of ~10 MB in layer 3).  When a bucket's gradients are enqueued the executor calls back with the stream that carries
@@ -28,7 +31,7 @@ from .ema import ModelEma
 
 class TrainEngine:
     def __init__(self, model, criterion, lr=1e-4, momentum=0.9, weight_decay=5e-4, device="cuda", bucket_mb=10, native_exchange=None,
-                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True, accum_steps=1, accum_average=False):
         """max_grad_norm: clip the global L2 norm of the (rank-averaged) gradient of the trained tensors to this value before the update, as
         torch.nn.utils.clip_grad_norm_ between backward() and optimizer.step() would (tinyfaces/trainer.py:86-87).  skip_nonfinite: a step
         whose gradient norm is NaN or Inf changes neither the parameters nor the momentum (`skipped_steps` counts them; what the FORWARD
@@ -41,7 +44,15 @@ class TrainEngine:
         update t is min(ema_decay, (1 + t) / (10 + t)).  `ema.updates` advances on EVERY step, one the non-finite guard drops included (the
         device leaves the average alone on such a step, but the host cannot know without a sync): the warm-up is indexed by steps taken.
         Data-parallel runs need no collective for it: every rank applies the same update to the same parameters.  None (the default):
-        `self.ema` is None, no buffer, no new call."""
+        `self.ema` is None, no buffer, no new call.
+        accum_steps: one optimizer step covers this many calls of step() (micro-batches), what a torch loop does when it calls
+        loss.backward() N times between optimizer.zero_grad() and optimizer.step().  The applied gradient is the SUM over the window, added
+        left to right in fp32 -- the loss is a sum over the batch (loss.py:87), so under frozen BatchNorm N micro-batches of B images are
+        the step of one batch of N * B images up to summation order; accum_average=True applies the mean instead (the `loss / N` habit),
+        folded into the grad_scale the norm and SGD launches take.  Clipping, the guard, the exchange between ranks (one per window, behind
+        the last backward pass, not overlapped with it, through torch.distributed) and the model EMA act once per window, on the
+        accumulated gradient; BatchNorm running statistics and the loss meters advance with every micro-batch.  One more flat fp32 buffer,
+        allocated when first used; fixed for the engine's life.  1 (the default): no buffer, no new call."""
         self.device = torch.device(device)
         self.model = model.to(self.device).train()
         self.criterion = criterion
@@ -57,7 +68,15 @@ class TrainEngine:
         self.groups = self.model.group_ranges()
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.bucket_elems = int(bucket_mb * (1 << 20) // 4)
-        self.steps = 0
+        self.steps = 0                        # optimizer steps
+        self.micro_steps = 0                  # calls of step(): equal to `steps` unless gradients are accumulated
+        self.accum_steps = int(accum_steps)
+        if self.accum_steps < 1:
+            raise ValueError(f"accum_steps must be >= 1, got {accum_steps}")
+        self.accum_average = bool(accum_average)
+        self._accum = None                    # the accumulator: flat fp32 like flat_m, allocated by the first micro-batch that is not applied
+        self._accum_segs = None               # the ranges the open window accumulates over
+        self._window = 0                      # micro-batches in the accumulator
         # r6: None = the default rule (_want_native): the library's own RCCL hook when the world is larger than one rank and librccl resolves,
         # the torch.distributed callback otherwise and whenever the native set-up or a native step reports an error
         self.native_exchange = native_exchange
@@ -77,6 +96,9 @@ class TrainEngine:
         if self._clip_on() and self.sgd_per_bucket:
             raise ValueError("max_grad_norm / skip_nonfinite cannot be combined with TINYFACES_SGD_PER_BUCKET: a bucket cannot be applied "
                              "before the global gradient norm exists")
+        if self.accum_steps > 1 and self.sgd_per_bucket:
+            raise ValueError("accum_steps > 1 cannot be combined with TINYFACES_SGD_PER_BUCKET: a bucket cannot be applied before the "
+                             "window's last micro-batch")
         if parallel.is_distributed() or self.sgd_per_bucket:
             self._setup_overlap()
 
@@ -167,12 +189,13 @@ class TrainEngine:
         # through the torch.distributed group that already exists (any backend).  Opt-in: like the torch path it has only ever seen a
         # 1-rank group on hardware (tests/test_gpu_dist.py); the default stays the torch.distributed callback below.
         self._native = None
-        if self._want_native() and not self._use_comm_stream and not self.sgd_per_bucket:
+        if self._want_native() and not self._use_comm_stream and not self.sgd_per_bucket and self.accum_steps == 1:
             self._native = self._setup_native(ranges)
         self._works, self._cb_error, self._ext_streams = [], None, {}
         self._block_range = {r[0]: (r[1], r[2]) for r in ranges}
         self._cb = C.CFUNCTYPE(None, C.c_int, C.c_void_p, C.c_void_p)(self._on_bucket)
-        self.model._grad_callback = None if self._use_comm_stream else self._cb
+        # accum_steps > 1: no gradient-ready hook on any micro-batch, the window's one exchange is issued behind its last backward pass
+        self.model._grad_callback = None if self._use_comm_stream or self.accum_steps > 1 else self._cb
         self.model._grad_callback_user = None
         if self._native is not None:          # the C hook + its plan instead of the ctypes callback
             self.model._grad_callback = C.cast(lib().tf_comm_allreduce_hook, C.c_void_p)
@@ -243,7 +266,7 @@ class TrainEngine:
     def _on_bucket(self, block, stream_ptr, _user):
         """Called by the executor while it enqueues the backward pass: bucket `block` is final at the tail of `stream_ptr`."""
         try:
-            if not (parallel.is_distributed() and not self.skip_allreduce) or self.sgd_per_bucket:
+            if not (parallel.is_distributed() and not self.skip_allreduce) or self.sgd_per_bucket or self.accum_steps > 1:
                 return
             start, end = self._block_range[block]
             g = self.model._grad_flat_persistent
@@ -377,6 +400,9 @@ class TrainEngine:
         the reference's resume path (`optimizer.load_state_dict(checkpoint['optimizer'])`, main.py:76) accepts a checkpoint
         written by the fused trainer: one `momentum_buffer` per trained parameter (a slice of the flat momentum buffer), the
         four parameter groups with lr / initial_lr (StepLR needs it when constructed with last_epoch >= 0, main.py:81-83)."""
+        if self._window:
+            raise RuntimeError(f"optimizer_state_dict: {self._window} of {self.accum_steps} micro-batches are accumulated and not applied; "
+                               "finish the window first (step(..., apply=True))")
         base_lr = self.lr if base_lr is None else base_lr
         seg = self.model._segments
         state, groups, idx = {}, [], 0
@@ -429,6 +455,13 @@ class TrainEngine:
         if os.environ.get("TINYFACES_ALLREDUCE_ON_MAIN"):      # diagnostic: no communication stream, one synchronous collective per bucket behind the backward pass
             for (_, start, end) in (self._overlap["ranges"] if self._overlap is not None else [(0, 0, gflat.numel())]):
                 dist.all_reduce(gflat[start:end], op=dist.ReduceOp.SUM)
+            return
+        if self.accum_steps > 1:
+            # no hook ran (a window has one exchange, behind its last backward pass): the engine's bucket ranges, issued here and waited for
+            ranges = [(start, end) for _, start, end in self._overlap["ranges"]] if self._overlap is not None else [(0, gflat.numel())]
+            works = [dist.all_reduce(gflat[start:end], op=dist.ReduceOp.SUM, async_op=True) for start, end in ranges]
+            for w in works:
+                w.wait()
             return
         if self._native is not None:
             # the collectives were issued by tf_comm_allreduce_hook during the backward call: the training stream waits for the communicator
@@ -551,7 +584,39 @@ class TrainEngine:
         segs = [(max(s, a), min(e, b)) for s, e in self._trained_segments() if e > a and s < b]
         ops.sgd_step_segments(self.flat_p, gflat, self.flat_m, segs, self.lr * mult, self.momentum, self.weight_decay, scale, **kw)
 
-    def step(self, x, class_map, regression_map):
+    @property
+    def pending_micro_batches(self):
+        """Micro-batches accumulated and not yet applied (0: no window is open)."""
+        return self._window
+
+    def _applies(self, apply):
+        """Whether the micro-batch about to run ends its window.  None: when the window is full; True: now; False: never, which the micro-batch
+        that would fill the window cannot ask for (a window never holds more than accum_steps micro-batches)."""
+        full = self._window + 1 >= self.accum_steps
+        if apply is None:
+            return full
+        if not apply and full:
+            raise ValueError(f"step(apply=False): this micro-batch fills the window of accum_steps = {self.accum_steps}; it has to be applied")
+        return bool(apply)
+
+    def _accumulate(self, gflat, last):
+        """The gradient the backward pass has just left in `gflat` joins the window: STORE / ADD into the accumulator, or, for the window's
+        last micro-batch, FINISH -- the accumulator added into `gflat`, where the tail of the step reads it.  Over _norm_segments(): what the
+        norm and the update read, pads included."""
+        segs = self._norm_segments()
+        if self._window == 0:
+            if last:
+                return                                    # a window of one micro-batch: the plain step, no launch
+            if self._accum is None:
+                self._accum = torch.empty_like(self.flat_m)      # never read before STORE has written it
+            self._accum_segs = segs
+        elif segs is not self._accum_segs:
+            raise RuntimeError("TrainEngine.step: the trained tensors changed (freeze_batchnorm / set_trainable_layers) while a window of "
+                               "accumulated gradients is open")
+        mode = ops.ACCUM_FINISH if last else ops.ACCUM_STORE if self._window == 0 else ops.ACCUM_ADD
+        ops.grad_accumulate(self._accum, gflat, segs, mode)
+
+    def step(self, x, class_map, regression_map, apply=None):
         """x (B,3,H,W) f32, class_map (B,nt,h,w) f32 (mined in place), regression_map (B,4nt,h,w) f32: all on the device.
         Returns the device tensor [sum cls loss, sum reg loss] (float64) without synchronising.
         The step follows the model's BatchNorm mode (DetectionModel.freeze_batchnorm): frozen, the forward and backward run the folded-BN
@@ -559,8 +624,13 @@ class TrainEngine:
         DetectionModel.set_trainable_layers(k < 4), the conv weights of the frozen stages; the bucket plan of the gradient exchange stays
         as it is (frozen ranges are reduced as zeros).
         With max_grad_norm / skip_nonfinite the update is clipped / guarded on the device (see __init__); a skipped step still counts in
-        `steps` and still returns its loss.  With ema_decay the same launches also advance `self.ema` (see __init__)."""
+        `steps` and still returns its loss.  With ema_decay the same launches also advance `self.ema` (see __init__).
+        With accum_steps = N > 1 every call is one micro-batch (`micro_steps`), and the N-th of a window is the optimizer step (`steps`) on
+        the sum of the window's gradients.  apply=True: apply now, over the k <= N micro-batches accumulated (the last batch of an epoch);
+        apply=False: accumulate only (ValueError on the micro-batch that fills the window); None: apply when the window is full."""
         m, c = self.model, self.criterion
+        accumulating = self.accum_steps > 1
+        applies = self._applies(apply) if accumulating or apply is not None else True
         m._check_partial_freeze()
         m._sync_tables(x.device)
         out = m._run_forward(x, training=True)
@@ -575,10 +645,22 @@ class TrainEngine:
         except BaseException:
             self._drain_exchange()               # collectives already queued by the hooks are joined before the error travels on
             raise
+        self.micro_steps += 1
+        if hasattr(c, "_pending") and (parallel.rank() == 0 or not parallel.is_distributed()):
+            c._pending.append((loss2, x.shape[0]))       # only the logging rank ever flushes the meters
+        if accumulating:
+            self._accumulate(gflat, applies)
+            if not applies:
+                self._window += 1
+                return loss2
         scale = 1.0
         reduce = parallel.is_distributed() and not self.skip_allreduce
         if reduce:
             scale = 1.0 / parallel.world_size()          # average over ranks, folded into the SGD kernel
+        if accumulating:
+            if self.accum_average:
+                scale = scale * (1.0 / (self._window + 1))       # the mean over the micro-batches actually accumulated
+            self._window = 0
         if self.ema is not None:
             if self.ema._src is not self.flat_p or m._flat_params is not self.flat_p:
                 raise RuntimeError("TrainEngine.step: the model was flattened again after the engine was built; its model EMA would follow a "
@@ -595,6 +677,4 @@ class TrainEngine:
                     continue                              # score4_upsample: lr 0 (model.py:84) -> nothing to do
                 self._sgd(gflat, s, e, mult, scale, clip)
         self.steps += 1
-        if hasattr(c, "_pending") and (parallel.rank() == 0 or not parallel.is_distributed()):
-            c._pending.append((loss2, x.shape[0]))       # only the logging rank ever flushes the meters
         return loss2

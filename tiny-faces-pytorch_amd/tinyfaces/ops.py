@@ -626,6 +626,27 @@ def ema_update_segments(ema, param, segments, weight, clip_state=None):
                                            stream()), "tf_ema_update_segments")
 
 
+ACCUM_STORE, ACCUM_ADD, ACCUM_FINISH = _hip.TF_ACCUM_STORE, _hip.TF_ACCUM_ADD, _hip.TF_ACCUM_FINISH
+
+
+def grad_accumulate(acc, grad, segments, mode):
+    """One micro-batch of a gradient-accumulation window over the element ranges `segments` ([(start, end)], ascending, disjoint) of two flat
+    fp32 buffers of one length (tf_grad_accumulate_segments), what autograd does when loss.backward() runs again before optimizer.step()
+    (tinyfaces/trainer.py:85-87): ACCUM_STORE acc = grad (the first one: acc is not read), ACCUM_ADD acc = acc + grad, ACCUM_FINISH
+    grad = acc + grad (the last one: the sum lands in `grad`, acc keeps its bits).  Plain fp32 adds, left to right; everything outside the
+    ranges is untouched."""
+    require_gpu(acc, "grad_accumulate")
+    if mode not in (ACCUM_STORE, ACCUM_ADD, ACCUM_FINISH):
+        raise ValueError(f"grad_accumulate: mode must be ACCUM_STORE, ACCUM_ADD or ACCUM_FINISH, got {mode!r}")
+    assert acc.dtype == grad.dtype == torch.float32 and acc.is_contiguous() and grad.is_contiguous()
+    assert acc.device == grad.device and acc.numel() == grad.numel()
+    table, nseg = _segment_table("grad_accumulate", segments, acc.numel())
+    if nseg == 0:
+        return
+    with torch.cuda.device(acc.device):
+        check(lib().tf_grad_accumulate_segments(ptr(acc), ptr(grad), table, nseg, int(mode), stream()), "tf_grad_accumulate_segments")
+
+
 # --------------------------------------------------------------------------- conv engine (used directly by the parity tests)
 def pack_weight(w_oihw, dtype, transpose=False, cols_pad=None):
     require_gpu(w_oihw, "pack_weight")

@@ -30,7 +30,8 @@ def _is_logging_rank():
     return parallel.rank() == 0 or not parallel.is_distributed()
 
 
-def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=None, skip_nonfinite=False, ema=None):
+def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=None, skip_nonfinite=False, ema=None, accum_steps=1,
+          accum_average=False):
     """One epoch with the reference's step order (trainer.py:68-90): forward, criterion, zero_grad, backward, [all-reduce],
     optimizer step, progress line.
 
@@ -41,26 +42,42 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
     optimizer does with a zero gradient.  Only the fused engine (TrainEngine(skip_nonfinite=True)) leaves a skipped step untouched.
 
     ema (a tinyfaces.ema.ModelEma of `model`): ema.update() right behind optimizer.step(), the spot of AveragedModel.update_parameters in a
-    torch training loop -- one launch per 128 trained tensors on the device, no host sync."""
+    torch training loop -- one launch per 128 trained tensors on the device, no host sync.
+
+    accum_steps = N > 1: one optimizer step per window of N batches.  zero_grad() runs at the start of a window only, so autograd sums the
+    window's gradients in `.grad`; the window ends when it is full or with the loader's last batch, and only there follow the averaging over
+    ranks, the 1 / k scaling of accum_average (k batches in the window: the mean instead of the sum), the clip, optimizer.step() and
+    ema.update(), in that order.  With the default the loop is the one above, call for call."""
     net = model.to(device).train()
     reducer = parallel.reducer_for(net)
     n_batches = len(dataloader)
     clip = max_grad_norm is not None or skip_nonfinite
     if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
         raise ValueError(f"max_grad_norm must be positive or None, got {max_grad_norm}")
-    clipped = [p for g in optimizer.param_groups for p in g["params"]] if clip else None
+    accum_steps = int(accum_steps)
+    if accum_steps < 1:
+        raise ValueError(f"accum_steps must be >= 1, got {accum_steps}")
+    average = bool(accum_average) and accum_steps > 1
+    clipped = [p for g in optimizer.param_groups for p in g["params"]] if clip or average else None
+    window = 0                                  # batches whose gradients `.grad` holds
     for step, batch in enumerate(dataloader):
         image, cls_target, reg_target = (t.float().to(device, non_blocking=True) for t in batch)
         loss = loss_fn(net(image), cls_target, reg_target)
-        optimizer.zero_grad()
+        if window == 0:
+            optimizer.zero_grad()
         loss.backward()
-        if reducer is not None:
-            reducer.average_gradients()
-        if clip:
-            ops.clip_grad_norm_(clipped, float("inf") if max_grad_norm is None else max_grad_norm, skip_nonfinite=skip_nonfinite)
-        optimizer.step()
-        if ema is not None:
-            ema.update()
+        window += 1
+        if window == accum_steps or step + 1 == n_batches:
+            if reducer is not None:
+                reducer.average_gradients()
+            if average and window > 1:
+                torch._foreach_mul_([p.grad for p in clipped if p.grad is not None], 1.0 / window)      # (this path's update is torch's own, too)
+            if clip:
+                ops.clip_grad_norm_(clipped, float("inf") if max_grad_norm is None else max_grad_norm, skip_nonfinite=skip_nonfinite)
+            optimizer.step()
+            if ema is not None:
+                ema.update()
+            window = 0
         if _is_logging_rank():
             flush = getattr(loss_fn, "flush_meters", None)
             if flush is not None:
