@@ -48,7 +48,7 @@ def balance_sampling(label_cls, pos_fraction=0.5, sample_size=256, rng=np.random
 
 
 def criterion(output, class_map, regression_map, n_templates=25, reg_weight=1,
-              pos_fraction=0.5, rng=np.random, want_grad=True):
+              pos_fraction=0.5, rng=np.random, want_grad=True, ohem_thresh=0.03):
     """loss.py:65-93.  output (B,5nt,H,W) f32 tensor; class_map (B,nt,H,W) f32 (cloned, the
     reference mutates it in place); regression_map (B,4nt,H,W) f32.
     Returns dict(total, cls, reg, class_map_final, grad, records)."""
@@ -58,7 +58,7 @@ def criterion(output, class_map, regression_map, n_templates=25, reg_weight=1,
     regression = output[:, n_templates:]
     # hard negative mining (loss.py:59-63)
     l = F.soft_margin_loss(classification.detach(), class_map, reduction="none")
-    class_map[l < 0.03] = 0
+    class_map[l < ohem_thresh] = 0                  # loss.py:61 hard-codes 0.03; 0 mines nothing
     # balance sampling (loss.py:47-57)
     lab = class_map.numpy()
     records = []

@@ -108,6 +108,54 @@ def gen_targets(out):
     out["cases"] = np.array(cases)
 
 
+def gen_targets_geometry(out):
+    """DataProcessor / compute_dense_overlap on maps that are not square: image 340 x 500 -> map (43, 63) and image
+    500 x 316 -> map (63, 40) (rows first), each with a paste box that is not symmetric in x and y, one flipped; the
+    second also with the first seven template rows only; and the first once more under a receptive field whose stride and
+    offset differ between y and x (map (43, 32)).  tests/golden/targets.npz only knows 63 x 63 and stride 8, offset -1 in both."""
+    templates = load_templates()
+    cases = []
+    rng = np.random.RandomState(4321)
+    rf_yx = {"size": [859, 859], "stride": [8, 16], "offset": [-1, 3]}          # (y, x) like RF
+    for ci, (ih, iw, hm, g, paste, flip, nt, rf) in enumerate([(340, 500, (43, 63), 5, [37, 21, 471, 318], True, 25, RF),
+                                                               (500, 316, (63, 40), 4, [12, 83, 290, 455], False, 25, RF),
+                                                               (500, 316, (63, 40), 6, [61, 9, 301, 470], True, 7, RF),
+                                                               (340, 500, (43, 32), 5, [37, 21, 471, 318], True, 25, rf_yx)]):
+        w = np.exp(rng.uniform(np.log(20), np.log(120), g))
+        h = w * rng.uniform(1.0, 1.5, g)
+        x1, y1 = rng.uniform(-10, iw - w, g), rng.uniform(-10, ih - h, g)
+        boxes = np.round(np.stack([x1, y1, x1 + w, y1 + h], 1), 3)
+        t = templates[:nt]
+        proc = DataProcessor((ih, iw), hm, 0.7, 0.3, t, rf=rf)
+        pad_mask = proc.get_padding(paste)
+        if flip:
+            pad_mask = np.fliplr(pad_mask)                            # wider_face.py:165
+        seed = 200 + ci
+        np.random.seed(seed)
+        cm, rm, iou_pert = proc.get_heatmaps(boxes.copy(), pad_mask)
+        (ofy, ofx), (sty, stx) = rf["offset"], rf["stride"]
+        iou = compute_dense_overlap(ofx, ofy, stx, sty, hm[1], hm[0], t[:, 0], t[:, 1], t[:, 2], t[:, 3], boxes[:, 0], boxes[:, 1],
+                                    boxes[:, 2], boxes[:, 3], 1, 1)
+        tag = f"g{ci}"
+        out[f"{tag}_input_size"], out[f"{tag}_heatmap_size"] = np.array([ih, iw]), np.array(hm)
+        out[f"{tag}_nt"] = np.array(nt)
+        out[f"{tag}_rf_stride"], out[f"{tag}_rf_offset"] = np.array(rf["stride"]), np.array(rf["offset"])
+        out[f"{tag}_boxes"] = boxes
+        out[f"{tag}_paste"] = np.array(paste, dtype=np.int64)
+        out[f"{tag}_flip"] = np.array(int(flip))
+        out[f"{tag}_pad"] = np.packbits(pad_mask)
+        # noise is NOT stored: tests regenerate it with np.random.seed(seed); np.random.rand(vsy, vsx, nt, G)
+        out[f"{tag}_seed"] = np.array(seed)
+        out[f"{tag}_class"] = cm.astype(np.int8)
+        out[f"{tag}_iou"] = iou[::4, ::4]
+        out[f"{tag}_reg"] = rm[::4, ::4]
+        out[f"{tag}_iou_sum"] = np.array(iou.sum())
+        out[f"{tag}_reg_sum"] = np.array(rm.sum())
+        out[f"{tag}_ioupert_max"] = iou_pert.max(axis=(0, 1, 2))
+        cases.append(tag)
+    out["cases"] = np.array(cases)
+
+
 def gen_decode(out):
     templates = load_templates()
     cases = []
@@ -378,7 +426,7 @@ def gen_cli(out):
     out["evaluate_model"] = np.array(json.dumps(defaults(os.path.join(refstub.REFERENCE_ROOT, "evaluate_model.py"), ["DATA"]), sort_keys=True))
 
 
-GENERATORS = {"cli": gen_cli, "clustering": gen_clustering, "targets": gen_targets, "decode": gen_decode, "criterion": gen_criterion, "nms": gen_nms,
+GENERATORS = {"cli": gen_cli, "clustering": gen_clustering, "targets": gen_targets, "targets_geometry": gen_targets_geometry, "decode": gen_decode, "criterion": gen_criterion, "nms": gen_nms,
               "model": gen_model, "detections": gen_detections, "trainer": gen_trainer, "augment": gen_augment}
 
 
