@@ -128,6 +128,40 @@ int tf_box_vote_f64(const double* boxes /*[n][4]*/, const double* scores /*[n]*/
  * *last - *first that sizes the grid (rows beyond it are left alone); 0 launches nothing, < 0 is TF_ERR_ARG. */
 int tf_boxes_unflip_f64(double* dets /*[cap][5]*/, const int32_t* first, const int32_t* last, int max_rows, double c, void* stream);
 
+/* ---- Soft-NMS, float64 (Bodla et al., ICCV 2017, "Improving object detection with one line of code"; Detectron's soft_nms) ----------
+ * An addition next to tf_nms_f64: a candidate that overlaps a better one is not dropped; its score is decayed, the list is re-ranked,
+ * and it survives unless its score falls under score_thresh.  Per segment (batching as tf_nms_f64_batched: S <= TF_NMS_MAX_SEGMENTS
+ * segments described by a HOST offset table, side by side in the same two launches):
+ *   1. s_j = 1 / (1 + exp(-scores[j])) with score_mode TF_VOTE_WEIGHT_SIGMOID (tf_decode_compact emits logits; the vote's expression),
+ *      s_j = scores[j] with TF_VOTE_WEIGHT_SCORE.  Candidate j is live iff s_j >= score_thresh; a NaN is never live.
+ *   2. While a candidate is live: m = the live candidate with the largest s, the LOWEST input index on a bit-equal tie;
+ *      keep_out[off + r] = m (an index into the CONCATENATED input), score_out[off + r] = s_m, ++r; m is no longer live.
+ *   3. Every j still live is decayed: ovr = tf_nms_f64's IoU in the same operation order (areas without +1,
+ *      inter / (a_m + a_j - inter); the file is compiled without FMA contraction, so these are the very bits the hard NMS compares).
+ *      inter == 0 or a NaN ovr: s_j unchanged.  TF_SOFT_NMS_LINEAR: if ovr > iou_thresh (strict, as the hard NMS) s_j = s_j * (1 - ovr).
+ *      TF_SOFT_NMS_GAUSSIAN: if ovr > 0, s_j = s_j * exp(-(ovr * ovr) / sigma) (iou_thresh is ignored).  Then j stays live iff
+ *      s_j >= score_thresh.
+ *   4. num_keep[s] = r.  Every factor is <= 1: the emitted scores never increase.  They are decayed PROBABILITIES (not logits).
+ * Rows r >= num_keep[s] of keep_out / score_out are NOT written, nothing outside [off[s], off[s] + num_keep[s]) is.  No atomics: the same
+ * bits on every run.  An unknown method or score mode, sigma that is not > 0, iou_thresh outside [0, 1], a negative or NaN score_thresh and
+ * bad segment tables (S outside 1..TF_NMS_MAX_SEGMENTS, offsets that do not start at 0 or descend) are TF_ERR_ARG.  n == 0 launches
+ * nothing and leaves num_keep as the caller zeroed it.  A segment longer than TF_SOFT_NMS_MAX_BOXES is TF_ERR_UNSUPPORTED (the selection
+ * of a segment runs inside one 1024-thread workgroup, one 64-candidate word per thread).  ws: tf_soft_nms_batched_workspace_bytes()
+ * (n_s^2 / 8 bytes of adjacency bits per segment plus the running scores; 0 for n == 0). */
+#define TF_SOFT_NMS_LINEAR   1
+#define TF_SOFT_NMS_GAUSSIAN 2
+#define TF_SOFT_NMS_MAX_BOXES 65536   /* largest segment (the hard NMS takes 524 160) */
+size_t tf_soft_nms_batched_workspace_bytes(const int32_t* host_seg_offsets, int num_segments);
+int tf_soft_nms_f64_batched(const double* boxes /*[n][4]*/, const double* scores /*[n]*/, const int32_t* host_seg_offsets /*[S+1]*/,
+                            int num_segments, int method, double iou_thresh, double sigma, double score_thresh,
+                            int score_mode /* TF_VOTE_WEIGHT_* */, int64_t* keep_out /*[n], indices into the concatenated input*/,
+                            double* score_out /*[n]*/, int32_t* num_keep /*device [S]*/, void* ws, size_t ws_bytes, void* stream);
+/* one segment: the batched form with S = 1, as tf_nms_f64 is of tf_nms_f64_batched */
+size_t tf_soft_nms_workspace_bytes(int n);
+int tf_soft_nms_f64(const double* boxes /*[n][4]*/, const double* scores /*[n]*/, int n, int method, double iou_thresh, double sigma,
+                    double score_thresh, int score_mode, int64_t* keep_out /*[n]*/, double* score_out /*[n]*/,
+                    int32_t* num_keep /*device [1]*/, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- score map -> boxes: sigmoid + threshold + ORDERED compaction + refinement ------
  * Replaces evaluation.py:61-78 + get_bboxes / regression_refinement
  * (tinyfaces/models/utils.py:4-100).  score [5nt][H][W] f32 (one image, NCHW).

@@ -17,6 +17,7 @@
 #   eval-table                 the same table for the configs[1] pyramid (per image)-> gpurun_out/eval_layer_table.{json,md}
 #   contention | floor | nms   the round-3 micro-benchmarks (scripts/contention.py, floor.py, nms_bench.py under the tracer)
 #   tta                        cost of the test-time augmentation: vote vs NMS kernels, pyramid with / without flip and voting (scripts/tta_numbers.py) -> $TTA_OUT (default profiles/tta.jsonl)
+#   soft-nms                   cost of Soft-NMS: kernels vs the hard NMS at 65 536 candidates, pyramid plain / linear / gaussian, parity (scripts/soft_nms_numbers.py) -> $SOFT_NMS_OUT (default profiles/soft_nms.jsonl)
 #   dist-smoke                 RCCL 1-rank group, 2 gloo ranks on one GPU, 2 nccl ranks on one GPU (expected refusal) -> gpurun_out/dist_smoke.txt
 #   final                      tests + bench + prof + pmc-traffic + layer-table + timeline + eval prof + smoke: the artefacts of a round
 set -u
@@ -90,6 +91,12 @@ print(d['value'], d['ms_per_step'], 'frac', r.get('frac'), 'fwd', r.get('forward
     timeout -k 10 ${TTA_TIMEOUT:-300} python scripts/tta_numbers.py --step kernels > "$out" 2> "$err" &&
       timeout -k 10 ${TTA_TIMEOUT:-300} python scripts/tta_numbers.py --step pyramid >> "$out" 2>> "$err"
     echo "tta exit $?"; cat "$out"; tail -3 "$err" ;;
+  soft-nms)   # one process and one time limit per step; a step only behind a clean one before it
+    out=${SOFT_NMS_OUT:-$R/profiles/soft_nms.jsonl}; err=${out%.jsonl}.err; par=${out%.jsonl}_parity.txt
+    timeout -k 10 ${SOFT_NMS_TIMEOUT:-300} python scripts/soft_nms_numbers.py --step kernels > "$out" 2> "$err" &&
+      timeout -k 10 ${SOFT_NMS_TIMEOUT:-300} python scripts/soft_nms_numbers.py --step pyramid >> "$out" 2>> "$err" &&
+      timeout -k 10 ${SOFT_NMS_TIMEOUT:-300} python scripts/soft_nms_numbers.py --step parity > "$par" 2>> "$err"
+    echo "soft-nms exit $?"; cat "$out"; tail -3 "$err" ;;
   dist-smoke) bash scripts/gpu_dist_smoke.sh ;;
   final)
     # the profile passes FIRST: bench.py quotes the committed kernel-stats / PMC files, so they are refreshed in the box's copy of profiles/
@@ -103,5 +110,5 @@ print(d['value'], d['ms_per_step'], 'frac', r.get('frac'), 'fwd', r.get('forward
     bash "$0" layer-table; bash "$0" timeline; bash "$0" prof eval; bash "$0" eval-table
     python scripts/gridbar.py 2>&1 | grep -v amdgpu.ids > "$R/gpurun_out/gridbar.txt"; tail -5 "$R/gpurun_out/gridbar.txt"
     timeout 200 python __graft_entry__.py smoke 2>&1 | tail -2 ;;
-  *) sed -n 2,22p "$0" ;;
+  *) sed -n 2,23p "$0" ;;
 esac

@@ -70,6 +70,38 @@ def tta_arguments(argv=None):
     return args
 
 
+SOFT_NMS_HELP = ("--soft-nms {linear,gaussian}: Soft-NMS instead of the hard NMS -- an overlapped candidate is decayed (linear: by 1 - IoU above "
+                 "--nms_thresh; gaussian: by exp(-IoU^2 / S) with --soft-nms-sigma S) and kept while its score stays >= --soft-nms-score-thresh T; "
+                 "the scores written are the decayed probabilities")
+
+
+def _positive(text):
+    v = float(text)
+    if not v > 0.0:
+        raise argparse.ArgumentTypeError(f"--soft-nms-sigma {text}: the gaussian decay needs sigma > 0")
+    return v
+
+
+def _non_negative(text):
+    v = float(text)
+    if not v >= 0.0:
+        raise argparse.ArgumentTypeError(f"--soft-nms-score-thresh {text}: the score threshold is >= 0")
+    return v
+
+
+def soft_nms_arguments(argv=None):
+    """`tta_arguments` plus `soft_nms` / `soft_nms_sigma` / `soft_nms_score_thresh` from --soft-nms / --soft-nms-sigma / --soft-nms-score-thresh,
+    parsed apart in the same way."""
+    parser = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    parser.add_argument("--soft-nms", dest="soft_nms", choices=["linear", "gaussian"], default=None, help=SOFT_NMS_HELP)
+    parser.add_argument("--soft-nms-sigma", dest="soft_nms_sigma", type=_positive, default=0.5, metavar="S", help=SOFT_NMS_HELP)
+    parser.add_argument("--soft-nms-score-thresh", dest="soft_nms_score_thresh", type=_non_negative, default=0.001, metavar="T", help=SOFT_NMS_HELP)
+    known, rest = parser.parse_known_args(argv)
+    args = tta_arguments(rest)
+    args.soft_nms, args.soft_nms_sigma, args.soft_nms_score_thresh = known.soft_nms, known.soft_nms_sigma, known.soft_nms_score_thresh
+    return args
+
+
 def dataloader(args):
     """evaluate_model.py:34-45."""
     tf = transforms.Compose([transforms.ToTensor(), transforms.Normalize([0.485, 0.456, 0.406], [0.229, 0.224, 0.225])])
@@ -79,14 +111,16 @@ def dataloader(args):
 
 
 def run(model, val_loader, templates, prob_thresh, nms_thresh, device, split, results_dir=None, debug=False, mask_axis="w",
-        flip=False, box_voting=None):
+        flip=False, box_voting=None, soft_nms=None, soft_nms_sigma=0.5, soft_nms_score_thresh=0.001):
     """evaluate_model.py:48-68, statement for statement: `img[0]` / `filename[0]` undo the batch axis the loader adds.  The
     only addition is the keyword that builds the pyramid levels on the GPU (same detections bit for bit).
-    flip / box_voting: get_detections' test-time augmentation, off by default."""
+    flip / box_voting: get_detections' test-time augmentation, off by default.  soft_nms / soft_nms_sigma / soft_nms_score_thresh:
+    get_detections' Soft-NMS, off by default."""
     dets = None
     for _, (img, filename) in enumerate(val_loader):
         dets = get_detections(model, img[0], templates, val_loader.dataset.rf, val_loader.dataset.transforms, prob_thresh, nms_thresh,
-                              device=device, pyramid_on_gpu=True, mask_axis=mask_axis, flip=flip, box_voting=box_voting)
+                              device=device, pyramid_on_gpu=True, mask_axis=mask_axis, flip=flip, box_voting=box_voting,
+                              soft_nms=soft_nms, soft_nms_sigma=soft_nms_sigma, soft_nms_score_thresh=soft_nms_score_thresh)
         write_results(dets, filename[0], split, results_dir)
         if debug:
             print(f"{filename[0]}: {dets.shape[0]} detections")
@@ -94,7 +128,7 @@ def run(model, val_loader, templates, prob_thresh, nms_thresh, device, split, re
 
 
 def main():
-    args = tta_arguments()
+    args = soft_nms_arguments()
     if not torch.cuda.is_available():
         raise SystemExit("this build of the tiny-faces hot path runs on MI355X only (no CPU fallback)")
     # Multi-GPU evaluation = replicas only: under torchrun every rank takes a strided shard of the image list
@@ -111,7 +145,8 @@ def main():
     model = model.to(device).eval()
     with torch.no_grad(), model.constant_weights():          # the checkpoint does not change between images: pack the weights once
         run(model, val_loader, templates, args.prob_thresh, args.nms_thresh, device, args.split, results_dir=args.results_dir,
-            debug=args.debug or args.dataset == "synthetic", mask_axis=args.mask_axis, flip=args.flip, box_voting=args.box_voting)
+            debug=args.debug or args.dataset == "synthetic", mask_axis=args.mask_axis, flip=args.flip, box_voting=args.box_voting,
+            soft_nms=args.soft_nms, soft_nms_sigma=args.soft_nms_sigma, soft_nms_score_thresh=args.soft_nms_score_thresh)
     if distributed:
         torch.distributed.barrier()
         if parallel.rank() == 0:

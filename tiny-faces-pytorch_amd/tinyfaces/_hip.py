@@ -111,6 +111,10 @@ _SIGNATURES = {
     "tf_box_vote_f64": (i32, [vp, vp, i32, vp, vp, f64, i32, vp, vp, vp]),
     "tf_box_vote_f64_batched": (i32, [vp, vp, C.POINTER(i32), i32, vp, vp, f64, i32, vp, vp, vp]),
     "tf_boxes_unflip_f64": (i32, [vp, vp, vp, i32, f64, vp]),
+    "tf_soft_nms_workspace_bytes": (sz, [i32]),
+    "tf_soft_nms_f64": (i32, [vp, vp, i32, i32, f64, f64, f64, i32, vp, vp, vp, vp, sz, vp]),
+    "tf_soft_nms_batched_workspace_bytes": (sz, [C.POINTER(i32), i32]),
+    "tf_soft_nms_f64_batched": (i32, [vp, vp, C.POINTER(i32), i32, i32, f64, f64, f64, i32, vp, vp, vp, vp, sz, vp]),
     "tf_criterion_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "tf_criterion_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, f32, vp, vp, u64, vp, vp, vp, vp, vp, sz, vp]),
     "tf_image_prepare": (i32, [C.POINTER(ImagePrepareArgs), vp]),

@@ -118,8 +118,30 @@ def _decode_image(model, levels, flip, *args):
     _decode_levels(model, levels[half:], *args, mirrored=True)
 
 
+def _check_soft_nms(soft_nms, nms_thresh, sigma, score_thresh):
+    """The keywords of get_detections / get_detections_batch, refused before the model runs."""
+    if soft_nms is None:
+        return
+    if soft_nms not in ops.SOFT_NMS_METHODS:
+        raise ValueError(f"soft_nms={soft_nms!r}: expected None or one of {sorted(ops.SOFT_NMS_METHODS)}")
+    ops._soft_nms_mode(soft_nms, nms_thresh if soft_nms == "linear" else 0.0, sigma, score_thresh, "sigmoid")
+
+
+def _soft_nms_rows(cand, offs, method, nms_thresh, sigma, score_thresh, box_voting):
+    """Soft-NMS over the segments `offs` of the device candidate list (rows x1, y1, x2, y2, logit) -> ([keep], [(K_s, 5) device rows]):
+    cand[keep] in selection order, or the voted rows, with the decayed probability in column 4.  One synchronisation."""
+    boxes, scores = cand[:, :4].contiguous(), cand[:, 4].contiguous()
+    thr = nms_thresh if method == "linear" else 0.0             # the gaussian method ignores it
+    if box_voting is not None:
+        res, rows = ops.soft_nms_batched(boxes, scores, offs, method, thr, sigma, score_thresh, vote=(box_voting, "sigmoid"))
+        return [k for k, _ in res], rows
+    res = ops.soft_nms_batched(boxes, scores, offs, method, thr, sigma, score_thresh)
+    return [k for k, _ in res], [torch.cat([boxes[k], ks.unsqueeze(1)], dim=1) for k, ks in res]
+
+
 def get_detections(model, img, templates, rf, img_transforms, prob_thresh=0.65, nms_thresh=0.3, scales=(-2, -1, 0, 1),
-                   device=None, mask_axis="w", return_candidates=False, pyramid_on_gpu=False, flip=False, box_voting=None):
+                   device=None, mask_axis="w", return_candidates=False, pyramid_on_gpu=False, flip=False, box_voting=None,
+                   soft_nms=None, soft_nms_sigma=0.5, soft_nms_score_thresh=0.001):
     """evaluation.py:20-87.  Returns (K,5) float64: the reference's (K,4) rows in the same order
     with the score re-attached as column 4 (defect D2: the reference drops it although
     write_results reads x[4], evaluation.py:111).  mask_axis='w' reproduces defect D1
@@ -131,10 +153,16 @@ def get_detections(model, img, templates, rf, img_transforms, prob_thresh=0.65, 
     flip=True: every pyramid level is also run mirrored left-right and its candidates, mirrored back, follow those of the unmirrored
     levels in the candidate list; the one NMS runs over the union.
     box_voting=t: every NMS survivor is replaced by the sigmoid-weighted mean of all candidates with IoU >= t (`ops.box_voting`:
-    Detectron's box_voting, scoring ID -- the candidates' scores are logits); the rows returned are the voted rows in keep order."""
+    Detectron's box_voting, scoring ID -- the candidates' scores are logits); the rows returned are the voted rows in keep order.
+    soft_nms="linear" | "gaussian" (an addition as well; None: the hard NMS above, the same launches and rows): Soft-NMS (`ops.soft_nms`)
+    instead of the hard NMS -- an overlapped candidate is decayed, not dropped, and survives while its score stays >= soft_nms_score_thresh.
+    nms_thresh is the linear method's IoU threshold, soft_nms_sigma the gaussian method's (which ignores nms_thresh).  The rows are
+    cand[keep] in selection order with column 4 replaced by the DECAYED PROBABILITY (not a logit); with box_voting the voted rows, column 4
+    likewise; return_candidates returns that keep."""
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
         raise RuntimeError("get_detections: the detector only runs on MI355X (no CPU fallback)")
+    _check_soft_nms(soft_nms, nms_thresh, soft_nms_sigma, soft_nms_score_thresh)
     model = _on_device(model, device)
     model.eval()
     nt = templates.shape[0]
@@ -152,7 +180,13 @@ def get_detections(model, img, templates, rf, img_transforms, prob_thresh=0.65, 
         raise RuntimeError(f"get_detections: {n} candidates above prob_thresh={prob_thresh} exceed the {ops.NMS_MAX_BOXES} boxes one NMS call "
                            "takes (64 KiB of LDS for the suppression bitmap); a trained detector keeps a few thousand -- untrained weights?")
     cand = dets[:n]
-    if box_voting is None:
+    if soft_nms is not None:
+        if n > ops.SOFT_NMS_MAX_BOXES:
+            raise RuntimeError(f"get_detections: {n} candidates above prob_thresh={prob_thresh} exceed the {ops.SOFT_NMS_MAX_BOXES} boxes one "
+                               f"Soft-NMS call takes (the hard NMS takes {ops.NMS_MAX_BOXES}): raise prob_thresh or use soft_nms=None")
+        keep, rows = _soft_nms_rows(cand, [0, n], soft_nms, nms_thresh, soft_nms_sigma, soft_nms_score_thresh, box_voting)
+        keep, result = keep[0], rows[0].cpu().numpy()
+    elif box_voting is None:
         keep = ops.nms(cand[:, :4].contiguous(), cand[:, 4].contiguous(), nms_thresh)      # :80-84
         result = cand[keep].cpu().numpy()
     else:
@@ -165,15 +199,18 @@ def get_detections(model, img, templates, rf, img_transforms, prob_thresh=0.65, 
 
 
 def get_detections_batch(model, imgs, templates, rf, img_transforms, prob_thresh=0.65, nms_thresh=0.3, scales=(-2, -1, 0, 1),
-                         device=None, mask_axis="w", pyramid_on_gpu=False, flip=False, box_voting=None):
+                         device=None, mask_axis="w", pyramid_on_gpu=False, flip=False, box_voting=None,
+                         soft_nms=None, soft_nms_sigma=0.5, soft_nms_score_thresh=0.001):
     """`[get_detections(model, img, ...) for img in imgs]` (evaluation.py:20-87 once per image, as evaluate_model.py:60-68 does) with
     the per-image NMS calls batched: every image's multi-scale candidates go into ONE device list, the per-image segments are
     suppressed by ONE tf_nms_f64_batched call (three launches whatever the number of images; BASELINE.json configs[4]) and the
     only host synchronisation of the whole batch is the read of the candidate counts.  Row for row identical to the loop.
-    flip / box_voting: as in get_detections; an image's mirrored candidates follow its unmirrored ones, so its segment stays contiguous."""
+    flip / box_voting: as in get_detections; an image's mirrored candidates follow its unmirrored ones, so its segment stays contiguous.
+    soft_nms / soft_nms_sigma / soft_nms_score_thresh: as in get_detections, one tf_soft_nms_f64_batched call over the per-image segments."""
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
         raise RuntimeError("get_detections_batch: the detector only runs on MI355X (no CPU fallback)")
+    _check_soft_nms(soft_nms, nms_thresh, soft_nms_sigma, soft_nms_score_thresh)
     imgs = list(imgs)
     if not 1 <= len(imgs) <= ops.NMS_MAX_SEGMENTS:
         raise ValueError(f"get_detections_batch: 1..{ops.NMS_MAX_SEGMENTS} images per call, got {len(imgs)}")
@@ -194,6 +231,13 @@ def get_detections_batch(model, imgs, templates, rf, img_transforms, prob_thresh
     if max(b - a for a, b in zip(offs, offs[1:])) > ops.NMS_MAX_BOXES:
         raise RuntimeError(f"get_detections_batch: an image has more than {ops.NMS_MAX_BOXES} candidates above prob_thresh={prob_thresh}")
     cand = dets[:offs[-1]]
+    if soft_nms is not None:
+        longest = max(b - a for a, b in zip(offs, offs[1:]))
+        if longest > ops.SOFT_NMS_MAX_BOXES:
+            raise RuntimeError(f"get_detections_batch: an image has {longest} candidates above prob_thresh={prob_thresh}, more than the "
+                               f"{ops.SOFT_NMS_MAX_BOXES} boxes one Soft-NMS call takes (the hard NMS takes {ops.NMS_MAX_BOXES})")
+        _, rows = _soft_nms_rows(cand, offs, soft_nms, nms_thresh, soft_nms_sigma, soft_nms_score_thresh, box_voting)
+        return [r.cpu().numpy() for r in rows]
     if box_voting is not None:
         _, voted = ops.nms_batched(cand[:, :4].contiguous(), cand[:, 4].contiguous(), offs, nms_thresh, vote=(box_voting, "sigmoid"))
         return [v.cpu().numpy() for v in voted]

@@ -313,6 +313,105 @@ def boxes_unflip_(dets, first, last, max_rows, c):
     return dets
 
 
+# --------------------------------------------------------------------------- Soft-NMS
+SOFT_NMS_METHODS = {"linear": 1, "gaussian": 2}           # TF_SOFT_NMS_* (include/tinyfaces_hip.h)
+SOFT_NMS_MAX_BOXES = 65536                                # TF_SOFT_NMS_MAX_BOXES: one segment is selected inside one 1024-thread workgroup
+
+
+def _soft_nms_mode(method, iou_threshold, sigma, score_threshold, score):
+    """The host-side refusals of tf_soft_nms_f64_batched, raised before anything is launched."""
+    if method not in SOFT_NMS_METHODS:
+        raise ValueError(f"soft_nms: method={method!r}, expected one of {sorted(SOFT_NMS_METHODS)}")
+    if score not in VOTE_WEIGHTS:
+        raise ValueError(f"soft_nms: score={score!r}, expected one of {sorted(VOTE_WEIGHTS)}")
+    t, sg, st = float(iou_threshold), float(sigma), float(score_threshold)
+    if not 0.0 <= t <= 1.0:
+        raise ValueError(f"soft_nms: iou_threshold={iou_threshold!r} is outside [0, 1]")
+    if not sg > 0.0:
+        raise ValueError(f"soft_nms: sigma={sigma!r} is not > 0")
+    if not st >= 0.0:
+        raise ValueError(f"soft_nms: score_threshold={score_threshold!r} is negative or NaN")
+    return SOFT_NMS_METHODS[method], t, sg, st, VOTE_WEIGHTS[score]
+
+
+def soft_nms(boxes, scores, method="linear", iou_threshold=0.3, sigma=0.5, score_threshold=0.001, score="sigmoid"):
+    """Soft-NMS (Bodla et al., ICCV 2017; Detectron's soft_nms) on float64 device tensors, tf_soft_nms_f64: the best live candidate is
+    selected, every live candidate that overlaps it is decayed -- "linear": s *= 1 - IoU where IoU > iou_threshold; "gaussian":
+    s *= exp(-IoU^2 / sigma) where IoU > 0 --, the list is re-ranked, and a candidate lives while s >= score_threshold.
+    score: "sigmoid" (s = 1 / (1 + exp(-score)): decode_compact's scores are logits) or "score" (s = score as given).
+    Returns (keep int64 (K,), kept_scores float64 (K,)) in selection order: the decayed probabilities, non-increasing."""
+    require_gpu(boxes, "soft_nms")
+    res = soft_nms_batched(boxes, scores, [0, int(boxes.shape[0])], method, iou_threshold, sigma, score_threshold, score)
+    return res[0]
+
+
+def soft_nms_batched(boxes, scores, seg_offsets, method="linear", iou_threshold=0.3, sigma=0.5, score_threshold=0.001, score="sigmoid",
+                     mask_budget_bytes=None, vote=None):
+    """`soft_nms` per segment [seg_offsets[s], seg_offsets[s+1]) in one tf_soft_nms_f64_batched call per group of consecutive segments whose
+    adjacency bit matrices (n_s^2 / 8 bytes each) fit `mask_budget_bytes` (default NMS_MASK_BUDGET_BYTES), exactly as `nms_batched` groups.
+    Returns a list of S (keep, kept_scores): keep indexes the CONCATENATED input.
+    vote = (vote_thresh, weight): `box_voting_batched` is enqueued behind the selection on its device-side keep list and counts, before the
+    one synchronisation; the vote's weights and membership use the candidates' ORIGINAL scores, column 4 of a voted row is the Soft-NMS
+    score.  Returns (the list above, [(K_s, 5) voted rows in selection order])."""
+    require_gpu(boxes, "soft_nms_batched")
+    require_gpu(scores, "soft_nms_batched")
+    mode = _soft_nms_mode(method, iou_threshold, sigma, score_threshold, score)
+    if vote is not None:
+        _vote_mode(vote[0], vote[1])
+    offs = [int(o) for o in seg_offsets]
+    S = len(offs) - 1
+    if S < 1 or S > NMS_MAX_SEGMENTS or offs[0] != 0 or any(b < a for a, b in zip(offs, offs[1:])) or offs[-1] != boxes.shape[0]:
+        raise ValueError(f"soft_nms_batched: bad segment offsets {offs[:4]}... for {boxes.shape[0]} boxes (1..{NMS_MAX_SEGMENTS} segments)")
+    longest = max(b - a for a, b in zip(offs, offs[1:]))
+    if longest > SOFT_NMS_MAX_BOXES:
+        raise RuntimeError(f"soft_nms_batched: a segment of {longest} boxes exceeds the {SOFT_NMS_MAX_BOXES} one Soft-NMS selection takes "
+                           f"(TF_SOFT_NMS_MAX_BOXES; the hard NMS takes {NMS_MAX_BOXES})")
+    budget = NMS_MASK_BUDGET_BYTES if mask_budget_bytes is None else int(mask_budget_bytes)
+    sizes = [_mask_bytes(b - a) for a, b in zip(offs, offs[1:])]
+    boxes = boxes.to(torch.float64).contiguous()
+    scores = scores.to(torch.float64).contiguous()
+    # the calls of every group are enqueued first; the counts are read afterwards: one synchronisation whatever the number of groups
+    calls, first, acc = [], 0, 0
+    for s in range(S + 1):
+        if s == S or (s > first and acc + sizes[s] > budget):
+            a = offs[first]
+            calls.append((first, s, _soft_nms_call(boxes[a:offs[s]], scores[a:offs[s]], [o - a for o in offs[first:s + 1]], mode, vote)))
+            first, acc = s, 0
+        if s < S:
+            acc += sizes[s]
+    res, rows = [], []
+    for first, last, (keep, kept, cnt, voted) in calls:
+        counts, a = cnt.tolist(), offs[first]
+        for s in range(first, last):
+            lo, c = offs[s] - a, counts[s - first]
+            k = keep[lo: lo + c]
+            res.append((k + a if a else k, kept[lo: lo + c]))         # indices into the caller's concatenated input
+            if voted is not None:
+                rows.append(voted[lo: lo + c])
+    return res if vote is None else (res, rows)
+
+
+def _soft_nms_call(boxes, scores, offs, mode, vote):
+    """One tf_soft_nms_f64_batched call [+ the chained vote] on contiguous float64 operands; nothing is synchronised.  Returns the raw
+    (keep (n,), kept scores (n,), counts (S,), voted rows (n, 5) or None): only the first counts[s] rows of a segment are written."""
+    method, t, sigma, st, smode = mode
+    S, n, dev = len(offs) - 1, offs[-1], boxes.device
+    keep = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    kept = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+    cnt = torch.zeros(S, dtype=torch.int32, device=dev)
+    host = (C.c_int32 * (S + 1))(*offs)
+    wsb = lib().tf_soft_nms_batched_workspace_bytes(host, S)
+    ws = _workspace("soft_nms", wsb, dev)
+    with torch.cuda.device(dev):
+        check(lib().tf_soft_nms_f64_batched(ptr(boxes), ptr(scores), host, S, method, t, sigma, st, smode, ptr(keep), ptr(kept), ptr(cnt),
+                                            ptr(ws), wsb, stream()), "tf_soft_nms_f64_batched")
+    voted = None
+    if vote is not None:
+        voted = _box_vote_launch(boxes, scores, host, S, keep, cnt, vote[0], vote[1])[0]
+        voted[:, 4] = kept                                    # the vote kernel wrote the original score there; rows >= counts[s] hold nothing either way
+    return keep, kept, cnt, voted
+
+
 # --------------------------------------------------------------------------- decode
 def template_masks(templates, scale, width, mask_axis="w"):
     """Validity masks reproducing tinyfaces/models/utils.py:17-44.  mask_axis='w' is the
