@@ -193,6 +193,26 @@ int tf_criterion_fwd_bwd(const float* output, float* class_map, const float* reg
                          float* label_out, float* grad_out, double* loss_out /*[2]*/,
                          int32_t* counts_out /*[B][2] or NULL*/, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- detection criterion, focal form: sigmoid focal loss over EVERY labelled element + SmoothL1 over every positive ----
+ * No OHEM, no sampling, no RNG; class_map (labels +1 / -1 / 0 = ignore) is only read.  Same layout as tf_criterion_fwd_bwd.
+ * With s the class logit, x = y s, softplus(v) = max(v, 0) + log1p(exp(-|v|)) and a_t = alpha (y = +1), 1 - alpha (y = -1), or 1 when
+ * alpha < 0 (torchvision's sigmoid_focal_loss convention):
+ *   FL     = a_t exp(-gamma softplus(x)) softplus(-x)                  ( = -a_t (1 - p_t)^gamma log p_t )
+ *   dFL/ds = -y a_t exp(-gamma softplus(x)) (gamma sigmoid(x) softplus(-x) + sigmoid(-x))
+ * Regression: SmoothL1 (beta = 1) over the four channels of every y = +1 element, gradient times reg_weight.
+ * normalize = TF_FOCAL_NORM_POS: both sums and all five gradient channels of image b are multiplied by 1 / max(1, npos_b), npos_b = its
+ * number of +1 labels, and the images are SUMMED (an image's loss does not depend on its batch); TF_FOCAL_NORM_NONE: the plain sum.
+ * loss_out[0] = sum cls, loss_out[1] = sum reg (unweighted), both normalised as above; npos_out[b] = npos_b.  grad_out is written
+ * completely (no memset needed).  No floating-point atomics: the same bits on every run.  TF_ERR_ARG: a NULL operand, a non-positive
+ * dimension, gamma negative or not finite, alpha not finite or > 1, an unknown normalize. */
+#define TF_FOCAL_NORM_NONE 0
+#define TF_FOCAL_NORM_POS  1
+size_t tf_criterion_focal_workspace_bytes(int B, int nt, int H, int W);
+int tf_criterion_focal_fwd_bwd(const float* output, const float* class_map, const float* reg_map, int B, int nt, int H, int W,
+                               float gamma, float alpha, int normalize, float reg_weight,
+                               float* grad_out, double* loss_out /*[2]*/, int32_t* npos_out /*[B], may be NULL*/,
+                               void* ws, size_t ws_bytes, void* stream);
+
 /* ---- fused SGD step (momentum, weight decay) over a flat fp32 segment ---------------
  * Replaces torch.optim.SGD.step as configured at main.py:67-70 for one parameter group. */
 int tf_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n,

@@ -11,6 +11,9 @@
 //       a bitmap (one wave, counter RNG)
 //   K3  ordered rank of every label (ballot prefix), sampling decision, loss terms, gradient;
 //       every element of grad_out is written exactly once (no memset needed)
+// Below them: the focal-loss form of the same pass (tf_criterion_focal_fwd_bwd), kernels F1-F3.
+#include <cmath>
+
 #include "common.h"
 
 namespace {
@@ -206,6 +209,169 @@ extern "C" int tf_criterion_fwd_bwd(const float* output, float* class_map, const
   hipLaunchKernelGGL(crit_ohem_count_kernel, grid, dim3(256), 0, stream, p);
   hipLaunchKernelGGL(crit_scan_sample_kernel, dim3(B), dim3(64), 0, stream, p);
   hipLaunchKernelGGL(crit_apply_kernel, grid, dim3(256), 0, stream, p);
+  TF_CHECK_LAUNCH();
+  return TF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- focal loss
+// Sigmoid focal loss (Lin et al. 2017; alpha as in torchvision's sigmoid_focal_loss) over EVERY labelled element + SmoothL1 over every
+// positive: no mining, no sampling, class_map is only read.  With x = y s:
+//   FL     = a_t exp(-gamma softplus(x)) softplus(-x)
+//   dFL/ds = -y a_t exp(-gamma softplus(x)) (gamma sigmoid(x) softplus(-x) + sigmoid(-x))
+// and, for normalize = 1, both sums and all five gradient channels of image b times 1 / max(1, npos_b); images are summed.
+//   F1  +1 labels of every block (ballot + popcount), one int per block, no atomics
+//   F2  the block adds its image's counts (the same order in every block), then labels, logits, loss terms and the gradient:
+//       every element of grad_out is written exactly once; one fp64 partial pair per block
+//   F3  one block: per image the partials in a fixed order, times the normaliser, then the images in index order
+namespace {
+
+struct FocalParams {
+  const float* out; const float* cls; const float* reg;
+  int B, E, nblk;
+  float gamma, alpha; int normalize; float reg_weight;
+  float* grad; double* loss; int* npos_out;
+  double* partial;        // [B][nblk][2]
+  int* blkpos;            // [B][nblk]
+};
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// the +1 labels of image b, from the per-block counts: every thread of the (256-thread) block returns the total
+__device__ __forceinline__ int focal_image_npos(const FocalParams& p, int b, int* wn /*[4], shared*/) {
+  int n = 0;
+  for (int i = threadIdx.x; i < p.nblk; i += 256) n += p.blkpos[(size_t)b * p.nblk + i];
+  n = wave_sum_int(n);
+  if ((threadIdx.x & 63) == 0) wn[threadIdx.x >> 6] = n;
+  __syncthreads();
+  return wn[0] + wn[1] + wn[2] + wn[3];
+}
+
+__global__ void __launch_bounds__(256) focal_count_kernel(FocalParams p) {
+  const int b = blockIdx.y, blk = blockIdx.x;
+  __shared__ int wn[4];
+  int n = 0;
+#pragma unroll
+  for (int k = 0; k < EPB / 256; ++k) {
+    const int e = blk * EPB + k * 256 + threadIdx.x;
+    const bool isp = e < p.E && p.cls[(size_t)b * p.E + e] == 1.f;
+    n += __popcll(__ballot(isp));
+  }
+  if ((threadIdx.x & 63) == 0) wn[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) p.blkpos[(size_t)b * p.nblk + blk] = wn[0] + wn[1] + wn[2] + wn[3];
+}
+
+__global__ void __launch_bounds__(256) focal_apply_kernel(FocalParams p) {
+  const int b = blockIdx.y, blk = blockIdx.x;
+  __shared__ int wn[4];
+  __shared__ double wloss[4][2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int npos = focal_image_npos(p, b, wn);
+  const float inv = p.normalize ? 1.f / (float)(npos > 1 ? npos : 1) : 1.f;
+  double lcls = 0.0, lreg = 0.0;
+#pragma unroll
+  for (int k = 0; k < EPB / 256; ++k) {
+    const int e = blk * EPB + k * 256 + threadIdx.x;
+    if (e < p.E) {
+      const float y = p.cls[(size_t)b * p.E + e];
+      const bool isp = y == 1.f, isn = y == -1.f;
+      const size_t oi = (size_t)b * 5 * p.E + e;
+      float g = 0.f;
+      if (isp || isn) {
+        const float s = p.out[oi];
+        const float x = isp ? s : -s;
+        const float ez = expf(-fabsf(x)), t = log1pf(ez);          // stable softplus: max(v, 0) + log1p(exp(-|v|))
+        const float sp_x = fmaxf(x, 0.f) + t, sp_mx = fmaxf(-x, 0.f) + t;
+        const float r = 1.f / (1.f + ez);
+        const float sg_x = x >= 0.f ? r : ez * r, sg_mx = x >= 0.f ? ez * r : r;
+        const float at = p.alpha < 0.f ? 1.f : (isp ? p.alpha : 1.f - p.alpha);
+        const float mod = at * expf(-p.gamma * sp_x);
+        lcls += (double)(mod * sp_mx);
+        g = (isp ? -inv : inv) * mod * (p.gamma * sg_x * sp_mx + sg_mx);
+      }
+      p.grad[oi] = g;
+#pragma unroll
+      for (int c = 1; c <= 4; ++c) {                                // tx | ty | tw | th blocks
+        const size_t ri = oi + (size_t)c * p.E;
+        float gr = 0.f;
+        if (isp) {
+          const float d = p.out[ri] - p.reg[(size_t)b * 4 * p.E + (size_t)(c - 1) * p.E + e];
+          const float ad = fabsf(d);
+          lreg += (double)(ad < 1.f ? 0.5f * d * d : ad - 0.5f);     // SmoothL1, beta = 1
+          gr = p.reg_weight * inv * (d < -1.f ? -1.f : (d > 1.f ? 1.f : d));
+        }
+        p.grad[ri] = gr;
+      }
+    }
+  }
+  lcls = tf::wave_sum(lcls); lreg = tf::wave_sum(lreg);
+  if (lane == 0) { wloss[wave][0] = lcls; wloss[wave][1] = lreg; }
+  __syncthreads();
+  if (threadIdx.x < 2)
+    p.partial[((size_t)b * p.nblk + blk) * 2 + threadIdx.x] = wloss[0][threadIdx.x] + wloss[1][threadIdx.x] + wloss[2][threadIdx.x] + wloss[3][threadIdx.x];
+}
+
+// one block of 256 threads
+__global__ void __launch_bounds__(256) focal_finish_kernel(FocalParams p) {
+  __shared__ int wn[4];
+  __shared__ double wloss[4][2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double total[2] = {0.0, 0.0};                                    // thread 0's
+  for (int b = 0; b < p.B; ++b) {
+    const int npos = focal_image_npos(p, b, wn);
+    double a0 = 0.0, a1 = 0.0;
+    for (int i = threadIdx.x; i < p.nblk; i += 256) {
+      const double* q = p.partial + ((size_t)b * p.nblk + i) * 2;
+      a0 += q[0]; a1 += q[1];
+    }
+    a0 = tf::wave_sum(a0); a1 = tf::wave_sum(a1);
+    if (lane == 0) { wloss[wave][0] = a0; wloss[wave][1] = a1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const double norm = p.normalize ? 1.0 / (double)(npos > 1 ? npos : 1) : 1.0;
+      total[0] += (wloss[0][0] + wloss[1][0] + wloss[2][0] + wloss[3][0]) * norm;
+      total[1] += (wloss[0][1] + wloss[1][1] + wloss[2][1] + wloss[3][1]) * norm;
+      if (p.npos_out) p.npos_out[b] = npos;
+    }
+    __syncthreads();                                               // wn / wloss are reused by the next image
+  }
+  if (threadIdx.x == 0) { p.loss[0] = total[0]; p.loss[1] = total[1]; }
+}
+
+}  // namespace
+
+extern "C" size_t tf_criterion_focal_workspace_bytes(int B, int nt, int H, int W) {
+  if (B <= 0 || nt <= 0 || H <= 0 || W <= 0) return 0;
+  const size_t E = (size_t)nt * H * W, nblk = (E + EPB - 1) / EPB;
+  return a256((size_t)B * nblk * 2 * sizeof(double)) + a256((size_t)B * nblk * sizeof(int));
+}
+
+extern "C" int tf_criterion_focal_fwd_bwd(const float* output, const float* class_map, const float* reg_map, int B, int nt, int H, int W,
+                                          float gamma, float alpha, int normalize, float reg_weight,
+                                          float* grad_out, double* loss_out, int32_t* npos_out,
+                                          void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!output || !class_map || !reg_map || !grad_out || !loss_out || B <= 0 || nt <= 0 || H <= 0 || W <= 0) return TF_ERR_ARG;
+  if (B > 65535 || (size_t)nt * H * W > ((size_t)1 << 30)) return TF_ERR_ARG;      // grid.y; element indices are ints
+  if (!(gamma >= 0.f) || !std::isfinite(gamma) || !std::isfinite(alpha) || alpha > 1.f) return TF_ERR_ARG;
+  if (normalize != 0 && normalize != 1) return TF_ERR_ARG;
+  if (!ws || ws_bytes < tf_criterion_focal_workspace_bytes(B, nt, H, W)) return TF_ERR_WORKSPACE;
+  FocalParams p;
+  p.out = output; p.cls = class_map; p.reg = reg_map; p.B = B;
+  p.E = nt * H * W; p.nblk = (p.E + EPB - 1) / EPB;
+  p.gamma = gamma; p.alpha = alpha; p.normalize = normalize; p.reg_weight = reg_weight;
+  p.grad = grad_out; p.loss = loss_out; p.npos_out = npos_out;
+  char* w = (char*)ws;
+  p.partial = (double*)w;        w += a256((size_t)B * p.nblk * 2 * sizeof(double));
+  p.blkpos = (int*)w;
+  dim3 grid(p.nblk, B);
+  hipLaunchKernelGGL(focal_count_kernel, grid, dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(focal_apply_kernel, grid, dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(256), 0, stream, p);
   TF_CHECK_LAUNCH();
   return TF_OK;
 }

@@ -8,6 +8,7 @@ Additions (existing flags keep their names and defaults): --fused / --no-fused (
 autograd), --dtype bf16|fp32, --synthetic-len.  The schedule is the reference's: SGD(momentum, weight decay), StepLR(20),
 a checkpoint every --save-every epochs (main.py:39-104)."""
 import argparse
+import math
 import os
 from pathlib import Path
 
@@ -96,6 +97,27 @@ ACCUM_AVERAGE_HELP = ("--accum-average: apply the MEAN of the accumulated gradie
                       "reference's loss is a sum over the batch, so the sum is what a batch N times as large gives), default off")
 
 
+FOCAL_HELP = ("--cls-loss {soft-margin,focal}: classification loss of the criterion; focal = sigmoid focal loss (Lin et al. 2017) over every "
+              "labelled anchor and SmoothL1 over every positive, with no OHEM and no 256-sample draw (--ohem-thresh is unused), default soft-margin; "
+              "--focal-gamma G: its focusing exponent, G >= 0, default 2; --focal-alpha A: weight A on positives and 1 - A on negatives, A <= 1, "
+              "negative = no weighting, default 0.25; --focal-normalize {pos,none}: pos divides every image's loss by max(1, its positives) "
+              "before the images are summed, none leaves the plain sum, default pos")
+
+
+def _focal_gamma(text):
+    value = float(text)
+    if not (math.isfinite(value) and value >= 0.0):
+        raise argparse.ArgumentTypeError(f"must be a finite number >= 0, got {text}")
+    return value
+
+
+def _focal_alpha(text):
+    value = float(text)
+    if not (math.isfinite(value) and value <= 1.0):
+        raise argparse.ArgumentTypeError(f"must be a finite number <= 1 (negative: no weighting), got {text}")
+    return value
+
+
 def _accum_steps(text):
     value = int(text)
     if value < 1:
@@ -119,7 +141,7 @@ def _positive_float(text):
 
 
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP)))
+    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP)))
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
@@ -128,7 +150,8 @@ def arguments(argv=None):
 def trunk_arguments(argv=None):
     """`arguments` plus `base_model` from --base-model, `freeze_bn` from --freeze-bn, `trainable_layers` from --trainable-layers, `clip_grad_norm`
     from --clip-grad-norm, `skip_nonfinite` from --skip-nonfinite, `model_ema` from --model-ema, `accum_steps` from --accum-steps and `accum_average`
-    from --accum-average.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
+    from --accum-average, `cls_loss` ("soft_margin" | "focal") from --cls-loss, `focal_gamma`, `focal_alpha` and `focal_normalize` from
+    --focal-gamma, --focal-alpha and --focal-normalize.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
     options and the additions above."""
     parser = argparse.ArgumentParser(add_help=False)
     parser.add_argument("--base-model", dest="base_model", default="resnet101", choices=list(model_zoo.TRUNKS), help=TRUNK_HELP)
@@ -139,6 +162,10 @@ def trunk_arguments(argv=None):
     parser.add_argument("--model-ema", dest="model_ema", default=None, type=_ema_decay, metavar="DECAY", help=EMA_HELP)
     parser.add_argument("--accum-steps", dest="accum_steps", default=1, type=_accum_steps, metavar="N", help=ACCUM_HELP)
     parser.add_argument("--accum-average", dest="accum_average", action="store_true", help=ACCUM_AVERAGE_HELP)
+    parser.add_argument("--cls-loss", dest="cls_loss", default="soft-margin", choices=["soft-margin", "focal"], help=FOCAL_HELP)
+    parser.add_argument("--focal-gamma", dest="focal_gamma", default=2.0, type=_focal_gamma, metavar="G", help=FOCAL_HELP)
+    parser.add_argument("--focal-alpha", dest="focal_alpha", default=0.25, type=_focal_alpha, metavar="A", help=FOCAL_HELP)
+    parser.add_argument("--focal-normalize", dest="focal_normalize", default="pos", choices=["pos", "none"], help=FOCAL_HELP)
     known, rest = parser.parse_known_args(argv)
     if known.trainable_layers < 4 and not known.freeze_bn:
         parser.error(f"--trainable-layers {known.trainable_layers} freezes stages of the trunk, which is defined on frozen BatchNorm only: add --freeze-bn")
@@ -151,7 +178,20 @@ def trunk_arguments(argv=None):
     args.model_ema = known.model_ema
     args.accum_steps = known.accum_steps
     args.accum_average = known.accum_average
+    args.cls_loss = known.cls_loss.replace("-", "_")
+    args.focal_gamma = known.focal_gamma
+    args.focal_alpha = known.focal_alpha
+    args.focal_normalize = known.focal_normalize
     return args
+
+
+def loss_description(args):
+    """The criterion's classification loss as the start-up line prints it."""
+    if args.cls_loss != "focal":
+        return f"classification loss soft-margin (OHEM threshold {args.ohem_thresh:g}, 128 + 128 samples per image)"
+    alpha = f"alpha {args.focal_alpha:g}" if args.focal_alpha >= 0 else "no alpha weighting"
+    norm = "per image by its positives" if args.focal_normalize == "pos" else "not normalised"
+    return f"classification loss focal (gamma {args.focal_gamma:g}, {alpha}, {norm}; every labelled anchor, every positive regresses)"
 
 
 def lr_at(base_lr, epoch):
@@ -205,8 +245,13 @@ def main():
               f"{args.trainable_layers} of 4 ({len(model.trainable_parameter_names())} trained tensors)")
         print(f"effective batch {args.batch_size * args.accum_steps * parallel.world_size()} = batch_size {args.batch_size} x accum-steps "
               f"{args.accum_steps} x world {parallel.world_size()}" + (", gradients averaged over the window" if args.accum_average and args.accum_steps > 1 else ""))
-    loss_fn = DetectionCriterion(NUM_TEMPLATES, seed=args.seed * parallel.world_size() + parallel.rank(), lazy_meters=True)
+    loss_fn = DetectionCriterion(NUM_TEMPLATES, seed=args.seed * parallel.world_size() + parallel.rank(), lazy_meters=True, cls_loss=args.cls_loss,
+                                 focal_gamma=args.focal_gamma, focal_alpha=args.focal_alpha, focal_normalize=args.focal_normalize)
     loss_fn.ohem_thresh = args.ohem_thresh
+    if parallel.rank() == 0:
+        print(loss_description(args))
+        if args.cls_loss == "focal":
+            print("--ohem-thresh is unused with --cls-loss focal: nothing is mined or sampled")
 
     first_epoch = args.start_epoch
     state = None

@@ -617,7 +617,7 @@ class TrainEngine:
         ops.grad_accumulate(self._accum, gflat, segs, mode)
 
     def step(self, x, class_map, regression_map, apply=None):
-        """x (B,3,H,W) f32, class_map (B,nt,h,w) f32 (mined in place), regression_map (B,4nt,h,w) f32: all on the device.
+        """x (B,3,H,W) f32, class_map (B,nt,h,w) f32 (mined in place by the soft-margin criterion; only read with cls_loss="focal"), regression_map (B,4nt,h,w) f32: all on the device.
         Returns the device tensor [sum cls loss, sum reg loss] (float64) without synchronising.
         The step follows the model's BatchNorm mode (DetectionModel.freeze_batchnorm): frozen, the forward and backward run the folded-BN
         graph, and the update skips the BatchNorm vectors (no weight decay, no momentum: their momentum buffers stay zero) and, with
@@ -634,8 +634,7 @@ class TrainEngine:
         m._check_partial_freeze()
         m._sync_tables(x.device)
         out = m._run_forward(x, training=True)
-        loss2, grad, _ = ops.criterion_fwd_bwd(out, class_map, regression_map, c.n_templates, c.reg_weight, c.ohem_thresh, c.max_pos,
-                                               c.max_neg, c._pos_keep, c._neg_keep, c._next_seed())
+        loss2, grad, _ = c._fwd_bwd(out, class_map, regression_map)
         if self._native is not None:         # (bench.py measures a step without the exchange: the C hook is simply not installed for it)
             m._grad_callback = None if self.skip_allreduce else C.cast(lib().tf_comm_allreduce_hook, C.c_void_p)
             self._native["plan"].issued, self._native["plan"].rc = 0, 0       # a step that raised half-way must not poison the next one

@@ -1,6 +1,8 @@
 """DetectionCriterion -- call surface of the reference's tinyfaces/models/loss.py:7-97, computed by
 one fused HIP pass (csrc/criterion.hip): OHEM, balance sampling, masked SoftMargin + SmoothL1 sums
-and d(total)/d(output), with no device->host->device round trip (loss.py:47-57 does one per step)."""
+and d(total)/d(output), with no device->host->device round trip (loss.py:47-57 does one per step).
+`cls_loss="focal"` is the one addition to that surface: sigmoid focal loss over every labelled anchor, no mining and no sampling, by the
+focal form of the same pass (tf_criterion_focal_fwd_bwd)."""
 import torch
 from torch import nn
 
@@ -30,9 +32,7 @@ class AvgMeter:
 class _CriterionFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, output, owner, class_map, regression_map):
-        loss2, grad, labels = ops.criterion_fwd_bwd(
-            output.detach(), class_map, regression_map, owner.n_templates, owner.reg_weight, owner.ohem_thresh,
-            owner.max_pos, owner.max_neg, owner._pos_keep, owner._neg_keep, owner._next_seed(), want_labels=owner.keep_labels)
+        loss2, grad, labels = owner._fwd_bwd(output.detach(), class_map, regression_map, want_labels=owner.keep_labels)
         ctx.save_for_backward(grad)
         owner._loss2 = loss2
         owner.sampled_class_map = labels
@@ -49,10 +49,24 @@ class DetectionCriterion(nn.Module):
     """The loss for the Tiny Faces detector (loss.py:24-97).
 
     `lazy_meters=True` (used by the fast trainer) defers the two `float(loss)` host syncs of
-    loss.py:90-91 to the moment `.class_average.average` is read."""
+    loss.py:90-91 to the moment `.class_average.average` is read.
 
-    def __init__(self, n_templates=25, reg_weight=1, pos_fraction=0.5, seed=0, lazy_meters=False, keep_labels=False):
+    `cls_loss="focal"`: sigmoid focal loss (Lin et al. 2017) with `focal_gamma` and `focal_alpha` (torchvision's sigmoid_focal_loss
+    convention: a negative alpha switches the weighting off) over EVERY labelled anchor, SmoothL1 over every positive; no OHEM, no
+    sampling (`ohem_thresh`, `max_pos` / `max_neg`, the seed and `inject_sampling` do not apply) and `class_map` is only read.
+    `focal_normalize="pos"`: every image's two sums and its gradient are divided by max(1, its number of positives) and the images are
+    summed, so an image's loss does not depend on the batch it is in; "none": the plain sums.  The meters receive the normalised sums."""
+
+    CLS_LOSSES = ("soft_margin", "focal")
+
+    def __init__(self, n_templates=25, reg_weight=1, pos_fraction=0.5, seed=0, lazy_meters=False, keep_labels=False,
+                 cls_loss="soft_margin", focal_gamma=2.0, focal_alpha=0.25, focal_normalize="pos"):
         super().__init__()
+        if cls_loss not in self.CLS_LOSSES:
+            raise ValueError(f"DetectionCriterion: cls_loss must be one of {self.CLS_LOSSES}, got {cls_loss!r}")
+        ops.check_focal(focal_gamma, focal_alpha, focal_normalize)
+        self.cls_loss = cls_loss
+        self.focal_gamma, self.focal_alpha, self.focal_normalize = float(focal_gamma), float(focal_alpha), focal_normalize
         self.n_templates = n_templates
         self.reg_weight = reg_weight
         self.pos_fraction = pos_fraction
@@ -78,7 +92,22 @@ class DetectionCriterion(nn.Module):
     def inject_sampling(self, pos_keep, neg_keep):
         """Parity hook: keep flags indexed by C-order rank of the positive / negative labels of
         each image, (B, nt*H*W) uint8 -- replays the reference's np.random.permutation draws."""
+        if self.cls_loss == "focal":
+            raise RuntimeError("DetectionCriterion.inject_sampling: cls_loss='focal' samples nothing (every labelled anchor contributes)")
         self._pos_keep, self._neg_keep = pos_keep, neg_keep
+
+    def _fwd_bwd(self, out, class_map, regression_map, want_labels=False):
+        """The fused loss + gradient pass of this criterion's `cls_loss`, for the autograd function above and for TrainEngine.step:
+        (loss[2] f64 device tensor, d(total)/d(out), labels that entered the loss).  soft_margin mines `class_map` in place and returns
+        the sampled labels if `want_labels`, else None; focal only reads `class_map`, which IS the labels that entered."""
+        if self.cls_loss == "focal":
+            loss2, grad, _ = ops.criterion_focal_fwd_bwd(out, class_map, regression_map, self.n_templates, self.reg_weight, self.focal_gamma,
+                                                         self.focal_alpha, self.focal_normalize)
+            return loss2, grad, class_map
+        if self.cls_loss != "soft_margin":
+            raise ValueError(f"DetectionCriterion: cls_loss must be one of {self.CLS_LOSSES}, got {self.cls_loss!r}")
+        return ops.criterion_fwd_bwd(out, class_map, regression_map, self.n_templates, self.reg_weight, self.ohem_thresh, self.max_pos,
+                                     self.max_neg, self._pos_keep, self._neg_keep, self._next_seed(), want_labels=want_labels)
 
     def flush_meters(self, lag=0):
         """Feed the loss meters from the device values of the steps enqueued so far.  `lag` = the number of MOST RECENT steps left pending: reading a

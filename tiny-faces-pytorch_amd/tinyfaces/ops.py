@@ -481,6 +481,49 @@ def criterion_fwd_bwd(output, class_map, regression_map, n_templates=25, reg_wei
     return loss, grad, labels
 
 
+FOCAL_NORMALIZE = {"none": 0, "pos": 1}                  # TF_FOCAL_NORM_*
+
+
+def check_focal(gamma, alpha, normalize):
+    """ValueError unless gamma is finite and >= 0, alpha finite and <= 1 (negative: no alpha weighting) and normalize one of FOCAL_NORMALIZE."""
+    if not (np.isfinite(gamma) and gamma >= 0):
+        raise ValueError(f"focal loss: gamma must be a finite number >= 0, got {gamma}")
+    if not (np.isfinite(alpha) and alpha <= 1):
+        raise ValueError(f"focal loss: alpha must be a finite number <= 1 (negative switches the weighting off), got {alpha}")
+    if normalize not in FOCAL_NORMALIZE:
+        raise ValueError(f"focal loss: normalize must be one of {sorted(FOCAL_NORMALIZE)}, got {normalize!r}")
+
+
+def criterion_focal_fwd_bwd(output, class_map, regression_map, n_templates=25, reg_weight=1.0, gamma=2.0, alpha=0.25, normalize="pos",
+                            grad=None):
+    """Sigmoid focal loss over every labelled element + SmoothL1 over every positive, loss and d(total)/d(output) in one device pass
+    (tf_criterion_focal_fwd_bwd): no OHEM, no sampling, class_map is only read.  normalize="pos": image b's sums and gradient times
+    1 / max(1, npos_b), images summed; "none": the plain sum.  alpha < 0: no alpha weighting.
+    Returns (loss[2] f64 device tensor = [sum cls, sum reg], grad wrt output, npos[B] int32 = the +1 labels of every image).
+    grad: write the gradient into this contiguous fp32 tensor of output's shape (every element is written exactly once, no memset needed)."""
+    require_gpu(output, "criterion_focal")
+    check_focal(gamma, alpha, normalize)
+    assert output.dtype == torch.float32 and class_map.dtype == torch.float32 and regression_map.dtype == torch.float32
+    output, regression_map = output.contiguous(), regression_map.contiguous()
+    assert class_map.is_contiguous()
+    B, C5, H, W = output.shape
+    nt = n_templates
+    assert C5 == 5 * nt and class_map.shape == (B, nt, H, W) and regression_map.shape == (B, 4 * nt, H, W)
+    dev = output.device
+    if grad is None:
+        grad = torch.empty_like(output)
+    assert grad.shape == output.shape and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == dev
+    loss = torch.empty(2, dtype=torch.float64, device=dev)
+    npos = torch.empty(B, dtype=torch.int32, device=dev)
+    wsb = lib().tf_criterion_focal_workspace_bytes(B, nt, H, W)
+    ws = _workspace("criterion_focal", wsb, dev)
+    with torch.cuda.device(dev):
+        check(lib().tf_criterion_focal_fwd_bwd(ptr(output), ptr(class_map), ptr(regression_map), B, nt, H, W, float(gamma), float(alpha),
+                                               FOCAL_NORMALIZE[normalize], float(reg_weight), ptr(grad), ptr(loss), ptr(npos),
+                                               ptr(ws), wsb, stream()), "tf_criterion_focal_fwd_bwd")
+    return loss, grad, npos
+
+
 # --------------------------------------------------------------------------- SGD
 NMS_MAX_BOXES = 524160                                   # csrc/nms.hip: (n/64 + 2) 8-byte words must fit 64 KiB of LDS
 IMAGE_MEAN, IMAGE_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)        # main.py:44-46
