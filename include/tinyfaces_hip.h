@@ -213,6 +213,37 @@ int tf_criterion_focal_fwd_bwd(const float* output, const float* class_map, cons
                                float* grad_out, double* loss_out /*[2]*/, int32_t* npos_out /*[B], may be NULL*/,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* ---- detection criterion, focal form with an overlap regression loss: IoU, GIoU (Rezatofighi et al. 2019), DIoU (Zheng et al. 2020) ----
+ * tf_criterion_focal_fwd_bwd with the SmoothL1 regression replaced: same operands, same workspace query (tf_criterion_focal_workspace_bytes),
+ * same three launches, same classification loss, normaliser, summation order and determinism.  reg_form = TF_REG_SMOOTH_L1 runs the
+ * kernels of tf_criterion_focal_fwd_bwd itself (the same bits).  Otherwise, for every element with label +1, with p = (px, py, pw, ph) from
+ * channel blocks 1..4 of output and t = (tx, ty, tw, th) from reg_map (tx = (fcx - cx) / dw, tw = log(fw / dw), ...: in the anchor's
+ * template-normalised frame a prediction is the box with centre (px, py) and size (e^pw, e^ph)):
+ *   clamp   pw, ph to [-C, C], C = log(1000 / 16) (torchvision's bbox_xform_clip); the gradient through the clamp is 1 inside the closed
+ *           interval and 0 outside (torch.clamp); the targets are not clamped
+ *   boxes   predicted [px -+ e^pw / 2] x [py -+ e^ph / 2], target the same from t;
+ *           iw = max(0, min(x2) - max(x1)), ih likewise, I = iw ih, U = e^(pw + ph) + e^(tw + th) - I, IoU = I / U;
+ *           enclosing box cw = max(x2) - min(x1), ch likewise, Cbox = cw ch.  All areas are > 0 under the clamp: no epsilon anywhere
+ *   TF_REG_IOU   1 - IoU
+ *   TF_REG_GIOU  1 - IoU + (Cbox - U) / Cbox
+ *   TF_REG_DIOU  1 - IoU + ((a dx)^2 + dy^2) / ((a cw)^2 + ch^2), a = dw / dh of the anchor's template (template_wh[t] = (dw, dh),
+ *                dw = x2 - x1 + 1 of the template box), dx = px - tx, dy = py - ty
+ * IoU and GIoU do not change under a per-axis scaling, so they need neither the anchor centre nor the template table.
+ * ONE term per positive element (not four) is added to loss_out[1]; its four partial derivatives, times reg_weight and the image's
+ * normaliser, go to the four regression channels of grad_out.  The loss is continuous; on a kink (two edges tie, iw or ih exactly 0, |pw|
+ * or |ph| exactly C) the gradient is some finite one-sided value.  Arithmetic per element is fp32, the sums fp64.
+ * template_wh: [nt][2] f32 on the device, required for TF_REG_DIOU and ignored otherwise.
+ * TF_ERR_ARG: as tf_criterion_focal_fwd_bwd, and reg_weight not finite, an unknown reg_form, TF_REG_DIOU without template_wh. */
+#define TF_REG_SMOOTH_L1 0
+#define TF_REG_IOU       1
+#define TF_REG_GIOU      2
+#define TF_REG_DIOU      3
+int tf_criterion_focal_box_fwd_bwd(const float* output, const float* class_map, const float* reg_map, int B, int nt, int H, int W,
+                                   float gamma, float alpha, int normalize, float reg_weight,
+                                   int reg_form, const float* template_wh /*[nt][2], device; may be NULL unless TF_REG_DIOU*/,
+                                   float* grad_out, double* loss_out /*[2]*/, int32_t* npos_out /*[B], may be NULL*/,
+                                   void* ws, size_t ws_bytes, void* stream);
+
 /* ---- fused SGD step (momentum, weight decay) over a flat fp32 segment ---------------
  * Replaces torch.optim.SGD.step as configured at main.py:67-70 for one parameter group. */
 int tf_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n,

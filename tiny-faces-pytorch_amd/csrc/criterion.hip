@@ -11,7 +11,8 @@
 //       a bitmap (one wave, counter RNG)
 //   K3  ordered rank of every label (ballot prefix), sampling decision, loss terms, gradient;
 //       every element of grad_out is written exactly once (no memset needed)
-// Below them: the focal-loss form of the same pass (tf_criterion_focal_fwd_bwd), kernels F1-F3.
+// Below them: the focal-loss form of the same pass (tf_criterion_focal_fwd_bwd), kernels F1-F3, and its overlap regression forms
+// (tf_criterion_focal_box_fwd_bwd: IoU / GIoU / DIoU instantiations of F2).
 #include <cmath>
 
 #include "common.h"
@@ -232,7 +233,62 @@ struct FocalParams {
   float* grad; double* loss; int* npos_out;
   double* partial;        // [B][nblk][2]
   int* blkpos;            // [B][nblk]
+  const float* twh;       // [nt][2] template (dw, dh): the DIoU form only
+  int HW;                 // elements per template: e / HW is the template of element e
 };
+
+// Overlap forms of the regression term (tf_criterion_focal_box_fwd_bwd; the definition is in include/tinyfaces_hip.h).  In the anchor's
+// template-normalised frame the prediction is the box with centre (px, py) and size (e^pw, e^ph), pw / ph clamped to [-C, C], the target the
+// same from t; IoU and GIoU do not change under a per-axis scaling, DIoU needs the template's aspect a = dw / dh.  One term per positive.
+enum { REG_SMOOTH_L1 = 0, REG_IOU = 1, REG_GIOU = 2, REG_DIOU = 3 };
+constexpr float BOX_CLIP = 4.135166556742356f;     // log(1000 / 16), torchvision's bbox_xform_clip
+
+// -> the term; g[0..3] = its derivatives with respect to px, py, pw, ph.  All areas are > 0 under the clamp: no epsilon.  On a kink (two edges
+// tie, iw or ih exactly 0, |pw| or |ph| exactly C) the one-sided choice below is taken: finite.
+template <int REG>
+__device__ __forceinline__ float box_term(float px, float py, float pw, float ph, float tx, float ty, float tw, float th, float a, float* g) {
+  const float mw = (pw >= -BOX_CLIP && pw <= BOX_CLIP) ? 1.f : 0.f, mh = (ph >= -BOX_CLIP && ph <= BOX_CLIP) ? 1.f : 0.f;   // torch.clamp's gradient
+  const float hwp = 0.5f * expf(fminf(fmaxf(pw, -BOX_CLIP), BOX_CLIP)), hhp = 0.5f * expf(fminf(fmaxf(ph, -BOX_CLIP), BOX_CLIP));
+  const float hwt = 0.5f * expf(tw), hht = 0.5f * expf(th);
+  // The edges enter only through their differences, taken from the centre offset and the half sizes so that nothing is lost to the size of
+  // the centres themselves: x2p - x2t = dx + (hwp - hwt), x1p - x1t = dx - (hwp - hwt), and for two intervals of half widths u, v whose centres
+  // are d apart  min(x2) - max(x1) = min(2u, 2v, u + v - |d|),  max(x2) - min(x1) = max(2u, 2v, u + v + |d|).  Equal boxes give exactly 0.
+  const float dx = px - tx, dy = py - ty;
+  const float rx2 = dx + (hwp - hwt), rx1 = dx - (hwp - hwt), ry2 = dy + (hhp - hht), ry1 = dy - (hhp - hht);
+  const float iwr = fminf(2.f * fminf(hwp, hwt), hwp + hwt - fabsf(dx)), ihr = fminf(2.f * fminf(hhp, hht), hhp + hht - fabsf(dy));
+  const float iw = fmaxf(iwr, 0.f), ih = fmaxf(ihr, 0.f);
+  const float cw = fmaxf(2.f * fmaxf(hwp, hwt), hwp + hwt + fabsf(dx)), ch = fmaxf(2.f * fmaxf(hhp, hht), hhp + hht + fabsf(dy));
+  const float ap = 4.f * hwp * hhp, at = 4.f * hwt * hht;
+  const float I = iw * ih, U = ap + at - I, rU = 1.f / U, iou = I * rU;
+  // d iw / d (px, pw) and d ih / d (py, ph): which of the prediction's edges bound the intersection
+  const float ox = iwr > 0.f ? 1.f : 0.f, oy = ihr > 0.f ? 1.f : 0.f;
+  const float ix2 = rx2 < 0.f ? ox : 0.f, ix1 = rx1 > 0.f ? ox : 0.f, iy2 = ry2 < 0.f ? oy : 0.f, iy1 = ry1 > 0.f ? oy : 0.f;
+  const float dI[4] = {ih * (ix2 - ix1), iw * (iy2 - iy1), ih * hwp * (ix2 + ix1), iw * hhp * (iy2 + iy1)};
+  const float dU[4] = {-dI[0], -dI[1], ap - dI[2], ap - dI[3]};
+  float term = (U - I) * rU;                                          // 1 - IoU
+#pragma unroll
+  for (int k = 0; k < 4; ++k) g[k] = -(dI[k] - iou * dU[k]) * rU;
+  if (REG == REG_GIOU || REG == REG_DIOU) {
+    // ... and which bound the enclosing box
+    const float ex2 = rx2 > 0.f ? 1.f : 0.f, ex1 = rx1 < 0.f ? 1.f : 0.f, ey2 = ry2 > 0.f ? 1.f : 0.f, ey1 = ry1 < 0.f ? 1.f : 0.f;
+    const float dcw[4] = {ex2 - ex1, 0.f, hwp * (ex2 + ex1), 0.f}, dch[4] = {0.f, ey2 - ey1, 0.f, hhp * (ey2 + ey1)};
+    if (REG == REG_GIOU) {
+      const float Cb = cw * ch, rC = 1.f / Cb, uc = U * rC;
+      term += (Cb - U) * rC;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) g[k] -= (dU[k] - uc * (ch * dcw[k] + cw * dch[k])) * rC;
+    } else {
+      const float a2 = a * a;
+      const float N = a2 * dx * dx + dy * dy, D = a2 * cw * cw + ch * ch, rD = 1.f / D, R = N * rD;
+      const float dN[4] = {2.f * a2 * dx, 2.f * dy, 0.f, 0.f};
+      term += R;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) g[k] += (dN[k] - R * 2.f * (a2 * cw * dcw[k] + ch * dch[k])) * rD;
+    }
+  }
+  g[2] *= mw; g[3] *= mh;
+  return term;
+}
 
 __device__ __forceinline__ int wave_sum_int(int v) {
 #pragma unroll
@@ -265,6 +321,7 @@ __global__ void __launch_bounds__(256) focal_count_kernel(FocalParams p) {
   if (threadIdx.x == 0) p.blkpos[(size_t)b * p.nblk + blk] = wn[0] + wn[1] + wn[2] + wn[3];
 }
 
+template <int REG>
 __global__ void __launch_bounds__(256) focal_apply_kernel(FocalParams p) {
   const int b = blockIdx.y, blk = blockIdx.x;
   __shared__ int wn[4];
@@ -294,17 +351,37 @@ __global__ void __launch_bounds__(256) focal_apply_kernel(FocalParams p) {
         g = (isp ? -inv : inv) * mod * (p.gamma * sg_x * sp_mx + sg_mx);
       }
       p.grad[oi] = g;
+      if constexpr (REG == REG_SMOOTH_L1) {
 #pragma unroll
-      for (int c = 1; c <= 4; ++c) {                                // tx | ty | tw | th blocks
-        const size_t ri = oi + (size_t)c * p.E;
-        float gr = 0.f;
-        if (isp) {
-          const float d = p.out[ri] - p.reg[(size_t)b * 4 * p.E + (size_t)(c - 1) * p.E + e];
-          const float ad = fabsf(d);
-          lreg += (double)(ad < 1.f ? 0.5f * d * d : ad - 0.5f);     // SmoothL1, beta = 1
-          gr = p.reg_weight * inv * (d < -1.f ? -1.f : (d > 1.f ? 1.f : d));
+        for (int c = 1; c <= 4; ++c) {                              // tx | ty | tw | th blocks
+          const size_t ri = oi + (size_t)c * p.E;
+          float gr = 0.f;
+          if (isp) {
+            const float d = p.out[ri] - p.reg[(size_t)b * 4 * p.E + (size_t)(c - 1) * p.E + e];
+            const float ad = fabsf(d);
+            lreg += (double)(ad < 1.f ? 0.5f * d * d : ad - 0.5f);   // SmoothL1, beta = 1
+            gr = p.reg_weight * inv * (d < -1.f ? -1.f : (d > 1.f ? 1.f : d));
+          }
+          p.grad[ri] = gr;
         }
-        p.grad[ri] = gr;
+      } else {                                                      // ONE overlap term per positive, its four derivatives in registers
+        float gr[4] = {0.f, 0.f, 0.f, 0.f};
+        if (isp) {
+          float q[4], t[4];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            q[c] = p.out[oi + (size_t)(c + 1) * p.E];
+            t[c] = p.reg[(size_t)b * 4 * p.E + (size_t)c * p.E + e];
+          }
+          float a = 1.f;
+          if (REG == REG_DIOU) { const float* wh = p.twh + 2 * (e / p.HW); a = wh[0] / wh[1]; }
+          lreg += (double)box_term<REG>(q[0], q[1], q[2], q[3], t[0], t[1], t[2], t[3], a, gr);
+          const float sc = p.reg_weight * inv;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) gr[c] *= sc;
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) p.grad[oi + (size_t)(c + 1) * p.E] = gr[c];
       }
     }
   }
@@ -350,28 +427,56 @@ extern "C" size_t tf_criterion_focal_workspace_bytes(int B, int nt, int H, int W
   return a256((size_t)B * nblk * 2 * sizeof(double)) + a256((size_t)B * nblk * sizeof(int));
 }
 
-extern "C" int tf_criterion_focal_fwd_bwd(const float* output, const float* class_map, const float* reg_map, int B, int nt, int H, int W,
-                                          float gamma, float alpha, int normalize, float reg_weight,
-                                          float* grad_out, double* loss_out, int32_t* npos_out,
-                                          void* ws, size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+namespace {
+
+// the three launches of the focal pass; the regression form selects the instantiation of the apply kernel
+int focal_launch(const float* output, const float* class_map, const float* reg_map, int B, int nt, int H, int W,
+                 float gamma, float alpha, int normalize, float reg_weight, int reg_form, const float* template_wh,
+                 float* grad_out, double* loss_out, int32_t* npos_out, void* ws, size_t ws_bytes, hipStream_t stream) {
   if (!output || !class_map || !reg_map || !grad_out || !loss_out || B <= 0 || nt <= 0 || H <= 0 || W <= 0) return TF_ERR_ARG;
   if (B > 65535 || (size_t)nt * H * W > ((size_t)1 << 30)) return TF_ERR_ARG;      // grid.y; element indices are ints
   if (!(gamma >= 0.f) || !std::isfinite(gamma) || !std::isfinite(alpha) || alpha > 1.f) return TF_ERR_ARG;
   if (normalize != 0 && normalize != 1) return TF_ERR_ARG;
+  if (reg_form < REG_SMOOTH_L1 || reg_form > REG_DIOU || (reg_form == REG_DIOU && !template_wh)) return TF_ERR_ARG;
   if (!ws || ws_bytes < tf_criterion_focal_workspace_bytes(B, nt, H, W)) return TF_ERR_WORKSPACE;
   FocalParams p;
   p.out = output; p.cls = class_map; p.reg = reg_map; p.B = B;
   p.E = nt * H * W; p.nblk = (p.E + EPB - 1) / EPB;
   p.gamma = gamma; p.alpha = alpha; p.normalize = normalize; p.reg_weight = reg_weight;
   p.grad = grad_out; p.loss = loss_out; p.npos_out = npos_out;
+  p.twh = reg_form == REG_DIOU ? template_wh : nullptr; p.HW = H * W;
   char* w = (char*)ws;
   p.partial = (double*)w;        w += a256((size_t)B * p.nblk * 2 * sizeof(double));
   p.blkpos = (int*)w;
   dim3 grid(p.nblk, B);
   hipLaunchKernelGGL(focal_count_kernel, grid, dim3(256), 0, stream, p);
-  hipLaunchKernelGGL(focal_apply_kernel, grid, dim3(256), 0, stream, p);
+  switch (reg_form) {
+    case REG_IOU:  hipLaunchKernelGGL(focal_apply_kernel<REG_IOU>, grid, dim3(256), 0, stream, p); break;
+    case REG_GIOU: hipLaunchKernelGGL(focal_apply_kernel<REG_GIOU>, grid, dim3(256), 0, stream, p); break;
+    case REG_DIOU: hipLaunchKernelGGL(focal_apply_kernel<REG_DIOU>, grid, dim3(256), 0, stream, p); break;
+    default:       hipLaunchKernelGGL(focal_apply_kernel<REG_SMOOTH_L1>, grid, dim3(256), 0, stream, p); break;
+  }
   hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(256), 0, stream, p);
   TF_CHECK_LAUNCH();
   return TF_OK;
+}
+
+}  // namespace
+
+extern "C" int tf_criterion_focal_fwd_bwd(const float* output, const float* class_map, const float* reg_map, int B, int nt, int H, int W,
+                                          float gamma, float alpha, int normalize, float reg_weight,
+                                          float* grad_out, double* loss_out, int32_t* npos_out,
+                                          void* ws, size_t ws_bytes, void* stream_) {
+  return focal_launch(output, class_map, reg_map, B, nt, H, W, gamma, alpha, normalize, reg_weight, REG_SMOOTH_L1, nullptr,
+                      grad_out, loss_out, npos_out, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+extern "C" int tf_criterion_focal_box_fwd_bwd(const float* output, const float* class_map, const float* reg_map, int B, int nt, int H, int W,
+                                              float gamma, float alpha, int normalize, float reg_weight,
+                                              int reg_form, const float* template_wh,
+                                              float* grad_out, double* loss_out, int32_t* npos_out,
+                                              void* ws, size_t ws_bytes, void* stream_) {
+  if (!std::isfinite(reg_weight)) return TF_ERR_ARG;
+  return focal_launch(output, class_map, reg_map, B, nt, H, W, gamma, alpha, normalize, reg_weight, reg_form, template_wh,
+                      grad_out, loss_out, npos_out, ws, ws_bytes, (hipStream_t)stream_);
 }

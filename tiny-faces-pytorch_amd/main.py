@@ -17,6 +17,7 @@ from torch import optim
 
 from tinyfaces import ops, parallel, trainer, transforms
 from tinyfaces.datasets import get_dataloader
+from tinyfaces.datasets.templates import load_templates
 from tinyfaces.ema import ModelEma, ema_decay_at
 from tinyfaces.engine import TrainEngine
 from tinyfaces.models.loss import DetectionCriterion
@@ -104,6 +105,19 @@ FOCAL_HELP = ("--cls-loss {soft-margin,focal}: classification loss of the criter
               "before the images are summed, none leaves the plain sum, default pos")
 
 
+BOX_LOSS_HELP = ("--reg-loss {smooth-l1,iou,giou,diou}: regression loss of the criterion; iou / giou / diou (Rezatofighi et al. 2019, Zheng et al. 2020) "
+                 "put one box-overlap term per positive anchor in place of the four SmoothL1 terms and need --cls-loss focal (the soft-margin pass "
+                 "keeps the reference's SmoothL1), default smooth-l1; --reg-weight W: weight of the regression loss in the total, finite, W >= 0, "
+                 "default 1 (an overlap loss is bounded by 2 per anchor and is normally weighted up)")
+
+
+def _reg_weight(text):
+    value = float(text)
+    if not (math.isfinite(value) and value >= 0.0):
+        raise argparse.ArgumentTypeError(f"must be a finite number >= 0, got {text}")
+    return value
+
+
 def _focal_gamma(text):
     value = float(text)
     if not (math.isfinite(value) and value >= 0.0):
@@ -141,7 +155,7 @@ def _positive_float(text):
 
 
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP)))
+    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP)))
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
@@ -151,7 +165,8 @@ def trunk_arguments(argv=None):
     """`arguments` plus `base_model` from --base-model, `freeze_bn` from --freeze-bn, `trainable_layers` from --trainable-layers, `clip_grad_norm`
     from --clip-grad-norm, `skip_nonfinite` from --skip-nonfinite, `model_ema` from --model-ema, `accum_steps` from --accum-steps and `accum_average`
     from --accum-average, `cls_loss` ("soft_margin" | "focal") from --cls-loss, `focal_gamma`, `focal_alpha` and `focal_normalize` from
-    --focal-gamma, --focal-alpha and --focal-normalize.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
+    --focal-gamma, --focal-alpha and --focal-normalize, `reg_loss` ("smooth_l1" | "iou" | "giou" | "diou") from --reg-loss and `reg_weight` from
+    --reg-weight.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
     options and the additions above."""
     parser = argparse.ArgumentParser(add_help=False)
     parser.add_argument("--base-model", dest="base_model", default="resnet101", choices=list(model_zoo.TRUNKS), help=TRUNK_HELP)
@@ -166,9 +181,13 @@ def trunk_arguments(argv=None):
     parser.add_argument("--focal-gamma", dest="focal_gamma", default=2.0, type=_focal_gamma, metavar="G", help=FOCAL_HELP)
     parser.add_argument("--focal-alpha", dest="focal_alpha", default=0.25, type=_focal_alpha, metavar="A", help=FOCAL_HELP)
     parser.add_argument("--focal-normalize", dest="focal_normalize", default="pos", choices=["pos", "none"], help=FOCAL_HELP)
+    parser.add_argument("--reg-loss", dest="reg_loss", default="smooth-l1", choices=["smooth-l1", "iou", "giou", "diou"], help=BOX_LOSS_HELP)
+    parser.add_argument("--reg-weight", dest="reg_weight", default=1.0, type=_reg_weight, metavar="W", help=BOX_LOSS_HELP)
     known, rest = parser.parse_known_args(argv)
     if known.trainable_layers < 4 and not known.freeze_bn:
         parser.error(f"--trainable-layers {known.trainable_layers} freezes stages of the trunk, which is defined on frozen BatchNorm only: add --freeze-bn")
+    if known.reg_loss != "smooth-l1" and known.cls_loss != "focal":
+        parser.error(f"--reg-loss {known.reg_loss} needs --cls-loss focal: the soft-margin pass keeps the reference's SmoothL1")
     args = arguments(rest)
     args.base_model = known.base_model
     args.freeze_bn = known.freeze_bn
@@ -182,16 +201,22 @@ def trunk_arguments(argv=None):
     args.focal_gamma = known.focal_gamma
     args.focal_alpha = known.focal_alpha
     args.focal_normalize = known.focal_normalize
+    args.reg_loss = known.reg_loss.replace("-", "_")
+    args.reg_weight = known.reg_weight
     return args
 
 
 def loss_description(args):
-    """The criterion's classification loss as the start-up line prints it."""
+    """The criterion's two losses as the start-up line prints them."""
+    reg_loss, reg_weight = getattr(args, "reg_loss", "smooth_l1"), getattr(args, "reg_weight", 1.0)
+    reg = {"smooth_l1": "SmoothL1 on the four offsets", "iou": "IoU, one term per positive", "giou": "GIoU, one term per positive",
+           "diou": "DIoU, one term per positive"}[reg_loss]
+    reg = f"; regression loss {reg}, weight {reg_weight:g}"
     if args.cls_loss != "focal":
-        return f"classification loss soft-margin (OHEM threshold {args.ohem_thresh:g}, 128 + 128 samples per image)"
+        return f"classification loss soft-margin (OHEM threshold {args.ohem_thresh:g}, 128 + 128 samples per image)" + reg
     alpha = f"alpha {args.focal_alpha:g}" if args.focal_alpha >= 0 else "no alpha weighting"
     norm = "per image by its positives" if args.focal_normalize == "pos" else "not normalised"
-    return f"classification loss focal (gamma {args.focal_gamma:g}, {alpha}, {norm}; every labelled anchor, every positive regresses)"
+    return f"classification loss focal (gamma {args.focal_gamma:g}, {alpha}, {norm}; every labelled anchor, every positive regresses)" + reg
 
 
 def lr_at(base_lr, epoch):
@@ -245,8 +270,9 @@ def main():
               f"{args.trainable_layers} of 4 ({len(model.trainable_parameter_names())} trained tensors)")
         print(f"effective batch {args.batch_size * args.accum_steps * parallel.world_size()} = batch_size {args.batch_size} x accum-steps "
               f"{args.accum_steps} x world {parallel.world_size()}" + (", gradients averaged over the window" if args.accum_average and args.accum_steps > 1 else ""))
-    loss_fn = DetectionCriterion(NUM_TEMPLATES, seed=args.seed * parallel.world_size() + parallel.rank(), lazy_meters=True, cls_loss=args.cls_loss,
-                                 focal_gamma=args.focal_gamma, focal_alpha=args.focal_alpha, focal_normalize=args.focal_normalize)
+    loss_fn = DetectionCriterion(NUM_TEMPLATES, reg_weight=args.reg_weight, seed=args.seed * parallel.world_size() + parallel.rank(), lazy_meters=True,
+                                 cls_loss=args.cls_loss, focal_gamma=args.focal_gamma, focal_alpha=args.focal_alpha, focal_normalize=args.focal_normalize,
+                                 reg_loss=args.reg_loss, templates=load_templates(NUM_TEMPLATES) if args.reg_loss == "diou" else None)
     loss_fn.ohem_thresh = args.ohem_thresh
     if parallel.rank() == 0:
         print(loss_description(args))

@@ -119,6 +119,7 @@ _SIGNATURES = {
     "tf_criterion_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, f32, vp, vp, u64, vp, vp, vp, vp, vp, sz, vp]),
     "tf_criterion_focal_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "tf_criterion_focal_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, f32, vp, vp, vp, vp, sz, vp]),
+    "tf_criterion_focal_box_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, f32, i32, vp, vp, vp, vp, vp, sz, vp]),
     "tf_image_prepare": (i32, [C.POINTER(ImagePrepareArgs), vp]),
     "tf_sgd_step": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, vp]),
     "tf_sgd_step_segments": (i32, [vp, vp, vp, C.POINTER(i64), i32, f32, f32, f32, f32, vp]),

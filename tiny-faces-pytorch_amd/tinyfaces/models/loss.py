@@ -2,7 +2,8 @@
 one fused HIP pass (csrc/criterion.hip): OHEM, balance sampling, masked SoftMargin + SmoothL1 sums
 and d(total)/d(output), with no device->host->device round trip (loss.py:47-57 does one per step).
 `cls_loss="focal"` is the one addition to that surface: sigmoid focal loss over every labelled anchor, no mining and no sampling, by the
-focal form of the same pass (tf_criterion_focal_fwd_bwd)."""
+focal form of the same pass (tf_criterion_focal_fwd_bwd); `reg_loss="iou" | "giou" | "diou"` gives that form an overlap regression loss, one
+term per positive in place of the four SmoothL1 terms (tf_criterion_focal_box_fwd_bwd)."""
 import torch
 from torch import nn
 
@@ -55,16 +56,28 @@ class DetectionCriterion(nn.Module):
     convention: a negative alpha switches the weighting off) over EVERY labelled anchor, SmoothL1 over every positive; no OHEM, no
     sampling (`ohem_thresh`, `max_pos` / `max_neg`, the seed and `inject_sampling` do not apply) and `class_map` is only read.
     `focal_normalize="pos"`: every image's two sums and its gradient are divided by max(1, its number of positives) and the images are
-    summed, so an image's loss does not depend on the batch it is in; "none": the plain sums.  The meters receive the normalised sums."""
+    summed, so an image's loss does not depend on the batch it is in; "none": the plain sums.  The meters receive the normalised sums.
+
+    `reg_loss="iou" | "giou" | "diou"` (with cls_loss="focal" only): every positive's regression term is 1 - IoU (plus GIoU's enclosing-box
+    term, Rezatofighi et al. 2019, or DIoU's centre-distance term, Zheng et al. 2020) of the predicted and the target box in the anchor's
+    template-normalised frame, predicted log sizes clamped to +-log(1000 / 16); include/tinyfaces_hip.h has the definition.  One term per
+    positive, so `reg_average` receives a sum bounded by 2 per positive: `reg_weight` is normally raised with it.  `templates`: the (nt, 4 or 5)
+    table of tinyfaces/datasets/templates.py, required for "diou" (its centre distance needs every template's aspect ratio).  It is held as a plain
+    tensor and moved to the output's device on first use, not as a registered buffer: the criterion stays a module without state."""
 
     CLS_LOSSES = ("soft_margin", "focal")
+    REG_LOSSES = ("smooth_l1", "iou", "giou", "diou")
 
     def __init__(self, n_templates=25, reg_weight=1, pos_fraction=0.5, seed=0, lazy_meters=False, keep_labels=False,
-                 cls_loss="soft_margin", focal_gamma=2.0, focal_alpha=0.25, focal_normalize="pos"):
+                 cls_loss="soft_margin", focal_gamma=2.0, focal_alpha=0.25, focal_normalize="pos", reg_loss="smooth_l1", templates=None):
         super().__init__()
         if cls_loss not in self.CLS_LOSSES:
             raise ValueError(f"DetectionCriterion: cls_loss must be one of {self.CLS_LOSSES}, got {cls_loss!r}")
         ops.check_focal(focal_gamma, focal_alpha, focal_normalize)
+        self._template_wh = None if templates is None else ops.template_wh(templates)
+        ops.check_reg_loss(reg_loss, reg_weight, self._template_wh, n_templates)
+        self._check_reg_with_cls(reg_loss, cls_loss)
+        self.reg_loss = reg_loss
         self.cls_loss = cls_loss
         self.focal_gamma, self.focal_alpha, self.focal_normalize = float(focal_gamma), float(focal_alpha), focal_normalize
         self.n_templates = n_templates
@@ -85,6 +98,12 @@ class DetectionCriterion(nn.Module):
         self._pos_keep = self._neg_keep = None
         self._pending = []
 
+    @staticmethod
+    def _check_reg_with_cls(reg_loss, cls_loss):
+        if reg_loss != "smooth_l1" and cls_loss == "soft_margin":
+            raise ValueError(f"DetectionCriterion: reg_loss={reg_loss!r} needs cls_loss='focal'; the soft-margin pass is the reference's surface (OHEM, "
+                             "the 256-sample draw, SmoothL1) and its kernels are left as they are")
+
     def _next_seed(self):
         self._calls += 1
         return (self._seed * 0x9E3779B97F4A7C15 + self._calls) & (2**64 - 1)
@@ -100,6 +119,15 @@ class DetectionCriterion(nn.Module):
         """The fused loss + gradient pass of this criterion's `cls_loss`, for the autograd function above and for TrainEngine.step:
         (loss[2] f64 device tensor, d(total)/d(out), labels that entered the loss).  soft_margin mines `class_map` in place and returns
         the sampled labels if `want_labels`, else None; focal only reads `class_map`, which IS the labels that entered."""
+        if self.reg_loss != "smooth_l1":
+            ops.check_reg_loss(self.reg_loss, self.reg_weight, self._template_wh, self.n_templates)
+            self._check_reg_with_cls(self.reg_loss, self.cls_loss)
+        if self.cls_loss == "focal" and self.reg_loss != "smooth_l1":
+            if self._template_wh is not None and self._template_wh.device != out.device:
+                self._template_wh = self._template_wh.to(out.device)
+            loss2, grad, _ = ops.criterion_focal_box_fwd_bwd(out, class_map, regression_map, self.n_templates, self.reg_weight, self.focal_gamma,
+                                                             self.focal_alpha, self.focal_normalize, self.reg_loss, self._template_wh)
+            return loss2, grad, class_map
         if self.cls_loss == "focal":
             loss2, grad, _ = ops.criterion_focal_fwd_bwd(out, class_map, regression_map, self.n_templates, self.reg_weight, self.focal_gamma,
                                                          self.focal_alpha, self.focal_normalize)

@@ -524,6 +524,69 @@ def criterion_focal_fwd_bwd(output, class_map, regression_map, n_templates=25, r
     return loss, grad, npos
 
 
+REG_LOSSES = {"smooth_l1": 0, "iou": 1, "giou": 2, "diou": 3}      # TF_REG_*
+BOX_CLIP = float(np.log(1000.0 / 16.0))                           # the clamp of the predicted log sizes (torchvision's bbox_xform_clip)
+
+
+def template_wh(templates):
+    """(nt, 2) float32 (dw, dh) = (x2 - x1 + 1, y2 - y1 + 1) of the (nt, >= 4) template table (tinyfaces/datasets/templates.py): the sizes the
+    regression targets are normalised by, of which the DIoU loss needs the aspect ratio."""
+    t = torch.as_tensor(np.asarray(templates.detach().cpu() if torch.is_tensor(templates) else templates, dtype=np.float64))
+    if t.dim() != 2 or t.shape[1] < 4:
+        raise ValueError(f"templates must be an (nt, >= 4) table of (x1, y1, x2, y2[, scale]), got shape {tuple(t.shape)}")
+    wh = torch.stack([t[:, 2] - t[:, 0] + 1.0, t[:, 3] - t[:, 1] + 1.0], 1)
+    if not (bool(torch.isfinite(wh).all()) and bool((wh > 0).all())):
+        raise ValueError("templates: every template needs a finite positive width and height")
+    return wh.float().contiguous()
+
+
+def check_reg_loss(reg_loss, reg_weight=1.0, template_wh=None, n_templates=None):
+    """ValueError unless reg_loss is one of REG_LOSSES, reg_weight is finite, and -- for "diou" -- template_wh is an (nt, 2) tensor."""
+    if reg_loss not in REG_LOSSES:
+        raise ValueError(f"regression loss: reg_loss must be one of {tuple(REG_LOSSES)}, got {reg_loss!r}")
+    if not np.isfinite(reg_weight):
+        raise ValueError(f"regression loss: reg_weight must be finite, got {reg_weight}")
+    if reg_loss == "diou":
+        if template_wh is None:
+            raise ValueError("regression loss: reg_loss='diou' needs template_wh (the (dw, dh) of every template: ops.template_wh(templates))")
+        if not torch.is_tensor(template_wh) or template_wh.dim() != 2 or template_wh.shape[1] != 2 or \
+                (n_templates is not None and template_wh.shape[0] != n_templates):
+            raise ValueError(f"regression loss: template_wh must be an (n_templates, 2) tensor, got {getattr(template_wh, 'shape', template_wh)!r}")
+
+
+def criterion_focal_box_fwd_bwd(output, class_map, regression_map, n_templates=25, reg_weight=1.0, gamma=2.0, alpha=0.25, normalize="pos",
+                                reg_loss="smooth_l1", template_wh=None, grad=None):
+    """criterion_focal_fwd_bwd with the regression loss `reg_loss` (tf_criterion_focal_box_fwd_bwd): "iou", "giou" and "diou" put ONE overlap
+    term per positive in place of the four SmoothL1 terms (include/tinyfaces_hip.h has the definition); "smooth_l1" runs the kernels of
+    criterion_focal_fwd_bwd through this entry point (the same bits).  template_wh: (nt, 2) (dw, dh) of the templates, needed by "diou" only.
+    Same returns as criterion_focal_fwd_bwd; loss[1] is the sum of the overlap terms."""
+    require_gpu(output, "criterion_focal_box")
+    check_focal(gamma, alpha, normalize)
+    check_reg_loss(reg_loss, reg_weight, template_wh, n_templates)
+    assert output.dtype == torch.float32 and class_map.dtype == torch.float32 and regression_map.dtype == torch.float32
+    output, regression_map = output.contiguous(), regression_map.contiguous()
+    assert class_map.is_contiguous()
+    B, C5, H, W = output.shape
+    nt = n_templates
+    assert C5 == 5 * nt and class_map.shape == (B, nt, H, W) and regression_map.shape == (B, 4 * nt, H, W)
+    dev = output.device
+    twh = None
+    if reg_loss == "diou":
+        twh = template_wh.to(device=dev, dtype=torch.float32).contiguous()
+    if grad is None:
+        grad = torch.empty_like(output)
+    assert grad.shape == output.shape and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == dev
+    loss = torch.empty(2, dtype=torch.float64, device=dev)
+    npos = torch.empty(B, dtype=torch.int32, device=dev)
+    wsb = lib().tf_criterion_focal_workspace_bytes(B, nt, H, W)
+    ws = _workspace("criterion_focal", wsb, dev)
+    with torch.cuda.device(dev):
+        check(lib().tf_criterion_focal_box_fwd_bwd(ptr(output), ptr(class_map), ptr(regression_map), B, nt, H, W, float(gamma), float(alpha),
+                                                   FOCAL_NORMALIZE[normalize], float(reg_weight), REG_LOSSES[reg_loss], ptr(twh),
+                                                   ptr(grad), ptr(loss), ptr(npos), ptr(ws), wsb, stream()), "tf_criterion_focal_box_fwd_bwd")
+    return loss, grad, npos
+
+
 # --------------------------------------------------------------------------- SGD
 NMS_MAX_BOXES = 524160                                   # csrc/nms.hip: (n/64 + 2) 8-byte words must fit 64 KiB of LDS
 IMAGE_MEAN, IMAGE_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)        # main.py:44-46
