@@ -330,6 +330,57 @@ int tf_ema_update_segments(float* ema, const float* param, const int64_t* host_s
 #define TF_ACCUM_FINISH 2
 int tf_grad_accumulate_segments(float* acc, float* grad, const int64_t* host_segments, int nseg, int mode, void* stream);
 
+/* ---- fused AdamW step (decoupled weight decay) -------------------------------------------------
+ * Replaces torch.optim.AdamW.step (single-tensor path; amsgrad, maximize, capturable off) where main.py:67-70 builds torch.optim.SGD, for one
+ * parameter group.  Four flat fp32 buffers laid out alike (param, grad, exp_avg, exp_avg_sq) and, optionally, the model EMA as a fifth.
+ *
+ * The step counter and the two bias corrections live in DEVICE memory (one tf_adam_state, 24 bytes, zeroed by the caller), because the verdict
+ * of the non-finite guard lives there too: bias correction must not advance on a step the guard dropped, and the host learns of that only
+ * through a sync.  tf_adamw_advance (one thread, once per optimizer step, behind tf_grad_clip_coef when there is one): with clip given and
+ * clip->skip set it returns without touching *st; otherwise  step += 1, bias1 = 1 - beta1^step, bias2 = 1 - beta2^step.  The power is
+ * square-and-multiply, least significant bit first, on double-double values (hi, lo), the result being r.hi:
+ *     r = (1, 0); x = (beta, 0); t = step; while (t) { if (t & 1) r = mul(r, x); x = mul(x, x); t >>= 1; }
+ *     mul(x, y):       (p, e) = two_prod(x.hi, y.hi);  e = e + (x.hi * y.lo + x.lo * y.hi);  s = p + e;  return (s, e - (s - p))
+ *     two_prod(a, b):  p = a * b;  ca = 134217729 * a;  ah = ca - (ca - a);  al = a - ah;  cb, bh, bl likewise from b;
+ *                      e = ((ah * bh - p) + ah * bl + al * bh) + al * bl;  return (p, e)          (Dekker's exact product, no fma)
+ * Every operation is one plain double operation in the order written, so a host can repeat it operation for operation (libm's pow
+ * gives no such promise), and the power is right to about one ulp for every step count: with plain double products the squarings
+ * would carry up to (step - 1) * 2^-53 of relative error.
+ *
+ * The hyper-parameters travel as doubles: every per-element constant is derived once on the host in double and rounded once to float
+ * (1 - beta2 taken from a float32 beta2 costs 1.3e-5 relative accuracy in exp_avg_sq).
+ *     host:      decay = (float)(1 - lr*wd)   w1 = (float)(1 - beta1)   b2 = (float)beta2   w2 = (float)(1 - beta2)   e = (float)eps
+ *     prologue:  ss = (float)(lr / st->bias1)   c2 = (float)sqrt(st->bias2)      (double arithmetic, uniform)
+ *                gs = grad_scale [* clip->coef, one fp32 product, as the SGD entry points do]
+ *     element:   g = grad * gs
+ *                p = p * decay
+ *                m = fmaf(w1, g - m, m)                  (torch.lerp(m, g, w1) for w1 < 0.5, explicitly fused)
+ *                v = (b2 * v) + ((w2 * g) * g)
+ *                d = (sqrtf(v) / c2) + e
+ *                p = p - ss * (m / d)
+ *                ema = fmaf(ema_weight, p - ema, ema)    (ema != NULL: on the updated p, as tf_sgd_step_ema)
+ * Every line is one fp32 operation rounded to nearest (sqrt and the divisions correctly rounded), nothing else is contracted.
+ *
+ * tf_adamw_step / tf_adamw_step_segments mirror tf_sgd_step_ema / tf_sgd_step_segments_ema: the same range table (HOST memory, ascending and
+ * disjoint, TF_SGD_MAX_SEGMENTS per launch), 16-byte moves when every base is 16-byte aligned (and the table 4-aligned), element-wise
+ * otherwise, nothing outside [0, n) / the ranges read or written.  ema and clip may be NULL.  With clip->skip set the launch is a no-op:
+ * param, both moments and ema keep their bits.  n == 0 / nseg == 0: TF_OK without a launch.  A null operand or state, an unordered table, a
+ * beta outside [0, 1) or eps <= 0 is TF_ERR_ARG -- eps > 0 is required because a launch may walk alignment pads where grad, exp_avg and
+ * exp_avg_sq are all zero, and 0 / (0 + 0) would plant NaNs there.  28 B per element (36 B with the EMA), no LDS, no atomics. */
+typedef struct tf_adam_state { int64_t step; double bias1; double bias2; } tf_adam_state;
+int tf_adamw_advance(tf_adam_state* st /*device*/, double beta1, double beta2, const tf_clip_state* clip /*may be NULL*/, void* stream);
+int tf_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema /*may be NULL*/, int64_t n,
+                  double lr, double beta1, double beta2, double eps, double weight_decay, float grad_scale, float ema_weight,
+                  const tf_adam_state* st /*device*/, const tf_clip_state* clip /*may be NULL*/, void* stream);
+int tf_adamw_step_segments(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema /*may be NULL*/,
+                           const int64_t* host_segments, int nseg,
+                           double lr, double beta1, double beta2, double eps, double weight_decay, float grad_scale, float ema_weight,
+                           const tf_adam_state* st /*device*/, const tf_clip_state* clip /*may be NULL*/, void* stream);
+
+/* Linear learning-rate warm-up (host arithmetic, main.py --warmup-iters N --warmup-factor F; no entry point):
+ *     lr(epoch, T) = lr_at(base, epoch) * (F + (1 - F) * min(T, N) / N),   T = epoch * S + s,  S = ceil(len(loader) / accum_steps)
+ * i.e. torch.optim.lr_scheduler.LinearLR(start_factor=F, total_iters=N) multiplied into StepLR's closed form; N = 0 turns it off. */
+
 /* ---- convolution as MFMA implicit GEMM (NHWC) --------------------------------------
  * Replaces every nn.Conv2d on the path (tinyfaces/models/model.py:25-32,90-106 and the
  * torchvision Bottleneck convs) plus the BN / ReLU / residual passes fused around them.

@@ -6,7 +6,7 @@
 
 Additions (existing flags keep their names and defaults): --fused / --no-fused (TrainEngine vs torch.optim.SGD through
 autograd), --dtype bf16|fp32, --synthetic-len.  The schedule is the reference's: SGD(momentum, weight decay), StepLR(20),
-a checkpoint every --save-every epochs (main.py:39-104)."""
+a checkpoint every --save-every epochs (main.py:39-104); --optimizer adamw and --warmup-iters are opt-in."""
 import argparse
 import math
 import os
@@ -111,6 +111,44 @@ BOX_LOSS_HELP = ("--reg-loss {smooth-l1,iou,giou,diou}: regression loss of the c
                  "default 1 (an overlap loss is bounded by 2 per anchor and is normally weighted up)")
 
 
+OPTIMIZER_HELP = ("--optimizer {sgd,adamw}: the update rule; adamw = torch.optim.AdamW's arithmetic (decoupled --weight-decay; --momentum is unused), "
+                  "fused into the engine's update launches or torch's own on the autograd path, default sgd; --adam-beta1 B / --adam-beta2 B: its "
+                  "decay rates, 0 <= B < 1, defaults 0.9 / 0.999; --adam-eps E: added to the denominator, E > 0, default 1e-8")
+
+
+WARMUP_HELP = ("--warmup-iters N: linear learning-rate warm-up over the first N optimizer steps (torch.optim.lr_scheduler.LinearLR multiplied into "
+               "the StepLR schedule; what torchvision's detection references do in epoch 0), N >= 0, default 0 = off; --warmup-factor F: the factor "
+               "of step 0, 0 < F <= 1, default 1e-3")
+
+
+def _adam_beta(text):
+    value = float(text)
+    if not (math.isfinite(value) and 0.0 <= value < 1.0):
+        raise argparse.ArgumentTypeError(f"must be a number in [0, 1), got {text}")
+    return value
+
+
+def _adam_eps(text):
+    value = float(text)
+    if not (math.isfinite(value) and value > 0.0):
+        raise argparse.ArgumentTypeError(f"must be a finite number > 0, got {text}")
+    return value
+
+
+def _warmup_iters(text):
+    value = int(text)
+    if value < 0:
+        raise argparse.ArgumentTypeError(f"must be an integer >= 0, got {text}")
+    return value
+
+
+def _warmup_factor(text):
+    value = float(text)
+    if not (math.isfinite(value) and 0.0 < value <= 1.0):
+        raise argparse.ArgumentTypeError(f"must be a number in (0, 1], got {text}")
+    return value
+
+
 def _reg_weight(text):
     value = float(text)
     if not (math.isfinite(value) and value >= 0.0):
@@ -155,7 +193,7 @@ def _positive_float(text):
 
 
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP)))
+    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP)))
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
@@ -166,7 +204,8 @@ def trunk_arguments(argv=None):
     from --clip-grad-norm, `skip_nonfinite` from --skip-nonfinite, `model_ema` from --model-ema, `accum_steps` from --accum-steps and `accum_average`
     from --accum-average, `cls_loss` ("soft_margin" | "focal") from --cls-loss, `focal_gamma`, `focal_alpha` and `focal_normalize` from
     --focal-gamma, --focal-alpha and --focal-normalize, `reg_loss` ("smooth_l1" | "iou" | "giou" | "diou") from --reg-loss and `reg_weight` from
-    --reg-weight.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
+    --reg-weight, `optimizer` ("sgd" | "adamw"), `adam_beta1`, `adam_beta2` and `adam_eps` from --optimizer, --adam-beta1, --adam-beta2 and --adam-eps,
+    `warmup_iters` and `warmup_factor` from --warmup-iters and --warmup-factor.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
     options and the additions above."""
     parser = argparse.ArgumentParser(add_help=False)
     parser.add_argument("--base-model", dest="base_model", default="resnet101", choices=list(model_zoo.TRUNKS), help=TRUNK_HELP)
@@ -183,6 +222,12 @@ def trunk_arguments(argv=None):
     parser.add_argument("--focal-normalize", dest="focal_normalize", default="pos", choices=["pos", "none"], help=FOCAL_HELP)
     parser.add_argument("--reg-loss", dest="reg_loss", default="smooth-l1", choices=["smooth-l1", "iou", "giou", "diou"], help=BOX_LOSS_HELP)
     parser.add_argument("--reg-weight", dest="reg_weight", default=1.0, type=_reg_weight, metavar="W", help=BOX_LOSS_HELP)
+    parser.add_argument("--optimizer", dest="optimizer", default="sgd", choices=["sgd", "adamw"], help=OPTIMIZER_HELP)
+    parser.add_argument("--adam-beta1", dest="adam_beta1", default=0.9, type=_adam_beta, metavar="B", help=OPTIMIZER_HELP)
+    parser.add_argument("--adam-beta2", dest="adam_beta2", default=0.999, type=_adam_beta, metavar="B", help=OPTIMIZER_HELP)
+    parser.add_argument("--adam-eps", dest="adam_eps", default=1e-8, type=_adam_eps, metavar="E", help=OPTIMIZER_HELP)
+    parser.add_argument("--warmup-iters", dest="warmup_iters", default=0, type=_warmup_iters, metavar="N", help=WARMUP_HELP)
+    parser.add_argument("--warmup-factor", dest="warmup_factor", default=1e-3, type=_warmup_factor, metavar="F", help=WARMUP_HELP)
     known, rest = parser.parse_known_args(argv)
     if known.trainable_layers < 4 and not known.freeze_bn:
         parser.error(f"--trainable-layers {known.trainable_layers} freezes stages of the trunk, which is defined on frozen BatchNorm only: add --freeze-bn")
@@ -203,6 +248,9 @@ def trunk_arguments(argv=None):
     args.focal_normalize = known.focal_normalize
     args.reg_loss = known.reg_loss.replace("-", "_")
     args.reg_weight = known.reg_weight
+    args.optimizer = known.optimizer
+    args.adam_beta1, args.adam_beta2, args.adam_eps = known.adam_beta1, known.adam_beta2, known.adam_eps
+    args.warmup_iters, args.warmup_factor = known.warmup_iters, known.warmup_factor
     return args
 
 
@@ -223,10 +271,27 @@ def lr_at(base_lr, epoch):
     return base_lr * 0.1 ** (epoch // LR_STEP)
 
 
-def run_fused_epoch(engine, loss_fn, loader, epoch, device, base_lr):
+def steps_per_epoch(n_batches, accum_steps=1):
+    """Optimizer steps of one epoch: the last window of an epoch is applied full or not."""
+    return -(-int(n_batches) // int(accum_steps))
+
+
+def lr_with_warmup(base_lr, epoch, step, warmup_iters=0, warmup_factor=1e-3):
+    """lr_at(base_lr, epoch) * (F + (1 - F) * min(T, N) / N) for the global optimizer-step index T = `step` (epoch * steps_per_epoch + s):
+    StepLR's closed form times LinearLR's (trainer.warmup_factor), so a resumed run lands on the same value.  N = 0: lr_at alone."""
+    return lr_at(base_lr, epoch) * trainer.warmup_factor(step, warmup_iters, warmup_factor)
+
+
+def run_fused_epoch(engine, loss_fn, loader, epoch, device, base_lr, warmup=None):
+    """warmup = (N, F): engine.set_lr(lr_with_warmup(...)) once per optimizer step while the warm-up lasts; None / N = 0: once per epoch."""
     engine.set_lr(lr_at(base_lr, epoch))
     total = len(loader)
+    warm = warmup is not None and int(warmup[0]) > 0
+    first = epoch * steps_per_epoch(total, engine.accum_steps)
+    steps0 = engine.steps
     for idx, batch in enumerate(loader):
+        if warm:
+            engine.set_lr(lr_with_warmup(base_lr, epoch, first + (engine.steps - steps0), warmup[0], warmup[1]))
         # the epoch's last batch ends its window, full or not: no checkpoint is ever written with gradients accumulated and not applied
         engine.step(*(t.float().to(device, non_blocking=True) for t in batch), apply=True if idx + 1 == total else None)
         if parallel.rank() == 0:
@@ -298,15 +363,25 @@ def main():
     if args.fused:
         engine = TrainEngine(model, loss_fn, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay, device=device,
                              max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, ema_decay=args.model_ema,
-                             accum_steps=args.accum_steps, accum_average=args.accum_average)
+                             accum_steps=args.accum_steps, accum_average=args.accum_average, optimizer=args.optimizer,
+                             betas=(args.adam_beta1, args.adam_beta2), eps=args.adam_eps)
         ema = engine.ema                  # (built from the weights --resume / --pretrained left in the model)
         if state is not None:
-            engine.load_optimizer_state_dict(state.get("optimizer"))      # momentum buffers (a torch.optim.SGD state_dict)
+            engine.load_optimizer_state_dict(state.get("optimizer"))      # momentum buffers / moments (a torch.optim.SGD / AdamW state_dict)
     else:
         model = model.to(device)          # before load_state_dict: torch casts the momentum buffers to the device the parameters are on THEN
-        optimizer = optim.SGD(model.learnable_parameters(args.lr), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
+        if args.optimizer == "adamw":
+            optimizer = optim.AdamW(model.learnable_parameters(args.lr), lr=args.lr, betas=(args.adam_beta1, args.adam_beta2), eps=args.adam_eps,
+                                    weight_decay=args.weight_decay)
+        else:
+            optimizer = optim.SGD(model.learnable_parameters(args.lr), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
         if state is not None and state.get("optimizer", {}).get("param_groups"):
-            optimizer.load_state_dict(state["optimizer"])                 # main.py:76
+            theirs = "adamw" if "betas" in state["optimizer"]["param_groups"][0] else "sgd"
+            if theirs == args.optimizer:
+                optimizer.load_state_dict(state["optimizer"])             # main.py:76
+            elif parallel.rank() == 0:
+                print(f"WARNING: {args.resume} holds the state of optimizer {theirs}, this run uses {args.optimizer}: "
+                      f"the moments of {args.optimizer} start from zero")
         for mult, g in zip((1.0, 0.1, 1.0, 0.0), optimizer.param_groups):
             g.setdefault("initial_lr", args.lr * mult)                    # StepLR(last_epoch >= 0) requires it (main.py:81-83)
         scheduler = optim.lr_scheduler.StepLR(optimizer, step_size=LR_STEP, last_epoch=first_epoch - 1)
@@ -342,10 +417,11 @@ def main():
         elif hasattr(getattr(train_loader, "sampler", None), "set_epoch"):
             train_loader.sampler.set_epoch(epoch)
         if engine is not None:
-            run_fused_epoch(engine, loss_fn, train_loader, epoch, device, args.lr)
+            run_fused_epoch(engine, loss_fn, train_loader, epoch, device, args.lr, warmup=(args.warmup_iters, args.warmup_factor))
         else:
             trainer.train(model, loss_fn, optimizer, train_loader, epoch, device=device, max_grad_norm=args.clip_grad_norm,
-                          skip_nonfinite=args.skip_nonfinite, ema=ema, accum_steps=args.accum_steps, accum_average=args.accum_average)
+                          skip_nonfinite=args.skip_nonfinite, ema=ema, accum_steps=args.accum_steps, accum_average=args.accum_average,
+                          warmup=(args.warmup_iters, args.warmup_factor, epoch * steps_per_epoch(len(train_loader), args.accum_steps)))
             scheduler.step()
         if args.skip_nonfinite and parallel.rank() == 0:
             total = engine.skipped_steps if engine is not None else ops.clip_skipped_steps(device)

@@ -65,6 +65,11 @@ class ClipState(C.Structure):
     _fields_ = [("sumsq", C.c_double), ("norm", C.c_double), ("coef", f32), ("skip", i32), ("skipped", i64)]
 
 
+class AdamState(C.Structure):
+    """tf_adam_state (include/tinyfaces_hip.h): the step counter and bias corrections tf_adamw_advance keeps in device memory, 24 bytes."""
+    _fields_ = [("step", i64), ("bias1", C.c_double), ("bias2", C.c_double)]
+
+
 TF_CLIP_SKIP_NONFINITE = 1
 TF_ACCUM_STORE, TF_ACCUM_ADD, TF_ACCUM_FINISH = 0, 1, 2
 
@@ -132,6 +137,9 @@ _SIGNATURES = {
     "tf_sgd_step_segments_ema": (i32, [vp, vp, vp, vp, C.POINTER(i64), i32, f32, f32, f32, f32, f32, vp, vp]),
     "tf_ema_update_segments": (i32, [vp, vp, C.POINTER(i64), i32, f32, vp, vp]),
     "tf_grad_accumulate_segments": (i32, [vp, vp, C.POINTER(i64), i32, i32, vp]),
+    "tf_adamw_advance": (i32, [vp, f64, f64, vp, vp]),
+    "tf_adamw_step": (i32, [vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, f32, f32, vp, vp, vp]),
+    "tf_adamw_step_segments": (i32, [vp, vp, vp, vp, vp, C.POINTER(i64), i32, f64, f64, f64, f64, f64, f32, f32, vp, vp, vp]),
     "tf_conv_mtiles": (i32, [C.POINTER(ConvArgs)]),
     "tf_conv2d": (i32, [C.POINTER(ConvArgs), vp]),
     "tf_pack_weight": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp]),

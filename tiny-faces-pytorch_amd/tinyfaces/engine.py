@@ -31,7 +31,8 @@ from .ema import ModelEma
 
 class TrainEngine:
     def __init__(self, model, criterion, lr=1e-4, momentum=0.9, weight_decay=5e-4, device="cuda", bucket_mb=10, native_exchange=None,
-                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True, accum_steps=1, accum_average=False):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True, accum_steps=1, accum_average=False,
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8):
         """max_grad_norm: clip the global L2 norm of the (rank-averaged) gradient of the trained tensors to this value before the update, as
         torch.nn.utils.clip_grad_norm_ between backward() and optimizer.step() would (tinyfaces/trainer.py:86-87).  skip_nonfinite: a step
         whose gradient norm is NaN or Inf changes neither the parameters nor the momentum (`skipped_steps` counts them; what the FORWARD
@@ -52,7 +53,12 @@ class TrainEngine:
         folded into the grad_scale the norm and SGD launches take.  Clipping, the guard, the exchange between ranks (one per window, behind
         the last backward pass, not overlapped with it, through torch.distributed) and the model EMA act once per window, on the
         accumulated gradient; BatchNorm running statistics and the loss meters advance with every micro-batch.  One more flat fp32 buffer,
-        allocated when first used; fixed for the engine's life.  1 (the default): no buffer, no new call."""
+        allocated when first used; fixed for the engine's life.  1 (the default): no buffer, no new call.
+        optimizer: "sgd" (the default: nothing new is allocated or launched) or "adamw", torch.optim.AdamW's single-tensor arithmetic
+        (include/tinyfaces_hip.h) with `betas` and `eps`; `weight_decay` is then decoupled, `momentum` unused, `flat_m` is exp_avg and
+        `flat_v`, one more flat fp32 buffer, exp_avg_sq.  The step counter of the bias correction lives on the device (`adam_state`, an
+        ops.AdamState) and does not advance on a step the non-finite guard drops.  The groups, their lr multipliers, the trained segments,
+        the fused EMA and the clip state are the ones SGD uses."""
         self.device = torch.device(device)
         self.model = model.to(self.device).train()
         self.criterion = criterion
@@ -67,6 +73,20 @@ class TrainEngine:
         self._ema_weight = None               # float32(1 - d_t) of the step under way: taken once per step, not once per group
         self.groups = self.model.group_ranges()
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
+        if optimizer not in ("sgd", "adamw"):
+            raise ValueError(f"optimizer must be 'sgd' or 'adamw', got {optimizer!r}")
+        self.optimizer = optimizer
+        if optimizer == "adamw":
+            b1, b2 = (float(b) for b in betas)
+            if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+                raise ValueError(f"betas must lie in [0, 1), got {betas!r}")
+            if not float(eps) > 0.0:
+                raise ValueError(f"eps must be positive, got {eps!r}")
+            if os.environ.get("TINYFACES_SGD_PER_BUCKET"):
+                raise ValueError("optimizer='adamw' cannot be combined with TINYFACES_SGD_PER_BUCKET: the per-bucket update is an SGD experiment")
+            self.betas, self.eps = (b1, b2), float(eps)
+            self.flat_v = torch.zeros_like(self.flat_p)          # exp_avg_sq; flat_m is exp_avg
+            self.adam_state = ops.AdamState(self.device)
         self.bucket_elems = int(bucket_mb * (1 << 20) // 4)
         self.steps = 0                        # optimizer steps
         self.micro_steps = 0                  # calls of step(): equal to `steps` unless gradients are accumulated
@@ -404,6 +424,8 @@ class TrainEngine:
             raise RuntimeError(f"optimizer_state_dict: {self._window} of {self.accum_steps} micro-batches are accumulated and not applied; "
                                "finish the window first (step(..., apply=True))")
         base_lr = self.lr if base_lr is None else base_lr
+        if self.optimizer == "adamw":
+            return self._adamw_state_dict(base_lr)          # torch.optim.AdamW's format instead
         seg = self.model._segments
         state, groups, idx = {}, [], 0
         for mult, params in self._group_params():
@@ -425,6 +447,9 @@ class TrainEngine:
         momentum_buffer (never stepped, `model.fc.*`, lr-0 upsample) start from zero like torch does."""
         if not sd or not sd.get("param_groups"):
             return False
+        theirs = "adamw" if "betas" in sd["param_groups"][0] else "sgd"
+        if self.optimizer == "adamw" or theirs == "adamw":
+            return self._load_adamw_state_dict(sd, theirs)
         seg = self.model._segments
         flat = [kp for _, params in self._group_params() for kp in params]
         ids = [i for g in sd["param_groups"] for i in g["params"]]
@@ -444,6 +469,71 @@ class TrainEngine:
             loaded += 1
         g0 = sd["param_groups"][0]
         self.momentum = float(g0.get("momentum", self.momentum))
+        self.weight_decay = float(g0.get("weight_decay", self.weight_decay))
+        self.steps = max(self.steps, 1 if loaded else 0)
+        return True
+
+    # ---- the same interop with torch.optim.AdamW ----------------------------------------------------------------------
+    def _adamw_state_dict(self, base_lr):
+        """optimizer_state_dict() under optimizer="adamw": the format of `torch.optim.AdamW(model.learnable_parameters(lr), betas=, eps=,
+        weight_decay=).state_dict()` as the installed torch writes it -- the group keys are taken from a real instance -- with `step` (a 0-d
+        float32 CPU tensor holding the DEVICE step count, read here and nowhere else), `exp_avg` and `exp_avg_sq` per trained parameter.
+        Frozen tensors and the lr-0 group have no state: torch creates state lazily, on the first step with a gradient."""
+        keys = torch.optim.AdamW([torch.zeros(1)], lr=1.0, betas=self.betas, eps=self.eps,
+                                 weight_decay=self.weight_decay).state_dict()["param_groups"][0]
+        seg = self.model._segments
+        trained = set(self.model.trainable_parameter_names())
+        t = float(self.adam_state.step()) if self.steps > 0 else 0.0
+        state, groups, idx = {}, [], 0
+        for mult, params in self._group_params():
+            ids = []
+            for k, p in params:
+                if k in seg and k in trained and mult != 0.0 and self.steps > 0:
+                    o, n = seg[k]
+                    state[idx] = {"step": torch.tensor(t, dtype=torch.float32),
+                                  "exp_avg": self.flat_m[o:o + n].view_as(p).detach().clone().cpu(),
+                                  "exp_avg_sq": self.flat_v[o:o + n].view_as(p).detach().clone().cpu()}
+                ids.append(idx)
+                idx += 1
+            group = dict(keys)
+            group.update(lr=self.lr * mult, initial_lr=base_lr * mult, params=ids)
+            groups.append(group)
+        return {"state": state, "param_groups": groups}
+
+    def _load_adamw_state_dict(self, sd, theirs):
+        """load_optimizer_state_dict() when the engine or the state dict (`theirs`) is AdamW.  Both AdamW: the moments are copied into the flat
+        buffers and the device step is set (the bias corrections follow from it at the next step).  One of each: the moments start from
+        zero and rank 0 says so -- an SGD momentum buffer is not an exp_avg."""
+        self.flat_m.zero_()
+        if self.optimizer == "adamw":
+            self.flat_v.zero_()
+            self.adam_state.set_step(0)
+        if theirs != self.optimizer:
+            if parallel.rank() == 0 or not parallel.is_distributed():
+                print(f"WARNING: the checkpoint holds the state of optimizer {theirs}, this run uses {self.optimizer}: "
+                      f"the moments of {self.optimizer} start from zero")
+            return True
+        seg = self.model._segments
+        flat = [kp for _, params in self._group_params() for kp in params]
+        ids = [i for g in sd["param_groups"] for i in g["params"]]
+        if len(ids) != len(flat):
+            raise ValueError(f"optimizer state has {len(ids)} parameters, the model has {len(flat)}")
+        loaded, t = 0, 0
+        for i, (k, p) in zip(ids, flat):
+            st = sd["state"].get(i)
+            if st is None or k not in seg or st.get("exp_avg") is None or st.get("exp_avg_sq") is None:
+                continue
+            o, n = seg[k]
+            for name, dst in (("exp_avg", self.flat_m), ("exp_avg_sq", self.flat_v)):
+                if st[name].numel() != n:
+                    raise ValueError(f"{name} of {k}: {st[name].numel()} elements, expected {n}")
+                dst[o:o + n].copy_(st[name].reshape(-1).to(dst.device, torch.float32))
+            t = max(t, int(float(st.get("step", 0))))
+            loaded += 1
+        self.adam_state.set_step(t)
+        g0 = sd["param_groups"][0]
+        self.betas = tuple(float(b) for b in g0.get("betas", self.betas))
+        self.eps = float(g0.get("eps", self.eps))
         self.weight_decay = float(g0.get("weight_decay", self.weight_decay))
         self.steps = max(self.steps, 1 if loaded else 0)
         return True
@@ -570,10 +660,23 @@ class TrainEngine:
     def _sgd(self, gflat, a, b, mult, scale, clip=None):
         """The SGD update of the flat range [a, b) (inside one parameter group, lr multiplier `mult`).  With the model's BatchNorm frozen
         only the trained segments of the range are touched, in one launch per TF_SGD_MAX_SEGMENTS segments (ops.sgd_step_segments).
-        clip: the ClipState of this step (_clip_coef) -- the clipped / guarded forms of the same two launches."""
+        clip: the ClipState of this step (_clip_coef) -- the clipped / guarded forms of the same two launches.
+        optimizer="adamw": the AdamW launches over the same ranges (ops.adamw_step / ops.adamw_step_segments)."""
         kw = {} if clip is None else {"clip_state": clip}       # (the default step calls the ops exactly as it always did)
         if self.ema is not None:
             kw["ema_weight"] = self._ema_weight
+        if self.optimizer == "adamw":
+            hyper = (self.lr * mult, self.betas, self.eps, self.weight_decay, scale)
+            if not self.model.batchnorm_frozen:
+                if self.ema is not None:
+                    kw["ema"] = self.ema.flat[a:b]
+                ops.adamw_step(self.flat_p[a:b], gflat[a:b], self.flat_m[a:b], self.flat_v[a:b], self.adam_state, *hyper, **kw)
+                return
+            if self.ema is not None:
+                kw["ema"] = self.ema.flat
+            segs = [(max(s, a), min(e, b)) for s, e in self._trained_segments() if e > a and s < b]
+            ops.adamw_step_segments(self.flat_p, gflat, self.flat_m, self.flat_v, self.adam_state, segs, *hyper, **kw)
+            return
         if not self.model.batchnorm_frozen:
             if self.ema is not None:
                 kw["ema"] = self.ema.flat[a:b]
@@ -671,6 +774,8 @@ class TrainEngine:
             if reduce:
                 self._allreduce(gflat)
             clip = self._clip_coef(gflat, scale) if self._clip_on() else None      # behind the join: the norm of the summed gradient
+            if self.optimizer == "adamw":
+                ops.adamw_advance(self.adam_state, self.betas, clip)      # once per optimizer step; a skipped step leaves the counter alone
             for s, e, mult in self.groups:
                 if mult == 0.0:
                     continue                              # score4_upsample: lr 0 (model.py:84) -> nothing to do

@@ -831,6 +831,100 @@ def ema_update_segments(ema, param, segments, weight, clip_state=None):
                                            stream()), "tf_ema_update_segments")
 
 
+class AdamState:
+    """The 24 bytes of device memory AdamW keeps its step counter and bias corrections in (tf_adam_state, include/tinyfaces_hip.h): advanced
+    by `adamw_advance` once per optimizer step (not at all on a step the non-finite guard drops), read by `adamw_step` /
+    `adamw_step_segments` on the device.  The readers below copy it to the host, i.e. they synchronise."""
+
+    def __init__(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"AdamState: device {device}; the tiny-faces hot path only exists as HIP kernels for MI355X (gfx950) -- "
+                               "there is no CPU fallback.")
+        self.buf = torch.zeros(C.sizeof(_hip.AdamState), dtype=torch.uint8, device=device)
+
+    def read(self):
+        """The whole state as a host-side _hip.AdamState (synchronises)."""
+        return _hip.AdamState.from_buffer_copy(self.buf.cpu().numpy().tobytes())
+
+    def step(self):
+        return int(self.read().step)
+
+    def bias1(self):
+        return float(self.read().bias1)
+
+    def bias2(self):
+        return float(self.read().bias2)
+
+    def set_step(self, t):
+        """Resume: the counter becomes t (>= 0); bias1 and bias2 are zeroed, the next adamw_advance recomputes them for t + 1."""
+        t = int(t)
+        if t < 0:
+            raise ValueError(f"AdamState.set_step: step must be >= 0, got {t}")
+        host = torch.zeros(3, dtype=torch.int64)
+        host[0] = t
+        self.buf.copy_(host.view(torch.uint8))
+        return self
+
+
+def _adam_hyper(what, lr, betas, eps, weight_decay):
+    b1, b2 = (float(b) for b in betas)
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"{what}: betas must lie in [0, 1), got {betas!r}")
+    if not float(eps) > 0.0:
+        raise ValueError(f"{what}: eps must be positive, got {eps!r}")
+    return float(lr), b1, b2, float(eps), float(weight_decay)
+
+
+def adamw_advance(state, betas=(0.9, 0.999), clip_state=None):
+    """One optimizer step of the AdamW bookkeeping on the device (tf_adamw_advance): step += 1 and the two bias corrections, unless
+    clip_state (filled by grad_clip_coef earlier on this stream) says skip.  Call it once per optimizer step, in front of the step's
+    adamw_step / adamw_step_segments launches."""
+    _, b1, b2, _, _ = _adam_hyper("adamw_advance", 0.0, betas, 1.0, 0.0)
+    with torch.cuda.device(state.buf.device):
+        check(lib().tf_adamw_advance(ptr(state.buf), b1, b2, None if clip_state is None else ptr(clip_state.buf), stream()),
+              "tf_adamw_advance")
+    return state
+
+
+def adamw_step(param, grad, exp_avg, exp_avg_sq, state, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, *, ema=None,
+               ema_weight=None, clip_state=None):
+    """torch.optim.AdamW.step for one flat fp32 segment (tf_adamw_step), with the bias corrections `state` (AdamState) holds on the device:
+    adamw_advance comes first.  ema, ema_weight, clip_state: as in sgd_step -- the model EMA in the same launch, grad_scale * coef, and
+    nothing at all (param, both moments and ema keep their bits) when the state says skip."""
+    require_gpu(param, "adamw_step")
+    assert param.dtype == grad.dtype == exp_avg.dtype == exp_avg_sq.dtype == torch.float32
+    assert param.is_contiguous() and grad.is_contiguous() and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous()
+    n = param.numel()
+    assert grad.numel() == n and exp_avg.numel() == n and exp_avg_sq.numel() == n and state.buf.device == param.device
+    lr, b1, b2, eps, wd = _adam_hyper("adamw_step", lr, betas, eps, weight_decay)
+    avg = _ema_pair("adamw_step", param, ema, ema_weight)
+    with torch.cuda.device(param.device):
+        check(lib().tf_adamw_step(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), None if avg is None else ptr(avg[0]), n, lr, b1, b2,
+                                  eps, wd, float(grad_scale), 0.0 if avg is None else avg[1], ptr(state.buf),
+                                  None if clip_state is None else ptr(clip_state.buf), stream()), "tf_adamw_step")
+
+
+def adamw_step_segments(param, grad, exp_avg, exp_avg_sq, state, segments, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                        grad_scale=1.0, *, ema=None, ema_weight=None, clip_state=None):
+    """adamw_step over the element ranges `segments` ([(start, end)], ascending, disjoint) of four (with ema: five) flat fp32 buffers of one
+    length; everything outside the ranges is left untouched (tf_adamw_step_segments)."""
+    require_gpu(param, "adamw_step_segments")
+    assert param.dtype == grad.dtype == exp_avg.dtype == exp_avg_sq.dtype == torch.float32
+    assert param.is_contiguous() and grad.is_contiguous() and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous()
+    n = param.numel()
+    assert grad.numel() == n and exp_avg.numel() == n and exp_avg_sq.numel() == n and state.buf.device == param.device
+    lr, b1, b2, eps, wd = _adam_hyper("adamw_step_segments", lr, betas, eps, weight_decay)
+    avg = _ema_pair("adamw_step_segments", param, ema, ema_weight)
+    table, nseg = _segment_table("adamw_step_segments", segments, n)
+    if nseg == 0:
+        return
+    with torch.cuda.device(param.device):
+        check(lib().tf_adamw_step_segments(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), None if avg is None else ptr(avg[0]), table,
+                                           nseg, lr, b1, b2, eps, wd, float(grad_scale), 0.0 if avg is None else avg[1], ptr(state.buf),
+                                           None if clip_state is None else ptr(clip_state.buf), stream()), "tf_adamw_step_segments")
+
+
 ACCUM_STORE, ACCUM_ADD, ACCUM_FINISH = _hip.TF_ACCUM_STORE, _hip.TF_ACCUM_ADD, _hip.TF_ACCUM_FINISH
 
 

@@ -30,8 +30,22 @@ def _is_logging_rank():
     return parallel.rank() == 0 or not parallel.is_distributed()
 
 
+def warmup_factor(step, iters, factor):
+    """Linear learning-rate warm-up in closed form: factor + (1 - factor) * min(step, iters) / iters for the optimizer step `step` (0-based,
+    counted from the start of training), 1 when iters is 0 (off).  torch.optim.lr_scheduler.LinearLR(start_factor=factor,
+    total_iters=iters) after `step` calls of its step(); a resumed run lands on the same value."""
+    iters, factor = int(iters), float(factor)
+    if iters < 0:
+        raise ValueError(f"warm-up iterations must be >= 0, got {iters}")
+    if not 0.0 < factor <= 1.0:
+        raise ValueError(f"warm-up factor must lie in (0, 1], got {factor}")
+    if iters == 0:
+        return 1.0
+    return factor + (1.0 - factor) * min(int(step), iters) / iters
+
+
 def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=None, skip_nonfinite=False, ema=None, accum_steps=1,
-          accum_average=False):
+          accum_average=False, warmup=None):
     """One epoch with the reference's step order (trainer.py:68-90): forward, criterion, zero_grad, backward, [all-reduce],
     optimizer step, progress line.
 
@@ -40,6 +54,7 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
     (trainer.py:86-87), without a host round trip.  skip_nonfinite alone (max_grad_norm None) only guards.  On a step the guard skips the
     gradient is scaled to ZERO, and torch.optim.SGD still applies weight decay and momentum to the parameters: that is what torch's
     optimizer does with a zero gradient.  Only the fused engine (TrainEngine(skip_nonfinite=True)) leaves a skipped step untouched.
+    Under torch.optim.AdamW a zero gradient likewise still decays the weights and moves them along exp_avg (and advances `step`).
 
     ema (a tinyfaces.ema.ModelEma of `model`): ema.update() right behind optimizer.step(), the spot of AveragedModel.update_parameters in a
     torch training loop -- one launch per 128 trained tensors on the device, no host sync.
@@ -47,7 +62,11 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
     accum_steps = N > 1: one optimizer step per window of N batches.  zero_grad() runs at the start of a window only, so autograd sums the
     window's gradients in `.grad`; the window ends when it is full or with the loader's last batch, and only there follow the averaging over
     ranks, the 1 / k scaling of accum_average (k batches in the window: the mean instead of the sum), the clip, optimizer.step() and
-    ema.update(), in that order.  With the default the loop is the one above, call for call."""
+    ema.update(), in that order.  With the default the loop is the one above, call for call.
+
+    warmup = (N, F, first_T): linear learning-rate warm-up.  Before the k-th optimizer.step() of this call every group's lr is set to the lr
+    this call found there times warmup_factor(first_T + k, N, F); the found values are put back at the end (the epoch scheduler goes on
+    from them).  first_T is the global index of this epoch's first optimizer step.  None or N = 0: the groups are not touched."""
     net = model.to(device).train()
     reducer = parallel.reducer_for(net)
     n_batches = len(dataloader)
@@ -60,28 +79,40 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
     average = bool(accum_average) and accum_steps > 1
     clipped = [p for g in optimizer.param_groups for p in g["params"]] if clip or average else None
     window = 0                                  # batches whose gradients `.grad` holds
-    for step, batch in enumerate(dataloader):
-        image, cls_target, reg_target = (t.float().to(device, non_blocking=True) for t in batch)
-        loss = loss_fn(net(image), cls_target, reg_target)
-        if window == 0:
-            optimizer.zero_grad()
-        loss.backward()
-        window += 1
-        if window == accum_steps or step + 1 == n_batches:
-            if reducer is not None:
-                reducer.average_gradients()
-            if average and window > 1:
-                torch._foreach_mul_([p.grad for p in clipped if p.grad is not None], 1.0 / window)      # (this path's update is torch's own, too)
-            if clip:
-                ops.clip_grad_norm_(clipped, float("inf") if max_grad_norm is None else max_grad_norm, skip_nonfinite=skip_nonfinite)
-            optimizer.step()
-            if ema is not None:
-                ema.update()
-            window = 0
-        if _is_logging_rank():
-            flush = getattr(loss_fn, "flush_meters", None)
-            if flush is not None:
-                flush()
-            print_state(step, epoch, n_batches, loss_fn.class_average.average, loss_fn.reg_average.average)
-        elif getattr(loss_fn, "_pending", None):
-            loss_fn._pending.clear()            # lazy meters are only ever read on the logging rank: do not pin device scalars elsewhere
+    found = [g["lr"] for g in optimizer.param_groups] if warmup is not None and int(warmup[0]) > 0 else None
+    applied = 0                                 # optimizer steps taken by this call
+    try:
+        for step, batch in enumerate(dataloader):
+            image, cls_target, reg_target = (t.float().to(device, non_blocking=True) for t in batch)
+            loss = loss_fn(net(image), cls_target, reg_target)
+            if window == 0:
+                optimizer.zero_grad()
+            loss.backward()
+            window += 1
+            if window == accum_steps or step + 1 == n_batches:
+                if reducer is not None:
+                    reducer.average_gradients()
+                if average and window > 1:
+                    torch._foreach_mul_([p.grad for p in clipped if p.grad is not None], 1.0 / window)      # (this path's update is torch's own, too)
+                if clip:
+                    ops.clip_grad_norm_(clipped, float("inf") if max_grad_norm is None else max_grad_norm, skip_nonfinite=skip_nonfinite)
+                if found is not None:
+                    factor = warmup_factor(int(warmup[2]) + applied, warmup[0], warmup[1])
+                    for g, lr in zip(optimizer.param_groups, found):
+                        g["lr"] = lr * factor
+                optimizer.step()
+                applied += 1
+                if ema is not None:
+                    ema.update()
+                window = 0
+            if _is_logging_rank():
+                flush = getattr(loss_fn, "flush_meters", None)
+                if flush is not None:
+                    flush()
+                print_state(step, epoch, n_batches, loss_fn.class_average.average, loss_fn.reg_average.average)
+            elif getattr(loss_fn, "_pending", None):
+                loss_fn._pending.clear()            # lazy meters are only ever read on the logging rank: do not pin device scalars elsewhere
+    finally:
+        if found is not None:
+            for g, lr in zip(optimizer.param_groups, found):
+                g["lr"] = lr
