@@ -168,7 +168,17 @@ int tf_soft_nms_f64(const double* boxes /*[n][4]*/, const double* scores /*[n]*/
  * Candidates are appended to dets[*count ...] as rows (x1,y1,x2,y2,score) f64 in the
  * reference's order: C-order over (y, x, template).  valid_x[W] / valid_t[nt] (u8) express
  * the template mask; the reference's defect D1 (utils.py:44 masks the W axis) is
- * reproduced by the caller passing it through valid_x. */
+ * reproduced by the caller passing it through valid_x.  A masked entry has probability 0
+ * (it passes only a negative prob_thresh); an entry is a candidate iff prob > prob_thresh,
+ * both fp32; a NaN logit is never one.  templates [nt][tstride] f64, tstride >= 4: columns
+ * 0..3 are read, the rest is padding.
+ * *count (DEVICE int32) is read as the row the first candidate goes to and comes back as
+ * *count + the TRUE number of candidates of this map, whatever cap is: a caller chains maps
+ * through it and checks *count <= cap once at the end.  Rows r >= cap are NOT written, so
+ * exactly rows [*count before, min(*count after, cap)) are; no other row of dets is touched.
+ * nt is bounded by the write pass's LDS slab: 5 * nt * 64 * 4 bytes plus the kernel's 20
+ * static bytes must fit 64 KiB, i.e. nt <= 51; a larger nt is TF_ERR_UNSUPPORTED, refused
+ * on the host before anything is launched (*count and dets stay as they were). */
 size_t tf_decode_workspace_bytes(int H, int W, int nt);
 int tf_decode_compact(const float* score, int nt, int H, int W,
                       const double* templates, int tstride,

@@ -207,6 +207,30 @@ def test_conv_pws_tile_loop_keeps_its_ring_rules(tmp_path):
     assert any("stores" in b for b in isa_audit.audit(broken))
 
 
+def test_decode_refuses_an_nt_whose_lds_slab_does_not_fit_without_launching(hip):
+    """tf_decode_compact's write pass stages 5 * nt * 64 floats in LDS next to 20 static bytes: nt = 51 is the last that fits 64 KiB.  From
+    nt = 52 the call is TF_ERR_UNSUPPORTED, decided on the host before the workspace is looked at and before anything is enqueued (the
+    count pass and the scan would run and advance *count over rows the failing write pass never writes).  Runs without a GPU: the operands
+    are host memory nobody dereferences."""
+    import ctypes as C
+    l = hip.lib()
+    ERR_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE = -1, -3, -4
+    buf = (C.c_double * 64)()
+    p = C.cast(buf, C.c_void_p)
+    assert 5 * 51 * 64 * 4 + 20 <= 64 << 10 < 5 * 52 * 64 * 4 + 20
+    wsb = l.tf_decode_workspace_bytes(3, 7, 52)
+
+    def call(nt, ws=p, ws_bytes=wsb, score=p):
+        return l.tf_decode_compact(score, nt, 3, 7, p, 5, p, p, 0.5, 1.0, 8, 8, -1, -1, p, p, 10, ws, ws_bytes, None)
+
+    for nt in (52, 53, 64, 1000, 1 << 20):
+        assert call(nt) == ERR_UNSUPPORTED
+        assert call(nt, ws=None, ws_bytes=0) == ERR_UNSUPPORTED              # refused before the workspace check
+    assert call(52, score=None) == ERR_ARG and call(0) == ERR_ARG            # a NULL operand or nt <= 0 stays TF_ERR_ARG
+    assert call(51, ws_bytes=wsb - 1) == ERR_WORKSPACE                       # 51 passes the limit: the next check answers, nothing is launched
+    assert call(51, ws=None) == ERR_WORKSPACE
+
+
 def test_round4_entry_points_refuse_bad_arguments_without_launching(hip):
     """The entry points added in round 4 check their arguments on the host before anything is enqueued: a NULL operand or an operand type a
     kernel does not exist for comes back as TF_ERR_ARG / TF_ERR_UNSUPPORTED (the reference-side binding maps these to exceptions), never

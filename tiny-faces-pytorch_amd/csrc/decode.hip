@@ -11,6 +11,8 @@
 namespace {
 
 constexpr int PXB = 64;   // pixels per block
+constexpr size_t DEC_STATIC_LDS = 5 * sizeof(int);   // decode_kernel's wave_cnt[4] + run_base
+constexpr size_t DEC_LDS_LIMIT = 64 << 10;           // LDS one launch gets without raising hipFuncAttributeMaxDynamicSharedMemorySize
 
 struct DecParams {
   const float* score; int nt, H, W;
@@ -128,6 +130,9 @@ extern "C" int tf_decode_compact(const float* score, int nt, int H, int W, const
                                  void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!score || !templates || !valid_x || !valid_t || !dets || !count || nt <= 0 || H <= 0 || W <= 0 || scale <= 0) return TF_ERR_ARG;
+  // the write pass stages a [5nt][PXB] fp32 slab next to decode_kernel's static LDS (wave_cnt + run_base): beyond 64 KiB that launch
+  // fails AFTER the scan has advanced *count over rows nobody writes, so such an nt is refused here, before anything is enqueued
+  if ((size_t)5 * nt * PXB * sizeof(float) + DEC_STATIC_LDS > DEC_LDS_LIMIT) return TF_ERR_UNSUPPORTED;   // nt <= 51
   if (!ws || ws_bytes < tf_decode_workspace_bytes(H, W, nt)) return TF_ERR_WORKSPACE;
   DecParams p;
   p.score = score; p.nt = nt; p.H = H; p.W = W; p.tpl = templates; p.tstride = tstride;
