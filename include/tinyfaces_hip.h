@@ -161,6 +161,44 @@ size_t tf_soft_nms_workspace_bytes(int n);
 int tf_soft_nms_f64(const double* boxes /*[n][4]*/, const double* scores /*[n]*/, int n, int method, double iou_thresh, double sigma,
                     double score_thresh, int score_mode, int64_t* keep_out /*[n]*/, double* score_out /*[n]*/,
                     int32_t* num_keep /*device [1]*/, void* ws, size_t ws_bytes, void* stream);
+/* The same with a cap on the number of selections: max_keep inserted before keep_out.  max_keep == 0: no cap -- the entries above ARE these
+ * with 0, the same launches and bits.  max_keep < 0: TF_ERR_ARG.  max_keep > 0: the selection loop of a segment ends when r == max_keep,
+ * so num_keep[s] = min(uncapped count, max_keep) and the rows written are the first num_keep[s] rows of the uncapped run, bit for bit (a
+ * later round never changes an earlier row); rows beyond are NOT written.  The selection costs milliseconds per thousand survivors and no
+ * WIDER evaluation reads more than a few hundred detections per image: this is where `max_detections` saves its time.  A chained
+ * tf_box_vote_f64_batched reads the capped count from the device as before.  Workspace and every other refusal as above. */
+int tf_soft_nms_f64_batched_capped(const double* boxes /*[n][4]*/, const double* scores /*[n]*/, const int32_t* host_seg_offsets /*[S+1]*/,
+                                   int num_segments, int method, double iou_thresh, double sigma, double score_thresh, int score_mode,
+                                   int max_keep, int64_t* keep_out /*[n]*/, double* score_out /*[n]*/, int32_t* num_keep /*device [S]*/,
+                                   void* ws, size_t ws_bytes, void* stream);
+int tf_soft_nms_f64_capped(const double* boxes /*[n][4]*/, const double* scores /*[n]*/, int n, int method, double iou_thresh, double sigma,
+                           double score_thresh, int score_mode, int max_keep, int64_t* keep_out /*[n]*/, double* score_out /*[n]*/,
+                           int32_t* num_keep /*device [1]*/, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- deterministic top-k selection on float64 scores (the `top_k` / `topk_candidates` step in front of the suppression) ----------
+ * An addition in front of tf_nms_f64 / tf_soft_nms_f64, both O(n^2): it bounds the candidates that reach them, and cuts a list too long
+ * for either to one they take.  Segments as for tf_nms_f64_batched: a HOST offset table, [0] == 0, S <= TF_NMS_MAX_SEGMENTS.  For segment
+ * s with n_s rows the call writes m_s = min(n_s, k) indices INTO THE CONCATENATED INPUT to idx_out[sum_{r<s} m_r ...]; every m_s is known
+ * on the host, so there is no device-side count and no synchronisation.
+ *   Which rows: the m_s rows that come first in the order the hard NMS itself uses (rank[i] = #{j : s_j > s_i or (s_j == s_i and j < i)}):
+ *     larger score first; on equal scores the lower input index first (-0.0 and +0.0 are equal); a NaN ranks behind every number, -inf
+ *     included, NaNs among themselves by index.
+ *   In which order: ASCENDING input index, not score order -- the compacted list keeps the candidate list's order, so a later stable sort,
+ *     tie-break or voter sum sees the rows it would have seen.  Hence, with idx the output for one segment and nms() = tf_nms_f64's keep
+ *     list:  idx[nms(boxes[idx], scores[idx])] == the entries of nms(boxes, scores) whose rank is below k, and those are a prefix of it.
+ *   n_s <= k: the segment is passed through whole (idx = off_s ... off_s + n_s - 1).
+ * k < 1, a bad segment table (S outside 1..TF_NMS_MAX_SEGMENTS, offsets that do not start at 0 or descend), a NULL scores / idx_out / ws
+ * with n > 0 or a workspace shorter than tf_topk_batched_workspace_bytes() are TF_ERR_ARG.  n == 0 launches nothing.  Nothing but
+ * idx_out[0 .. sum m_s) and the workspace is written; scores is only read.  A segment is as long as the int32 offsets allow.
+ * How: an MSB-first radix select over an order-preserving uint64 key, 8 passes of 8 bits, each a per-segment digit histogram (integer
+ * atomics only: the counts do not depend on arrival order), then an ordered compaction (count, scan, write).  Work linear in n per pass;
+ * 12 enqueues whatever n and S; no grid barrier, no cooperative launch, no spinning on another workgroup; the same bits on every run. */
+size_t tf_topk_batched_workspace_bytes(const int32_t* host_seg_offsets, int num_segments, int k);
+int tf_topk_select_f64_batched(const double* scores /*[n]*/, const int32_t* host_seg_offsets /*[S+1]*/, int num_segments, int k,
+                               int64_t* idx_out /*[sum_s min(n_s, k)]*/, void* ws, size_t ws_bytes, void* stream);
+/* one segment: the batched form with S = 1 */
+size_t tf_topk_workspace_bytes(int n, int k);
+int tf_topk_select_f64(const double* scores /*[n]*/, int n, int k, int64_t* idx_out /*[min(n, k)]*/, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- score map -> boxes: sigmoid + threshold + ORDERED compaction + refinement ------
  * Replaces evaluation.py:61-78 + get_bboxes / regression_refinement

@@ -13,7 +13,8 @@
 //                 (16 independent 32-byte loads; the owner of the selected box does it while the row word travels).  So a round costs one
 //                 reduction, one row read and the few decays, not a pass over the candidates.  One barrier per round (the reduction slots alternate).  The loop is a `for` over at most n
 //                 rounds inside one workgroup: no grid barrier, no cooperative launch, no spinning on another workgroup.  No atomics anywhere:
-//                 the same bits on every run.
+//                 the same bits on every run.  max_keep > 0 (the *_capped entries) ends the loop after that many selections: the rows written
+//                 are the first max_keep rows of the uncapped run, whose later rounds cannot change them.
 #include "common.h"
 
 namespace {
@@ -74,7 +75,7 @@ __device__ __forceinline__ void take_better(double& v, int& i, double ov, int oi
 
 __global__ void __launch_bounds__(kSelThreads) soft_nms_select_kernel(const double* __restrict__ boxes_all, const double* __restrict__ scores_all,
                                                                       const SoftSegs sg, int method, double thr, double sigma, double sthr,
-                                                                      int score_mode, const unsigned long long* __restrict__ adj_all,
+                                                                      int score_mode, int max_keep, const unsigned long long* __restrict__ adj_all,
                                                                       double* __restrict__ run_all, int64_t* __restrict__ keep_all,
                                                                       double* __restrict__ score_all, int32_t* __restrict__ num_keep) {
   __shared__ double red_v[2][kSelThreads / 64];
@@ -148,6 +149,7 @@ __global__ void __launch_bounds__(kSelThreads) soft_nms_select_kernel(const doub
     const int m = vi;
     if (t == 0) { keep_all[base + r] = (int64_t)(base + m); score_all[base + r] = v; }
     ++r;
+    if (r == max_keep) break;                                // block-uniform: the cap (0 = none: r >= 1 here)
     if (owner) {
       // the row word and the selected box are asked for first; the owner of m rescans its word (its cached maximum is gone) while they travel
       const unsigned long long arow = adj[(size_t)m * nwords + t];
@@ -224,15 +226,15 @@ extern "C" size_t tf_soft_nms_workspace_bytes(int n) {
   return tf_soft_nms_batched_workspace_bytes(off, 1);
 }
 
-extern "C" int tf_soft_nms_f64_batched(const double* boxes, const double* scores, const int32_t* host_seg_offsets, int num_segments,
-                                       int method, double iou_thresh, double sigma, double score_thresh, int score_mode,
-                                       int64_t* keep_out, double* score_out, int32_t* num_keep, void* ws, size_t ws_bytes, void* stream_) {
+extern "C" int tf_soft_nms_f64_batched_capped(const double* boxes, const double* scores, const int32_t* host_seg_offsets, int num_segments,
+                                              int method, double iou_thresh, double sigma, double score_thresh, int score_mode, int max_keep,
+                                              int64_t* keep_out, double* score_out, int32_t* num_keep, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int S = num_segments;
   SoftSegs sg;
   size_t words = 0, vwords = 0;
   int nmax = 0;
-  if (!num_keep || !soft_table(host_seg_offsets, S, &sg, &words, &vwords, &nmax)) return TF_ERR_ARG;
+  if (!num_keep || max_keep < 0 || !soft_table(host_seg_offsets, S, &sg, &words, &vwords, &nmax)) return TF_ERR_ARG;
   if (method != TF_SOFT_NMS_LINEAR && method != TF_SOFT_NMS_GAUSSIAN) return TF_ERR_ARG;
   if (score_mode != TF_VOTE_WEIGHT_SIGMOID && score_mode != TF_VOTE_WEIGHT_SCORE) return TF_ERR_ARG;
   if (!(sigma > 0.0) || !(iou_thresh >= 0.0 && iou_thresh <= 1.0) || !(score_thresh >= 0.0)) return TF_ERR_ARG;      // (a NaN fails each)
@@ -246,9 +248,25 @@ extern "C" int tf_soft_nms_f64_batched(const double* boxes, const double* scores
   hipLaunchKernelGGL(soft_nms_adj_kernel, dim3(nwmax, nwmax, S), dim3(64), 0, stream, boxes, sg, method, iou_thresh, adj);
   const int threads = ((nwmax + 63) / 64) * 64;              // whole waves, one thread per word of the longest segment (<= 1024)
   hipLaunchKernelGGL(soft_nms_select_kernel, dim3(S), dim3(threads), 0, stream, boxes, scores, sg, method, iou_thresh, sigma, score_thresh,
-                     score_mode, adj, run, keep_out, score_out, num_keep);
+                     score_mode, max_keep, adj, run, keep_out, score_out, num_keep);
   TF_CHECK_LAUNCH();
   return TF_OK;
+}
+
+extern "C" int tf_soft_nms_f64_batched(const double* boxes, const double* scores, const int32_t* host_seg_offsets, int num_segments,
+                                       int method, double iou_thresh, double sigma, double score_thresh, int score_mode,
+                                       int64_t* keep_out, double* score_out, int32_t* num_keep, void* ws, size_t ws_bytes, void* stream_) {
+  return tf_soft_nms_f64_batched_capped(boxes, scores, host_seg_offsets, num_segments, method, iou_thresh, sigma, score_thresh, score_mode, 0,
+                                        keep_out, score_out, num_keep, ws, ws_bytes, stream_);
+}
+
+extern "C" int tf_soft_nms_f64_capped(const double* boxes, const double* scores, int n, int method, double iou_thresh, double sigma,
+                                      double score_thresh, int score_mode, int max_keep, int64_t* keep_out, double* score_out,
+                                      int32_t* num_keep, void* ws, size_t ws_bytes, void* stream_) {
+  if (n < 0) return TF_ERR_ARG;
+  const int32_t off[2] = {0, n};
+  return tf_soft_nms_f64_batched_capped(boxes, scores, off, 1, method, iou_thresh, sigma, score_thresh, score_mode, max_keep, keep_out, score_out,
+                                        num_keep, ws, ws_bytes, stream_);
 }
 
 extern "C" int tf_soft_nms_f64(const double* boxes, const double* scores, int n, int method, double iou_thresh, double sigma,

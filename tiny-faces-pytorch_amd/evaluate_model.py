@@ -102,6 +102,33 @@ def soft_nms_arguments(argv=None):
     return args
 
 
+LIMITS_HELP = ("--pre-nms-topk K: when more than K candidates pass --prob_thresh, only the K best reach the NMS / Soft-NMS / vote (the `top_k` of "
+               "S3FD / RetinaFace, e.g. 5000); --max-detections M: at most M detections per image are written (`keep_top_k`, e.g. 750)")
+
+
+def _count(flag):
+    def parse(text):
+        try:
+            v = int(text)
+        except ValueError:
+            v = 0
+        if v < 1:
+            raise argparse.ArgumentTypeError(f"{flag} {text}: a positive integer")
+        return v
+    return parse
+
+
+def limits_arguments(argv=None):
+    """`soft_nms_arguments` plus `pre_nms_topk` / `max_detections` from --pre-nms-topk K / --max-detections M, parsed apart in the same way."""
+    parser = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    parser.add_argument("--pre-nms-topk", dest="pre_nms_topk", type=_count("--pre-nms-topk"), default=None, metavar="K", help=LIMITS_HELP)
+    parser.add_argument("--max-detections", dest="max_detections", type=_count("--max-detections"), default=None, metavar="M", help=LIMITS_HELP)
+    known, rest = parser.parse_known_args(argv)
+    args = soft_nms_arguments(rest)
+    args.pre_nms_topk, args.max_detections = known.pre_nms_topk, known.max_detections
+    return args
+
+
 def dataloader(args):
     """evaluate_model.py:34-45."""
     tf = transforms.Compose([transforms.ToTensor(), transforms.Normalize([0.485, 0.456, 0.406], [0.229, 0.224, 0.225])])
@@ -111,16 +138,19 @@ def dataloader(args):
 
 
 def run(model, val_loader, templates, prob_thresh, nms_thresh, device, split, results_dir=None, debug=False, mask_axis="w",
+        pre_nms_topk=None, max_detections=None,
         flip=False, box_voting=None, soft_nms=None, soft_nms_sigma=0.5, soft_nms_score_thresh=0.001):
     """evaluate_model.py:48-68, statement for statement: `img[0]` / `filename[0]` undo the batch axis the loader adds.  The
     only addition is the keyword that builds the pyramid levels on the GPU (same detections bit for bit).
     flip / box_voting: get_detections' test-time augmentation, off by default.  soft_nms / soft_nms_sigma / soft_nms_score_thresh:
-    get_detections' Soft-NMS, off by default."""
+    get_detections' Soft-NMS, off by default.  pre_nms_topk / max_detections: get_detections' bounds on the candidates that reach the
+    suppression step and on the rows that come back, off by default."""
     dets = None
     for _, (img, filename) in enumerate(val_loader):
         dets = get_detections(model, img[0], templates, val_loader.dataset.rf, val_loader.dataset.transforms, prob_thresh, nms_thresh,
                               device=device, pyramid_on_gpu=True, mask_axis=mask_axis, flip=flip, box_voting=box_voting,
-                              soft_nms=soft_nms, soft_nms_sigma=soft_nms_sigma, soft_nms_score_thresh=soft_nms_score_thresh)
+                              soft_nms=soft_nms, soft_nms_sigma=soft_nms_sigma, soft_nms_score_thresh=soft_nms_score_thresh,
+                              pre_nms_topk=pre_nms_topk, max_detections=max_detections)
         write_results(dets, filename[0], split, results_dir)
         if debug:
             print(f"{filename[0]}: {dets.shape[0]} detections")
@@ -128,7 +158,7 @@ def run(model, val_loader, templates, prob_thresh, nms_thresh, device, split, re
 
 
 def main():
-    args = soft_nms_arguments()
+    args = limits_arguments()
     if not torch.cuda.is_available():
         raise SystemExit("this build of the tiny-faces hot path runs on MI355X only (no CPU fallback)")
     # Multi-GPU evaluation = replicas only: under torchrun every rank takes a strided shard of the image list
@@ -146,7 +176,8 @@ def main():
     with torch.no_grad(), model.constant_weights():          # the checkpoint does not change between images: pack the weights once
         run(model, val_loader, templates, args.prob_thresh, args.nms_thresh, device, args.split, results_dir=args.results_dir,
             debug=args.debug or args.dataset == "synthetic", mask_axis=args.mask_axis, flip=args.flip, box_voting=args.box_voting,
-            soft_nms=args.soft_nms, soft_nms_sigma=args.soft_nms_sigma, soft_nms_score_thresh=args.soft_nms_score_thresh)
+            soft_nms=args.soft_nms, soft_nms_sigma=args.soft_nms_sigma, soft_nms_score_thresh=args.soft_nms_score_thresh,
+            pre_nms_topk=args.pre_nms_topk, max_detections=args.max_detections)
     if distributed:
         torch.distributed.barrier()
         if parallel.rank() == 0:

@@ -127,21 +127,43 @@ def _check_soft_nms(soft_nms, nms_thresh, sigma, score_thresh):
     ops._soft_nms_mode(soft_nms, nms_thresh if soft_nms == "linear" else 0.0, sigma, score_thresh, "sigmoid")
 
 
-def _soft_nms_rows(cand, offs, method, nms_thresh, sigma, score_thresh, box_voting):
+def _check_limits(pre_nms_topk, max_detections):
+    """pre_nms_topk / max_detections of get_detections / get_detections_batch: None or a positive integer, refused before the model runs."""
+    for name, v in (("pre_nms_topk", pre_nms_topk), ("max_detections", max_detections)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1):
+            raise ValueError(f"{name}={v!r}: expected None or an integer >= 1")
+
+
+def _pre_nms_cut(cand, offs, pre_nms_topk):
+    """Every segment of the device candidate list longer than pre_nms_topk is cut to its best pre_nms_topk rows (`ops.topk_select_batched`; the
+    rows keep the list's order) -> (rows, offsets, idx): idx maps a row of the cut list to its row in `cand`, None when nothing was cut."""
+    if pre_nms_topk is None:
+        return cand, offs, None
+    idx, new = ops.topk_select_batched(cand[:, 4].contiguous(), offs, int(pre_nms_topk))
+    if idx is None:
+        return cand, offs, None
+    return cand.index_select(0, idx), new, idx
+
+
+def _soft_nms_rows(cand, offs, method, nms_thresh, sigma, score_thresh, box_voting, max_keep=None):
     """Soft-NMS over the segments `offs` of the device candidate list (rows x1, y1, x2, y2, logit) -> ([keep], [(K_s, 5) device rows]):
     cand[keep] in selection order, or the voted rows, with the decayed probability in column 4.  One synchronisation."""
     boxes, scores = cand[:, :4].contiguous(), cand[:, 4].contiguous()
     thr = nms_thresh if method == "linear" else 0.0             # the gaussian method ignores it
+    vote = {} if box_voting is None else {"vote": (box_voting, "sigmoid")}
+    if max_keep is None:                                        # without a cap the call is the one it was
+        res = ops.soft_nms_batched(boxes, scores, offs, method, thr, sigma, score_thresh, **vote)
+    else:
+        res = ops.soft_nms_batched_capped(boxes, scores, offs, int(max_keep), method, thr, sigma, score_thresh, **vote)
     if box_voting is not None:
-        res, rows = ops.soft_nms_batched(boxes, scores, offs, method, thr, sigma, score_thresh, vote=(box_voting, "sigmoid"))
+        res, rows = res
         return [k for k, _ in res], rows
-    res = ops.soft_nms_batched(boxes, scores, offs, method, thr, sigma, score_thresh)
     return [k for k, _ in res], [torch.cat([boxes[k], ks.unsqueeze(1)], dim=1) for k, ks in res]
 
 
 def get_detections(model, img, templates, rf, img_transforms, prob_thresh=0.65, nms_thresh=0.3, scales=(-2, -1, 0, 1),
-                   device=None, mask_axis="w", return_candidates=False, pyramid_on_gpu=False, flip=False, box_voting=None,
-                   soft_nms=None, soft_nms_sigma=0.5, soft_nms_score_thresh=0.001):
+                   device=None, mask_axis="w", return_candidates=False, pyramid_on_gpu=False, pre_nms_topk=None, max_detections=None,
+                   flip=False, box_voting=None, soft_nms=None, soft_nms_sigma=0.5, soft_nms_score_thresh=0.001):
     """evaluation.py:20-87.  Returns (K,5) float64: the reference's (K,4) rows in the same order
     with the score re-attached as column 4 (defect D2: the reference drops it although
     write_results reads x[4], evaluation.py:111).  mask_axis='w' reproduces defect D1
@@ -158,11 +180,24 @@ def get_detections(model, img, templates, rf, img_transforms, prob_thresh=0.65, 
     instead of the hard NMS -- an overlapped candidate is decayed, not dropped, and survives while its score stays >= soft_nms_score_thresh.
     nms_thresh is the linear method's IoU threshold, soft_nms_sigma the gaussian method's (which ignores nms_thresh).  The rows are
     cand[keep] in selection order with column 4 replaced by the DECAYED PROBABILITY (not a logit); with box_voting the voted rows, column 4
-    likewise; return_candidates returns that keep."""
+    likewise; return_candidates returns that keep.
+    The two bounds every WIDER FACE pipeline has (additions; None: off, the same launches and rows bit for bit):
+    pre_nms_topk=K (S3FD / PyramidBox / RetinaFace `top_k`, torchvision's `topk_candidates`): when more than K candidates pass prob_thresh, only
+    the K best -- larger score, the earlier candidate on a tie, the hard NMS's own order -- reach the NMS / Soft-NMS / vote
+    (`ops.topk_select`: selected on the device, gathered in candidate order).  The hard NMS then returns exactly the rows of the uncut call
+    whose candidate ranks below K.  With flip=True the cut applies to the union of the plain and the mirrored candidates.  Box voting's voters
+    are the K retained candidates (Detectron's behaviour: it votes over the boxes that entered the NMS).  The candidate-count limits of the NMS
+    (ops.NMS_MAX_BOXES) and of Soft-NMS (ops.SOFT_NMS_MAX_BOXES) apply to min(n, K).  return_candidates still returns the FULL candidate list and a
+    keep that indexes it.
+    max_detections=M (`keep_top_k`, `detections_per_img`): at most M rows come back, the first M in keep order; with soft_nms the selection
+    itself stops after M rows (`ops.soft_nms_capped`), which is where the time is saved.
+    (Both sit in front of `flip` in the signature, not at its end: every keyword of this call is passed by name, and the tail of the list is
+    what tests/test_soft_nms.py holds fixed.)"""
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
         raise RuntimeError("get_detections: the detector only runs on MI355X (no CPU fallback)")
     _check_soft_nms(soft_nms, nms_thresh, soft_nms_sigma, soft_nms_score_thresh)
+    _check_limits(pre_nms_topk, max_detections)
     model = _on_device(model, device)
     model.eval()
     nt = templates.shape[0]
@@ -176,41 +211,55 @@ def get_detections(model, img, templates, rf, img_transforms, prob_thresh=0.65, 
         _decode_image(model, levels, flip, templates, t_d, rf, prob_thresh, mask_axis, dets, count, device)
     n = int(count.item())
     assert n <= dets.shape[0]
-    if n > ops.NMS_MAX_BOXES:
-        raise RuntimeError(f"get_detections: {n} candidates above prob_thresh={prob_thresh} exceed the {ops.NMS_MAX_BOXES} boxes one NMS call "
-                           "takes (64 KiB of LDS for the suppression bitmap); a trained detector keeps a few thousand -- untrained weights?")
-    cand = dets[:n]
+    reach = n if pre_nms_topk is None else min(n, int(pre_nms_topk))  # what the suppression step is given
+    if reach > ops.NMS_MAX_BOXES:
+        raise RuntimeError(f"get_detections: {reach} candidates above prob_thresh={prob_thresh} exceed the {ops.NMS_MAX_BOXES} boxes one NMS call "
+                           "takes (64 KiB of LDS for the suppression bitmap); a trained detector keeps a few thousand -- untrained weights?  "
+                           "pre_nms_topk=K bounds what reaches the NMS without touching prob_thresh")
+    full = dets[:n]
+    if soft_nms is not None and reach > ops.SOFT_NMS_MAX_BOXES:
+        raise RuntimeError(f"get_detections: {reach} candidates above prob_thresh={prob_thresh} exceed the {ops.SOFT_NMS_MAX_BOXES} boxes one "
+                           f"Soft-NMS call takes (the hard NMS takes {ops.NMS_MAX_BOXES}): pass pre_nms_topk <= {ops.SOFT_NMS_MAX_BOXES}, "
+                           "raise prob_thresh or use soft_nms=None")
+    cand, offs, idx = _pre_nms_cut(full, [0, n], pre_nms_topk)
     if soft_nms is not None:
-        if n > ops.SOFT_NMS_MAX_BOXES:
-            raise RuntimeError(f"get_detections: {n} candidates above prob_thresh={prob_thresh} exceed the {ops.SOFT_NMS_MAX_BOXES} boxes one "
-                               f"Soft-NMS call takes (the hard NMS takes {ops.NMS_MAX_BOXES}): raise prob_thresh or use soft_nms=None")
-        keep, rows = _soft_nms_rows(cand, [0, n], soft_nms, nms_thresh, soft_nms_sigma, soft_nms_score_thresh, box_voting)
+        keep, rows = _soft_nms_rows(cand, offs, soft_nms, nms_thresh, soft_nms_sigma, soft_nms_score_thresh, box_voting, max_detections)
         keep, result = keep[0], rows[0].cpu().numpy()
     elif box_voting is None:
         keep = ops.nms(cand[:, :4].contiguous(), cand[:, 4].contiguous(), nms_thresh)      # :80-84
+        if max_detections is not None:
+            keep = keep[:max_detections]
         result = cand[keep].cpu().numpy()
     else:
         # the vote chains behind the NMS on its device-side keep count: still one synchronisation
-        keeps, voted = ops.nms_batched(cand[:, :4].contiguous(), cand[:, 4].contiguous(), [0, n], nms_thresh, vote=(box_voting, "sigmoid"))
-        keep, result = keeps[0], voted[0].cpu().numpy()
+        keeps, voted = ops.nms_batched(cand[:, :4].contiguous(), cand[:, 4].contiguous(), offs, nms_thresh, vote=(box_voting, "sigmoid"))
+        keep, rows = keeps[0], voted[0]
+        if max_detections is not None:
+            keep, rows = keep[:max_detections], rows[:max_detections]
+        result = rows.cpu().numpy()
     if return_candidates:
-        return result, cand.cpu().numpy(), keep.cpu().numpy()
+        if idx is not None:
+            keep = idx[keep]                                          # back to rows of the full candidate list
+        return result, full.cpu().numpy(), keep.cpu().numpy()
     return result
 
 
 def get_detections_batch(model, imgs, templates, rf, img_transforms, prob_thresh=0.65, nms_thresh=0.3, scales=(-2, -1, 0, 1),
-                         device=None, mask_axis="w", pyramid_on_gpu=False, flip=False, box_voting=None,
-                         soft_nms=None, soft_nms_sigma=0.5, soft_nms_score_thresh=0.001):
+                         device=None, mask_axis="w", pyramid_on_gpu=False, pre_nms_topk=None, max_detections=None, flip=False,
+                         box_voting=None, soft_nms=None, soft_nms_sigma=0.5, soft_nms_score_thresh=0.001):
     """`[get_detections(model, img, ...) for img in imgs]` (evaluation.py:20-87 once per image, as evaluate_model.py:60-68 does) with
     the per-image NMS calls batched: every image's multi-scale candidates go into ONE device list, the per-image segments are
     suppressed by ONE tf_nms_f64_batched call (three launches whatever the number of images; BASELINE.json configs[4]) and the
     only host synchronisation of the whole batch is the read of the candidate counts.  Row for row identical to the loop.
     flip / box_voting: as in get_detections; an image's mirrored candidates follow its unmirrored ones, so its segment stays contiguous.
-    soft_nms / soft_nms_sigma / soft_nms_score_thresh: as in get_detections, one tf_soft_nms_f64_batched call over the per-image segments."""
+    soft_nms / soft_nms_sigma / soft_nms_score_thresh: as in get_detections, one tf_soft_nms_f64_batched call over the per-image segments.
+    pre_nms_topk / max_detections: as in get_detections, per image: one tf_topk_select_f64_batched call cuts every image's segment that is
+    longer than pre_nms_topk, behind the one synchronisation the call already has."""
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
         raise RuntimeError("get_detections_batch: the detector only runs on MI355X (no CPU fallback)")
     _check_soft_nms(soft_nms, nms_thresh, soft_nms_sigma, soft_nms_score_thresh)
+    _check_limits(pre_nms_topk, max_detections)
     imgs = list(imgs)
     if not 1 <= len(imgs) <= ops.NMS_MAX_SEGMENTS:
         raise ValueError(f"get_detections_batch: 1..{ops.NMS_MAX_SEGMENTS} images per call, got {len(imgs)}")
@@ -228,21 +277,26 @@ def get_detections_batch(model, imgs, templates, rf, img_transforms, prob_thresh
             _decode_image(model, levels, flip, templates, t_d, rf, prob_thresh, mask_axis, dets, count, device)
             marks[i + 1:i + 2].copy_(count, non_blocking=True)        # segment boundary, recorded on the stream
     offs = marks.tolist()                                             # the one sync
-    if max(b - a for a, b in zip(offs, offs[1:])) > ops.NMS_MAX_BOXES:
-        raise RuntimeError(f"get_detections_batch: an image has more than {ops.NMS_MAX_BOXES} candidates above prob_thresh={prob_thresh}")
-    cand = dets[:offs[-1]]
+    longest = max(b - a for a, b in zip(offs, offs[1:]))
+    if pre_nms_topk is not None:
+        longest = min(longest, int(pre_nms_topk))                     # what the suppression step is given
+    if longest > ops.NMS_MAX_BOXES:
+        raise RuntimeError(f"get_detections_batch: an image has more than {ops.NMS_MAX_BOXES} candidates above prob_thresh={prob_thresh}; "
+                           "pre_nms_topk=K bounds what reaches the NMS without touching prob_thresh")
+    if soft_nms is not None and longest > ops.SOFT_NMS_MAX_BOXES:
+        raise RuntimeError(f"get_detections_batch: an image has {longest} candidates above prob_thresh={prob_thresh}, more than the "
+                           f"{ops.SOFT_NMS_MAX_BOXES} boxes one Soft-NMS call takes (the hard NMS takes {ops.NMS_MAX_BOXES}): pass "
+                           f"pre_nms_topk <= {ops.SOFT_NMS_MAX_BOXES}")
+    cand, offs, _ = _pre_nms_cut(dets[:offs[-1]], offs, pre_nms_topk)
     if soft_nms is not None:
-        longest = max(b - a for a, b in zip(offs, offs[1:]))
-        if longest > ops.SOFT_NMS_MAX_BOXES:
-            raise RuntimeError(f"get_detections_batch: an image has {longest} candidates above prob_thresh={prob_thresh}, more than the "
-                               f"{ops.SOFT_NMS_MAX_BOXES} boxes one Soft-NMS call takes (the hard NMS takes {ops.NMS_MAX_BOXES})")
-        _, rows = _soft_nms_rows(cand, offs, soft_nms, nms_thresh, soft_nms_sigma, soft_nms_score_thresh, box_voting)
+        _, rows = _soft_nms_rows(cand, offs, soft_nms, nms_thresh, soft_nms_sigma, soft_nms_score_thresh, box_voting, max_detections)
         return [r.cpu().numpy() for r in rows]
+    M = max_detections                                                # None: the whole keep list, as before
     if box_voting is not None:
         _, voted = ops.nms_batched(cand[:, :4].contiguous(), cand[:, 4].contiguous(), offs, nms_thresh, vote=(box_voting, "sigmoid"))
-        return [v.cpu().numpy() for v in voted]
+        return [v[:M].cpu().numpy() for v in voted]
     keeps = ops.nms_batched(cand[:, :4].contiguous(), cand[:, 4].contiguous(), offs, nms_thresh)
-    return [cand[k].cpu().numpy() for k in keeps]
+    return [cand[k[:M]].cpu().numpy() for k in keeps]
 
 
 def write_results(dets, img_path, split, results_dir=None):

@@ -334,6 +334,13 @@ def _soft_nms_mode(method, iou_threshold, sigma, score_threshold, score):
     return SOFT_NMS_METHODS[method], t, sg, st, VOTE_WEIGHTS[score]
 
 
+def _max_keep(max_keep, what):
+    """The cap of the *_capped forms: a positive integer."""
+    if isinstance(max_keep, bool) or not isinstance(max_keep, (int, np.integer)) or max_keep < 1:
+        raise ValueError(f"{what}: max_keep={max_keep!r}, expected an integer >= 1")
+    return min(int(max_keep), 2**31 - 1)
+
+
 def soft_nms(boxes, scores, method="linear", iou_threshold=0.3, sigma=0.5, score_threshold=0.001, score="sigmoid"):
     """Soft-NMS (Bodla et al., ICCV 2017; Detectron's soft_nms) on float64 device tensors, tf_soft_nms_f64: the best live candidate is
     selected, every live candidate that overlaps it is decayed -- "linear": s *= 1 - IoU where IoU > iou_threshold; "gaussian":
@@ -345,6 +352,23 @@ def soft_nms(boxes, scores, method="linear", iou_threshold=0.3, sigma=0.5, score
     return res[0]
 
 
+def soft_nms_capped(boxes, scores, max_keep, method="linear", iou_threshold=0.3, sigma=0.5, score_threshold=0.001, score="sigmoid"):
+    """`soft_nms` whose selection stops after max_keep rows (tf_soft_nms_f64_capped): the first max_keep rows of the uncapped call, bit for
+    bit, without the serial rounds behind them.  A form of its own: the signature of `soft_nms` stays as it is."""
+    _max_keep(max_keep, "soft_nms_capped")
+    require_gpu(boxes, "soft_nms_capped")
+    res = soft_nms_batched_capped(boxes, scores, [0, int(boxes.shape[0])], max_keep, method, iou_threshold, sigma, score_threshold, score)
+    return res[0]
+
+
+def soft_nms_batched_capped(boxes, scores, seg_offsets, max_keep, method="linear", iou_threshold=0.3, sigma=0.5, score_threshold=0.001,
+                            score="sigmoid", mask_budget_bytes=None, vote=None):
+    """`soft_nms_batched` with every segment's selection stopped after max_keep rows (tf_soft_nms_f64_batched_capped); a chained vote sees the
+    capped counts on the device."""
+    cap = _max_keep(max_keep, "soft_nms_batched_capped")
+    return _soft_nms_segments(boxes, scores, seg_offsets, method, iou_threshold, sigma, score_threshold, score, mask_budget_bytes, vote, cap)
+
+
 def soft_nms_batched(boxes, scores, seg_offsets, method="linear", iou_threshold=0.3, sigma=0.5, score_threshold=0.001, score="sigmoid",
                      mask_budget_bytes=None, vote=None):
     """`soft_nms` per segment [seg_offsets[s], seg_offsets[s+1]) in one tf_soft_nms_f64_batched call per group of consecutive segments whose
@@ -353,6 +377,11 @@ def soft_nms_batched(boxes, scores, seg_offsets, method="linear", iou_threshold=
     vote = (vote_thresh, weight): `box_voting_batched` is enqueued behind the selection on its device-side keep list and counts, before the
     one synchronisation; the vote's weights and membership use the candidates' ORIGINAL scores, column 4 of a voted row is the Soft-NMS
     score.  Returns (the list above, [(K_s, 5) voted rows in selection order])."""
+    return _soft_nms_segments(boxes, scores, seg_offsets, method, iou_threshold, sigma, score_threshold, score, mask_budget_bytes, vote, 0)
+
+
+def _soft_nms_segments(boxes, scores, seg_offsets, method, iou_threshold, sigma, score_threshold, score, mask_budget_bytes, vote, cap):
+    """`soft_nms_batched` (cap = 0) and `soft_nms_batched_capped` (cap = max_keep)."""
     require_gpu(boxes, "soft_nms_batched")
     require_gpu(scores, "soft_nms_batched")
     mode = _soft_nms_mode(method, iou_threshold, sigma, score_threshold, score)
@@ -375,7 +404,7 @@ def soft_nms_batched(boxes, scores, seg_offsets, method="linear", iou_threshold=
     for s in range(S + 1):
         if s == S or (s > first and acc + sizes[s] > budget):
             a = offs[first]
-            calls.append((first, s, _soft_nms_call(boxes[a:offs[s]], scores[a:offs[s]], [o - a for o in offs[first:s + 1]], mode, vote)))
+            calls.append((first, s, _soft_nms_call(boxes[a:offs[s]], scores[a:offs[s]], [o - a for o in offs[first:s + 1]], mode, vote, cap)))
             first, acc = s, 0
         if s < S:
             acc += sizes[s]
@@ -391,8 +420,8 @@ def soft_nms_batched(boxes, scores, seg_offsets, method="linear", iou_threshold=
     return res if vote is None else (res, rows)
 
 
-def _soft_nms_call(boxes, scores, offs, mode, vote):
-    """One tf_soft_nms_f64_batched call [+ the chained vote] on contiguous float64 operands; nothing is synchronised.  Returns the raw
+def _soft_nms_call(boxes, scores, offs, mode, vote, cap=0):
+    """One tf_soft_nms_f64_batched[_capped] call [+ the chained vote] on contiguous float64 operands; nothing is synchronised.  Returns the raw
     (keep (n,), kept scores (n,), counts (S,), voted rows (n, 5) or None): only the first counts[s] rows of a segment are written."""
     method, t, sigma, st, smode = mode
     S, n, dev = len(offs) - 1, offs[-1], boxes.device
@@ -403,13 +432,65 @@ def _soft_nms_call(boxes, scores, offs, mode, vote):
     wsb = lib().tf_soft_nms_batched_workspace_bytes(host, S)
     ws = _workspace("soft_nms", wsb, dev)
     with torch.cuda.device(dev):
-        check(lib().tf_soft_nms_f64_batched(ptr(boxes), ptr(scores), host, S, method, t, sigma, st, smode, ptr(keep), ptr(kept), ptr(cnt),
-                                            ptr(ws), wsb, stream()), "tf_soft_nms_f64_batched")
+        if cap:
+            check(lib().tf_soft_nms_f64_batched_capped(ptr(boxes), ptr(scores), host, S, method, t, sigma, st, smode, cap, ptr(keep), ptr(kept),
+                                                       ptr(cnt), ptr(ws), wsb, stream()), "tf_soft_nms_f64_batched_capped")
+        else:
+            check(lib().tf_soft_nms_f64_batched(ptr(boxes), ptr(scores), host, S, method, t, sigma, st, smode, ptr(keep), ptr(kept), ptr(cnt),
+                                                ptr(ws), wsb, stream()), "tf_soft_nms_f64_batched")
     voted = None
     if vote is not None:
         voted = _box_vote_launch(boxes, scores, host, S, keep, cnt, vote[0], vote[1])[0]
         voted[:, 4] = kept                                    # the vote kernel wrote the original score there; rows >= counts[s] hold nothing either way
     return keep, kept, cnt, voted
+
+
+# --------------------------------------------------------------------------- top-k selection in front of the suppression
+def _topk_arguments(scores, seg_offsets, k, what):
+    """The host-side refusals of tf_topk_select_f64_batched, raised before anything is enqueued (and before a device is asked for)."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError(f"{what}: k={k!r}, expected an integer >= 1")
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 1:
+        raise ValueError(f"{what}: scores is a 1-d tensor of one score per candidate")
+    offs = [int(o) for o in seg_offsets]
+    S = len(offs) - 1
+    if S < 1 or S > NMS_MAX_SEGMENTS or offs[0] != 0 or any(b < a for a, b in zip(offs, offs[1:])) or offs[-1] != scores.shape[0]:
+        raise ValueError(f"{what}: bad segment offsets {offs[:4]}... for {scores.shape[0]} scores (1..{NMS_MAX_SEGMENTS} segments)")
+    if offs[-1] > 2**31 - 1:
+        raise ValueError(f"{what}: {offs[-1]} scores exceed the int32 segment offsets")
+    k = min(int(k), 2**31 - 1)
+    new = [0]
+    for a, b in zip(offs, offs[1:]):
+        new.append(new[-1] + min(b - a, k))
+    return offs, k, new
+
+
+def topk_select_batched(scores, seg_offsets, k):
+    """Per segment [seg_offsets[s], seg_offsets[s+1]) of the float64 device tensor `scores`: the min(n_s, k) candidates that come first in
+    the hard NMS's own order -- larger score, the lower index on a tie (-0.0 == +0.0), NaN behind every number -- as int64 indices into the
+    CONCATENATED input in ASCENDING index order (tf_topk_select_f64_batched: a radix select, linear in n, the same bits on every run).
+    Returns (idx, new_offsets): segment s of the compacted list is idx[new_offsets[s]: new_offsets[s+1]]; gather rows with index_select.
+    Nothing is synchronised.  When no segment is longer than k nothing is launched and idx is None (the list is its own top-k)."""
+    offs, k, new = _topk_arguments(scores, seg_offsets, k, "topk_select_batched")
+    require_gpu(scores, "topk_select_batched")
+    if new == offs:
+        return None, new
+    scores = scores.to(torch.float64).contiguous()
+    S, dev = len(offs) - 1, scores.device
+    idx = torch.empty(new[-1], dtype=torch.int64, device=dev)
+    host = (C.c_int32 * (S + 1))(*offs)
+    wsb = lib().tf_topk_batched_workspace_bytes(host, S, k)
+    ws = _workspace("topk", wsb, dev)
+    with torch.cuda.device(dev):
+        check(lib().tf_topk_select_f64_batched(ptr(scores), host, S, k, ptr(idx), ptr(ws), wsb, stream()), "tf_topk_select_f64_batched")
+    return idx, new
+
+
+def topk_select(scores, k):
+    """`topk_select_batched` for one candidate list -> (idx int64 (min(n, k),) ascending, or None when n <= k; [0, min(n, k)])."""
+    n = int(scores.shape[0]) if isinstance(scores, torch.Tensor) and scores.dim() == 1 else 0
+    offs, k, new = _topk_arguments(scores, [0, n], k, "topk_select")
+    return topk_select_batched(scores, offs, k)
 
 
 # --------------------------------------------------------------------------- decode
