@@ -825,6 +825,39 @@ typedef struct tf_image_prepare_args {
 } tf_image_prepare_args;
 int tf_image_prepare(const tf_image_prepare_args* a, void* stream);
 
+/* ---- f1: colour jitter between the augmented uint8 image and ToTensor + Normalize ---------------------------------------
+ * torchvision.transforms.ColorJitter acting on the PIL image that the reference's process_inputs returns (the pasted, flipped
+ * OH x OW image, mean-colour padding included), i.e. Pillow's ImageEnhance plus an HSV round trip, restated in integers and
+ * float32 (tests/color_jitter_ref.py is the same arithmetic in numpy, pinned to Pillow by tests/test_color_jitter.py).
+ * Every op maps a uint8 RGB image to a uint8 RGB image; f32(.) rounds to float32, nothing is contracted into an FMA:
+ *   blend(d, x, f)   t = f32(d) + f32(f) * (f32(x) - f32(d)); 0 <= f <= 1: t truncated; else 0 if t <= 0, 255 if t >= 255, else t truncated
+ *   L(r, g, b)       (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16
+ *   brightness(f)    blend(0, x, f)
+ *   saturation(f)    blend(L(pixel), x, f) on the three channels
+ *   contrast(f)      blend(m, x, f), m = (2 S + n) / (2 n) in integers (= floor(S / n + 0.5)), S = the sum of L over the n = OH * OW
+ *                    pixels of the image as it stands at that point of the chain
+ *   hue(shift)       RGB -> HSV (Pillow's rgb2hsv: float32 s and rc / gc / bc, h through double), h = (h + shift) & 255, HSV -> RGB
+ *                    (Pillow's hsv2rgb, evaluated in DOUBLE here: fh = h * 6.0 / 255.0, fs = s / 255.0, floor(x + 0.5) rounding).
+ *                    A shift of 0 still makes the round trip, which is not the identity.
+ * op[i] is one of TF_JITTER_*, each kind at most once, applied in the order given; factor[i] >= 0 is the enhancement factor, for
+ * TF_JITTER_HUE the integer shift 0 ... 255.  n_ops = 0 runs the plain pass.
+ * Launches: a chain without contrast is ONE launch (resample, the chain in registers, normalise; `ws` is not touched and may be NULL).
+ * A chain with contrast is TWO: the first applies the ops in front of contrast, writes the uint8 image to `ws` and one integer partial
+ * sum of L per block; the second sums the partials (integers: no order dependence), applies contrast and the rest, normalises.
+ * No memset, no atomics, no host sync: the first launch writes every word the second reads.
+ * Workspace: tf_image_prepare_jitter_workspace_bytes(OH, OW, n_ops, op) = 0 without contrast, else
+ *   round_up(4 * ceil(OW / 64) * ceil(OH / 4), 256) + 3 * OH * OW.
+ * Refused before anything is enqueued (TF_ERR_ARG; TF_ERR_WORKSPACE for a workspace that is too small): what tf_image_prepare refuses,
+ * n_ops outside 0 ... 4, an unknown or repeated kind, a negative or non-finite factor, a hue shift that is no integer in 0 ... 255,
+ * OH * OW > 2^24 (the bound up to which the integer mean equals Pillow's double form). */
+#define TF_JITTER_BRIGHTNESS 0
+#define TF_JITTER_CONTRAST 1
+#define TF_JITTER_SATURATION 2
+#define TF_JITTER_HUE 3
+size_t tf_image_prepare_jitter_workspace_bytes(int OH, int OW, int n_ops, const int* op);
+int tf_image_prepare_jitter(const tf_image_prepare_args* a, int n_ops, const int* op /*[n_ops]*/, const float* factor /*[n_ops]*/,
+                            void* ws, size_t ws_bytes, void* stream);
+
 /* ---- measurement hooks (bench.py `roofline`) ------------------------------------------
  * While enabled, every MFMA kernel launch (conv_igemm / wgrad) is bracketed by HIP events on
  * the stream it is launched on.  tf_profile_collect blocks until they completed and writes

@@ -19,6 +19,7 @@
 #   tta                        cost of the test-time augmentation: vote vs NMS kernels, pyramid with / without flip and voting (scripts/tta_numbers.py) -> $TTA_OUT (default profiles/tta.jsonl)
 #   soft-nms                   cost of Soft-NMS: kernels vs the hard NMS at 65 536 candidates, pyramid plain / linear / gaussian, parity (scripts/soft_nms_numbers.py) -> $SOFT_NMS_OUT (default profiles/soft_nms.jsonl)
 #   topk                       cost of the pre-NMS top-k and the detection cap: select + NMS vs the full NMS at 65 536 / 600 000 candidates, Soft-NMS capped vs uncapped, pyramid plain / soft / soft + both bounds (scripts/topk_numbers.py) -> $TOPK_OUT (default profiles/topk.jsonl)
+#   color-jitter               cost of the colour jitter: image_prepare plain / three ops / four ops / contrast alone on the 500x500 window, batch building with / without it (scripts/color_jitter_numbers.py) -> $COLOR_JITTER_OUT (default profiles/color_jitter.jsonl)
 #   dist-smoke                 RCCL 1-rank group, 2 gloo ranks on one GPU, 2 nccl ranks on one GPU (expected refusal) -> gpurun_out/dist_smoke.txt
 #   final                      tests + bench + prof + pmc-traffic + layer-table + timeline + eval prof + smoke: the artefacts of a round
 set -u
@@ -103,6 +104,11 @@ print(d['value'], d['ms_per_step'], 'frac', r.get('frac'), 'fwd', r.get('forward
     timeout -k 10 ${TOPK_TIMEOUT:-300} python scripts/topk_numbers.py --step kernels > "$out" 2> "$err" &&
       timeout -k 10 ${TOPK_TIMEOUT:-300} python scripts/topk_numbers.py --step pyramid >> "$out" 2>> "$err"
     echo "topk exit $?"; cat "$out"; tail -3 "$err" ;;
+  color-jitter)   # one process and one time limit per step; the second step only behind a clean first one
+    out=${COLOR_JITTER_OUT:-$R/profiles/color_jitter.jsonl}; err=${out%.jsonl}.err
+    timeout -k 10 ${COLOR_JITTER_TIMEOUT:-300} python scripts/color_jitter_numbers.py --step kernels > "$out" 2> "$err" &&
+      timeout -k 10 ${COLOR_JITTER_TIMEOUT:-300} python scripts/color_jitter_numbers.py --step batch >> "$out" 2>> "$err"
+    echo "color-jitter exit $?"; cat "$out"; tail -3 "$err" ;;
   dist-smoke) bash scripts/gpu_dist_smoke.sh ;;
   final)
     # the profile passes FIRST: bench.py quotes the committed kernel-stats / PMC files, so they are refreshed in the box's copy of profiles/

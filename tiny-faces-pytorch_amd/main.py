@@ -6,7 +6,7 @@
 
 Additions (existing flags keep their names and defaults): --fused / --no-fused (TrainEngine vs torch.optim.SGD through
 autograd), --dtype bf16|fp32, --synthetic-len.  The schedule is the reference's: SGD(momentum, weight decay), StepLR(20),
-a checkpoint every --save-every epochs (main.py:39-104); --optimizer adamw and --warmup-iters are opt-in."""
+a checkpoint every --save-every epochs (main.py:39-104); --optimizer adamw, --warmup-iters and --color-jitter are opt-in."""
 import argparse
 import math
 import os
@@ -121,6 +121,18 @@ WARMUP_HELP = ("--warmup-iters N: linear learning-rate warm-up over the first N 
                "of step 0, 0 < F <= 1, default 1e-3")
 
 
+JITTER_HELP = ("--color-jitter B C S H: torchvision's ColorJitter(brightness=B, contrast=C, saturation=S, hue=H) on every training image between the "
+               "augmentation and ToTensor (brightness, contrast and saturation factors from [max(0, 1 - x), 1 + x], the hue factor from [-H, H], the four "
+               "ops in a random order; computed on the device), four finite numbers >= 0 with H <= 0.5, default off")
+
+
+def _jitter_amplitude(text):
+    value = float(text)
+    if not (math.isfinite(value) and value >= 0.0):
+        raise argparse.ArgumentTypeError(f"must be a finite number >= 0, got {text}")
+    return value
+
+
 def _adam_beta(text):
     value = float(text)
     if not (math.isfinite(value) and 0.0 <= value < 1.0):
@@ -193,7 +205,7 @@ def _positive_float(text):
 
 
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP)))
+    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP, JITTER_HELP)))
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
@@ -205,7 +217,7 @@ def trunk_arguments(argv=None):
     from --accum-average, `cls_loss` ("soft_margin" | "focal") from --cls-loss, `focal_gamma`, `focal_alpha` and `focal_normalize` from
     --focal-gamma, --focal-alpha and --focal-normalize, `reg_loss` ("smooth_l1" | "iou" | "giou" | "diou") from --reg-loss and `reg_weight` from
     --reg-weight, `optimizer` ("sgd" | "adamw"), `adam_beta1`, `adam_beta2` and `adam_eps` from --optimizer, --adam-beta1, --adam-beta2 and --adam-eps,
-    `warmup_iters` and `warmup_factor` from --warmup-iters and --warmup-factor.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
+    `warmup_iters` and `warmup_factor` from --warmup-iters and --warmup-factor, `color_jitter` (None or the four amplitudes) from --color-jitter.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
     options and the additions above."""
     parser = argparse.ArgumentParser(add_help=False)
     parser.add_argument("--base-model", dest="base_model", default="resnet101", choices=list(model_zoo.TRUNKS), help=TRUNK_HELP)
@@ -228,7 +240,10 @@ def trunk_arguments(argv=None):
     parser.add_argument("--adam-eps", dest="adam_eps", default=1e-8, type=_adam_eps, metavar="E", help=OPTIMIZER_HELP)
     parser.add_argument("--warmup-iters", dest="warmup_iters", default=0, type=_warmup_iters, metavar="N", help=WARMUP_HELP)
     parser.add_argument("--warmup-factor", dest="warmup_factor", default=1e-3, type=_warmup_factor, metavar="F", help=WARMUP_HELP)
+    parser.add_argument("--color-jitter", dest="color_jitter", default=None, type=_jitter_amplitude, nargs=4, metavar=("B", "C", "S", "H"), help=JITTER_HELP)
     known, rest = parser.parse_known_args(argv)
+    if known.color_jitter is not None and known.color_jitter[3] > 0.5:
+        parser.error(f"--color-jitter: the hue amplitude H must be <= 0.5, got {known.color_jitter[3]:g}")
     if known.trainable_layers < 4 and not known.freeze_bn:
         parser.error(f"--trainable-layers {known.trainable_layers} freezes stages of the trunk, which is defined on frozen BatchNorm only: add --freeze-bn")
     if known.reg_loss != "smooth-l1" and known.cls_loss != "focal":
@@ -251,7 +266,16 @@ def trunk_arguments(argv=None):
     args.optimizer = known.optimizer
     args.adam_beta1, args.adam_beta2, args.adam_eps = known.adam_beta1, known.adam_beta2, known.adam_eps
     args.warmup_iters, args.warmup_factor = known.warmup_iters, known.warmup_factor
+    args.color_jitter = None if known.color_jitter is None else tuple(known.color_jitter)
     return args
+
+
+def jitter_description(args):
+    """The colour jitter as the start-up line prints it."""
+    cj = getattr(args, "color_jitter", None)
+    if cj is None:
+        return "colour jitter off"
+    return f"colour jitter brightness {cj[0]:g}, contrast {cj[1]:g}, saturation {cj[2]:g}, hue {cj[3]:g} (on the device, in front of ToTensor)"
 
 
 def loss_description(args):
@@ -327,7 +351,7 @@ def main():
     parallel.init_from_env(os.environ.get("TINYFACES_DIST_BACKEND"))      # (gloo: several ranks on one device, the functional tests of a 1-GPU box)
     device = torch.device("cuda", torch.cuda.current_device())
     preprocess = transforms.Compose([transforms.ToTensor(), transforms.Normalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225])])
-    train_loader, _ = get_dataloader(args.traindata, args, NUM_TEMPLATES, img_transforms=preprocess)
+    train_loader, _ = get_dataloader(args.traindata, args, NUM_TEMPLATES, img_transforms=preprocess, color_jitter=args.color_jitter)
     model = DetectionModel(base_model=getattr(model_zoo, args.base_model), num_objects=1, num_templates=NUM_TEMPLATES).set_compute_dtype(args.dtype)
     model.freeze_batchnorm(args.freeze_bn).set_trainable_layers(args.trainable_layers)
     if parallel.rank() == 0:
@@ -341,6 +365,7 @@ def main():
     loss_fn.ohem_thresh = args.ohem_thresh
     if parallel.rank() == 0:
         print(loss_description(args))
+        print(jitter_description(args))
         if args.cls_loss == "focal":
             print("--ohem-thresh is unused with --cls-loss focal: nothing is mined or sampled")
 

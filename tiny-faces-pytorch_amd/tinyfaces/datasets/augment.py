@@ -5,7 +5,10 @@ Division of labour: the random decisions (scale, crop origin, paste origin, flip
 dozen floats per image and stay on the host, drawn from np.random in the reference's order so that a seeded run makes the
 same decisions; the pixels -- resize, crop, paste on the mean colour, flip, ToTensor + Normalize -- are ONE HIP kernel per
 image (ops.image_prepare) that only resamples the 500x500 window instead of resizing the whole image on the CPU.
-The output tensor is bit-identical to the reference's CPU pipeline followed by main.py:44-46's transforms."""
+The output tensor is bit-identical to the reference's CPU pipeline followed by main.py:44-46's transforms.
+
+Optional colour jitter (`color_jitter=(b, c, s, h)`, off by default): torchvision's ColorJitter on the augmented uint8 image in front of
+ToTensor, computed inside the same launch(es) (ops.image_prepare(jitter=)); its order and factors are drawn here, after the flip draw."""
 from copy import deepcopy
 
 import numpy as np
@@ -64,13 +67,52 @@ def crop_decisions(img_h, img_w, bboxes, input_size=(500, 500), neg_thresh=0.3, 
     return (crop_y1, crop_x1, crop_h, crop_w), paste, bboxes
 
 
+JITTER_ORDER = ("brightness", "contrast", "saturation", "hue")      # ColorJitter's numbering of its four ops
+
+
+def check_color_jitter(color_jitter):
+    """None, or the four amplitudes (brightness, contrast, saturation, hue) of torchvision's ColorJitter as a tuple of floats: finite, >= 0,
+    hue <= 0.5."""
+    if color_jitter is None:
+        return None
+    try:
+        amps = tuple(float(v) for v in color_jitter)
+    except (TypeError, ValueError):
+        raise ValueError(f"color_jitter: expected four numbers (brightness, contrast, saturation, hue), got {color_jitter!r}")
+    if len(amps) != 4:
+        raise ValueError(f"color_jitter: expected four numbers (brightness, contrast, saturation, hue), got {color_jitter!r}")
+    for name, a in zip(JITTER_ORDER, amps):
+        if not (np.isfinite(a) and a >= 0.0):
+            raise ValueError(f"color_jitter: the {name} amplitude must be finite and >= 0, got {a}")
+    if amps[3] > 0.5:
+        raise ValueError(f"color_jitter: the hue amplitude must be <= 0.5, got {amps[3]}")
+    return amps
+
+
+def draw_color_jitter(color_jitter, rng=np.random):
+    """The chain [(kind, factor)] of one image: order = rng.permutation(4), then one rng.uniform for each of brightness, contrast, saturation,
+    hue whose amplitude a is > 0 -- from [max(0, 1 - a), 1 + a], for the hue from [-a, a] -- and the drawn ops in `order`.  An amplitude of 0
+    draws nothing and applies nothing."""
+    amps = check_color_jitter(color_jitter)
+    order = rng.permutation(4)
+    factors = {}
+    for k, (name, a) in enumerate(zip(JITTER_ORDER, amps)):
+        if a > 0.0:
+            factors[k] = float(rng.uniform(-a, a) if name == "hue" else rng.uniform(max(0.0, 1.0 - a), 1.0 + a))
+    return [(JITTER_ORDER[k], factors[k]) for k in order.tolist() if k in factors]
+
+
 def process_inputs(image_u8, bboxes, input_size=(500, 500), neg_thresh=0.3, rng=np.random, out=None, mean=ops.IMAGE_MEAN,
-                   std=ops.IMAGE_STD):
+                   std=ops.IMAGE_STD, color_jitter=None, chain_out=None):
     """WIDERFace.process_inputs up to get_heatmaps, for a decoded uint8 (H, W, 3) image that is already on the device.
     Returns (x float32 (3, ih, iw) device tensor = Normalize(ToTensor(augmented image)), bboxes float64 (G', 4),
-    paste_box [x1, y1, x2, y2], flip) -- paste_box / flip are what ops.dense_overlap_targets* take for the padding mask."""
+    paste_box [x1, y1, x2, y2], flip) -- paste_box / flip are what ops.dense_overlap_targets* take for the padding mask.
+    color_jitter = (b, c, s, h): torchvision's ColorJitter(b, c, s, h) on the augmented uint8 image in front of ToTensor, in the same launch
+    (ops.image_prepare(jitter=)); its draws (draw_color_jitter) come AFTER the flip draw and only when it is not None, so a seeded run without it
+    makes the decisions it always made.  chain_out: a list that receives the drawn [(kind, factor)] chain."""
     if not image_u8.is_cuda:
         raise RuntimeError("process_inputs: the image must be on the GPU (no CPU fallback for the hot path)")
+    color_jitter = check_color_jitter(color_jitter)
     H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
     bboxes = np.array(bboxes, dtype=np.float64).reshape(-1, 4)
     rnd = rng.rand()                                             # wider_face.py:135
@@ -87,8 +129,13 @@ def process_inputs(image_u8, bboxes, input_size=(500, 500), neg_thresh=0.3, rng=
         lx1, lx2 = np.array(bboxes[:, 0]), np.array(bboxes[:, 2])
         bboxes[:, 0] = input_size[1] - lx2 + 1
         bboxes[:, 2] = input_size[1] - lx1 + 1
+    chain = None
+    if color_jitter is not None:
+        chain = draw_color_jitter(color_jitter, rng)
+        if chain_out is not None:
+            chain_out[:] = chain
     x = ops.image_prepare(image_u8, resized_hw=(rh, rw), crop=crop, paste=(paste[1], paste[0]), flip=flip, out_hw=input_size, mean=mean,
-                          std=std, out=out)
+                          std=std, out=out, jitter=chain)
     return x, bboxes, paste, flip
 
 

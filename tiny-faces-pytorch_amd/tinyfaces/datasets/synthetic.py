@@ -163,8 +163,12 @@ class SyntheticFaces(data.Dataset):
     VAL_ZOOM = 1          # evaluation sees the images at their own size: run evaluate_model.py with --mask-axis template (with the reference's mask, defect D1,
                           # the 1/4 level of a 500-pixel image raises IndexError: the mask indexes the 16 heat-map columns with the 25 template indices)
 
-    def __init__(self, templates, length=8, seed=0, train=True, device="cuda", size=(500, 500), img_transforms=None):
+    def __init__(self, templates, length=8, seed=0, train=True, device="cuda", size=(500, 500), img_transforms=None, color_jitter=None):
         self.templates, self.length, self.seed, self.train, self.device, self.size = templates, length, seed, train, device, size
+        # (b, c, s, h) of torchvision's ColorJitter for the training samples: they then travel as uint8 and `collate` jitters + normalises them on the
+        # device (ops.image_prepare(jitter=), chains drawn from np.random per sample); None = off, samples are normalised on the host as before
+        from .augment import check_color_jitter
+        self.color_jitter = check_color_jitter(color_jitter)
         # anchors are positive from IoU 0.7 (like WIDER training, wider_face.py:26) and negative below 0.7 (there: 0.3): with eight layouts the wide "ignored"
         # band of the reference would stay untrained -- its anchors answer with arbitrary scores and unregressed boxes, which an AP at IoU 0.5 counts as misses
         self.assigner = TargetAssigner(templates, seed=seed, pos_thresh=float(os.environ.get("FACES_POS", "0.7")), neg_thresh=float(os.environ.get("FACES_NEG", "0.7")))
@@ -193,7 +197,10 @@ class SyntheticFaces(data.Dataset):
             if (i, v) not in self._views:
                 # view 0 IS the evaluation image of the layout (the judge's "the same images"); the others: backgrounds and zooms of their own
                 u8, boxes = self.samples[i] if v == 0 else self._train_view(np.random.RandomState(self.seed * 104729 + 31 * (v * len(self.samples) + i) + 7), i, v)
-                self._views[(i, v)] = (torch.from_numpy(np.stack([self._LUTN[c][u8[:, :, c]] for c in range(3)])), boxes)
+                if self.color_jitter is not None:
+                    self._views[(i, v)] = (torch.from_numpy(np.ascontiguousarray(u8)), boxes)
+                else:
+                    self._views[(i, v)] = (torch.from_numpy(np.stack([self._LUTN[c][u8[:, :, c]] for c in range(3)])), boxes)
             return self._views[(i, v)]
         # uint8 -> float through 256-entry tables (ToTensor, and ToTensor + Normalize): exactly torch's arithmetic, a fraction of its time on the host
         if not self.train:
@@ -235,7 +242,13 @@ class SyntheticFaces(data.Dataset):
     def collate(self, batch):
         if not self.train:
             return torch.stack([b[0] for b in batch]), [b[1] for b in batch]
-        imgs = _stack_on_device([b[0] for b in batch], self.device)
         H, W = self.size
+        if self.color_jitter is not None:
+            from .augment import draw_color_jitter
+            imgs = torch.empty(len(batch), 3, H, W, dtype=torch.float32, device=self.device)
+            for k, b in enumerate(batch):
+                ops.image_prepare(b[0].to(self.device), mean=self.MEAN, std=self.STD, out=imgs[k], jitter=draw_color_jitter(self.color_jitter))
+        else:
+            imgs = _stack_on_device([b[0] for b in batch], self.device)
         cm, rm = self.assigner([b[1] for b in batch], paste_boxes=[[0, 0, W, H]] * len(batch), device=self.device)
         return imgs, cm, rm

@@ -9,7 +9,8 @@ work moved to the GPU.
                            batch is (img (B,3,500,500), class_map (B,25,63,63), regression_map (B,100,63,63)) as
                            wider_face.py:219-222 + the default collate produce.
   * val / test             image tensor + path, as wider_face.py:224-239.
-np.random is drawn in the reference's per-sample order (scale, crop x/y, paste x/y, flip); the balance sampling inside the
+np.random is drawn in the reference's per-sample order (scale, crop x/y, paste x/y, flip; with `color_jitter` set, the jitter's order and factors
+after the flip); the balance sampling inside the
 target kernel uses the device RNG (documented deviation, see ops.dense_overlap_targets)."""
 from pathlib import Path
 
@@ -70,8 +71,9 @@ def parse_annotations(path, split="train"):
 
 class WIDERFace(dataset.Dataset):
     def __init__(self, path, templates, img_transforms=None, dataset_root="", split="train", input_size=(500, 500),
-                 heatmap_size=(63, 63), pos_thresh=0.7, neg_thresh=0.3, pos_fraction=0.5, debug=False, device="cuda", seed=0):
+                 heatmap_size=(63, 63), pos_thresh=0.7, neg_thresh=0.3, pos_fraction=0.5, debug=False, device="cuda", seed=0, color_jitter=None):
         super().__init__()
+        self.color_jitter = augment.check_color_jitter(color_jitter)      # (b, c, s, h) of torchvision's ColorJitter, applied in `collate`; None = off
         self.split = split
         self.data = parse_annotations(path, split)
         print("Dataset loaded")
@@ -131,7 +133,8 @@ class WIDERFace(dataset.Dataset):
             boxes, pastes, flips = [], [], []
             for i, (img, bb) in enumerate(samples):
                 u8 = torch.from_numpy(img).to(self.device)      # blocking on THIS stream only: the decoded (pageable) array is not ours to keep alive
-                _, b, paste, flip = augment.process_inputs(u8, bb, self.input_size, self.neg_thresh, out=x[i], mean=mean, std=std)
+                _, b, paste, flip = augment.process_inputs(u8, bb, self.input_size, self.neg_thresh, out=x[i], mean=mean, std=std,
+                                                             color_jitter=self.color_jitter)
                 boxes.append(b); pastes.append(paste); flips.append(int(flip))
             self._step += 1
             cm, rm = ops.dense_overlap_targets(boxes, self.templates, self.heatmap_size, self.rf, paste_boxes=pastes, flips=flips,

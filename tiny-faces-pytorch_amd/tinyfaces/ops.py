@@ -4,6 +4,7 @@ Each function is the MI355X replacement of the reference call cited in its docst
 (file:line relative to the reference repo).  PyTorch only supplies memory and streams.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -673,13 +674,43 @@ NMS_MAX_BOXES = 524160                                   # csrc/nms.hip: (n/64 +
 IMAGE_MEAN, IMAGE_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)        # main.py:44-46
 
 
+JITTER_KINDS = {"brightness": 0, "contrast": 1, "saturation": 2, "hue": 3}        # TF_JITTER_* (include/tinyfaces_hip.h)
+JITTER_MAX_PIXELS = 1 << 24
+
+
+def jitter_chain(jitter):
+    """[(kind, factor)] -> ([TF_JITTER_* code], [float factor]) as tf_image_prepare_jitter takes them: every kind at most once, factors finite and
+    >= 0; for "hue" the factor is torchvision's hue_factor in [-0.5, 0.5] and becomes the shift int(hue_factor * 255) mod 256 of the uint8 hue
+    (truncated toward zero, wrapped like its np.uint8)."""
+    codes, factors = [], []
+    for item in jitter:
+        kind, f = item
+        if kind not in JITTER_KINDS:
+            raise ValueError(f"image_prepare: unknown jitter op {kind!r} (one of {sorted(JITTER_KINDS)})")
+        if JITTER_KINDS[kind] in codes:
+            raise ValueError(f"image_prepare: jitter op {kind!r} appears twice")
+        f = float(f)
+        if kind == "hue":
+            if not (math.isfinite(f) and -0.5 <= f <= 0.5):
+                raise ValueError(f"image_prepare: hue factor must be in [-0.5, 0.5], got {f}")
+            f = float(int(f * 255) % 256)
+        elif not (math.isfinite(f) and f >= 0.0):
+            raise ValueError(f"image_prepare: {kind} factor must be finite and >= 0, got {f}")
+        codes.append(JITTER_KINDS[kind])
+        factors.append(f)
+    return codes, factors
+
+
 def image_prepare(img_u8, resized_hw=None, crop=None, paste=(0, 0), flip=False, out_hw=None, mean=IMAGE_MEAN, std=IMAGE_STD,
-                  out=None):
+                  out=None, jitter=None):
     """uint8 (H, W, 3) device image -> normalised float32 (3, OH, OW) device tensor in one HIP pass (tf_image_prepare):
     PIL-exact BILINEAR resize to `resized_hw`, window `crop` = (y, x, h, w) of the resized image pasted at `paste` = (y, x)
     on the mean colour, optional mirror, ToTensor + Normalize.  Defaults: no resize, whole image, out_hw = window size
     (the evaluation pyramid level of tinyfaces/evaluation.py:46-53); training passes the 500x500 crop parameters of
-    tinyfaces/datasets/processor.py:41-76."""
+    tinyfaces/datasets/processor.py:41-76.
+    jitter: a sequence of (kind, factor), kind in "brightness" | "contrast" | "saturation" | "hue", applied in this order to the uint8 OH x OW
+    image (padding included) before ToTensor -- torchvision's ColorJitter on the PIL image, bit for bit (tf_image_prepare_jitter: one launch,
+    two when contrast is in the chain).  None or empty: tf_image_prepare, exactly as without the argument."""
     require_gpu(img_u8, "image_prepare")
     if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3:
         raise ValueError("image_prepare: expected a uint8 (H, W, 3) tensor")
@@ -698,8 +729,24 @@ def image_prepare(img_u8, resized_hw=None, crop=None, paste=(0, 0), flip=False, 
         a.mean[c], a.std[c] = float(mean[c]), float(std[c])
         a.bg[c] = int(np.int8(np.float64(mean[c]) * 255)) & 0xFF          # processor.py:66-71: (mean * 255).astype(int8)
     a.out = ptr(out)
+    if not jitter:
+        with torch.cuda.device(img_u8.device):
+            check(lib().tf_image_prepare(C.byref(a), stream()), "tf_image_prepare")
+        return out
+    codes, factors = jitter_chain(jitter)
+    if OH * OW > JITTER_MAX_PIXELS:
+        raise ValueError(f"image_prepare: jitter is defined for at most 2^24 output pixels, got {OH} x {OW}")
+    n = len(codes)
+    op, fac = (C.c_int * 4)(*codes), (C.c_float * 4)(*factors)
     with torch.cuda.device(img_u8.device):
-        check(lib().tf_image_prepare(C.byref(a), stream()), "tf_image_prepare")
+        st = stream()
+        wsb = lib().tf_image_prepare_jitter_workspace_bytes(OH, OW, n, op)
+        ws = None
+        if wsb:
+            # one buffer per device AND stream: WIDERFace.collate builds its batch on an input stream of its own while another stream may prepare images too
+            ws = _workspace(f"image_jitter@{st}", wsb, img_u8.device)
+            ws.record_stream(torch.cuda.current_stream())
+        check(lib().tf_image_prepare_jitter(C.byref(a), n, op, fac, ptr(ws), wsb, st), "tf_image_prepare_jitter")
     return out
 
 
