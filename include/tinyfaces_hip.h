@@ -200,6 +200,46 @@ int tf_topk_select_f64_batched(const double* scores /*[n]*/, const int32_t* host
 size_t tf_topk_workspace_bytes(int n, int k);
 int tf_topk_select_f64(const double* scores /*[n]*/, int n, int k, int64_t* idx_out /*[min(n, k)]*/, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- WIDER FACE evaluation on the device: matching and the precision / recall table ----------
+ * The device form of tinyfaces/wider_eval.py's image_evaluation and image_pr_info, held to them bit for bit (every output is an integer).
+ * Segments are images: HOST int32 offset tables that start at 0 and never descend, as tf_nms_f64_batched takes them, but with no bound on
+ * the number of segments (the tables ride in the kernel arguments, 256 segments per launch).  Empty segments are legal.
+ *
+ * tf_wider_match_f64_batched.  rows: detections in result-file form (x, y, w, h, score), each segment score-descending (the score is not
+ * read here).  gt: boxes (x, y, w, h) with an offset table of their own over the SAME num_segments.  keep[k][j] != 0: box j counts in
+ * setting k.  Once for all settings, per detection h of an image:
+ *     corners    x + w, y + h: one fp64 addition each, for detections and boxes alike;
+ *     IoU        wider_eval.box_overlap: w = min(x2) - max(x1) + 1, h likewise, 0 when w <= 0 or h <= 0 (decided before the division), else
+ *                inter / ((a + b) - inter) with a, b the +1 areas; every operation rounded on its own (the file is built without FMA
+ *                contraction).  Coordinates are finite numbers;
+ *     best[h]    the box of largest IoU, the LOWEST index on a tie (np.argmax); a match iff that IoU >= iou_thresh.
+ * Per setting k:  proposal[h] = -1 iff h matched a box with keep[k] == 0, else 1;
+ *     counted[k][h]  = #{h' <= h in the segment : proposal[h'] == 1}                       (np.cumsum(proposal == 1))
+ *     recalled[k][h] = #{boxes j with keep[k][j] : some h' <= h matched j}                 (pred_recall)
+ * computed as first[j] = min{h : best[h] == j} (an integer min) and two prefix sums.  An image without boxes matches nothing: counted is
+ * 1, 2, 3, ..., recalled 0.  One 256-thread workgroup per image; the boxes pass through LDS in tiles of TF_WIDER_GT_TILE, so their number
+ * is not bounded by LDS.  Writes counted / recalled rows [0, n) of every setting and the workspace, nothing else; no floating-point
+ * atomics, no grid barrier, no memset, no host synchronisation; the same bits on every run.  ws: tf_wider_match_workspace_bytes(n, g).
+ * TF_ERR_ARG before anything is enqueued: nset < 1, a NaN iou_thresh, num_segments < 1, a NULL table or one that does not start at 0 or
+ * descends, a NULL rows / counted / recalled / ws with n > 0, a NULL gt / keep with g > 0, a short workspace.  n == 0 launches nothing. */
+#define TF_WIDER_GT_TILE 256
+size_t tf_wider_match_workspace_bytes(int n, int g);
+int tf_wider_match_f64_batched(const double* rows /*[n][5]*/, const int32_t* host_det_offsets /*[S+1]*/, const double* gt /*[g][4]*/,
+                               const int32_t* host_gt_offsets /*[S+1]*/, int num_segments, const uint8_t* keep /*[nset][g]*/, int nset,
+                               double iou_thresh, int32_t* counted /*[nset][n]*/, int32_t* recalled /*[nset][n]*/, void* ws, size_t ws_bytes,
+                               void* stream);
+/* tf_wider_pr_accumulate ADDS image_pr_info, summed over the segments, into pr[nset][T][2] (int64; the caller zeroes it once).  scores[n]:
+ * the raw scores under the same detection table, each segment non-increasing.  lo_d: DEVICE double[2] = (lo, d) of norm_scores, so no
+ * host read sits between the matching and the table.  thresh: DEVICE double[T], filled by the host with 1 - (t + 1) / T.  For segment s
+ * and threshold t: r = the last row of s with (scores[r] - lo) / d >= thresh[t] (one fp64 subtraction, one fp64 division: norm_scores'
+ * bits; found by binary search, the normalisation being monotone); if there is one, pr[k][t][0] += counted[k][r] and
+ * pr[k][t][1] += recalled[k][r].  64-bit integer atomics only: the same table in any arrival order.  TF_ERR_ARG as above (nset < 1,
+ * T < 0, a bad table, a NULL operand with n > 0 and T > 0); n == 0 or T == 0 launches nothing. */
+int tf_wider_pr_accumulate(const double* scores /*[n]*/, const int32_t* host_det_offsets /*[S+1]*/, int num_segments,
+                           const int32_t* counted /*[nset][n]*/, const int32_t* recalled /*[nset][n]*/, int nset,
+                           const double* lo_d /*device [2]*/, const double* thresh /*device [T]*/, int num_thresh,
+                           int64_t* pr /*[nset][T][2]*/, void* stream);
+
 /* ---- score map -> boxes: sigmoid + threshold + ORDERED compaction + refinement ------
  * Replaces evaluation.py:61-78 + get_bboxes / regression_refinement
  * (tinyfaces/models/utils.py:4-100).  score [5nt][H][W] f32 (one image, NCHW).

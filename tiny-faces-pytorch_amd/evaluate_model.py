@@ -118,15 +118,87 @@ def _count(flag):
     return parse
 
 
+AP_HELP = ("--ap: after the run, print the average precision of the detections (`AP <setting> = ...`), matched and accumulated on the device "
+           "(wider_eval.DeviceEvaluator, fed image by image; the result files are written as before); synthetic-faces: against the pasted boxes, "
+           "one setting `all`; a WIDER annotation file: --gt-dir DIR with the eval_tools ground truth (wider_face_val.mat, wider_{easy,medium,hard}_val.mat), "
+           "settings easy / medium / hard.  One rank only")
+
+
 def limits_arguments(argv=None):
-    """`soft_nms_arguments` plus `pre_nms_topk` / `max_detections` from --pre-nms-topk K / --max-detections M, parsed apart in the same way."""
+    """`soft_nms_arguments` plus `pre_nms_topk` / `max_detections` from --pre-nms-topk K / --max-detections M and `ap` / `gt_dir` from
+    --ap / --gt-dir DIR, parsed apart in the same way."""
     parser = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     parser.add_argument("--pre-nms-topk", dest="pre_nms_topk", type=_count("--pre-nms-topk"), default=None, metavar="K", help=LIMITS_HELP)
     parser.add_argument("--max-detections", dest="max_detections", type=_count("--max-detections"), default=None, metavar="M", help=LIMITS_HELP)
+    parser.add_argument("--ap", dest="ap", action="store_true", help=AP_HELP)
+    parser.add_argument("--gt-dir", dest="gt_dir", default=None, metavar="DIR", help=AP_HELP)
     known, rest = parser.parse_known_args(argv)
     args = soft_nms_arguments(rest)
     args.pre_nms_topk, args.max_detections = known.pre_nms_topk, known.max_detections
+    args.ap, args.gt_dir = known.ap, known.gt_dir
     return args
+
+
+def check_ap(args):
+    """--ap is refused, before anything is loaded, where it cannot be answered: under several ranks (every rank sees a shard of the images; the
+    table is not reduced across ranks) and for a WIDER annotation file without --gt-dir."""
+    if not getattr(args, "ap", False):
+        return
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1:
+        raise SystemExit(f"--ap runs on one rank only (WORLD_SIZE={world}): every rank evaluates a shard of the images and the precision / recall "
+                         "table is not reduced across ranks; run `python evaluate_model.py ... --ap` without torchrun, or evaluate the result "
+                         "files afterwards with `python -m tinyfaces.wider_eval`")
+    if args.dataset != "synthetic-faces" and not args.gt_dir:
+        raise SystemExit(f"--ap on {args.dataset} needs --gt-dir DIR, the eval_tools ground-truth directory (only synthetic-faces carries its own boxes)")
+
+
+def ap_ground_truth(args, dataset):
+    """(settings, gt_boxes {event: {image: (G,4)}}, keep_lists per setting {event: {image: indices}}) for --ap."""
+    import numpy as np
+    from tinyfaces import wider_eval
+    if args.dataset == "synthetic-faces":
+        gt = {"faces": dataset.ground_truth()}
+        return ("all",), gt, [{"faces": {k: np.arange(v.shape[0]) for k, v in gt["faces"].items()}}]
+    settings = ("easy", "medium", "hard")
+    loaded = [wider_eval.load_ground_truth(args.gt_dir, s) for s in settings]
+    return settings, loaded[0][0], [keep for _, keep in loaded]
+
+
+def feed_evaluator(evaluator, dets, img_path, gt_boxes, keep_lists):
+    """One image's detections (x1 y1 x2 y2 score, as write_results takes them) into a DeviceEvaluator, under the name its result file gets."""
+    import numpy as np
+    from tinyfaces import ops
+    event, name = os.path.split(img_path.replace("jpg", "txt"))
+    name = name[:-4] if name.endswith(".txt") else name
+    gt = gt_boxes.get(event, {}).get(name)
+    if gt is None:                                              # not in the ground truth: evaluate_setting never visits it, norm_scores does
+        gt = np.zeros((0, 4))
+    keeps = [[k.get(event, {}).get(name, [])] for k in keep_lists]
+    evaluator.add([ops.wider_rows(dets)], [gt], keeps)
+    return event, name
+
+
+def run_ap(model, val_loader, templates, prob_thresh, nms_thresh, device, split, evaluator, gt_boxes, keep_lists, results_dir=None, debug=False,
+           **detection_keywords):
+    """`run` with every image's detections fed to `evaluator` as well: the same calls in the same order, the same result files."""
+    import numpy as np
+    dets, seen, done = None, set(), set()
+    for _, (img, filename) in enumerate(val_loader):
+        dets = get_detections(model, img[0], templates, val_loader.dataset.rf, val_loader.dataset.transforms, prob_thresh, nms_thresh,
+                              device=device, pyramid_on_gpu=True, **detection_keywords)
+        write_results(dets, filename[0], split, results_dir)
+        if filename[0] not in seen:                             # (a data set longer than its images walks them again: one result file per name)
+            seen.add(filename[0])
+            done.add(feed_evaluator(evaluator, dets, filename[0], gt_boxes, keep_lists))
+        if debug:
+            print(f"{filename[0]}: {dets.shape[0]} detections")
+    # evaluate_setting walks the GROUND TRUTH: an image that was not run still counts its boxes in the recall
+    for event, images in gt_boxes.items():
+        for name, gt in images.items():
+            if (event, name) not in done:
+                evaluator.add([np.zeros((0, 5))], [gt], [[k.get(event, {}).get(name, [])] for k in keep_lists])
+    return dets
 
 
 def dataloader(args):
@@ -159,6 +231,7 @@ def run(model, val_loader, templates, prob_thresh, nms_thresh, device, split, re
 
 def main():
     args = limits_arguments()
+    check_ap(args)
     if not torch.cuda.is_available():
         raise SystemExit("this build of the tiny-faces hot path runs on MI355X only (no CPU fallback)")
     # Multi-GPU evaluation = replicas only: under torchrun every rank takes a strided shard of the image list
@@ -173,11 +246,23 @@ def main():
     val_loader, templates = dataloader(args)
     model = get_model(args.checkpoint, num_templates=templates.shape[0], ema=args.ema)
     model = model.to(device).eval()
+    evaluator = None
+    if args.ap:
+        from tinyfaces.wider_eval import DeviceEvaluator
+        settings, gt_boxes, keep_lists = ap_ground_truth(args, val_loader.dataset)
+        evaluator = DeviceEvaluator(settings, device=device)
     with torch.no_grad(), model.constant_weights():          # the checkpoint does not change between images: pack the weights once
-        run(model, val_loader, templates, args.prob_thresh, args.nms_thresh, device, args.split, results_dir=args.results_dir,
-            debug=args.debug or args.dataset == "synthetic", mask_axis=args.mask_axis, flip=args.flip, box_voting=args.box_voting,
-            soft_nms=args.soft_nms, soft_nms_sigma=args.soft_nms_sigma, soft_nms_score_thresh=args.soft_nms_score_thresh,
-            pre_nms_topk=args.pre_nms_topk, max_detections=args.max_detections)
+        keywords = dict(mask_axis=args.mask_axis, flip=args.flip, box_voting=args.box_voting,
+                        soft_nms=args.soft_nms, soft_nms_sigma=args.soft_nms_sigma, soft_nms_score_thresh=args.soft_nms_score_thresh,
+                        pre_nms_topk=args.pre_nms_topk, max_detections=args.max_detections)
+        debug = args.debug or args.dataset == "synthetic"
+        if evaluator is None:
+            run(model, val_loader, templates, args.prob_thresh, args.nms_thresh, device, args.split, results_dir=args.results_dir, debug=debug, **keywords)
+        else:
+            run_ap(model, val_loader, templates, args.prob_thresh, args.nms_thresh, device, args.split, evaluator, gt_boxes, keep_lists,
+                   results_dir=args.results_dir, debug=debug, **keywords)
+            for setting, (ap, _) in evaluator.finish().items():
+                print(f"AP {setting} = {ap!r}")              # repr: every digit, so that the line can be compared with the host evaluator's float
     if distributed:
         torch.distributed.barrier()
         if parallel.rank() == 0:

@@ -6,7 +6,8 @@
 
 Additions (existing flags keep their names and defaults): --fused / --no-fused (TrainEngine vs torch.optim.SGD through
 autograd), --dtype bf16|fp32, --synthetic-len.  The schedule is the reference's: SGD(momentum, weight decay), StepLR(20),
-a checkpoint every --save-every epochs (main.py:39-104); --optimizer adamw, --warmup-iters and --color-jitter are opt-in."""
+a checkpoint every --save-every epochs (main.py:39-104); --optimizer adamw, --warmup-iters, --color-jitter and
+--val-every (the AP on `valdata` after every N-th epoch; without it `valdata` is ignored, as in the reference) are opt-in."""
 import argparse
 import math
 import os
@@ -126,6 +127,35 @@ JITTER_HELP = ("--color-jitter B C S H: torchvision's ColorJitter(brightness=B, 
                "ops in a random order; computed on the device), four finite numbers >= 0 with H <= 0.5, default off")
 
 
+VAL_HELP = ("--val-every N: after every N-th epoch rank 0 runs the detector over `valdata` (synthetic-faces, or a WIDER annotation file with "
+            "--val-gt-dir DIR, the eval_tools ground-truth directory) on the averaged weights under --model-ema, else the live ones, prints one "
+            "`Val: [epoch] AP ...` line (matched and accumulated on the device, no result file), stores \"val_ap\" in the checkpoints and keeps "
+            "checkpoint_best.pth, the best first setting so far; N >= 0, default 0 = off (`valdata` is then ignored); --val-prob-thresh P / "
+            "--val-nms-thresh T: the detector's thresholds, in [0, 1], defaults 0.03 / 0.3 (evaluate_model.py's); --val-num-images M: the first M "
+            "validation images only, M >= 1, default all")
+
+
+def _val_every(text):
+    value = int(text)
+    if value < 0:
+        raise argparse.ArgumentTypeError(f"must be an integer >= 0, got {text}")
+    return value
+
+
+def _val_count(text):
+    value = int(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError(f"must be an integer >= 1, got {text}")
+    return value
+
+
+def _unit_interval(text):
+    value = float(text)
+    if not 0.0 <= value <= 1.0:
+        raise argparse.ArgumentTypeError(f"must be a number in [0, 1], got {text}")
+    return value
+
+
 def _jitter_amplitude(text):
     value = float(text)
     if not (math.isfinite(value) and value >= 0.0):
@@ -205,7 +235,7 @@ def _positive_float(text):
 
 
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP, JITTER_HELP)))
+    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP, JITTER_HELP, VAL_HELP)))
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
@@ -217,7 +247,8 @@ def trunk_arguments(argv=None):
     from --accum-average, `cls_loss` ("soft_margin" | "focal") from --cls-loss, `focal_gamma`, `focal_alpha` and `focal_normalize` from
     --focal-gamma, --focal-alpha and --focal-normalize, `reg_loss` ("smooth_l1" | "iou" | "giou" | "diou") from --reg-loss and `reg_weight` from
     --reg-weight, `optimizer` ("sgd" | "adamw"), `adam_beta1`, `adam_beta2` and `adam_eps` from --optimizer, --adam-beta1, --adam-beta2 and --adam-eps,
-    `warmup_iters` and `warmup_factor` from --warmup-iters and --warmup-factor, `color_jitter` (None or the four amplitudes) from --color-jitter.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
+    `warmup_iters` and `warmup_factor` from --warmup-iters and --warmup-factor, `color_jitter` (None or the four amplitudes) from --color-jitter,
+    `val_every`, `val_prob_thresh`, `val_nms_thresh`, `val_num_images` and `val_gt_dir` from --val-every and its companions.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
     options and the additions above."""
     parser = argparse.ArgumentParser(add_help=False)
     parser.add_argument("--base-model", dest="base_model", default="resnet101", choices=list(model_zoo.TRUNKS), help=TRUNK_HELP)
@@ -241,6 +272,11 @@ def trunk_arguments(argv=None):
     parser.add_argument("--warmup-iters", dest="warmup_iters", default=0, type=_warmup_iters, metavar="N", help=WARMUP_HELP)
     parser.add_argument("--warmup-factor", dest="warmup_factor", default=1e-3, type=_warmup_factor, metavar="F", help=WARMUP_HELP)
     parser.add_argument("--color-jitter", dest="color_jitter", default=None, type=_jitter_amplitude, nargs=4, metavar=("B", "C", "S", "H"), help=JITTER_HELP)
+    parser.add_argument("--val-every", dest="val_every", default=0, type=_val_every, metavar="N", help=VAL_HELP)
+    parser.add_argument("--val-prob-thresh", dest="val_prob_thresh", default=0.03, type=_unit_interval, metavar="P", help=VAL_HELP)
+    parser.add_argument("--val-nms-thresh", dest="val_nms_thresh", default=0.3, type=_unit_interval, metavar="T", help=VAL_HELP)
+    parser.add_argument("--val-num-images", dest="val_num_images", default=None, type=_val_count, metavar="M", help=VAL_HELP)
+    parser.add_argument("--val-gt-dir", dest="val_gt_dir", default=None, metavar="DIR", help=VAL_HELP)
     known, rest = parser.parse_known_args(argv)
     if known.color_jitter is not None and known.color_jitter[3] > 0.5:
         parser.error(f"--color-jitter: the hue amplitude H must be <= 0.5, got {known.color_jitter[3]:g}")
@@ -267,6 +303,8 @@ def trunk_arguments(argv=None):
     args.adam_beta1, args.adam_beta2, args.adam_eps = known.adam_beta1, known.adam_beta2, known.adam_eps
     args.warmup_iters, args.warmup_factor = known.warmup_iters, known.warmup_factor
     args.color_jitter = None if known.color_jitter is None else tuple(known.color_jitter)
+    args.val_every, args.val_num_images, args.val_gt_dir = known.val_every, known.val_num_images, known.val_gt_dir
+    args.val_prob_thresh, args.val_nms_thresh = known.val_prob_thresh, known.val_nms_thresh
     return args
 
 
@@ -435,6 +473,25 @@ def main():
     elif ema is None and state is not None and "model_ema" in state and parallel.rank() == 0:
         print(f"WARNING: {args.resume} holds a model EMA, which this run drops: pass --model-ema DECAY to continue it")
 
+    validator, val_ap, best_ap = None, None, None
+    if args.val_every > 0 and parallel.rank() == 0:              # off (the default): nothing below is imported, allocated or launched
+        from tinyfaces.validation import Validator
+        validator = Validator(args.valdata, NUM_TEMPLATES, device, preprocess, prob_thresh=args.val_prob_thresh, nms_thresh=args.val_nms_thresh,
+                              num_images=args.val_num_images, gt_dir=args.val_gt_dir, dataset_root=args.dataset_root, seed=args.seed)
+        if state is not None and isinstance(state.get("val_ap"), dict) and validator.settings[0] in state["val_ap"]:
+            best_ap = float(state["val_ap"][validator.settings[0]])      # (a resumed run does not overwrite a better checkpoint_best.pth with a worse one)
+
+    def snapshot_of(done):
+        if engine is not None:
+            engine.set_lr(lr_at(args.lr, done))                       # what StepLR would have left in the param groups
+        snapshot = {"epoch": done, "batch_size": train_loader.batch_size, "model": model.state_dict(),          # main.py:97-102
+                    "optimizer": optimizer.state_dict() if optimizer is not None else engine.optimizer_state_dict(base_lr=args.lr)}
+        if ema is not None:
+            snapshot["model_ema"], snapshot["ema"] = ema.state_dict(), ema.settings()
+        if val_ap is not None:
+            snapshot["val_ap"] = dict(val_ap)                         # of the last validation pass at or before this epoch
+        return snapshot
+
     skipped = 0
     for epoch in range(first_epoch, args.epochs):
         if hasattr(train_loader, "set_epoch"):
@@ -454,14 +511,18 @@ def main():
                 print(f"Epoch: [{epoch}]\t{total - skipped} step(s) skipped: the gradient norm was not finite ({total} since the start)")
                 skipped = total
         done = epoch + 1
+        if args.val_every > 0 and done % args.val_every == 0:
+            if validator is not None:                                     # rank 0; the weights are copied into the validator's own model
+                val_ap = validator.run(ema.state_dict() if ema is not None else model.state_dict())
+                print(f"Val: [{epoch}] AP " + ", ".join(f"{s} {v!r}" for s, v in val_ap.items()) + (" (model EMA)" if ema is not None else ""))
+                first = val_ap[validator.settings[0]]
+                if best_ap is None or first > best_ap:
+                    best_ap = first
+                    trainer.save_checkpoint(snapshot_of(done), filename="checkpoint_best.pth", save_path=Path(args.save_path))
+            if parallel.is_distributed():
+                torch.distributed.barrier()                               # the other ranks wait for rank 0's pass
         if done % args.save_every == 0 and parallel.rank() == 0:
-            if engine is not None:
-                engine.set_lr(lr_at(args.lr, done))                       # what StepLR would have left in the param groups
-            snapshot = {"epoch": done, "batch_size": train_loader.batch_size, "model": model.state_dict(),          # main.py:97-102
-                        "optimizer": optimizer.state_dict() if optimizer is not None else engine.optimizer_state_dict(base_lr=args.lr)}
-            if ema is not None:
-                snapshot["model_ema"], snapshot["ema"] = ema.state_dict(), ema.settings()
-            trainer.save_checkpoint(snapshot, filename=f"checkpoint_{done}.pth", save_path=Path(args.save_path))
+            trainer.save_checkpoint(snapshot_of(done), filename=f"checkpoint_{done}.pth", save_path=Path(args.save_path))
 
 
 if __name__ == "__main__":

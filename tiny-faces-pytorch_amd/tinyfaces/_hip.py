@@ -126,6 +126,9 @@ _SIGNATURES = {
     "tf_topk_select_f64": (i32, [vp, i32, i32, vp, vp, sz, vp]),
     "tf_topk_batched_workspace_bytes": (sz, [C.POINTER(i32), i32, i32]),
     "tf_topk_select_f64_batched": (i32, [vp, C.POINTER(i32), i32, i32, vp, vp, sz, vp]),
+    "tf_wider_match_workspace_bytes": (sz, [i32, i32]),
+    "tf_wider_match_f64_batched": (i32, [vp, C.POINTER(i32), vp, C.POINTER(i32), i32, vp, i32, f64, vp, vp, vp, sz, vp]),
+    "tf_wider_pr_accumulate": (i32, [vp, C.POINTER(i32), i32, vp, vp, i32, vp, vp, i32, vp, vp]),
     "tf_criterion_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "tf_criterion_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, f32, vp, vp, u64, vp, vp, vp, vp, vp, sz, vp]),
     "tf_criterion_focal_workspace_bytes": (sz, [i32, i32, i32, i32]),

@@ -494,6 +494,101 @@ def topk_select(scores, k):
     return topk_select_batched(scores, offs, k)
 
 
+# --------------------------------------------------------------------------- WIDER evaluation: matching and the PR table on the device
+WIDER_GT_TILE = 256                                       # TF_WIDER_GT_TILE: ground-truth boxes per LDS tile of the match kernel
+
+
+def wider_rows(dets):
+    """The rounding of evaluation.write_results on an (K,5) x1 y1 x2 y2 score array (numpy or tensor): rows in result-file form
+    round([x1, y1, x2 - x1 + 1, y2 - y1 + 1]) half to even, the score untouched -- what read_predictions parses back from the file, so the
+    in-memory path to the evaluator sees exactly what the file path reads.  Returns the type it was given, float64."""
+    if isinstance(dets, torch.Tensor):
+        d = dets.to(torch.float64).reshape(-1, 5)
+        geometry = torch.round(torch.stack([d[:, 0], d[:, 1], d[:, 2] - d[:, 0] + 1, d[:, 3] - d[:, 1] + 1], dim=1)) + 0.0
+        return torch.cat([geometry, d[:, 4:5]], dim=1)
+    d = np.asarray(dets, dtype=np.float64).reshape(-1, 5)
+    geometry = np.round(np.stack([d[:, 0], d[:, 1], d[:, 2] - d[:, 0] + 1, d[:, 3] - d[:, 1] + 1], axis=1)) + 0.0      # (the file holds "0", never "-0")
+    return np.concatenate([geometry, d[:, 4:5]], axis=1)
+
+
+def _wider_offsets(offsets, total, what, name):
+    offs = [int(o) for o in offsets]
+    if len(offs) < 2 or offs[0] != 0 or any(b < a for a, b in zip(offs, offs[1:])) or offs[-1] != total:
+        raise ValueError(f"{what}: bad {name} offsets {offs[:4]}... for {total} rows (they start at 0, never descend and end at the row count)")
+    if offs[-1] > 2**31 - 1:
+        raise ValueError(f"{what}: {offs[-1]} rows exceed the int32 segment offsets")
+    return offs
+
+
+def wider_match_batched(rows, det_offsets, gt, gt_offsets, keep_masks, iou_thresh=0.5):
+    """WIDER matching of a batch of images (tf_wider_match_f64_batched; host reference: wider_eval.image_evaluation).  rows (n,5) float64
+    x, y, w, h, score, every segment [det_offsets[s], det_offsets[s+1]) score-descending; gt (g,4) x, y, w, h under gt_offsets (the same number
+    of segments); keep_masks (nset, g) uint8 / bool, 1 = the box counts in that setting.  Returns (counted, recalled), int32 (nset, n): the
+    running number of detections with proposal == 1 and pred_recall, per setting.  Nothing is synchronised."""
+    what = "wider_match_batched"
+    for name, t, cols in (("rows", rows, 5), ("gt", gt, 4)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != cols:
+            raise ValueError(f"{what}: {name} is a 2-d tensor of {cols} columns")
+    if not isinstance(keep_masks, torch.Tensor) or keep_masks.dim() != 2 or keep_masks.shape[0] < 1 or keep_masks.shape[1] != gt.shape[0]:
+        raise ValueError(f"{what}: keep_masks is an (nset >= 1, {gt.shape[0]}) tensor, one row per setting")
+    if not math.isfinite(float(iou_thresh)):
+        raise ValueError(f"{what}: iou_thresh={iou_thresh!r}")
+    n, g, nset = int(rows.shape[0]), int(gt.shape[0]), int(keep_masks.shape[0])
+    doffs, goffs = _wider_offsets(det_offsets, n, what, "detection"), _wider_offsets(gt_offsets, g, what, "ground-truth")
+    if len(doffs) != len(goffs):
+        raise ValueError(f"{what}: {len(doffs) - 1} detection segments but {len(goffs) - 1} ground-truth segments")
+    require_gpu(rows, what)
+    S, dev = len(doffs) - 1, rows.device
+    rows = rows.to(torch.float64).contiguous()
+    gt = gt.to(device=dev, dtype=torch.float64).contiguous()
+    keep = keep_masks.to(device=dev, dtype=torch.uint8).contiguous()
+    counted = torch.empty(nset, n, dtype=torch.int32, device=dev)
+    recalled = torch.empty(nset, n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return counted, recalled
+    wsb = lib().tf_wider_match_workspace_bytes(n, g)
+    ws = _workspace("wider_match", wsb, dev)
+    with torch.cuda.device(dev):
+        check(lib().tf_wider_match_f64_batched(ptr(rows), (C.c_int32 * (S + 1))(*doffs), ptr(gt), (C.c_int32 * (S + 1))(*goffs), S, ptr(keep), nset,
+                                               float(iou_thresh), ptr(counted), ptr(recalled), ptr(ws), wsb, stream()), "tf_wider_match_f64_batched")
+    return counted, recalled
+
+
+def wider_pr_accumulate(scores, det_offsets, counted, recalled, lo_d, thresh, pr):
+    """Adds image_pr_info, summed over the segments, into pr (nset, T, 2) int64 in place (tf_wider_pr_accumulate).  scores (n,) float64 raw
+    scores, every segment non-increasing; counted / recalled (nset, n) int32 from `wider_match_batched`; lo_d: device float64 (2,) = (lo, d)
+    of norm_scores; thresh: device float64 (T,) = 1 - (t + 1) / T.  Nothing is synchronised.  Returns pr."""
+    what = "wider_pr_accumulate"
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 1:
+        raise ValueError(f"{what}: scores is a 1-d tensor of one score per detection")
+    n = int(scores.shape[0])
+    offs = _wider_offsets(det_offsets, n, what, "detection")
+    for name, t in (("counted", counted), ("recalled", recalled)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != n or t.dtype != torch.int32:
+            raise ValueError(f"{what}: {name} is an int32 (nset >= 1, {n}) tensor")
+    nset = int(counted.shape[0])
+    if recalled.shape[0] != nset:
+        raise ValueError(f"{what}: counted has {nset} settings, recalled {recalled.shape[0]}")
+    if not isinstance(lo_d, torch.Tensor) or lo_d.dtype != torch.float64 or lo_d.numel() != 2:
+        raise ValueError(f"{what}: lo_d is a float64 tensor of (lo, d)")
+    if not isinstance(thresh, torch.Tensor) or thresh.dtype != torch.float64 or thresh.dim() != 1:
+        raise ValueError(f"{what}: thresh is a 1-d float64 tensor")
+    T = int(thresh.shape[0])
+    if not isinstance(pr, torch.Tensor) or pr.dtype != torch.int64 or tuple(pr.shape) != (nset, T, 2) or not pr.is_contiguous():
+        raise ValueError(f"{what}: pr is a contiguous int64 ({nset}, {T}, 2) tensor")
+    require_gpu(scores, what)
+    for name, t in (("counted", counted), ("recalled", recalled), ("lo_d", lo_d), ("thresh", thresh), ("pr", pr)):
+        if t.device != scores.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, scores on {scores.device}")
+    scores, counted, recalled = scores.to(torch.float64).contiguous(), counted.contiguous(), recalled.contiguous()
+    lo_d, thresh = lo_d.contiguous(), thresh.contiguous()
+    S = len(offs) - 1
+    with torch.cuda.device(scores.device):
+        check(lib().tf_wider_pr_accumulate(ptr(scores), (C.c_int32 * (S + 1))(*offs), S, ptr(counted), ptr(recalled), nset, ptr(lo_d), ptr(thresh), T,
+                                           ptr(pr), stream()), "tf_wider_pr_accumulate")
+    return pr
+
+
 # --------------------------------------------------------------------------- decode
 def template_masks(templates, scale, width, mask_axis="w"):
     """Validity masks reproducing tinyfaces/models/utils.py:17-44.  mask_axis='w' is the

@@ -103,9 +103,122 @@ def evaluate_setting(preds, gt_boxes, keep_lists, iou_thresh=0.5, thresh_num=THR
             mask[keep] = True
             pred_recall, proposal = image_evaluation(pred, gt, mask, iou_thresh)
             pr += image_pr_info(pred[:, 4], proposal, pred_recall, thresh_num)
+    return precision_recall_ap(pr, count_face)
+
+
+def precision_recall_ap(pr, count_face):
+    """The tail of evaluate_setting, shared with DeviceEvaluator so that the two cannot drift: pr (T,2) float64 = (# counted detections,
+    # recalled boxes) per threshold, summed over the images; count_face = the boxes that count.  Returns (AP, pr_curve (T,2))."""
+    thresh_num = pr.shape[0]
     precision = np.divide(pr[:, 1], pr[:, 0], out=np.zeros(thresh_num), where=pr[:, 0] > 0)      # MATLAB's max() skips the 0/0 NaNs
     recall = pr[:, 1] / max(count_face, 1)
     return voc_ap(recall, precision), np.stack([precision, recall], 1)
+
+
+class DeviceEvaluator:
+    """evaluate_setting(norm_scores(...)) for several settings at once with the matching and the PR table on the device
+    (ops.wider_match_batched / ops.wider_pr_accumulate), held to the host functions above bit for bit: the table is integers.
+
+        ev = DeviceEvaluator(("easy", "medium", "hard"))
+        for every batch of images:  ev.add(rows, gt, keep_lists)
+        {setting: (ap, pr_curve)} = ev.finish()
+
+    Every image of the ground truth is added once, with an empty (0,5) array when it has no detection: its kept boxes count in the
+    recall.  Nothing is read back before finish(), which makes one host read of the nset x T x 2 table."""
+
+    def __init__(self, settings, iou_thresh=0.5, thresh_num=THRESH_NUM, device="cuda"):
+        import torch
+        self.settings = tuple(settings)
+        if not self.settings:
+            raise ValueError("DeviceEvaluator: at least one setting")
+        if isinstance(thresh_num, bool) or not isinstance(thresh_num, (int, np.integer)) or thresh_num < 1:
+            raise ValueError(f"DeviceEvaluator: thresh_num={thresh_num!r}, expected an integer >= 1")
+        self.iou_thresh, self.thresh_num, self.device = float(iou_thresh), int(thresh_num), torch.device(device)
+        self.reset()
+
+    def reset(self):
+        self.count_face = [0] * len(self.settings)
+        self._scores, self._counted, self._recalled, self._offsets = [], [], [], [0]
+        self._lo = self._hi = None
+
+    def _keep_of(self, keep_lists, n_images):
+        per_setting = [keep_lists[s] for s in self.settings] if isinstance(keep_lists, dict) else list(keep_lists)
+        if len(per_setting) != len(self.settings) or any(len(k) != n_images for k in per_setting):
+            raise ValueError(f"DeviceEvaluator.add: keep_lists holds one list of {n_images} index lists for each of the {len(self.settings)} settings")
+        return [[np.asarray(k, dtype=np.int64).reshape(-1) for k in ks] for ks in per_setting]
+
+    def add(self, rows, gt, keep_lists):
+        """One batch of images.  rows: per image an (K,5) array x, y, w, h, score in result-file form (ops.wider_rows), numpy or tensor, in
+        any order; gt: per image an (G,4) array x, y, w, h; keep_lists: per setting (a sequence in the order of `settings`, or a dict by
+        setting) one list per image of the 0-based indices of the boxes that count, as evaluate_setting takes them."""
+        import torch
+        from . import ops
+        dev = self.device
+        rows, gt = list(rows), list(gt)
+        if len(rows) != len(gt):
+            raise ValueError(f"DeviceEvaluator.add: {len(rows)} row arrays for {len(gt)} ground-truth arrays")
+        keeps = self._keep_of(keep_lists, len(gt))
+        gts = [np.asarray(g.cpu() if torch.is_tensor(g) else g, dtype=np.float64).reshape(-1, 4) for g in gt]
+        for k, ks in enumerate(keeps):
+            self.count_face[k] += sum(int(x.size) for x in ks)
+
+        def on_device(r):
+            if torch.is_tensor(r):
+                return r.detach().to(device=dev, dtype=torch.float64).reshape(-1, 5)
+            return torch.from_numpy(np.ascontiguousarray(np.asarray(r, dtype=np.float64).reshape(-1, 5))).to(dev)
+
+        if rows and not any(torch.is_tensor(r) for r in rows):           # host arrays: one upload
+            lens = [int(np.asarray(r).reshape(-1, 5).shape[0]) for r in rows]
+            every = on_device(np.concatenate([np.asarray(r, dtype=np.float64).reshape(-1, 5) for r in rows])) if sum(lens) else None
+            parts = list(torch.split(every, lens)) if every is not None else [torch.zeros(0, 5, dtype=torch.float64, device=dev)] * len(rows)
+        else:
+            parts = [on_device(r) for r in rows]
+        if sum(int(p.shape[0]) for p in parts) == 0:
+            return
+        # norm_scores: every score of the prediction set, the images that are skipped below included
+        lo, hi = torch.aminmax(torch.cat([p[:, 4] for p in parts]))
+        self._lo = lo if self._lo is None else torch.minimum(self._lo, lo)
+        self._hi = hi if self._hi is None else torch.maximum(self._hi, hi)
+        # evaluate_setting: an image without boxes or without rows adds nothing to the table
+        live = [i for i in range(len(gts)) if gts[i].shape[0] and parts[i].shape[0]]
+        if not live:
+            return
+        lens = [int(parts[i].shape[0]) for i in live]
+        glens = [int(gts[i].shape[0]) for i in live]
+        doffs, goffs = np.concatenate([[0], np.cumsum(lens)]), np.concatenate([[0], np.cumsum(glens)])
+        n, g = int(doffs[-1]), int(goffs[-1])
+        cat = torch.cat([parts[i] for i in live])
+        # read_predictions: a stable descending sort by score inside every image = a stable sort of everything by score, then a stable
+        # sort by segment (the segments lie back to back, so the second sort only gathers them again); no length is read from the device
+        seg = torch.repeat_interleave(torch.from_numpy(np.asarray(lens, dtype=np.int64)).to(dev), output_size=n)
+        by_score = torch.sort(cat[:, 4], descending=True, stable=True).indices
+        order = by_score[torch.sort(seg[by_score], stable=True).indices]
+        cat = cat[order].contiguous()
+        masks = np.zeros((len(self.settings), g), dtype=np.uint8)
+        for k, ks in enumerate(keeps):
+            for j, i in enumerate(live):
+                masks[k, goffs[j]:goffs[j + 1]][ks[i]] = 1                  # (a view of the image's boxes: evaluate_setting's mask[keep] = True)
+        counted, recalled = ops.wider_match_batched(cat, doffs.tolist(), torch.from_numpy(np.concatenate([gts[i] for i in live])).to(dev),
+                                                    goffs.tolist(), torch.from_numpy(masks).to(dev), self.iou_thresh)
+        self._scores.append(cat[:, 4].contiguous())
+        self._counted.append(counted)
+        self._recalled.append(recalled)
+        self._offsets += [self._offsets[-1] + int(o) for o in doffs[1:]]
+
+    def finish(self):
+        """{setting: (AP, pr_curve (T,2))}: norm_scores' (lo, d) on the device, one tf_wider_pr_accumulate call over everything that was
+        added, one host read of the table, then evaluate_setting's own lines (precision_recall_ap)."""
+        import torch
+        from . import ops
+        T, nset = self.thresh_num, len(self.settings)
+        pr = torch.zeros(nset, T, 2, dtype=torch.int64, device=self.device)
+        if self._scores:
+            d = torch.where(self._hi > self._lo, self._hi - self._lo, torch.ones_like(self._lo))
+            thresh = torch.tensor([1 - (t + 1) / T for t in range(T)], dtype=torch.float64).to(self.device)       # image_pr_info's expression
+            ops.wider_pr_accumulate(torch.cat(self._scores), self._offsets, torch.cat(self._counted, dim=1), torch.cat(self._recalled, dim=1),
+                                    torch.stack([self._lo, d]), thresh, pr)
+        table = pr.cpu().numpy().astype(np.float64)                        # the one host read; counts far below 2^53: exact
+        return {s: precision_recall_ap(table[k], self.count_face[k]) for k, s in enumerate(self.settings)}
 
 
 def read_predictions(pred_dir):
