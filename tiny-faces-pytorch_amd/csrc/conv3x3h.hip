@@ -269,6 +269,49 @@ __global__ void __launch_bounds__(NT, 2) conv3x3h_kernel(const HK a) {
   //  two-tap weight slabs (128 KiB), the next frame requested behind the weights so that one counted wait leaves it in flight; parity-green,
   //  208 VGPRs: 1296.9 / 1292.2 against 1297.3 / 1292.5 img/s, evaluation 5.16 against 4.93 ms per image.  Halving the barriers and counted
   //  waits of the K loop buys nothing: DESIGN.md 7 row 51.)
+  // Epilogue roles (phase 2 below): one 16-byte output chunk (8 consecutive channels) of one pixel per thread and pass.
+  constexpr int CPR = BN / EPS;                      // 16
+  const int chunk8 = tid % CPR, tc = tid / CPR;
+  const int ch0 = n0 + chunk8 * EPS;
+  const bool cok = ch0 < a.ldy;
+  // The aux chunks of ALL TR passes are requested here, behind the last counted wait of the stage loop (no count changes) and before the
+  // accumulators are parked: loaded at the point of use they were one cold round trip per pass, each behind the previous pass's store, with
+  // one block per CU and nothing else resident to hide them.  Unconditional, from clamped addresses; the bounds test stays at the use.
+  constexpr bool AUXPF = EPIC >= 0 && (EPIC & (TF_EPI_RES | TF_EPI_MASK | TF_EPI_STATS2));
+  float es[EPS], eh[EPS], ms[EPS], mh[EPS], s1[EPS], s2[EPS], sft[EPS];
+  auto load_coef = [&]() {
+#pragma unroll
+    for (int j = 0; j < EPS; ++j) { es[j] = 1.f; eh[j] = 0.f; ms[j] = 0.f; mh[j] = 0.f; s1[j] = 0.f; s2[j] = 0.f; sft[j] = 0.f; }
+    if (cok) {
+      if ((epi_flags & TF_EPI_STATS) && a.stat_shift) {    // sums of (x - shift), (x - shift)^2: see tf_conv_args.stat_shift
+#pragma unroll
+        for (int j = 0; j < EPS; ++j) sft[j] = a.stat_shift[ch0 + j];
+      }
+      if (epi_flags & TF_EPI_AFFINE) {
+#pragma unroll
+        for (int j = 0; j < EPS; ++j) { es[j] = a.epi_scale[ch0 + j]; eh[j] = a.epi_shift[ch0 + j]; }
+      }
+      if (epi_flags & TF_EPI_MASK) {
+#pragma unroll
+        for (int j = 0; j < EPS; ++j) { ms[j] = a.mask_scale[ch0 + j]; mh[j] = a.mask_shift[ch0 + j]; }
+      }
+    }
+  };
+  // COEF_EARLY: the training flag sets (the data gradient above, and the forward's STATS with its statistic shift)
+  constexpr bool COEF_EARLY = AUXPF || EPIC == TF_EPI_STATS;
+  uint4 apf[AUXPF ? TR : 1];
+  if constexpr (AUXPF) {
+#pragma unroll
+    for (int ps = 0; ps < TR; ++ps) {
+      const int oh = r0 + ps, ow = c0 + tc;
+      const bool ok = oh < a.H && ow < a.W && cok;
+      const size_t o = ok ? ((((size_t)img * a.H + oh) * a.W + ow) * a.ldy + ch0) * sizeof(T) : 0;
+      apf[ps] = *reinterpret_cast<const uint4*>(a.aux + o);
+    }
+    // ... and the per-channel coefficients with them: requested behind the first __syncthreads of the epilogue they were one more exposed round
+    // trip, and the conditional loads left the compiler a conservative vmcnt(0) in front of every pass -- behind the previous pass's store.
+  }
+  if constexpr (COEF_EARLY) load_coef();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (r5: no fragment read in flight when the rings become the staging tile)
   __builtin_amdgcn_s_barrier();                     // all waves done reading the rings -> reuse them as the staging tile
   if constexpr (TRACE) {
@@ -308,34 +351,15 @@ __global__ void __launch_bounds__(NT, 2) conv3x3h_kernel(const HK a) {
   if constexpr (TRACE) e_t[1] = __builtin_amdgcn_s_memtime();
 
   // ---------------- phase 2: one 16-byte output chunk (8 consecutive channels) of one pixel per thread and pass; a pass of
-  // 512 threads = one row of the output tile (32 pixels x 16 chunks)
-  constexpr int CPR = BN / EPS;                      // 16
-  const int chunk8 = tid % CPR, tc = tid / CPR;
-  const int ch0 = n0 + chunk8 * EPS;
-  const bool cok = ch0 < a.ldy;
-  float es[EPS], eh[EPS], ms[EPS], mh[EPS], s1[EPS], s2[EPS], sft[EPS];
-#pragma unroll
-  for (int j = 0; j < EPS; ++j) { es[j] = 1.f; eh[j] = 0.f; ms[j] = 0.f; mh[j] = 0.f; s1[j] = 0.f; s2[j] = 0.f; sft[j] = 0.f; }
-  if (cok) {
-    if ((epi_flags & TF_EPI_STATS) && a.stat_shift) {    // sums of (x - shift), (x - shift)^2: see tf_conv_args.stat_shift
-#pragma unroll
-      for (int j = 0; j < EPS; ++j) sft[j] = a.stat_shift[ch0 + j];
-    }
-    if (epi_flags & TF_EPI_AFFINE) {
-#pragma unroll
-      for (int j = 0; j < EPS; ++j) { es[j] = a.epi_scale[ch0 + j]; eh[j] = a.epi_shift[ch0 + j]; }
-    }
-    if (epi_flags & TF_EPI_MASK) {
-#pragma unroll
-      for (int j = 0; j < EPS; ++j) { ms[j] = a.mask_scale[ch0 + j]; mh[j] = a.mask_shift[ch0 + j]; }
-    }
-  }
+  // 512 threads = one row of the output tile (32 pixels x 16 chunks); chunk8 / tc / ch0 / cok: see the requests in front of phase 1
+  if constexpr (!COEF_EARLY) load_coef();
 #pragma unroll
   for (int ps = 0; ps < TR; ++ps) {
     if (ps == TR / 2) {                              // second pixel half: rows 2, 3 of the tile replace rows 0, 1 in the staging tiles
-      __syncthreads();
+      // (COEF_EARLY: LDS traffic only crosses these two barriers -- a __syncthreads would also wait for the stores of the first half to be acknowledged)
+      if constexpr (COEF_EARLY) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); } else __syncthreads();
       park(1);
-      __syncthreads();
+      if constexpr (COEF_EARLY) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); } else __syncthreads();
     }
     const int oh = r0 + ps, ow = c0 + tc;
     if (!(oh < a.H && ow < a.W && cok)) continue;   // tile pixels outside the image hold meaningless sums: no store, no statistics
@@ -353,7 +377,10 @@ __global__ void __launch_bounds__(NT, 2) conv3x3h_kernel(const HK a) {
     }
     const size_t o = ((((size_t)img * a.H + oh) * a.W + ow) * a.ldy + ch0) * sizeof(T);
     float ax[EPS];
-    if (epi_flags & (TF_EPI_RES | TF_EPI_MASK | TF_EPI_STATS2)) tf::unpack16<T>(*reinterpret_cast<const uint4*>(a.aux + o), ax);
+    if (epi_flags & (TF_EPI_RES | TF_EPI_MASK | TF_EPI_STATS2)) {
+      if constexpr (AUXPF) tf::unpack16<T>(apf[AUXPF ? ps : 0], ax);
+      else tf::unpack16<T>(*reinterpret_cast<const uint4*>(a.aux + o), ax);
+    }
     if (epi_flags & TF_EPI_AFFINE) {
 #pragma unroll
       for (int j = 0; j < EPS; ++j) v[j] = v[j] * es[j] + eh[j];
@@ -478,18 +505,14 @@ int launch(const tf_conv_args* A, hipStream_t stream) {
   if (A->epi & TF_EPI_MASK2) bytes += M * A->Cout * es;
   if (A->epi & TF_EPI_STATS3) bytes += M * A->Cout * es;
   tf::ProfScope prof(A->dtype == TF_BF16 ? 6 : 7, 2.0 * M * A->Cout * Kt, bytes, stream, (int)M, A->Cout, k.Ktot, 9, A->mode, A->epi, -1.0, true);   // 6 = conv3x3h bf16, 7 = f16
-  // Three flag sets have a specialised epilogue; every other one takes the run-time flags.  That generic arm is really the `else` of the
-  // chain.  It stands second, behind a negated test, for ONE reason: hipcc emits the instantiations in the order the chain names them, and
-  // this order keeps the code object byte-identical to the one the step A/Bs were taken on.  Whoever next changes this file's device code
-  // anyway should move it to the end as a plain `else`.
+  // Three flag sets have a specialised epilogue; every other one takes the run-time flags.
   const int e = A->epi;
-  const bool specialised = e == TF_EPI_STATS || e == (TF_EPI_MASK | TF_EPI_STATS2) || e == (TF_EPI_AFFINE | TF_EPI_RELU);
   if (g_trace) launch_var<T, true>(k, stream);
-  else if (!specialised) launch_var<T, false>(k, stream);                                                      // run-time epilogue flags
   else if (e == TF_EPI_STATS) launch_var<T, false, TF_EPI_STATS>(k, stream);                                   // training forward
   else if (e == (TF_EPI_MASK | TF_EPI_STATS2)) launch_var<T, false, TF_EPI_MASK | TF_EPI_STATS2>(k, stream);   // training data gradient
-  else if (tall) launch_var<T, false, TF_EPI_AFFINE | TF_EPI_RELU, 6>(k, stream);                              // evaluation (folded BN + ReLU), 6-row tiles
-  else launch_var<T, false, TF_EPI_AFFINE | TF_EPI_RELU>(k, stream);                                           // evaluation, 4-row tiles
+  else if (e == (TF_EPI_AFFINE | TF_EPI_RELU) && tall) launch_var<T, false, TF_EPI_AFFINE | TF_EPI_RELU, 6>(k, stream);   // evaluation (folded BN + ReLU), 6-row tiles
+  else if (e == (TF_EPI_AFFINE | TF_EPI_RELU)) launch_var<T, false, TF_EPI_AFFINE | TF_EPI_RELU>(k, stream);   // evaluation, 4-row tiles
+  else launch_var<T, false>(k, stream);                                                                        // run-time epilogue flags
   return hipGetLastError() == hipSuccess ? TF_OK : TF_ERR_LAUNCH;
 }
 

@@ -256,10 +256,21 @@ __global__ void __launch_bounds__(256, MMA == 32 ? 2 : (NS <= 2 && BM == 128 && 
   // operands (loads retire in order, so every later wait covers them).  For the count to be exact the requests are unconditional
   // (clamped addresses, the zero is selected afterwards).
   constexpr bool PF_COLD3 = PREF && EPIC >= 0 && (EPIC & TF_EPI_STATS3) && (EPIC & TF_EPI_RES) && !(EPIC & (TF_EPI_MASK | TF_EPI_STATS2 | TF_EPI_JOIN));
+  // Every OTHER instantiation with a compile-time flag set (the ring kernels, the gathers) used to load its operands at the point of use,
+  // inside the bounds test of the pass loop and behind the previous pass's store to y (the pointers are not restrict, nothing may be
+  // hoisted): one cold round trip per pass, 2 on the 64 x 64 tile, 4 on 64 x 128 / 32x32x16.  PFX: all of them are requested up front,
+  // unconditionally and from clamped addresses (pf1 = aux, pf2 = aux2, pf3 = aux3; the bounds test stays where the value is used), so the
+  // counted waits below know exactly how many loads are in flight.  JOIN's operands stay late loads (run-time-flag launches only).
+  // In place (aux == y, the scattered downsample gradient): reading aux before the K loop is legal only because every output element has a
+  // SINGLE writer in the launch, and that writer is the thread that requested it -- no other block's store can land between request and use.
+  // 64-pixel tiles only (64 x 64: 2 passes, 64 x 128 / 32x32x16: 4 passes under a 256-register bound): the 128 x 64 tile has four passes AND 64
+  // accumulator registers under a 96-register bound, and spills with them.
+  constexpr bool PFX = !PREF && BM == 64 && EPIC >= 0 && sizeof(T) == 2 && (EPIC & (TF_EPI_RES | TF_EPI_MASK | TF_EPI_STATS2 | TF_EPI_MASK2 | TF_EPI_STATS3)) && !(EPIC & TF_EPI_JOIN);
+  constexpr bool X1 = PFX && (EPIC & (TF_EPI_RES | TF_EPI_MASK | TF_EPI_STATS2)), X2 = PFX && (EPIC & TF_EPI_MASK2), X3 = PFX && (EPIC & TF_EPI_STATS3);
   constexpr int P_CPR = BN / EPS, P_RPP = 256 / P_CPR, P_PASSES = BM / P_RPP;
-  constexpr int NPF = PF_COLD3 ? 3 * P_PASSES : 0;
+  constexpr int NPF = PF_COLD3 ? 3 * P_PASSES : ((X1 ? 1 : 0) + (X2 ? 1 : 0) + (X3 ? 1 : 0)) * P_PASSES;
   uint4 pf1[P_PASSES], pf2[P_PASSES];      // (the third operand, JOIN's aux3, stays a late load: registers)
-  uint4 pf3[PF_COLD3 ? P_PASSES : 1];
+  uint4 pf3[PF_COLD3 || X3 ? P_PASSES : 1];
   auto prefetch = [&]() {
     const int pchunk = tid % P_CPR, prl = tid / P_CPR, pc0 = n0 + pchunk * EPS;
     const bool w1 = epi_flags & (TF_EPI_RES | TF_EPI_MASK | TF_EPI_STATS2), w2 = epi_flags & (TF_EPI_JOIN | TF_EPI_MASK2);
@@ -272,15 +283,22 @@ __global__ void __launch_bounds__(256, MMA == 32 ? 2 : (NS <= 2 && BM == 128 && 
         const uint4 t1 = *reinterpret_cast<const uint4*>(a.aux3 + o), t2 = *reinterpret_cast<const uint4*>(a.aux2 + o), t3 = *reinterpret_cast<const uint4*>(a.aux + o);
         const uint4 z = make_uint4(0, 0, 0, 0);
         pf1[ps] = ok ? t1 : z; pf2[ps] = ok ? t2 : z; pf3[ps] = ok ? t3 : z;
+      } else if constexpr (PFX) {            // (a clamped row's registers are never read: the epilogue tests p < M && cok before it unpacks them)
+        if constexpr (X1) pf1[ps] = *reinterpret_cast<const uint4*>(a.aux + o);
+        if constexpr (X2) pf2[ps] = *reinterpret_cast<const uint4*>(a.aux2 + o);
+        if constexpr (X3) pf3[ps] = *reinterpret_cast<const uint4*>(a.aux3 + o);
       } else {
         pf1[ps] = (ok && w1) ? *reinterpret_cast<const uint4*>(a.aux + o) : make_uint4(0, 0, 0, 0);
         pf2[ps] = (ok && w2) ? *reinterpret_cast<const uint4*>(a.aux2 + o) : make_uint4(0, 0, 0, 0);
       }
     }
   };
-  const bool pf_early = PF_COLD3 && (a.dbg & 32);    // TF_CONV_DBG=32 (A/B): requests in front of the first DMAs, first stage waited with vmcnt(0)
+  // PFX, up to two slots: the same placement as PF_COLD3 (behind the DMAs of the first stage, that stage waited for with vmcnt(NPF)).  Deeper
+  // rings have two or more stages in flight at the first wait: there the requests go in FRONT of the first DMAs, where no count changes.
+  constexpr bool PF_CNT = PF_COLD3 || PFX;           // the requests are counted loads
+  const bool pf_early = PF_CNT && (NS >= 3 || (a.dbg & (PF_COLD3 ? 32 : 64)));    // TF_CONV_DBG=32 / 64 (A/B, PF_COLD3 / PFX): requests in front of the first DMAs, first stage waited with vmcnt(0)
   if constexpr (PREF && !PF_COLD3) prefetch();
-  if constexpr (PF_COLD3) { if (pf_early) prefetch(); }
+  if constexpr (PF_CNT) { if (pf_early) prefetch(); }
 
   // stage iterator (scalar): stages are issued in order, so (slot, chunk, kw, kh) advance incrementally
   const bool par = KIND == 2 && a.scat == 2;       // parity class: only the taps kh0 + 2i, kw0 + 2j exist for these output pixels
@@ -340,7 +358,7 @@ __global__ void __launch_bounds__(256, MMA == 32 ? 2 : (NS <= 2 && BM == 128 && 
     for (int st = 0; st < nst; ++st) {
       if (st) __builtin_amdgcn_s_barrier();         // everyone finished reading the previous stage
       issue();
-      if constexpr (PF_COLD3) {
+      if constexpr (PF_CNT) {
         if (st == 0 && !pf_early) { prefetch(); wait_vmcnt<NPF>(); } else wait_vmcnt<0>();
       } else wait_vmcnt<0>();
       // (__syncthreads implies vmcnt(0), which the specialised instantiations must not pay: the raw barrier behind the counted wait is
@@ -352,12 +370,12 @@ __global__ void __launch_bounds__(256, MMA == 32 ? 2 : (NS <= 2 && BM == 128 && 
 #pragma unroll
   for (int j = 0; j < NS - 1; ++j)
     if (j < nst && !(a.dbg & 8)) issue();
-  if constexpr (PF_COLD3) { if (!pf_early) prefetch(); }      // (NS == 2: behind the DMAs of stage 0)
+  if constexpr (PF_CNT) { if (!pf_early) prefetch(); }        // (NS == 2: behind the DMAs of stage 0)
   int cs = 0;                                        // ring slot being computed
   for (int st = 0; st < nst; ++st) {
     // stage st has landed once at most min(NS-2, nst-1-st) younger stages are still in flight
     const int younger = nst - 1 - st;
-    if (PF_COLD3 && st == 0 && !pf_early) wait_vmcnt<NPF>();
+    if (PF_CNT && st == 0 && !pf_early) wait_vmcnt<NPF>();
     else if (younger >= NS - 2) wait_vmcnt<L*(NS - 2)>();
     else if (NS > 3 && younger == 1) wait_vmcnt<L>();
     else wait_vmcnt<0>();
@@ -368,6 +386,34 @@ __global__ void __launch_bounds__(256, MMA == 32 ? 2 : (NS <= 2 && BM == 128 && 
     if (++cs == NS) cs = 0;
   }
   }
+  // phase 2 roles: one 16-byte output chunk (EPS consecutive channels) of one pixel row per thread
+  constexpr int CPR = BN / EPS, RPP = 256 / CPR, PASSES = BM / RPP;
+  const int chunk = tid % CPR, rlane = tid / CPR;
+  const int c0 = n0 + chunk * EPS;
+  const bool cok = c0 < a.ldy;
+  float es[EPS], eh[EPS], ms[EPS], mh[EPS], s1[EPS], s2[EPS], sft[EPS];
+  auto load_coef = [&]() {
+#pragma unroll
+    for (int j = 0; j < EPS; ++j) { es[j] = 1.f; eh[j] = 0.f; ms[j] = 0.f; mh[j] = 0.f; s1[j] = 0.f; s2[j] = 0.f; sft[j] = 0.f; }
+    if (cok) {
+      if ((epi_flags & TF_EPI_STATS) && a.stat_shift) {    // sums of (x - shift), (x - shift)^2: see tf_conv_args.stat_shift
+#pragma unroll
+        for (int j = 0; j < EPS; ++j) sft[j] = a.stat_shift[c0 + j];
+      }
+      if (epi_flags & TF_EPI_AFFINE) {
+#pragma unroll
+        for (int j = 0; j < EPS; ++j) { es[j] = a.epi_scale[c0 + j]; eh[j] = a.epi_shift[c0 + j]; }
+      }
+      if (epi_flags & TF_EPI_MASK) {
+#pragma unroll
+        for (int j = 0; j < EPS; ++j) { ms[j] = a.mask_scale[c0 + j]; mh[j] = a.mask_shift[c0 + j]; }
+      }
+    }
+  };
+  // COEF_EARLY: the per-channel coefficients are requested HERE, behind the last counted wait: behind the __syncthreads of phase 1 they were one more
+  // exposed round trip per block, and the conditional loads left the compiler a vmcnt(0) in front of every pass, behind the previous pass's store.
+  constexpr bool COEF_EARLY = PFX || (EPIC == TF_EPI_STATS && sizeof(T) == 2);      // (... and the training forward's statistic shift)
+  if constexpr (COEF_EARLY) load_coef();
   __builtin_amdgcn_s_barrier();                     // all waves done reading the ring -> reuse it as the staging tile
   if (a.dbg & 4) { if (acc[0][0][0] == 123.456f) a.y[0] = 1; return; }
 
@@ -395,28 +441,8 @@ __global__ void __launch_bounds__(256, MMA == 32 ? 2 : (NS <= 2 && BM == 128 && 
   }
   __syncthreads();
 
-  // ---------------- phase 2: one 16-byte output chunk (EPS consecutive channels) of one pixel row per thread
-  constexpr int CPR = BN / EPS, RPP = 256 / CPR, PASSES = BM / RPP;
-  const int chunk = tid % CPR, rlane = tid / CPR;
-  const int c0 = n0 + chunk * EPS;
-  const bool cok = c0 < a.ldy;
-  float es[EPS], eh[EPS], ms[EPS], mh[EPS], s1[EPS], s2[EPS], sft[EPS];
-#pragma unroll
-  for (int j = 0; j < EPS; ++j) { es[j] = 1.f; eh[j] = 0.f; ms[j] = 0.f; mh[j] = 0.f; s1[j] = 0.f; s2[j] = 0.f; sft[j] = 0.f; }
-  if (cok) {
-    if ((epi_flags & TF_EPI_STATS) && a.stat_shift) {    // sums of (x - shift), (x - shift)^2: see tf_conv_args.stat_shift
-#pragma unroll
-      for (int j = 0; j < EPS; ++j) sft[j] = a.stat_shift[c0 + j];
-    }
-    if (epi_flags & TF_EPI_AFFINE) {
-#pragma unroll
-      for (int j = 0; j < EPS; ++j) { es[j] = a.epi_scale[c0 + j]; eh[j] = a.epi_shift[c0 + j]; }
-    }
-    if (epi_flags & TF_EPI_MASK) {
-#pragma unroll
-      for (int j = 0; j < EPS; ++j) { ms[j] = a.mask_scale[c0 + j]; mh[j] = a.mask_shift[c0 + j]; }
-    }
-  }
+  // ---------------- phase 2 (roles and coefficients: see in front of phase 1)
+  if constexpr (!COEF_EARLY) load_coef();
 #pragma unroll
   for (int ps = 0; ps < PASSES; ++ps) {
     const int row = rlane + ps * RPP;
@@ -436,7 +462,7 @@ __global__ void __launch_bounds__(256, MMA == 32 ? 2 : (NS <= 2 && BM == 128 && 
       float ax[EPS];
       if (epi_flags & (TF_EPI_RES | TF_EPI_MASK | TF_EPI_STATS2)) {
         if constexpr (PF_COLD3) tf::unpack16<T>(pf3[PF_COLD3 ? ps : 0], ax);
-        else if constexpr (PREF) tf::unpack16<T>(pf1[ps], ax);
+        else if constexpr (PREF || X1) tf::unpack16<T>(pf1[ps], ax);
         else tf::unpack16<T>(*reinterpret_cast<const uint4*>(a.aux + o), ax);
       }
       if (epi_flags & TF_EPI_AFFINE) {
@@ -460,7 +486,7 @@ __global__ void __launch_bounds__(256, MMA == 32 ? 2 : (NS <= 2 && BM == 128 && 
       }
       if (epi_flags & TF_EPI_MASK2) {
         float y2[EPS];
-        if constexpr (PREF) tf::unpack16<T>(pf2[ps], y2); else tf::unpack16<T>(*reinterpret_cast<const uint4*>(a.aux2 + o), y2);
+        if constexpr (PREF || X2) tf::unpack16<T>(pf2[ps], y2); else tf::unpack16<T>(*reinterpret_cast<const uint4*>(a.aux2 + o), y2);
 #pragma unroll
         for (int j = 0; j < EPS; ++j) v[j] = (y2[j] > 0.f) ? v[j] : 0.f;
       }
@@ -474,7 +500,9 @@ __global__ void __launch_bounds__(256, MMA == 32 ? 2 : (NS <= 2 && BM == 128 && 
       }
       if (epi_flags & TF_EPI_STATS3) {
         float x3[EPS];
-        if constexpr (PF_COLD3) tf::unpack16<T>(pf1[ps], x3); else tf::unpack16<T>(*reinterpret_cast<const uint4*>(a.aux3 + o), x3);
+        if constexpr (PF_COLD3) tf::unpack16<T>(pf1[ps], x3);
+        else if constexpr (X3) tf::unpack16<T>(pf3[X3 ? ps : 0], x3);
+        else tf::unpack16<T>(*reinterpret_cast<const uint4*>(a.aux3 + o), x3);
 #pragma unroll
         for (int j = 0; j < EPS; ++j) {
           // in place (r6): the launch that wrote the raster already counted ax = its (masked) value here; this launch adds what IT adds.
