@@ -81,7 +81,14 @@ int tf_pairwise_iou_distance(const double* boxes, int n, double* out, void* stre
 /* ---- greedy NMS, float64 -----------------------------------------------------------
  * Replaces torchvision.ops.nms as called at tinyfaces/evaluation.py:84 (float64 boxes and
  * scores): stable descending sort, areas without +1, strict `>` on IoU.  keep_out holds the
- * surviving INPUT indices in descending-score order; *num_keep (device int32) their count. */
+ * surviving INPUT indices in descending-score order; *num_keep (device int32) their count.
+ * Score order: the one torch.sort(scores, descending, stable) hands the reference's kernel, for ANY float64 scores: a NaN ranks above
+ * every number, +inf included, and NaNs among themselves by input index; -0.0 == +0.0; equal scores keep input order.  The order is a
+ * permutation of 0..n-1 whatever the scores: every element of the workspace's order / sorted-box arrays in [0, n) is written on every
+ * call, and keep_out holds each input index at most once.  Box coordinates must be finite (the reference's std::max, fmax and
+ * numpy's maximum each treat a NaN operand differently).  Any iou_thresh is accepted as given: a pair suppresses iff IoU > iou_thresh
+ * (strict), so a negative threshold suppresses disjoint boxes too (their IoU is 0), one >= 1 suppresses nothing, exact duplicates
+ * included (IoU 1), and a NaN IoU (0 / 0: two zero-area boxes) never suppresses.  -0.0 is 0.0. */
 size_t tf_nms_workspace_bytes(int n);
 int tf_nms_f64(const double* boxes /*[n][4]*/, const double* scores /*[n]*/, int n, double iou_thresh,
                int64_t* keep_out /*[n]*/, int32_t* num_keep, void* ws, size_t ws_bytes, void* stream);
@@ -182,7 +189,8 @@ int tf_soft_nms_f64_capped(const double* boxes /*[n][4]*/, const double* scores 
  * on the host, so there is no device-side count and no synchronisation.
  *   Which rows: the m_s rows that come first in the order the hard NMS itself uses (rank[i] = #{j : s_j > s_i or (s_j == s_i and j < i)}):
  *     larger score first; on equal scores the lower input index first (-0.0 and +0.0 are equal); a NaN ranks behind every number, -inf
- *     included, NaNs among themselves by index.
+ *     included, NaNs among themselves by index (HERE a NaN is never preferred to a number; tf_nms_f64 visits NaNs first, as torch.sort
+ *     does: the identity below is stated for scores without NaN).
  *   In which order: ASCENDING input index, not score order -- the compacted list keeps the candidate list's order, so a later stable sort,
  *     tie-break or voter sum sees the rows it would have seen.  Hence, with idx the output for one segment and nms() = tf_nms_f64's keep
  *     list:  idx[nms(boxes[idx], scores[idx])] == the entries of nms(boxes, scores) whose rank is below k, and those are a prefix of it.

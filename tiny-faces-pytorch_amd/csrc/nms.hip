@@ -3,6 +3,8 @@
 //
 //   1 rank sort   rank[i] = #{j : s_j > s_i  or (s_j == s_i and j < i)}  -> stable descending
 //                 order without a sorting network; O(N^2) compares, same order as the IoU work.
+//                 `>` and `==` are those of torch.sort(descending, stable): a NaN is greater than every number and equal to
+//                 every NaN, -0.0 == +0.0 -- a permutation of 0..n-1 for ANY score vector.
 //   2 bit matrix  mask[i][w] bit j = IoU(sorted i, sorted 64w+j) > thr, j > i (upper triangle),
 //                 one 64-thread wave per 64x64 block, column boxes staged in LDS.
 //   3 scan        two levels (r3): per super-chunk of 1024 boxes one workgroup resolves the 16 chunks against the diagonal
@@ -30,12 +32,18 @@ struct Segs {                     // passed by value as a kernel argument: no H2
 // 2048-score tile entirely below / above the block's 128 boxes takes ONE float64 compare per pair (r3: 0.94 -> 0.4 ms at N = 65 536).
 // Q boxes per thread: 4 (128 per block) for long lists, 1 (32 per block: four times the blocks) below 16 384 boxes, where the grid
 // of the wide form would leave most of the chip idle.
+// NaN scores: every float64 compare against a NaN is false, so the three paths above would give rank 0 to every NaN and count no NaN
+// in front of a number: several boxes in slot 0, the last slots of order / sboxes never written (the scan then emits whatever an
+// earlier call left there).  The order is torch.sort's, NaN first: the NaNs of the list are counted while the tiles are staged (one
+// compare per LOADED score, not per pair) and added to the rank of every number; a block that holds a NaN among its OWN boxes (block-
+// uniform, decided once) takes a fourth path with the whole predicate spelled out.  Lists without NaN run the compares they ran before.
 template <int Q>
 __global__ void __launch_bounds__(256) nms_rank_kernel(const double* __restrict__ scores_all, const double* __restrict__ boxes_all,
                                                        const Segs sg, int* __restrict__ order_all, double* __restrict__ sboxes_all) {
   __shared__ double tile[2048];
   constexpr int kRankBoxes = 32 * Q;
   __shared__ int part[8][kRankBoxes];
+  __shared__ int nan_total;
   const int base = sg.off[blockIdx.y], n = sg.off[blockIdx.y + 1] - base;
   const int i0 = blockIdx.x * kRankBoxes;
   if (i0 >= n) return;                                    // block-uniform: the grid is sized for the largest segment
@@ -45,14 +53,44 @@ __global__ void __launch_bounds__(256) nms_rank_kernel(const double* __restrict_
   double* sboxes = sboxes_all + 4 * (size_t)base;
   const int li = threadIdx.x & 31, p = threadIdx.x >> 5;
   double si[Q]; int rank[Q];
+  bool in[Q], any_in = false;
 #pragma unroll
-  for (int q = 0; q < Q; ++q) { const int i = i0 + li + 32 * q; si[q] = i < n ? scores[i] : 0.0; rank[q] = 0; }
+  for (int q = 0; q < Q; ++q) {
+    const int i = i0 + li + 32 * q;
+    si[q] = i < n ? scores[i] : 0.0; rank[q] = 0;
+    in[q] = si[q] != si[q]; any_in |= in[q];
+  }
+  if (threadIdx.x == 0) nan_total = 0;
+  const bool own_nan = __syncthreads_or(any_in);          // block-uniform; the barrier also orders the reset of nan_total
+  int nans = 0;                                           // NaNs among the scores THIS thread stages: every j of the list exactly once per block
   for (int j0 = 0; j0 < n; j0 += 2048) {
     __syncthreads();
-    for (int k = threadIdx.x; k < 2048; k += 256) tile[k] = (j0 + k < n) ? scores[j0 + k] : -1.0e300;
+    if (j0 + 2048 <= n) {                                 // a whole tile (all but the last): no bound to test per score
+#pragma unroll
+      for (int k = threadIdx.x; k < 2048; k += 256) {
+        const double v = scores[j0 + k];
+        tile[k] = v; nans += v != v;
+      }
+    } else {
+      for (int k = threadIdx.x; k < 2048; k += 256) {
+        const double v = (j0 + k < n) ? scores[j0 + k] : -1.0e300;
+        tile[k] = v; nans += v != v;
+      }
+    }
     __syncthreads();
     const int lim = min(2048, n - j0);
-    if (j0 + 2048 <= i0) {                                // every j of the tile is below every i of the block: ties count
+    if (own_nan) {                                        // a NaN among the block's own boxes: NaN > every number, NaN == NaN, ties by index
+#pragma unroll 2
+      for (int k = p; k < lim; k += 8) {
+        const double sj = tile[k];
+        const bool jn = sj != sj;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          const bool lower = (j0 + k) < i0 + li + 32 * q;
+          rank[q] += in[q] ? (jn && lower) : (jn || (sj > si[q]) || (sj == si[q] && lower));
+        }
+      }
+    } else if (j0 + 2048 <= i0) {                         // every j of the tile is below every i of the block: ties count
 #pragma unroll 4
       for (int k = p; k < lim; k += 8) {
         const double sj = tile[k];
@@ -77,11 +115,12 @@ __global__ void __launch_bounds__(256) nms_rank_kernel(const double* __restrict_
   }
 #pragma unroll
   for (int q = 0; q < Q; ++q) part[p][li + 32 * q] = rank[q];
+  if (nans) atomicAdd(&nan_total, nans);                  // an integer sum: the same whatever the arrival order
   __syncthreads();
   if (threadIdx.x < kRankBoxes) {
     const int i = i0 + threadIdx.x;
     if (i < n) {
-      int r = 0;
+      int r = own_nan ? 0 : nan_total;                    // every NaN of the list is in front of every number (the fourth path counted them)
 #pragma unroll
       for (int q = 0; q < 8; ++q) r += part[q][threadIdx.x];
       order[r] = i;

@@ -138,7 +138,12 @@ def pairwise_iou_distance(boxes, device="cuda"):
 # --------------------------------------------------------------------------- NMS
 def nms(boxes, scores, iou_threshold):
     """torchvision.ops.nms semantics on float64 device tensors (call site tinyfaces/evaluation.py:84).
-    Returns int64 indices of kept boxes in descending-score order."""
+    Returns int64 indices of kept boxes in descending-score order.
+    Score order (tf_nms_f64, include/tinyfaces_hip.h): that of torch.sort(scores, descending=True, stable=True) for ANY scores -- a NaN
+    ranks above every number, +inf included, NaNs among themselves by input index; -0.0 == +0.0; equal scores keep input order.  The keep
+    is always a duplicate-free list of indices into the input.  Box coordinates must be finite.  Any iou_threshold is taken as given:
+    suppression is the strict `IoU > iou_threshold`, so a negative one suppresses disjoint boxes too (IoU 0), one >= 1 suppresses nothing,
+    exact duplicates included, and a NaN IoU (0 / 0: two zero-area boxes) never suppresses."""
     require_gpu(boxes, "nms")
     boxes = boxes.to(torch.float64).contiguous()
     scores = scores.to(torch.float64).contiguous()
@@ -164,6 +169,8 @@ def nms_batched(boxes, scores, seg_offsets, iou_threshold, mask_budget_bytes=Non
     """`_nms_batched_call` over groups of consecutive segments whose bit matrices fit `mask_budget_bytes` (default 2 GiB): at the
     evaluation default prob_thresh = 0.03 an image can have tens of thousands of candidates (300 MB of matrix each), so a 64-image
     batch in one call would ask for tens of GB of workspace.  A single segment larger than the budget still goes alone.
+    Score order and threshold per segment as `nms`: torch.sort's order for any scores (NaN first, by input index; -0.0 == +0.0; ties keep
+    input order), finite box coordinates, any iou_threshold (strict `>`: a negative one suppresses disjoint boxes).
     vote = (vote_thresh, weight): as in `_nms_batched_call`, returns (keeps, voted rows)."""
     offs = [int(o) for o in seg_offsets]
     budget = NMS_MASK_BUDGET_BYTES if mask_budget_bytes is None else int(mask_budget_bytes)
