@@ -616,6 +616,39 @@ int tf_conv2d_wgrad_group(const tf_wgrad_args* problems, int n, void* stream);
 /* [Cout][taps][Cin] fp32 -> OIHW fp32 (overwrites) */
 int tf_unpack_dw(const float* packed, int Cout, int Cin, int taps, float* dw_oihw, void* stream);
 
+/* ---- deterministic weight gradients: the slab form of tf_conv2d_wgrad (no floating-point atomics; the same bits on every run) ----------
+ * tf_conv2d_wgrad_det takes the arguments, the operand contract and the kernel choice (`tile`) of tf_conv2d_wgrad.  Every block of the
+ * split-K kernel stores its fp32 tile with plain stores into its own place of the slab a->partial_ws (a->partial_ws_bytes bytes, 16-byte
+ * aligned; never read by that kernel, need not be zeroed), and one summing kernel adds the slices of every output element ONCE into dw:
+ *   dw = dw_in + row_scale[co] * total     (one writer per element; `packed`, dw_ld and the co < Cout, ci < Cin masks as in tf_conv2d_wgrad)
+ * THE PLAN.  M = N*OH*OW pixels (the all-taps 3x3 kernel: Mp = N*(H+2)*(W+2), the zero-padded raster), PK = 64 pixels per stage (fp32: 32),
+ * BC = 64 channels per tile side (the register-staged kernel with tile = 128: 128), tiles = KH*KW * ceil(Cout/BC) * ceil(Cin/BC).
+ *   sk     = a->splitk when > 0, else the kernel's own choice (that of tf_conv2d_wgrad);
+ *   sk     = min(sk, partial_ws_bytes / (tiles * BC*BC * 4))          -- a slab that is too small means fewer slices, never atomics;
+ *                                                                        TF_ERR_ARG (nothing enqueued) when not even one slice fits;
+ *   chunk  = ceil(ceil(M / sk) / PK) * PK;   slices = ceil(M / chunk); slice s reduces the pixels [s*chunk, min(M, (s+1)*chunk)): the slices
+ *            cover [0, M) exactly and none is empty.
+ * Slab layout: [slice][tap][co tile][ci tile][BC co][BC ci] fp32 (all-taps 3x3 kernel: [slice][co tile][ci tile][tap][64][64]).
+ * THE ORDER.  G = tf_wgrad_det_groups(slices) = 16 (slices >= 128) | 4 (>= 32) | 2 (>= 16) | 1.  For g in 0 .. G-1:
+ *   t_g = 0.0f; for s = g, g + G, g + 2G ... < slices: t_g = t_g + partial[s]        (fp32, rising s)
+ * total = t_0; for g = 1 .. G-1: total = total + t_g; then total = total * row_scale[co] (rounded, when given); dw = dw + total.
+ * tests/wgrad_det_ref.py restates both in numpy.  tf_wgrad_det_workspace_bytes: the preferred slab (slices uncapped) for any call
+ * tf_conv2d_wgrad accepts, never 0 for a valid call. */
+size_t tf_wgrad_det_workspace_bytes(const tf_wgrad_args* a);
+int tf_conv2d_wgrad_det(const tf_wgrad_args* a, void* stream);
+int tf_wgrad_det_groups(int slices);
+/* tf_stem_wgrad in the same form: every block of the grid stores its [64][147] fp32 tile into `slab` (16-byte aligned), the tiles are summed
+ * in THE ORDER above (slices = blocks) and added once into dw_oihw.  Preferred slab: the grid tf_stem_wgrad launches; a smaller slab means
+ * fewer blocks, below one tile TF_ERR_ARG. */
+size_t tf_stem_wgrad_det_workspace_bytes(int N, int H, int W);
+int tf_stem_wgrad_det(int dtype, const float* x_nchw, int N, int H, int W, const void* g, const void* x_conv, const float* cA, const float* cB,
+                      const float* cD, float* dw_oihw, void* slab, size_t slab_bytes, void* stream);
+/* Process-wide switch, like tf_set_stat_rows.  While on: tf_get_stat_rows() reports unfolded rows (plain-store BatchNorm statistics; the
+ * rows set with tf_set_stat_rows are kept and come back when the switch goes off) and the executor (tf_detnet_*backward*) takes only the
+ * deterministic weight-gradient entries above, with its own arena as the slab.  Same inputs, same weights in -> the same gradient bits out. */
+int tf_set_deterministic(int on);
+int tf_get_deterministic(void);
+
 
 /* ---- HBM-bound companions of the conv engine (NHWC, dtype TF_F32 | TF_BF16) ---------- */
 /* conv1 (7x7 s2 p3, 3->64; model.py:90): x NCHW fp32 -> im2col [N*OH*OW][ldc], k = c*49+kh*7+kw

@@ -20,6 +20,8 @@ static const char* const kSymbols[] = {
     "tf_grad_accumulate_segments",
     "tf_adamw_advance", "tf_adamw_step", "tf_adamw_step_segments",
     "tf_conv_mtiles", "tf_conv2d", "tf_pack_weight", "tf_pack_weights_batched", "tf_pack_weights_tiled", "tf_conv2d_wgrad", "tf_conv2d_wgrad_group", "tf_wgrad_workspace_bytes", "tf_unpack_dw",
+    "tf_wgrad_det_workspace_bytes", "tf_conv2d_wgrad_det", "tf_wgrad_det_groups", "tf_stem_wgrad_det", "tf_stem_wgrad_det_workspace_bytes",
+    "tf_set_deterministic", "tf_get_deterministic",
     "tf_stem_im2col", "tf_stem_conv", "tf_stem_wgrad", "tf_maxpool_fwd", "tf_maxpool_bwd", "tf_maxpool_bwd_stats", "tf_colstats_blocks", "tf_colstats",
     "tf_bn_finalize", "tf_bn_fold", "tf_bn_bwd_finalize", "tf_bn_bwd_apply", "tf_bn_relu", "tf_bn_add_relu",
     "tf_bn_relu_fused", "tf_bn_add_relu_fused", "tf_bn_bwd_apply_fused",
@@ -39,7 +41,7 @@ void set_next_stop_event(hipEvent_t e) { g_next_stop_event = e; }
 hipEvent_t take_next_stop_event() { hipEvent_t e = g_next_stop_event; g_next_stop_event = nullptr; return e; }
 }  // namespace tf
 
-extern "C" int tf_version(void) { return 740; }   // 740: WIDER evaluation on the device (tf_wider_match_f64_batched, tf_wider_pr_accumulate, tf_wider_match_workspace_bytes); 730: colour jitter (tf_image_prepare_jitter, tf_image_prepare_jitter_workspace_bytes); 720: top-k selection + the Soft-NMS cap (tf_topk_select_f64[_batched], tf_soft_nms_f64[_batched]_capped); 710: AdamW (tf_adamw_advance, tf_adamw_step, tf_adamw_step_segments); 700: IoU / GIoU / DIoU regression losses (tf_criterion_focal_box_fwd_bwd); 690: focal loss (tf_criterion_focal_fwd_bwd); 680: Soft-NMS (tf_soft_nms_f64, tf_soft_nms_f64_batched); 670: gradient accumulation (tf_grad_accumulate_segments); 660: test-time augmentation (tf_box_vote_f64, tf_box_vote_f64_batched, tf_boxes_unflip_f64); 650: model EMA (tf_sgd_step_ema, tf_sgd_step_segments_ema, tf_ema_update_segments); 640: gradient-norm clipping + the non-finite-step guard (tf_grad_clip_coef, tf_sgd_step*_clipped, tf_scale_segments); 630: partial freeze (tf_detnet_trunk_backward_frozen_from_ctx); 620: frozen BatchNorm (training = 2, tf_detnet_*backward_frozen_ctx, tf_sgd_step_segments); 610: tf_detnet_trunk_* (ResNet-50 / -152 trunks); r6: tf_build_id; r4: context + hooks + communicator entry points
+extern "C" int tf_version(void) { return 750; }   // 750: deterministic training (tf_set_deterministic, tf_conv2d_wgrad_det, tf_stem_wgrad_det and their workspace queries); 740: WIDER evaluation on the device (tf_wider_match_f64_batched, tf_wider_pr_accumulate, tf_wider_match_workspace_bytes); 730: colour jitter (tf_image_prepare_jitter, tf_image_prepare_jitter_workspace_bytes); 720: top-k selection + the Soft-NMS cap (tf_topk_select_f64[_batched], tf_soft_nms_f64[_batched]_capped); 710: AdamW (tf_adamw_advance, tf_adamw_step, tf_adamw_step_segments); 700: IoU / GIoU / DIoU regression losses (tf_criterion_focal_box_fwd_bwd); 690: focal loss (tf_criterion_focal_fwd_bwd); 680: Soft-NMS (tf_soft_nms_f64, tf_soft_nms_f64_batched); 670: gradient accumulation (tf_grad_accumulate_segments); 660: test-time augmentation (tf_box_vote_f64, tf_box_vote_f64_batched, tf_boxes_unflip_f64); 650: model EMA (tf_sgd_step_ema, tf_sgd_step_segments_ema, tf_ema_update_segments); 640: gradient-norm clipping + the non-finite-step guard (tf_grad_clip_coef, tf_sgd_step*_clipped, tf_scale_segments); 630: partial freeze (tf_detnet_trunk_backward_frozen_from_ctx); 620: frozen BatchNorm (training = 2, tf_detnet_*backward_frozen_ctx, tf_sgd_step_segments); 610: tf_detnet_trunk_* (ResNet-50 / -152 trunks); r6: tf_build_id; r4: context + hooks + communicator entry points
 #ifndef TF_BUILD_ID
 #define TF_BUILD_ID "unstamped"
 #endif
@@ -47,8 +49,13 @@ extern "C" int tf_version(void) { return 740; }   // 740: WIDER evaluation on th
 // committed profile is stamped with, so that a measurement taken with another binary is recognised as stale (bench.py `traffic_stale`)
 extern "C" const char* tf_build_id(void) { return TF_BUILD_ID; }
 static int g_stat_rows = 8;
+// deterministic switch: while on, the statistic rows read as unfolded whatever was set (a tf_set_stat_rows call in between is kept for when
+// the switch goes off) and the executor takes the slab forms of the weight gradients (csrc/detnet.hip)
+static int g_deterministic = 0;
 extern "C" int tf_set_stat_rows(int rows) { g_stat_rows = rows <= 0 ? (1 << 30) : (rows > TF_STAT_ROWS ? TF_STAT_ROWS : rows); return TF_OK; }
-extern "C" int tf_get_stat_rows(void) { return g_stat_rows; }
+extern "C" int tf_get_stat_rows(void) { return g_deterministic ? (1 << 30) : g_stat_rows; }
+extern "C" int tf_set_deterministic(int on) { g_deterministic = on ? 1 : 0; return TF_OK; }
+extern "C" int tf_get_deterministic(void) { return g_deterministic; }
 extern "C" int tf_symbol_count(void) { return (int)(sizeof(kSymbols) / sizeof(kSymbols[0])); }
 extern "C" const char* tf_symbol_name(int i) { return (i >= 0 && i < tf_symbol_count()) ? kSymbols[i] : nullptr; }
 

@@ -362,6 +362,9 @@ struct Ctx {
   int dtype; hipStream_t stream; void* const* params; void* const* grads; int rc;
   bool grads_zeroed = false;
   bool skip_fold = false;
+  // tf_set_deterministic(1): every weight gradient takes its slab form (tf_conv2d_wgrad_det / tf_stem_wgrad_det), all on wstream(), so
+  // consecutive gradients share the one slab (the arena's P.dwp)
+  bool det = false; float* det_slab = nullptr; size_t det_slab_bytes = 0;
   std::vector<tf_pack_job> jobs;
   std::vector<tf_pack2_job> jobs2;
   hipStream_t side = nullptr;                 // weight gradients run here, concurrently with the data-gradient chain
@@ -802,6 +805,14 @@ void wgrad(Ctx& c, const ConvUnit& u, int cout, int N, int H, int W, int OH, int
   const int cin = cin_override ? cin_override : u.cin, k = k_override ? k_override : u.k;
   tf_wgrad_args w = wgrad_args(c, u, cout, N, H, W, OH, OW, x, ldx, dy, lddy, cin_override, k_override, dw_ld);
   w.row_scale = row_scale;
+  if (c.det) {
+    // slab form: the slices of every split-K kernel go through the slab and are summed in a fixed order straight into the OIHW gradient
+    // (the stride-2 3x3 convs too: no packed scratch, no transposing copy); a slab too small for the preferred plan means fewer slices
+    if (!c.grads_zeroed && hipMemsetAsync(w.dw_oihw, 0, (size_t)cout * w.dw_ld * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
+    w.partial_ws = c.det_slab; w.partial_ws_bytes = c.det_slab_bytes;
+    c.chk(tf_conv2d_wgrad_det(&w, c.wstream()));
+    return;
+  }
   if (k > 1 && packed_scratch && c.grads_zeroed) {
     // 3x3 / stride 1: the all-taps kernel sums its split-K slices through the scratch straight into the (already zeroed) OIHW
     // gradient: no memset, no atomics, no transposing copy
@@ -869,6 +880,7 @@ int open_backward(const int* blocks, tf_detnet_ctx* xctx, const tf_detnet_hooks*
   if (!ar.ok) return TF_ERR_WORKSPACE;
   c = Ctx{dtype, (hipStream_t)stream_, params, grads, TF_OK};   // (grads_zeroed / jobs default-initialised)
   if (!tf::tuning().single_stream && !(hooks && hooks->single_stream) && xctx) { c.side = ctx_side(xctx); c.events = &xctx->events; }
+  c.det = tf_get_deterministic() != 0; c.det_slab = P.dwp; c.det_slab_bytes = P.dwp_floats * sizeof(float);
   return TF_OK;
 }
 
@@ -1021,7 +1033,11 @@ struct WgradGroups {
       auto fallback = [&](const std::vector<tf_wgrad_args>& v) {
         for (const tf_wgrad_args& w : v) {
           if (hipMemsetAsync(w.dw_oihw, 0, (size_t)w.Cout * w.dw_ld * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-          c.chk(tf_conv2d_wgrad(&w, c.wstream()));
+          if (c.det) {
+            tf_wgrad_args d = w;
+            d.partial_ws = c.det_slab; d.partial_ws_bytes = c.det_slab_bytes;
+            c.chk(tf_conv2d_wgrad_det(&d, c.wstream()));
+          } else c.chk(tf_conv2d_wgrad(&w, c.wstream()));
         }
       };
       const bool force_refuse = tf::tuning().dbg_group_refuse;      // test knob: exercise the fallback at any size
@@ -1242,7 +1258,8 @@ extern "C" int tf_detnet_trunk_backward_ctx(const int* blocks, tf_detnet_ctx* xc
     c.fork();
     if (stem_direct) {
       if (!c.grads_zeroed && hipMemsetAsync(c.G(A.stem.w), 0, (size_t)64 * 147 * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
-      c.chk(tf_stem_wgrad(dtype, x, N, H, W, gz, P.cstem, P.bn_stem.cA, P.bn_stem.cB, P.bn_stem.cD, c.G(A.stem.w), c.wstream()));
+      if (c.det) c.chk(tf_stem_wgrad_det(dtype, x, N, H, W, gz, P.cstem, P.bn_stem.cA, P.bn_stem.cB, P.bn_stem.cD, c.G(A.stem.w), c.det_slab, c.det_slab_bytes, c.wstream()));
+      else c.chk(tf_stem_wgrad(dtype, x, N, H, W, gz, P.cstem, P.bn_stem.cA, P.bn_stem.cB, P.bn_stem.cD, c.G(A.stem.w), c.wstream()));
     } else wgrad(c, s, 64, 1, 1, M1, 1, M1, P.col, kStemK, gz, 64, nullptr, 147, 1, 147);
   }
   return close_backward(c, hooks);
@@ -1350,7 +1367,8 @@ extern "C" int tf_detnet_trunk_backward_frozen_from_ctx(const int* blocks, tf_de
     if (stem_direct) {
       if (!c.grads_zeroed && hipMemsetAsync(c.G(A.stem.w), 0, (size_t)64 * 147 * 4, c.wstream()) != hipSuccess) c.chk(TF_ERR_LAUNCH);
       // operand = cA * g + cB * x_conv + cD with cA = the folded scale, cB = cD = 0
-      c.chk(tf_stem_wgrad(dtype, x, N, H, W, gz, P.cstem, P.bn_stem.scale, P.c_zero, P.c_zero, c.G(A.stem.w), c.wstream()));
+      if (c.det) c.chk(tf_stem_wgrad_det(dtype, x, N, H, W, gz, P.cstem, P.bn_stem.scale, P.c_zero, P.c_zero, c.G(A.stem.w), c.det_slab, c.det_slab_bytes, c.wstream()));
+      else c.chk(tf_stem_wgrad(dtype, x, N, H, W, gz, P.cstem, P.bn_stem.scale, P.c_zero, P.c_zero, c.G(A.stem.w), c.wstream()));
     } else wgrad(c, s, 64, 1, 1, M1, 1, M1, P.col, kStemK, gz, 64, P.bn_stem.scale, 147, 1, 147);      // (P.col still holds the im2col matrix of this forward)
   }
   return close_backward(c, hooks);

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "tuning.h"
 #include "profile.h"
+#include "wgrad_det.h"
 
 namespace {
 
@@ -276,7 +277,10 @@ struct StemWK {
 
 // APPLY (the training graph): the operand is  cA * g + cB * x_conv + cD  (tf_bn_bwd_apply of the stem's BatchNorm), formed while the gradient
 // tile is staged -- the applied tensor has no other reader (conv1 has no data gradient), so the 288 MB apply pass disappears
-template <typename T, bool APPLY>
+// DET (tf_stem_wgrad_det): a.dw is a slab of one [64][147] fp32 tile per block of the grid; the block stores its tile there with plain
+// stores (no read, no atomics) and the summing kernel of csrc/wgrad_det.hip adds the tiles in a fixed order.  A compile-time form of its own,
+// so that the default instantiation is the kernel it always was.
+template <typename T, bool APPLY, bool DET = false>
 __global__ void __launch_bounds__(256, 2) stem_wgrad_kernel(const StemWK a) {     // (1.5 blocks per CU are launched: registers over occupancy)
   __shared__ __attribute__((aligned(16))) char gt[TH * TW * 128];               // [pixel][64 channels], slot-swizzled
   __shared__ __attribute__((aligned(16))) uint16_t cp[NCOPY * COPY + CW];      // + one zero row (k >= 147)
@@ -422,7 +426,10 @@ __global__ void __launch_bounds__(256, 2) stem_wgrad_kernel(const StemWK a) {   
       const int k = (kf0 + j) * 16 + r;
       if (k < 147) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) atomicAdd(&a.dw[(size_t)((cf0 + n) * 16 + g * 4 + i) * 147 + k], acc[n][j][i]);
+        for (int i = 0; i < 4; ++i) {
+          if constexpr (DET) a.dw[(size_t)blockIdx.x * (64 * 147) + (size_t)((cf0 + n) * 16 + g * 4 + i) * 147 + k] = acc[n][j][i];
+          else atomicAdd(&a.dw[(size_t)((cf0 + n) * 16 + g * 4 + i) * 147 + k], acc[n][j][i]);
+        }
       }
     }
 }
@@ -499,4 +506,53 @@ extern "C" int tf_stem_wgrad(int dtype, const float* x_nchw, int N, int H, int W
     else TF_LAUNCH_TIMED((stem_wgrad_kernel<tf::f16_t, false>), dim3(grid), dim3(256), 0, stream, k);
   }
   return hipGetLastError() == hipSuccess ? TF_OK : TF_ERR_LAUNCH;
+}
+
+// tf_stem_wgrad without fp32 atomics: one [64][147] fp32 tile per block of the grid in `slab` (plain stores; never read by the kernel, never
+// zeroed), then dw_oihw += the sum of the tiles in the fixed order of the summing kernel (csrc/wgrad_det.hip).  The preferred slab holds the
+// grid tf_stem_wgrad launches; a smaller slab means a smaller grid, below one tile TF_ERR_ARG.
+extern "C" size_t tf_stem_wgrad_det_workspace_bytes(int N, int H, int W) {
+  if (N < 1 || H < 1 || W < 1) return 0;
+  const int OH = (H + 6 - 7) / 2 + 1, OW = (W + 6 - 7) / 2 + 1;
+  const long nt = (long)N * ((OW + TW - 1) / TW) * ((OH + TH - 1) / TH);
+  const unsigned want = (unsigned)tf::tuning().stem_wgrad_blocks;
+  long grid = want < 1 ? 1 : want;
+  if (grid > nt) grid = nt;
+  return (size_t)grid * 64 * 147 * sizeof(float);
+}
+extern "C" int tf_stem_wgrad_det(int dtype, const float* x_nchw, int N, int H, int W, const void* g, const void* x_conv, const float* cA, const float* cB,
+                                 const float* cD, float* dw_oihw, void* slab, size_t slab_bytes, void* stream_) {
+  if (!x_nchw || !g || !dw_oihw || N < 1 || H < 1 || W < 1) return TF_ERR_ARG;
+  if (dtype != TF_BF16 && dtype != TF_F16) return TF_ERR_UNSUPPORTED;
+  const bool apply = x_conv != nullptr;
+  if (apply && (!cA || !cB || !cD)) return TF_ERR_ARG;
+  if (!slab || ((uintptr_t)slab & 15)) return TF_ERR_ARG;
+  StemWK k;
+  k.x = x_nchw; k.g = (const char*)g; k.dw = (float*)slab; k.xc = (const char*)x_conv; k.cA = cA; k.cB = cB; k.cD = cD;
+  k.N = N; k.H = H; k.W = W; k.OH = (H + 6 - 7) / 2 + 1; k.OW = (W + 6 - 7) / 2 + 1;
+  k.tiles_w = (k.OW + TW - 1) / TW; k.tiles_h = (k.OH + TH - 1) / TH;
+  const long nt = (long)N * k.tiles_w * k.tiles_h;
+  if (nt > 0x7fffffffL) return TF_ERR_ARG;
+  k.ntiles = (int)nt;
+  const size_t tile_bytes = (size_t)64 * 147 * sizeof(float), fit = slab_bytes / tile_bytes;
+  if (fit < 1) return TF_ERR_ARG;
+  const unsigned want = (unsigned)tf::tuning().stem_wgrad_blocks;
+  unsigned grid = want < 1 ? 1 : want;
+  if ((long)grid > nt) grid = (unsigned)nt;
+  if ((size_t)grid > fit) grid = (unsigned)fit;
+  hipStream_t stream = (hipStream_t)stream_;
+  const double M = (double)N * k.OH * k.OW;
+  tf::ProfScope prof(22, 2.0 * M * 64 * 147, (double)N * 3 * H * W * 4 + M * 64 * 2 * (apply ? 2 : 1) + 64.0 * 147 * 4, stream, (int)M, 64, 147, 49, 2, 0,
+                     2.0 * M * 64 * KUSED);      // 22 = stem_wgrad, both launches
+  if (dtype == TF_BF16) {
+    if (apply) hipLaunchKernelGGL((stem_wgrad_kernel<tf::bf16_t, true, true>), dim3(grid), dim3(256), 0, stream, k);
+    else hipLaunchKernelGGL((stem_wgrad_kernel<tf::bf16_t, false, true>), dim3(grid), dim3(256), 0, stream, k);
+  } else {
+    if (apply) hipLaunchKernelGGL((stem_wgrad_kernel<tf::f16_t, true, true>), dim3(grid), dim3(256), 0, stream, k);
+    else hipLaunchKernelGGL((stem_wgrad_kernel<tf::f16_t, false, true>), dim3(grid), dim3(256), 0, stream, k);
+  }
+  if (hipGetLastError() != hipSuccess) return TF_ERR_LAUNCH;
+  tf_wdet_reduce r{};
+  r.slab = (const float*)slab; r.dw = dw_oihw; r.slices = (int)grid; r.flat_floats = 64 * 147;
+  return tf_wgrad_det_reduce_launch(r, stream);
 }

@@ -15,6 +15,7 @@
 // (coalesced 64-byte runs along ci for 1x1 convs).
 #include "common.h"
 #include "profile.h"
+#include "wgrad_det.h"
 
 int tf_wgrad_dma_launch(const tf_wgrad_args* a, hipStream_t stream);
 int tf_wgrad3x3_launch(const tf_wgrad_args* a, hipStream_t stream);       // wgrad3x3.hip   // wgrad_dma.hip
@@ -51,7 +52,10 @@ __device__ __forceinline__ bf16x8 frag_tr(const char* tile, int pitch, int pk0, 
 
 // BC = channels per tile side (co and ci): 128 or 64.  RS: tf_wgrad_args.row_scale (frozen-BN graph), a compile-time form of its own so that
 // the default instantiation is the kernel it always was (as a run-time branch it cost wgrad_dma_kernel 0.6 % of the step)
-template <typename T, int BC, bool RS = false>
+// DET: the slab epilogue (tf_conv2d_wgrad_det), compile-time for the same reason: a.dw is then the slab [slice][tap][co tile][ci tile][BC co][BC ci]
+// and the block stores its tile into its own place of it -- plain 16-byte stores through LDS, no read, no atomics; the row scale rides in the
+// summing kernel (csrc/wgrad_det.hip)
+template <typename T, int BC, bool RS = false, bool DET = false>
 __global__ void __launch_bounds__(256) wgrad_kernel(const WgK a) {
   constexpr int PK = WgTraits<T>::PK;
   constexpr int EPS = tf::Elem<T>::kPer16B;
@@ -172,6 +176,27 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const WgK a) {
     if (st + 1 < nst) commit(buf ^ 1);
     __syncthreads();
   }
+  if constexpr (DET) {
+    // (an empty slice would store zeros: every slice the summing kernel reads is written; the plan leaves none empty)
+    constexpr int SP = BC + 4;                           // floats per staged [co] row: 16-byte aligned, conflict-free for the 4 x 16 lane pattern
+    float* stg = reinterpret_cast<float*>(smem);
+    __syncthreads();                                     // both operand buffers are fully read
+#pragma unroll
+    for (int n = 0; n < NF; ++n)
+#pragma unroll
+      for (int m = 0; m < NF; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) stg[(wco * WC + n * 16 + lg * 4 + r) * SP + wci * WC + m * 16 + li] = acc[n][m][r];
+    __syncthreads();
+    const int tiles = gridDim.x / a.splitk;              // taps x co tiles x ci tiles
+    float* out = a.dw + ((size_t)ks * tiles + blockIdx.x / a.splitk) * (BC * BC);
+#pragma unroll
+    for (int k = 0; k < BC * BC / 1024; ++k) {
+      const int e4 = tid + k * 256, row = e4 / (BC / 4), c4 = e4 % (BC / 4);
+      *reinterpret_cast<f32x4*>(out + (size_t)e4 * 4) = *reinterpret_cast<const f32x4*>(stg + row * SP + c4 * 4);
+    }
+    return;
+  }
   if (nst == 0) return;
   // D[co][ci]: lane holds co = (l>>4)*4 + r, ci = l&15
 #pragma unroll
@@ -191,8 +216,10 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const WgK a) {
     }
 }
 
-template <typename T, int BC>
-int launch_wgrad(const tf_wgrad_args* A, hipStream_t stream) {
+// DET: the slab form (tf_conv2d_wgrad_det): the slice count capped by what A->partial_ws holds (TF_ERR_ARG below one slice), the tiles
+// stored there and summed by csrc/wgrad_det.hip.  query != NULL: the preferred slab bytes only
+template <typename T, int BC, bool DET = false>
+int launch_wgrad(const tf_wgrad_args* A, hipStream_t stream, size_t* query = nullptr) {
   constexpr int PK = WgTraits<T>::PK;
   WgK k;
   k.x = (const char*)A->x; k.dy = (const char*)A->dy; k.dw = A->dw_oihw; k.pro_scale = A->pro_scale; k.pro_shift = A->pro_shift; k.row_scale = A->row_scale;
@@ -209,10 +236,33 @@ int launch_wgrad(const tf_wgrad_args* A, hipStream_t stream) {
     if (sk > maxsk) sk = maxsk;
     if (sk < 1) sk = 1;
   }
+  if (DET && !query) {
+    const size_t fit = A->partial_ws ? A->partial_ws_bytes / ((size_t)tiles * BC * BC * sizeof(float)) : 0;
+    if (fit < 1) return TF_ERR_ARG;
+    if ((size_t)sk > fit) sk = (int)fit;
+  }
   k.chunk = (((k.M + sk - 1) / sk) + PK - 1) / PK * PK;
-  k.splitk = (k.M + k.chunk - 1) / k.chunk;
+  k.splitk = (k.M + k.chunk - 1) / k.chunk;                 // every slice owns pixels
   constexpr int PITCH = BC * (int)sizeof(T) + 32;
-  const size_t lds = (size_t)4 * PK * PITCH + (A->pro_scale ? (size_t)A->Cin * 8 : 0);
+  size_t lds = (size_t)4 * PK * PITCH + (A->pro_scale ? (size_t)A->Cin * 8 : 0);
+  if constexpr (DET) {
+    if (query) { *query = (size_t)k.splitk * tiles * BC * BC * sizeof(float); return TF_OK; }
+    static tf::PerDevice det_attr_set;
+    if (det_attr_set.first())
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, BC, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (lds < (size_t)BC * (BC + 4) * sizeof(float)) lds = (size_t)BC * (BC + 4) * sizeof(float);      // (the staged tile; never the case today)
+    const double es = sizeof(T), Md = k.M;
+    tf::ProfScope prof(8 + (sizeof(T) == 2 ? 2 : 0) + (BC == 128 ? 1 : 0), 2.0 * Md * A->Cout * A->Cin * k.ntaps,
+                       (Md * A->Cout + (double)A->N * A->H * A->W * A->Cin) * es + (double)A->Cout * A->Cin * k.ntaps * 4, stream);
+    k.dw = (float*)A->partial_ws;
+    hipLaunchKernelGGL((wgrad_kernel<T, BC, false, true>), dim3(tiles * k.splitk), dim3(256), lds, stream, k);
+    if (hipGetLastError() != hipSuccess) return TF_ERR_LAUNCH;
+    tf_wdet_reduce r{};
+    r.slab = k.dw; r.dw = A->dw_oihw; r.row_scale = A->row_scale; r.slices = k.splitk;
+    r.BC = BC; r.ntaps = k.ntaps; r.nco = k.nco; r.nci = k.nci; r.Cout = A->Cout; r.Cin = A->Cin; r.dw_ld = A->dw_ld;
+    r.ci_stride = k.ci_stride; r.tap_stride = k.tap_stride; r.flat_floats = 0;
+    return tf_wgrad_det_reduce_launch(r, stream);
+  }
   static tf::PerDevice attr_set;
   if (attr_set.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, BC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -227,6 +277,13 @@ int launch_wgrad(const tf_wgrad_args* A, hipStream_t stream) {
 }
 
 }  // namespace
+
+// the register-staged kernel's share of tf_conv2d_wgrad_det (the tile rule of tf_conv2d_wgrad below)
+int tf_wgrad_reg_det_launch(const tf_wgrad_args* a, hipStream_t stream, size_t* query) {
+  const bool small = a->tile ? a->tile == 64 : true;
+  if (a->dtype == TF_BF16) return small ? launch_wgrad<tf::bf16_t, 64, true>(a, stream, query) : launch_wgrad<tf::bf16_t, 128, true>(a, stream, query);
+  return small ? launch_wgrad<float, 64, true>(a, stream, query) : launch_wgrad<float, 128, true>(a, stream, query);
+}
 
 extern "C" int tf_conv2d_wgrad(const tf_wgrad_args* a, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;

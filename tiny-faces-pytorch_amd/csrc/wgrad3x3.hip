@@ -27,6 +27,7 @@
 #include "tuning.h"
 #include "profile.h"
 #include "lds_dma.h"
+#include "wgrad_det.h"
 
 namespace {
 
@@ -399,6 +400,23 @@ int tf_wgrad3x3_launch(const tf_wgrad_args* A, hipStream_t stream) {
     else                     hipLaunchKernelGGL(wgrad3x3_reduce_kernel<1>, dim3((unsigned)(total4 / 256)), dim3(256), 0, stream, k);
   }
   return hipGetLastError() == hipSuccess ? TF_OK : TF_ERR_LAUNCH;
+}
+
+// tf_conv2d_wgrad_det's way to the all-taps kernel: its existing two-phase form, with the slice count capped by what the slab holds (never
+// the atomic epilogue: TF_ERR_ARG when not even one slice fits).  query != NULL: the preferred slab bytes only.
+int tf_wgrad3x3_det_launch(const tf_wgrad_args* A, hipStream_t stream, size_t* query) {
+  W3K k;
+  if (!w3_plan(A, k)) return TF_ERR_UNSUPPORTED;
+  const size_t slice = (size_t)k.nco * k.nci * TILE_FLOATS * sizeof(float);
+  if (query) { *query = (size_t)k.splitk * slice; return TF_OK; }
+  const size_t fit = A->partial_ws ? A->partial_ws_bytes / slice : 0;
+  if (fit < 1) return TF_ERR_ARG;
+  tf_wgrad_args B = *A;
+  if ((size_t)k.splitk > fit) {
+    B.splitk = (int)fit;                                   // an explicit count: chunk = ceil(Mp / fit) rounded up to a stage, at most `fit` slices
+    if (!w3_plan(&B, k) || (size_t)k.splitk > fit) return TF_ERR_ARG;
+  }
+  return tf_wgrad3x3_launch(&B, stream);
 }
 
 // n problems of the SAME shape (3x3 / stride 1 / pad 1, bf16) in one launch, every tile reduced over the whole padded raster in-block;

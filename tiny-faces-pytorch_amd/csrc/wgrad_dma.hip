@@ -10,6 +10,7 @@
 #include "tuning.h"
 #include "profile.h"
 #include "lds_dma.h"
+#include "wgrad_det.h"
 
 namespace {
 
@@ -50,7 +51,11 @@ __device__ __forceinline__ bf16x8 frag_tr(const char* tile, int pk0, int c0) {
 
 // KIND 1: pointwise (1x1, stride 1, pad 0): X row of pixel p is row p.  KIND 0: generic tap gather.
 // RS: tf_wgrad_args.row_scale (frozen-BN graph) -- a compile-time form of its own, so that the default instantiation is the kernel it always was
-template <int KIND, bool RS = false>
+// DET: the slab epilogue (tf_conv2d_wgrad_det), compile-time for the same reason: a.dw is then the slab [slice][tap][co tile][ci tile][64 co][64 ci]
+// and the block stores its tile into its own place of it -- plain 16-byte stores through LDS, no read, no atomics; the row scale rides in
+// the summing kernel (csrc/wgrad_det.hip)
+constexpr int STG_PITCH = 68;                            // floats per staged [co] row of 64 ci (as in wgrad3x3.hip)
+template <int KIND, bool RS = false, bool DET = false>
 __global__ void __launch_bounds__(256) wgrad_dma_kernel(const WdK a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int b = blockIdx.x;
@@ -148,6 +153,27 @@ __global__ void __launch_bounds__(256) wgrad_dma_kernel(const WdK a) {
     }
     if (++cs == NS) cs = 0;
   }
+  if constexpr (DET) {
+    // (an empty slice would store zeros: every slice the summing kernel reads is written; the plan leaves none empty)
+    const int l = tid & 63, li = l & 15, lg = l >> 4;
+    float* stg = reinterpret_cast<float*>(smem);
+    __syncthreads();                                     // the ring is fully read (its last DMA landed behind the loop's vmcnt(0))
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) stg[(wco * 32 + n * 16 + lg * 4 + r) * STG_PITCH + wci * 32 + m * 16 + li] = acc[n][m][r];
+    __syncthreads();
+    const int tiles = gridDim.x / a.splitk;              // taps x co tiles x ci tiles
+    float* out = a.dw + ((size_t)ks * tiles + blockIdx.x / a.splitk) * 4096;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int e4 = tid + k * 256, row = e4 >> 4, c4 = e4 & 15;
+      *reinterpret_cast<f32x4*>(out + (size_t)e4 * 4) = *reinterpret_cast<const f32x4*>(stg + row * STG_PITCH + c4 * 4);
+    }
+    return;
+  }
   if (nst == 0) return;
   const int l = tid & 63, li = l & 15, lg = l >> 4;
 #pragma unroll
@@ -169,10 +195,10 @@ __global__ void __launch_bounds__(256) wgrad_dma_kernel(const WdK a) {
 
 }  // namespace
 
-// bf16, no prologue.  Returns TF_ERR_UNSUPPORTED for anything else (the caller falls back to the register-staged kernel).
-int tf_wgrad_dma_launch(const tf_wgrad_args* A, hipStream_t stream) {
-  if (A->dtype != TF_BF16 || A->pro_scale) return TF_ERR_UNSUPPORTED;
-  WdK k;
+namespace {
+// kernel arguments + split-K plan, shared by the atomic and the slab form.  slab_bytes != NULL (slab form): the slice count is capped by what
+// the slab holds; false when not even one slice fits.  Every slice owns pixels: splitk = ceil(M / chunk).
+bool wd_plan(const tf_wgrad_args* A, WdK& k, const size_t* slab_bytes) {
   k.x = (const char*)A->x; k.dy = (const char*)A->dy; k.dw = A->dw_oihw; k.row_scale = A->row_scale;
   k.H = A->H; k.W = A->W; k.Cin = A->Cin; k.OH = A->OH; k.OW = A->OW; k.Cout = A->Cout; k.KW = A->KW; k.stride = A->stride; k.pad = A->pad;
   k.M = A->N * A->OH * A->OW; k.OHW = A->OH * A->OW; k.ldx = A->ldx; k.lddy = A->lddy; k.dw_ld = A->dw_ld;
@@ -187,8 +213,23 @@ int tf_wgrad_dma_launch(const tf_wgrad_args* A, hipStream_t stream) {
     if (sk > maxsk) sk = maxsk;
     if (sk < 1) sk = 1;
   }
+  if (slab_bytes) {
+    const size_t fit = *slab_bytes / ((size_t)tiles * 4096 * sizeof(float));
+    if (fit < 1) return false;
+    if ((size_t)sk > fit) sk = (int)fit;
+  }
   k.chunk = (((k.M + sk - 1) / sk) + PK - 1) / PK * PK;
   k.splitk = (k.M + k.chunk - 1) / k.chunk;
+  return true;
+}
+}  // namespace
+
+// bf16, no prologue.  Returns TF_ERR_UNSUPPORTED for anything else (the caller falls back to the register-staged kernel).
+int tf_wgrad_dma_launch(const tf_wgrad_args* A, hipStream_t stream) {
+  if (A->dtype != TF_BF16 || A->pro_scale) return TF_ERR_UNSUPPORTED;
+  WdK k;
+  wd_plan(A, k, nullptr);
+  const int ntaps = A->KH * A->KW, tiles = k.nco * k.nci * ntaps;
   // ring depth: the weight gradients share every CU's 160 KiB of LDS with the data-gradient chain on the other stream
   // (profiles/r03_contention.txt); a 2-deep ring (a third less LDS per block) measured no faster
   const size_t lds = (size_t)NS * BUF;
@@ -207,4 +248,35 @@ int tf_wgrad_dma_launch(const tf_wgrad_args* A, hipStream_t stream) {
     TF_LAUNCH_TIMED((wgrad_dma_kernel<0>), grid, dim3(256), lds, stream, k);
   }
   return hipGetLastError() == hipSuccess ? TF_OK : TF_ERR_LAUNCH;
+}
+
+// slab form (tf_conv2d_wgrad_det): the same kernel choice and plan, the tiles stored into A->partial_ws and summed by csrc/wgrad_det.hip
+int tf_wgrad_dma_det_launch(const tf_wgrad_args* A, hipStream_t stream, size_t* query) {
+  if (A->dtype != TF_BF16 || A->pro_scale) return TF_ERR_UNSUPPORTED;
+  WdK k;
+  const int ntaps = A->KH * A->KW;
+  if (query) {
+    wd_plan(A, k, nullptr);
+    *query = (size_t)k.splitk * k.nco * k.nci * ntaps * 4096 * sizeof(float);
+    return TF_OK;
+  }
+  if (!A->partial_ws || !wd_plan(A, k, &A->partial_ws_bytes)) return TF_ERR_ARG;
+  const int tiles = k.nco * k.nci * ntaps;
+  k.dw = (float*)A->partial_ws;
+  const size_t lds = (size_t)NS * BUF;
+  const bool pointwise = ntaps == 1 && A->stride == 1 && A->pad == 0 && A->H == A->OH && A->W == A->OW;
+  const double Md = k.M;
+  // (kind 14, bracketing both launches: the summing kernel is a mandatory part of the gradient)
+  tf::ProfScope prof(14, 2.0 * Md * A->Cout * A->Cin * ntaps,
+                     (Md * A->Cout + (double)A->N * A->H * A->W * A->Cin) * 2 + (double)A->Cout * A->Cin * ntaps * 4, stream, k.M, A->Cout,
+                     A->Cin * ntaps, ntaps, 2, 0);
+  const dim3 grid(tiles * k.splitk);
+  if (pointwise) hipLaunchKernelGGL((wgrad_dma_kernel<1, false, true>), grid, dim3(256), lds, stream, k);
+  else hipLaunchKernelGGL((wgrad_dma_kernel<0, false, true>), grid, dim3(256), lds, stream, k);
+  if (hipGetLastError() != hipSuccess) return TF_ERR_LAUNCH;
+  tf_wdet_reduce r{};
+  r.slab = k.dw; r.dw = A->dw_oihw; r.row_scale = A->row_scale; r.slices = k.splitk;
+  r.BC = 64; r.ntaps = ntaps; r.nco = k.nco; r.nci = k.nci; r.Cout = A->Cout; r.Cin = A->Cin; r.dw_ld = A->dw_ld;
+  r.ci_stride = k.ci_stride; r.tap_stride = k.tap_stride; r.flat_floats = 0;
+  return tf_wgrad_det_reduce_launch(r, stream);
 }

@@ -99,6 +99,18 @@ ACCUM_AVERAGE_HELP = ("--accum-average: apply the MEAN of the accumulated gradie
                       "reference's loss is a sum over the batch, so the sum is what a batch N times as large gives), default off")
 
 
+DETERMINISTIC_HELP = ("--deterministic: run every training step without floating-point atomics (unfolded BatchNorm statistic rows, weight "
+                      "gradients summed from per-block slabs in a fixed order): the same seed, weights and batches give the same checkpoint bit "
+                      "for bit; slower than the default step, default off")
+
+
+def deterministic_description():
+    """What --deterministic guarantees and what it does not, as the start-up line prints it."""
+    return ("deterministic step: same weights, optimizer state and batches in -> same weights out, bit for bit, per process (no floating-point "
+            "atomics in the forward, the backward or the update); NOT covered: the soft-margin loss meters (fp64 atomics, logging only), the "
+            "order inside a multi-rank gradient exchange, the data loader's worker order")
+
+
 FOCAL_HELP = ("--cls-loss {soft-margin,focal}: classification loss of the criterion; focal = sigmoid focal loss (Lin et al. 2017) over every "
               "labelled anchor and SmoothL1 over every positive, with no OHEM and no 256-sample draw (--ohem-thresh is unused), default soft-margin; "
               "--focal-gamma G: its focusing exponent, G >= 0, default 2; --focal-alpha A: weight A on positives and 1 - A on negatives, A <= 1, "
@@ -235,7 +247,7 @@ def _positive_float(text):
 
 
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP, JITTER_HELP, VAL_HELP)))
+    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP, JITTER_HELP, VAL_HELP, DETERMINISTIC_HELP)))
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
@@ -277,6 +289,7 @@ def trunk_arguments(argv=None):
     parser.add_argument("--val-nms-thresh", dest="val_nms_thresh", default=0.3, type=_unit_interval, metavar="T", help=VAL_HELP)
     parser.add_argument("--val-num-images", dest="val_num_images", default=None, type=_val_count, metavar="M", help=VAL_HELP)
     parser.add_argument("--val-gt-dir", dest="val_gt_dir", default=None, metavar="DIR", help=VAL_HELP)
+    parser.add_argument("--deterministic", dest="deterministic", action="store_true", help=DETERMINISTIC_HELP)
     known, rest = parser.parse_known_args(argv)
     if known.color_jitter is not None and known.color_jitter[3] > 0.5:
         parser.error(f"--color-jitter: the hue amplitude H must be <= 0.5, got {known.color_jitter[3]:g}")
@@ -305,6 +318,7 @@ def trunk_arguments(argv=None):
     args.color_jitter = None if known.color_jitter is None else tuple(known.color_jitter)
     args.val_every, args.val_num_images, args.val_gt_dir = known.val_every, known.val_num_images, known.val_gt_dir
     args.val_prob_thresh, args.val_nms_thresh = known.val_prob_thresh, known.val_nms_thresh
+    args.deterministic = known.deterministic
     return args
 
 
@@ -404,6 +418,8 @@ def main():
     if parallel.rank() == 0:
         print(loss_description(args))
         print(jitter_description(args))
+        if args.deterministic:
+            print(deterministic_description())
         if args.cls_loss == "focal":
             print("--ohem-thresh is unused with --cls-loss focal: nothing is mined or sampled")
 
@@ -427,7 +443,7 @@ def main():
         engine = TrainEngine(model, loss_fn, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay, device=device,
                              max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, ema_decay=args.model_ema,
                              accum_steps=args.accum_steps, accum_average=args.accum_average, optimizer=args.optimizer,
-                             betas=(args.adam_beta1, args.adam_beta2), eps=args.adam_eps)
+                             betas=(args.adam_beta1, args.adam_beta2), eps=args.adam_eps, deterministic=args.deterministic)
         ema = engine.ema                  # (built from the weights --resume / --pretrained left in the model)
         if state is not None:
             engine.load_optimizer_state_dict(state.get("optimizer"))      # momentum buffers / moments (a torch.optim.SGD / AdamW state_dict)
@@ -503,7 +519,8 @@ def main():
         else:
             trainer.train(model, loss_fn, optimizer, train_loader, epoch, device=device, max_grad_norm=args.clip_grad_norm,
                           skip_nonfinite=args.skip_nonfinite, ema=ema, accum_steps=args.accum_steps, accum_average=args.accum_average,
-                          warmup=(args.warmup_iters, args.warmup_factor, epoch * steps_per_epoch(len(train_loader), args.accum_steps)))
+                          warmup=(args.warmup_iters, args.warmup_factor, epoch * steps_per_epoch(len(train_loader), args.accum_steps)),
+                          deterministic=args.deterministic)
             scheduler.step()
         if args.skip_nonfinite and parallel.rank() == 0:
             total = engine.skipped_steps if engine is not None else ops.clip_skipped_steps(device)

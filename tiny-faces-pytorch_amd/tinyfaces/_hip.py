@@ -216,6 +216,13 @@ _SIGNATURES = {
     "tf_detnet_set_grad_callback": (i32, [vp, vp]),
     "tf_set_stat_rows": (i32, [i32]),
     "tf_get_stat_rows": (i32, []),
+    "tf_wgrad_det_workspace_bytes": (sz, [C.POINTER(WgradArgs)]),
+    "tf_conv2d_wgrad_det": (i32, [C.POINTER(WgradArgs), vp]),
+    "tf_wgrad_det_groups": (i32, [i32]),
+    "tf_stem_wgrad_det_workspace_bytes": (sz, [i32, i32, i32]),
+    "tf_stem_wgrad_det": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "tf_set_deterministic": (i32, [i32]),
+    "tf_get_deterministic": (i32, []),
     "tf_profile_enable": (i32, [i32]),
     "tf_profile_shapes": (i32, [C.POINTER(C.c_double), i32]),
     "tf_profile_collect": (i32, [C.POINTER(C.c_double), i32]),

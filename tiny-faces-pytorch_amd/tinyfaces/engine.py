@@ -32,7 +32,7 @@ from .ema import ModelEma
 class TrainEngine:
     def __init__(self, model, criterion, lr=1e-4, momentum=0.9, weight_decay=5e-4, device="cuda", bucket_mb=10, native_exchange=None,
                  max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True, accum_steps=1, accum_average=False,
-                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8):
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, deterministic=False):
         """max_grad_norm: clip the global L2 norm of the (rank-averaged) gradient of the trained tensors to this value before the update, as
         torch.nn.utils.clip_grad_norm_ between backward() and optimizer.step() would (tinyfaces/trainer.py:86-87).  skip_nonfinite: a step
         whose gradient norm is NaN or Inf changes neither the parameters nor the momentum (`skipped_steps` counts them; what the FORWARD
@@ -58,7 +58,15 @@ class TrainEngine:
         (include/tinyfaces_hip.h) with `betas` and `eps`; `weight_decay` is then decoupled, `momentum` unused, `flat_m` is exp_avg and
         `flat_v`, one more flat fp32 buffer, exp_avg_sq.  The step counter of the bias correction lives on the device (`adam_state`, an
         ops.AdamState) and does not advance on a step the non-finite guard drops.  The groups, their lr multipliers, the trained segments,
-        the fused EMA and the clip state are the ones SGD uses."""
+        the fused EMA and the clip state are the ones SGD uses.
+        deterministic: every step() runs with the library's deterministic switch on (ops.set_deterministic: unfolded BatchNorm statistic rows,
+        the slab forms of the weight gradients -- no floating-point atomics) and puts back what it found, so that a deterministic and a default
+        engine can alternate in one process.  The same weights, optimizer state and batches in give the same weights out, bit for bit, per
+        process; the loss meters of the soft-margin criterion and the order inside a multi-rank exchange are not covered.  Slower than the
+        default step (README).  False (the default): no new call."""
+        if not isinstance(deterministic, bool):
+            raise ValueError(f"deterministic must be True or False, got {deterministic!r}")
+        self.deterministic = deterministic
         self.device = torch.device(device)
         self.model = model.to(self.device).train()
         self.criterion = criterion
@@ -720,6 +728,17 @@ class TrainEngine:
         ops.grad_accumulate(self._accum, gflat, segs, mode)
 
     def step(self, x, class_map, regression_map, apply=None):
+        """x (B,3,H,W) f32, class_map, regression_map, apply: see _step.  With deterministic=True the library's switch is on for the duration of
+        the call and is then put back to what it was."""
+        if not self.deterministic:
+            return self._step(x, class_map, regression_map, apply)
+        prev = ops.set_deterministic(True)
+        try:
+            return self._step(x, class_map, regression_map, apply)
+        finally:
+            ops.set_deterministic(prev)
+
+    def _step(self, x, class_map, regression_map, apply=None):
         """x (B,3,H,W) f32, class_map (B,nt,h,w) f32 (mined in place by the soft-margin criterion; only read with cls_loss="focal"), regression_map (B,4nt,h,w) f32: all on the device.
         Returns the device tensor [sum cls loss, sum reg loss] (float64) without synchronising.
         The step follows the model's BatchNorm mode (DetectionModel.freeze_batchnorm): frozen, the forward and backward run the folded-BN

@@ -1208,15 +1208,49 @@ def stem_conv(x_nchw, w_oihw, dtype, epi=0, scale=None, shift=None):
     return (y, st[:rows.value]) if st is not None else y
 
 
-def stem_wgrad(x_nchw, g_nhwc, x_conv=None, cA=None, cB=None, cD=None):
+def set_deterministic(on):
+    """Process-wide deterministic switch of the library (tf_set_deterministic): while on, the BatchNorm statistic rows are unfolded and the
+    training step takes the slab forms of its weight gradients -- no floating-point atomics, the same bits on every run.  Returns the
+    previous state."""
+    prev = bool(lib().tf_get_deterministic())
+    check(lib().tf_set_deterministic(int(bool(on))), "tf_set_deterministic")
+    return prev
+
+
+def is_deterministic():
+    """Whether the library's deterministic switch is on (tf_get_deterministic)."""
+    return bool(lib().tf_get_deterministic())
+
+
+def _det_slab(key, want, ws_bytes, slab, device):
+    """(pointer, bytes, keep-alive) of the slab a deterministic weight gradient gets: `slab` (a uint8 tensor, used whole) | ws_bytes bytes of the
+    cached workspace (less than the query: the capped plan; 0: none, the call is refused) | the query's preferred size."""
+    if slab is not None:
+        return ptr(slab), slab.numel() * slab.element_size(), slab
+    nbytes = want if ws_bytes is None else int(ws_bytes)
+    if nbytes <= 0:
+        return None, 0, None
+    ws = _workspace(key, nbytes, device)
+    return ptr(ws), nbytes, ws
+
+
+def stem_wgrad(x_nchw, g_nhwc, x_conv=None, cA=None, cB=None, cD=None, deterministic=False, ws_bytes=None, slab=None, out=None):
     """Weight gradient of conv1 straight from the image (tf_stem_wgrad, r4): x (N,3,H,W) fp32, g (N,OH,OW,64) bf16 | fp16 -> (64,3,7,7) fp32.
-    With x_conv (N,OH,OW,64) and cA / cB / cD (64,) fp32 the gradient operand is cA * g + cB * x_conv + cD (the stem's BN-backward apply)."""
+    With x_conv (N,OH,OW,64) and cA / cB / cD (64,) fp32 the gradient operand is cA * g + cB * x_conv + cD (the stem's BN-backward apply).
+    deterministic: tf_stem_wgrad_det -- one tile per block in a slab of tf_stem_wgrad_det_workspace_bytes (ws_bytes: a smaller one; slab: the
+    caller's own uint8 tensor), summed in a fixed order.  out: accumulate into this (64,3,7,7) fp32 tensor."""
     require_gpu(x_nchw, "stem_wgrad")
     x = x_nchw.float().contiguous()
     N, _, H, W = x.shape
     g = g_nhwc.contiguous()
-    dw = torch.zeros(64, 3, 7, 7, dtype=torch.float32, device=x.device)
+    dw = torch.zeros(64, 3, 7, 7, dtype=torch.float32, device=x.device) if out is None else out
     opt = [ptr(t.contiguous()) if t is not None else None for t in (x_conv, cA, cB, cD)]
+    if deterministic:
+        want = lib().tf_stem_wgrad_det_workspace_bytes(N, H, W)
+        sp, sb, keep = _det_slab("stem_wgrad_det", want, ws_bytes, slab, x.device)
+        with torch.cuda.device(x.device):
+            check(lib().tf_stem_wgrad_det(_hip.tf_dtype(g.dtype), ptr(x), N, H, W, ptr(g), *opt, ptr(dw), sp, sb, stream()), "tf_stem_wgrad_det")
+        return dw
     check(lib().tf_stem_wgrad(_hip.tf_dtype(g.dtype), ptr(x), N, H, W, ptr(g), *opt, ptr(dw), stream()), "tf_stem_wgrad")
     return dw
 
@@ -1265,13 +1299,10 @@ def conv2d_nhwc(x, w_packed, Cout, KH, KW, stride, pad, mode=0, out_hw=None, ldy
     return (y, stats) if want_stats else y
 
 
-def conv2d_wgrad(x, dy, Cin, Cout, KH, KW, stride, pad, pro=None, splitk=0, tile=0, out=None, packed=False, two_phase=False):
-    """x (N,H,W,ldx), dy (N,OH,OW,lddy) -> dW (Cout,Cin,KH,KW) fp32.  two_phase: hand the all-taps 3x3 kernel a partial-tile
-    workspace so that its split-K slices are summed by a second kernel instead of fp32 atomics."""
-    require_gpu(x, "conv2d_wgrad")
+def _wgrad_args(x, dy, dw, Cin, Cout, KH, KW, stride, pad, pro=None, splitk=0, tile=0, packed=False, row_scale=None):
+    """tf_wgrad_args of one weight-gradient call (x (N,H,W,ldx), dy (N,OH,OW,lddy), dw or any device tensor standing in for it)."""
     N, H, W, ldx = x.shape
     _, OH, OW, lddy = dy.shape
-    dw = torch.zeros(Cout, Cin, KH, KW, dtype=torch.float32, device=x.device) if out is None else out
     a = _hip.WgradArgs()
     a.tile = tile
     a.packed = int(packed)
@@ -1280,7 +1311,28 @@ def conv2d_wgrad(x, dy, Cin, Cout, KH, KW, stride, pad, pro=None, splitk=0, tile
     a.ldx, a.lddy, a.x, a.dy, a.dw_oihw, a.dw_ld, a.splitk = ldx, lddy, ptr(x), ptr(dy), ptr(dw), Cin * KH * KW, splitk
     if pro is not None:
         a.pro_scale, a.pro_shift, a.pro_relu = ptr(pro[0]), ptr(pro[1]), int(pro[2])
+    if row_scale is not None:
+        a.row_scale = ptr(row_scale)
+    return a
+
+
+def conv2d_wgrad(x, dy, Cin, Cout, KH, KW, stride, pad, pro=None, splitk=0, tile=0, out=None, packed=False, two_phase=False, row_scale=None,
+                 deterministic=False, ws_bytes=None, slab=None):
+    """x (N,H,W,ldx), dy (N,OH,OW,lddy) -> dW (Cout,Cin,KH,KW) fp32.  two_phase: hand the all-taps 3x3 kernel a partial-tile
+    workspace so that its split-K slices are summed by a second kernel instead of fp32 atomics.  row_scale (Cout,) fp32: dW[co] *= it.
+    deterministic: tf_conv2d_wgrad_det -- every kernel's slices through a slab of tf_wgrad_det_workspace_bytes (ws_bytes: a smaller one, the
+    plan is capped to it; slab: the caller's own uint8 tensor), summed in a fixed order and added once into dW: no atomics."""
+    require_gpu(x, "conv2d_wgrad")
+    dw = torch.zeros(Cout, Cin, KH, KW, dtype=torch.float32, device=x.device) if out is None else out
+    a = _wgrad_args(x, dy, dw, Cin, Cout, KH, KW, stride, pad, pro, splitk, tile, packed, row_scale)
     ws = None
+    if deterministic:
+        want = lib().tf_wgrad_det_workspace_bytes(C.byref(a))
+        sp, sb, ws = _det_slab("wgrad_det", want, ws_bytes, slab, x.device)
+        a.partial_ws, a.partial_ws_bytes = sp, sb
+        with torch.cuda.device(x.device):
+            check(lib().tf_conv2d_wgrad_det(C.byref(a), stream()), "tf_conv2d_wgrad_det")
+        return dw
     if two_phase:
         nbytes = lib().tf_wgrad_workspace_bytes(C.byref(a))
         if nbytes:
@@ -1289,6 +1341,11 @@ def conv2d_wgrad(x, dy, Cin, Cout, KH, KW, stride, pad, pro=None, splitk=0, tile
     with torch.cuda.device(x.device):
         check(lib().tf_conv2d_wgrad(C.byref(a), stream()), "tf_conv2d_wgrad")
     return dw
+
+
+def wgrad_det_workspace_bytes(x, dy, Cin, Cout, KH, KW, stride, pad, pro=None, splitk=0, tile=0):
+    """tf_wgrad_det_workspace_bytes of the call conv2d_wgrad(..., deterministic=True) would make: the preferred slab, in bytes."""
+    return int(lib().tf_wgrad_det_workspace_bytes(C.byref(_wgrad_args(x, dy, x, Cin, Cout, KH, KW, stride, pad, pro, splitk, tile))))
 
 
 def conv2d_wgrad_group(problems, K, pad, out=None):

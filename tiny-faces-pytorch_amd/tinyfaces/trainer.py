@@ -45,7 +45,7 @@ def warmup_factor(step, iters, factor):
 
 
 def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=None, skip_nonfinite=False, ema=None, accum_steps=1,
-          accum_average=False, warmup=None):
+          accum_average=False, warmup=None, deterministic=False):
     """One epoch with the reference's step order (trainer.py:68-90): forward, criterion, zero_grad, backward, [all-reduce],
     optimizer step, progress line.
 
@@ -66,7 +66,13 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
 
     warmup = (N, F, first_T): linear learning-rate warm-up.  Before the k-th optimizer.step() of this call every group's lr is set to the lr
     this call found there times warmup_factor(first_T + k, N, F); the found values are put back at the end (the epoch scheduler goes on
-    from them).  first_T is the global index of this epoch's first optimizer step.  None or N = 0: the groups are not touched."""
+    from them).  first_T is the global index of this epoch's first optimizer step.  None or N = 0: the groups are not touched.
+
+    deterministic: the library's deterministic switch (ops.set_deterministic) is on for the duration of the call and put back at its end: the
+    native forward and backward under autograd then run without floating-point atomics (what torch's own optimizer and losses do is theirs).
+    False (the default): no new call."""
+    if not isinstance(deterministic, bool):
+        raise ValueError(f"deterministic must be True or False, got {deterministic!r}")
     net = model.to(device).train()
     reducer = parallel.reducer_for(net)
     n_batches = len(dataloader)
@@ -81,6 +87,7 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
     window = 0                                  # batches whose gradients `.grad` holds
     found = [g["lr"] for g in optimizer.param_groups] if warmup is not None and int(warmup[0]) > 0 else None
     applied = 0                                 # optimizer steps taken by this call
+    det_prev = ops.set_deterministic(True) if deterministic else None
     try:
         for step, batch in enumerate(dataloader):
             image, cls_target, reg_target = (t.float().to(device, non_blocking=True) for t in batch)
@@ -113,6 +120,8 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
             elif getattr(loss_fn, "_pending", None):
                 loss_fn._pending.clear()            # lazy meters are only ever read on the logging rank: do not pin device scalars elsewhere
     finally:
+        if deterministic:
+            ops.set_deterministic(det_prev)
         if found is not None:
             for g, lr in zip(optimizer.param_groups, found):
                 g["lr"] = lr
