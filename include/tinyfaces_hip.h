@@ -67,6 +67,40 @@ int tf_dense_overlap_targets(const double* boxes, const int32_t* box_offsets, in
                              double pos_thresh, double neg_thresh,
                              float* class_map, float* reg_map,
                              void* ws, size_t ws_bytes, void* stream);
+/* ---- scale-compensated anchor matching (S3FD, Zhang et al. 2017): top-N positives per face ----------------------------
+ * tf_dense_overlap_targets_comp is tf_dense_overlap_targets followed by an optional second stage that tops every face up to N
+ * positive anchors.  The reference has no such stage; the rule below is the contract.  All symbols are per image.
+ *   v[a, g]   the perturbed IoU the first stage forms: iou14 + 1e-6 * noise
+ *   own(a)    the first arg-max over g of v[a, g];  best(a) = v[a, own(a)]
+ *   pad(a)    the padding predicate of the first stage (paste_boxes / flips)
+ *   F         the class map exactly as the first stage leaves it
+ *   1. count(g) = number of anchors with F = 1 and own(a) = g.  A face's forced best anchor counts for the face that OWNS it,
+ *      not for the face that forced it.
+ *   2. if count(g) < N, the candidates of g are the anchors with own(a) = g, !pad(a), F(a) != 1 and best(a) >= T.
+ *   3. the N - count(g) best candidates get F = 1: larger best first, on a tie the lower reference flat index (y * vsx + x) * nt + t.
+ *   4. if fewer candidates exist, all of them are promoted.
+ *   5. nothing else changes.
+ * Consequences: reg_map is bit for bit the map of the uncompensated call (an owned anchor already carries its owner's offsets, an
+ * unpadded anchor never had tx zeroed); every anchor has one owner, so two faces never claim the same anchor; one image's result does
+ * not depend on the rest of its batch.  Integer atomics only, no grid barrier, no host synchronisation: the same bits on every run
+ * (explicit noise, or the same seed).
+ *   N            1..64
+ *   T            finite, 0.01 <= T < pos_thresh; may lie below neg_thresh (the stage then promotes negatives as well as ignored anchors)
+ *   match_count  [total_boxes] i32 or NULL: the final number of positives each face owns, count(g) + its promotions
+ *   ws           sized by tf_targets_comp_workspace_bytes(total_boxes, B, nt, vsy, vsx); sty, stx > 0
+ * Refused before anything is enqueued: N or T out of range (TF_ERR_ARG), a workspace below the size for one box (TF_ERR_WORKSPACE).
+ * The number of boxes is only known on the device: if box_offsets[B] exceeds the slots the workspace holds, every kernel of the call
+ * returns without writing anything. */
+size_t tf_targets_comp_workspace_bytes(int total_boxes, int B, int nt, int vsy, int vsx);
+int tf_dense_overlap_targets_comp(const double* boxes, const int32_t* box_offsets, int B,
+                                  const double* templates, int nt, int tstride,
+                                  int vsy, int vsx, int ofy, int ofx, int sty, int stx,
+                                  const int32_t* paste_boxes, const int32_t* flips,
+                                  const double* noise, const int64_t* noise_offsets, uint64_t seed,
+                                  double pos_thresh, double neg_thresh,
+                                  int N, double T, int32_t* match_count,
+                                  float* class_map, float* reg_map,
+                                  void* ws, size_t ws_bytes, void* stream);
 /* test hook: the raw rounded IoU tensor [vsy][vsx][nt][G] f64 for ONE image */
 int tf_dense_overlap_iou(const double* boxes, int G, const double* templates, int nt, int tstride,
                          int vsy, int vsx, int ofy, int ofx, int sty, int stx,

@@ -139,6 +139,20 @@ JITTER_HELP = ("--color-jitter B C S H: torchvision's ColorJitter(brightness=B, 
                "ops in a random order; computed on the device), four finite numbers >= 0 with H <= 0.5, default off")
 
 
+COMPENSATION_HELP = ("--anchor-compensation N T: scale-compensated anchor matching (S3FD, Zhang et al. 2017) for the training targets: a face that owns "
+                     "fewer than N positive anchors is topped up, on the device, with its own best-overlapping unpadded anchors of IoU >= T, best first; "
+                     "N an integer in 1..64, T a number with 0.01 <= T < 0.7 (the positive threshold; below 0.3 the stage promotes negatives too), "
+                     "default off")
+
+
+def _compensation_value(text):
+    """One of the two values of --anchor-compensation: what either may be (N is narrowed to an integer in 1..64 once both are known)."""
+    value = float(text)
+    if not (math.isfinite(value) and 0.01 <= value <= 64.0):
+        raise argparse.ArgumentTypeError(f"must be an integer N in 1..64 or a threshold T with 0.01 <= T < 0.7, got {text}")
+    return value
+
+
 VAL_HELP = ("--val-every N: after every N-th epoch rank 0 runs the detector over `valdata` (synthetic-faces, or a WIDER annotation file with "
             "--val-gt-dir DIR, the eval_tools ground-truth directory) on the averaged weights under --model-ema, else the live ones, prints one "
             "`Val: [epoch] AP ...` line (matched and accumulated on the device, no result file), stores \"val_ap\" in the checkpoints and keeps "
@@ -247,7 +261,7 @@ def _positive_float(text):
 
 
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP, JITTER_HELP, VAL_HELP, DETERMINISTIC_HELP)))
+    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP, JITTER_HELP, VAL_HELP, DETERMINISTIC_HELP, COMPENSATION_HELP)))
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
@@ -260,6 +274,7 @@ def trunk_arguments(argv=None):
     --focal-gamma, --focal-alpha and --focal-normalize, `reg_loss` ("smooth_l1" | "iou" | "giou" | "diou") from --reg-loss and `reg_weight` from
     --reg-weight, `optimizer` ("sgd" | "adamw"), `adam_beta1`, `adam_beta2` and `adam_eps` from --optimizer, --adam-beta1, --adam-beta2 and --adam-eps,
     `warmup_iters` and `warmup_factor` from --warmup-iters and --warmup-factor, `color_jitter` (None or the four amplitudes) from --color-jitter,
+    `anchor_compensation` (None or (N, T)) from --anchor-compensation,
     `val_every`, `val_prob_thresh`, `val_nms_thresh`, `val_num_images` and `val_gt_dir` from --val-every and its companions.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
     options and the additions above."""
     parser = argparse.ArgumentParser(add_help=False)
@@ -290,7 +305,15 @@ def trunk_arguments(argv=None):
     parser.add_argument("--val-num-images", dest="val_num_images", default=None, type=_val_count, metavar="M", help=VAL_HELP)
     parser.add_argument("--val-gt-dir", dest="val_gt_dir", default=None, metavar="DIR", help=VAL_HELP)
     parser.add_argument("--deterministic", dest="deterministic", action="store_true", help=DETERMINISTIC_HELP)
+    parser.add_argument("--anchor-compensation", dest="anchor_compensation", default=None, type=_compensation_value, nargs=2, metavar=("N", "T"),
+                        help=COMPENSATION_HELP)
     known, rest = parser.parse_known_args(argv)
+    if known.anchor_compensation is not None:
+        n, t = known.anchor_compensation
+        if n != int(n) or not 1 <= int(n) <= 64:
+            parser.error(f"--anchor-compensation: N must be an integer in 1..64, got {n:g}")
+        if not 0.01 <= t < 0.7:
+            parser.error(f"--anchor-compensation: T must satisfy 0.01 <= T < 0.7 (the positive threshold), got {t:g}")
     if known.color_jitter is not None and known.color_jitter[3] > 0.5:
         parser.error(f"--color-jitter: the hue amplitude H must be <= 0.5, got {known.color_jitter[3]:g}")
     if known.trainable_layers < 4 and not known.freeze_bn:
@@ -319,7 +342,17 @@ def trunk_arguments(argv=None):
     args.val_every, args.val_num_images, args.val_gt_dir = known.val_every, known.val_num_images, known.val_gt_dir
     args.val_prob_thresh, args.val_nms_thresh = known.val_prob_thresh, known.val_nms_thresh
     args.deterministic = known.deterministic
+    args.anchor_compensation = None if known.anchor_compensation is None else (int(known.anchor_compensation[0]), float(known.anchor_compensation[1]))
     return args
+
+
+def compensation_description(args):
+    """The anchor matching as the start-up line prints it."""
+    ac = getattr(args, "anchor_compensation", None)
+    if ac is None:
+        return "anchor compensation off (positives from IoU 0.7 plus every face's best anchor)"
+    return (f"anchor compensation: every face topped up to {ac[0]} positive anchors from its own unpadded anchors of IoU >= {ac[1]:g}, best first "
+            "(on the device; the regression targets do not change)")
 
 
 def jitter_description(args):
@@ -373,6 +406,7 @@ def run_fused_epoch(engine, loss_fn, loader, epoch, device, base_lr, warmup=None
         if parallel.rank() == 0:
             loss_fn.flush_meters(lag=0 if idx + 1 == total else 1)      # one step behind: the host prepares batch idx + 1 while the GPU runs step idx
             trainer.print_state(idx, epoch, total, loss_fn.class_average.average, loss_fn.reg_average.average)
+            trainer.print_compensation(idx, epoch, total, loader, lag=0 if idx + 1 == total else 1)      # (nothing unless --anchor-compensation)
 
 
 def load_pretrained_trunk(model, path):
@@ -403,7 +437,8 @@ def main():
     parallel.init_from_env(os.environ.get("TINYFACES_DIST_BACKEND"))      # (gloo: several ranks on one device, the functional tests of a 1-GPU box)
     device = torch.device("cuda", torch.cuda.current_device())
     preprocess = transforms.Compose([transforms.ToTensor(), transforms.Normalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225])])
-    train_loader, _ = get_dataloader(args.traindata, args, NUM_TEMPLATES, img_transforms=preprocess, color_jitter=args.color_jitter)
+    train_loader, _ = get_dataloader(args.traindata, args, NUM_TEMPLATES, img_transforms=preprocess, color_jitter=args.color_jitter,
+                                     anchor_compensation=args.anchor_compensation)
     model = DetectionModel(base_model=getattr(model_zoo, args.base_model), num_objects=1, num_templates=NUM_TEMPLATES).set_compute_dtype(args.dtype)
     model.freeze_batchnorm(args.freeze_bn).set_trainable_layers(args.trainable_layers)
     if parallel.rank() == 0:
@@ -418,6 +453,7 @@ def main():
     if parallel.rank() == 0:
         print(loss_description(args))
         print(jitter_description(args))
+        print(compensation_description(args))
         if args.deterministic:
             print(deterministic_description())
         if args.cls_loss == "focal":
@@ -504,6 +540,8 @@ def main():
                     "optimizer": optimizer.state_dict() if optimizer is not None else engine.optimizer_state_dict(base_lr=args.lr)}
         if ema is not None:
             snapshot["model_ema"], snapshot["ema"] = ema.state_dict(), ema.settings()
+        if args.anchor_compensation is not None:
+            snapshot["args"] = {"anchor_compensation": list(args.anchor_compensation)}      # what the targets of this run were matched with
         if val_ap is not None:
             snapshot["val_ap"] = dict(val_ap)                         # of the last validation pass at or before this epoch
         return snapshot

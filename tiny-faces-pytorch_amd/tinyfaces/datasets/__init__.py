@@ -14,12 +14,14 @@ from .templates import load_templates
 
 
 def get_dataloader(datapath, args, num_templates=25, template_file="templates.json", img_transforms=None, train=True,
-                   split="train", color_jitter=None):
+                   split="train", color_jitter=None, anchor_compensation=None):
     """datasets/__init__.py:11-52.  `datapath == "synthetic"` (or a path that does not exist with
     args.synthetic set) yields seeded 500x500 crops + random boxes (BASELINE.json configs[2]);
     returns (loader, templates ndarray 25x5) like the reference.
     color_jitter = (b, c, s, h): torchvision's ColorJitter amplitudes for the training samples of WIDERFace and SyntheticFaces, applied on the
     device inside `collate` (datasets/augment.py); None = off, the loaders are then exactly what they were.
+    anchor_compensation = (N, T): scale-compensated anchor matching for the training targets of WIDERFace and SyntheticFaces (every face is topped
+    up to N positive anchors from its own best anchors with IoU >= T: ops.dense_overlap_targets(compensate=)); None = off, as before.
 
     Data parallel (one process per GPU, tinyfaces/parallel.py): every rank walks ITS shard of the data -- a
     DistributedSampler for annotation files, a rank-dependent seed for the synthetic crops -- so an epoch is one pass over
@@ -32,7 +34,8 @@ def get_dataloader(datapath, args, num_templates=25, template_file="templates.js
         # so that train -> checkpoint -> pyramid evaluation -> result files -> AP can be closed without WIDER assets.  Data parallel: every global
         # batch is split into disjoint rank shards (rotating, see below); evaluation: rank r takes images r, r + world, ...
         length = getattr(args, "synthetic_len", 8)
-        ds = SyntheticFaces(templates, length=length, seed=getattr(args, "seed", 0), train=train, img_transforms=img_transforms, color_jitter=color_jitter)
+        ds = SyntheticFaces(templates, length=length, seed=getattr(args, "seed", 0), train=train, img_transforms=img_transforms, color_jitter=color_jitter,
+                            anchor_compensation=anchor_compensation)
         idx = list(range(rank, length, world)) if world > 1 else None
         if world > 1 and train:
             # the shard of a rank ROTATES with the global batch: a fixed stride would show rank 0 the even layouts only, and the BatchNorm running
@@ -60,7 +63,8 @@ def get_dataloader(datapath, args, num_templates=25, template_file="templates.js
     from pathlib import Path
     from .wider_face import WIDERFace
     ds = WIDERFace(Path(datapath).expanduser(), templates, split=split, img_transforms=img_transforms,
-                   dataset_root=Path(getattr(args, "dataset_root", "")).expanduser(), debug=getattr(args, "debug", False), color_jitter=color_jitter)
+                   dataset_root=Path(getattr(args, "dataset_root", "")).expanduser(), debug=getattr(args, "debug", False), color_jitter=color_jitter,
+                   anchor_compensation=anchor_compensation)
     # decoding runs in the workers (identity collate there); the device half of a batch -- augmentation + targets -- runs in
     # this process, where the GPU context lives
     # training: equal shards (DistributedSampler pads the last ones with repeated samples when len(ds) % world != 0 -- a handful of

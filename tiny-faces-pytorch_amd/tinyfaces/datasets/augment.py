@@ -139,10 +139,12 @@ def process_inputs(image_u8, bboxes, input_size=(500, 500), neg_thresh=0.3, rng=
     return x, bboxes, paste, flip
 
 
-def collate_device(samples, templates_d, seed=0):
+def collate_device(samples, templates_d, seed=0, compensate=None):
     """[(x, bboxes, paste_box, flip)] -> (img (B,3,H,W), class_map, regression_map) with the targets assigned on the GPU
-    (what WIDERFace.__getitem__ + the default collate yield, wider_face.py:219-222)."""
+    (what WIDERFace.__getitem__ + the default collate yield, wider_face.py:219-222).  compensate = (N, T): scale-compensated matching
+    (ops.dense_overlap_targets(compensate=)); None = off."""
     xs = torch.stack([s[0] for s in samples])
     cm, rm = ops.dense_overlap_targets([s[1] for s in samples], templates_d, paste_boxes=[s[2] for s in samples],
-                                       flips=[int(s[3]) for s in samples], seed=seed, device=xs.device)      # boxes are already mirrored; flips mirrors the padding mask
+                                       flips=[int(s[3]) for s in samples], seed=seed, device=xs.device,      # boxes are already mirrored; flips mirrors the padding mask
+                                       compensate=compensate)
     return xs, cm, rm

@@ -33,19 +33,53 @@ def _stack_on_device(tensors, device):
         out[i].copy_(t)                  # (blocking: the pageable source of a sample may be freed or reused as soon as collate returns)
     return out
 
+class CompensationStats:
+    """Per-batch counters of the scale-compensated matching, kept on the device until the training loop reads them next to the loss meters
+    (DetectionCriterion.flush_meters): pushing enqueues two reductions of the match counts, popping reads the batches the meters have
+    already waited for."""
+
+    def __init__(self, n):
+        self.n, self._pending = int(n), []
+
+    def push(self, match_count):
+        self._pending.append((torch.stack([(match_count <= self.n).sum(), (match_count < self.n).sum()]), int(match_count.numel())))
+
+    def pop(self, lag=0):
+        """(faces, faces with at most N positives after the stage, faces still below N) summed over all but the `lag` most recent batches;
+        None when there is none."""
+        n = max(0, len(self._pending) - lag)
+        if n == 0:
+            return None
+        faces = at_most = below = 0
+        for counts, total in self._pending[:n]:
+            a, b = counts.tolist()
+            faces, at_most, below = faces + total, at_most + a, below + b
+        self._pending = self._pending[n:]
+        return faces, at_most, below
+
+
 class TargetAssigner:
     """boxes (+ paste box / flip) -> (class_map, regression_map) on the GPU.
-    Replaces DataProcessor.get_padding/get_heatmaps (tinyfaces/datasets/processor.py:114-277)."""
+    Replaces DataProcessor.get_padding/get_heatmaps (tinyfaces/datasets/processor.py:114-277).
+    compensate = (N, T): scale-compensated matching (ops.dense_overlap_targets(compensate=)); `stats` then collects its counters."""
 
-    def __init__(self, templates, heatmap_size=HEATMAP_SIZE, rf=ops.RF, pos_thresh=POS_THRESH, neg_thresh=NEG_THRESH, seed=0):
+    def __init__(self, templates, heatmap_size=HEATMAP_SIZE, rf=ops.RF, pos_thresh=POS_THRESH, neg_thresh=NEG_THRESH, seed=0, compensate=None):
         self.templates, self.heatmap_size, self.rf = templates, heatmap_size, rf
         self.pos_thresh, self.neg_thresh, self.seed, self.calls = pos_thresh, neg_thresh, seed, 0
+        self.compensate = ops.check_compensate(compensate, pos_thresh)
+        self.stats = None if self.compensate is None else CompensationStats(self.compensate[0])
 
     def __call__(self, boxes_per_image, paste_boxes=None, flips=None, device="cuda", noise=None):
         self.calls += 1
-        return ops.dense_overlap_targets(boxes_per_image, self.templates, self.heatmap_size, self.rf, paste_boxes, flips,
-                                         noise=noise, seed=self.seed * 1000003 + self.calls, pos_thresh=self.pos_thresh,
-                                         neg_thresh=self.neg_thresh, device=device)
+        if self.compensate is None:
+            return ops.dense_overlap_targets(boxes_per_image, self.templates, self.heatmap_size, self.rf, paste_boxes, flips,
+                                             noise=noise, seed=self.seed * 1000003 + self.calls, pos_thresh=self.pos_thresh,
+                                             neg_thresh=self.neg_thresh, device=device)
+        cm, rm, mc = ops.dense_overlap_targets(boxes_per_image, self.templates, self.heatmap_size, self.rf, paste_boxes, flips,
+                                               noise=noise, seed=self.seed * 1000003 + self.calls, pos_thresh=self.pos_thresh,
+                                               neg_thresh=self.neg_thresh, device=device, compensate=self.compensate, return_match_count=True)
+        self.stats.push(mc)
+        return cm, rm
 
 
 class SyntheticCrops(data.Dataset):
@@ -163,7 +197,8 @@ class SyntheticFaces(data.Dataset):
     VAL_ZOOM = 1          # evaluation sees the images at their own size: run evaluate_model.py with --mask-axis template (with the reference's mask, defect D1,
                           # the 1/4 level of a 500-pixel image raises IndexError: the mask indexes the 16 heat-map columns with the 25 template indices)
 
-    def __init__(self, templates, length=8, seed=0, train=True, device="cuda", size=(500, 500), img_transforms=None, color_jitter=None):
+    def __init__(self, templates, length=8, seed=0, train=True, device="cuda", size=(500, 500), img_transforms=None, color_jitter=None,
+                 anchor_compensation=None):
         self.templates, self.length, self.seed, self.train, self.device, self.size = templates, length, seed, train, device, size
         # (b, c, s, h) of torchvision's ColorJitter for the training samples: they then travel as uint8 and `collate` jitters + normalises them on the
         # device (ops.image_prepare(jitter=), chains drawn from np.random per sample); None = off, samples are normalised on the host as before
@@ -171,7 +206,10 @@ class SyntheticFaces(data.Dataset):
         self.color_jitter = check_color_jitter(color_jitter)
         # anchors are positive from IoU 0.7 (like WIDER training, wider_face.py:26) and negative below 0.7 (there: 0.3): with eight layouts the wide "ignored"
         # band of the reference would stay untrained -- its anchors answer with arbitrary scores and unregressed boxes, which an AP at IoU 0.5 counts as misses
-        self.assigner = TargetAssigner(templates, seed=seed, pos_thresh=float(os.environ.get("FACES_POS", "0.7")), neg_thresh=float(os.environ.get("FACES_NEG", "0.7")))
+        # anchor_compensation = (N, T): every face is topped up to N positive anchors (ops.dense_overlap_targets(compensate=)); None = off
+        self.assigner = TargetAssigner(templates, seed=seed, pos_thresh=float(os.environ.get("FACES_POS", "0.7")), neg_thresh=float(os.environ.get("FACES_NEG", "0.7")),
+                                       compensate=anchor_compensation)
+        self.compensation_stats = self.assigner.stats
         self.rf, self.transforms = ops.RF, img_transforms
         # the layouts (where the faces are) are the fixed part; `samples` = what evaluation sees: every layout on ONE background of its own.
         # Training sample i shows layout i % N_IMAGES on a background drawn for THAT sample (seeded by i): the pixels between the faces never repeat.

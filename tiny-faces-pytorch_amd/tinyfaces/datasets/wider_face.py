@@ -71,8 +71,15 @@ def parse_annotations(path, split="train"):
 
 class WIDERFace(dataset.Dataset):
     def __init__(self, path, templates, img_transforms=None, dataset_root="", split="train", input_size=(500, 500),
-                 heatmap_size=(63, 63), pos_thresh=0.7, neg_thresh=0.3, pos_fraction=0.5, debug=False, device="cuda", seed=0, color_jitter=None):
+                 heatmap_size=(63, 63), pos_thresh=0.7, neg_thresh=0.3, pos_fraction=0.5, debug=False, device="cuda", seed=0, color_jitter=None,
+                 anchor_compensation=None):
         super().__init__()
+        # (N, T) of the scale-compensated matching (ops.dense_overlap_targets(compensate=)), applied in `collate`; None = off
+        self.anchor_compensation = ops.check_compensate(anchor_compensation, pos_thresh)
+        self.compensation_stats = None
+        if self.anchor_compensation is not None:
+            from .synthetic import CompensationStats
+            self.compensation_stats = CompensationStats(self.anchor_compensation[0])
         self.color_jitter = augment.check_color_jitter(color_jitter)      # (b, c, s, h) of torchvision's ColorJitter, applied in `collate`; None = off
         self.split = split
         self.data = parse_annotations(path, split)
@@ -137,8 +144,14 @@ class WIDERFace(dataset.Dataset):
                                                              color_jitter=self.color_jitter)
                 boxes.append(b); pastes.append(paste); flips.append(int(flip))
             self._step += 1
-            cm, rm = ops.dense_overlap_targets(boxes, self.templates, self.heatmap_size, self.rf, paste_boxes=pastes, flips=flips,
-                                               seed=self._step, pos_thresh=self.pos_thresh, neg_thresh=self.neg_thresh, device=self.device)
+            if self.anchor_compensation is None:
+                cm, rm = ops.dense_overlap_targets(boxes, self.templates, self.heatmap_size, self.rf, paste_boxes=pastes, flips=flips,
+                                                   seed=self._step, pos_thresh=self.pos_thresh, neg_thresh=self.neg_thresh, device=self.device)
+            else:
+                cm, rm, mc = ops.dense_overlap_targets(boxes, self.templates, self.heatmap_size, self.rf, paste_boxes=pastes, flips=flips,
+                                                       seed=self._step, pos_thresh=self.pos_thresh, neg_thresh=self.neg_thresh, device=self.device,
+                                                       compensate=self.anchor_compensation, return_match_count=True)
+                self.compensation_stats.push(mc)
         cur = torch.cuda.current_stream(self.device)
         cur.wait_stream(self._in_stream)
         for t in (x, cm, rm):

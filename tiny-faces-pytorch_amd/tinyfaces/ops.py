@@ -32,16 +32,63 @@ def _workspace(key, nbytes, device):
 
 
 # --------------------------------------------------------------------------- targets
+def check_compensate(compensate, pos_thresh=0.7):
+    """compensate=(N, T) of the scale-compensated matching (include/tinyfaces_hip.h): N an integer in 1..64, T finite with
+    0.01 <= T < pos_thresh.  Returns (int N, float T), or None for None; anything else raises ValueError."""
+    if compensate is None:
+        return None
+    try:
+        n, t = compensate
+    except (TypeError, ValueError):
+        raise ValueError(f"compensate must be None or a pair (N, T), not {compensate!r}") from None
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= 64:
+        raise ValueError(f"compensate: N must be an integer in 1..64, not {n!r}")
+    if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)) or not math.isfinite(float(t)) \
+            or not 0.01 <= float(t) < float(pos_thresh):
+        raise ValueError(f"compensate: T must be finite with 0.01 <= T < pos_thresh = {pos_thresh}, not {t!r}")
+    return int(n), float(t)
+
+
+def _launch_targets(comp, total, boxes_d, offs_d, B, t_d, nt, tstride, vsy, vsx, rf, paste_d, flips_d, noise_d, noff_d, seed, pos_thresh,
+                    neg_thresh, cls, reg, device, return_match_count):
+    """The one place both target wrappers call the library from: tf_dense_overlap_targets, or with comp = (N, T) its compensated form.
+    Returns the match-count tensor (total,) int32, or None."""
+    ofy, ofx = rf["offset"]
+    sty, stx = rf["stride"]
+    if comp is None:
+        wsb = lib().tf_targets_workspace_bytes(total)
+        ws = _workspace("targets", wsb, device)
+        check(lib().tf_dense_overlap_targets(ptr(boxes_d), ptr(offs_d), B, ptr(t_d), nt, tstride, vsy, vsx, ofy, ofx, sty, stx,
+                                             ptr(paste_d), ptr(flips_d), ptr(noise_d), ptr(noff_d), int(seed) & (2**64 - 1),
+                                             float(pos_thresh), float(neg_thresh), ptr(cls), ptr(reg), ptr(ws), wsb, stream()),
+              "tf_dense_overlap_targets")
+        return None
+    mc = torch.empty(total, dtype=torch.int32, device=device) if return_match_count else None
+    wsb = lib().tf_targets_comp_workspace_bytes(total, B, nt, vsy, vsx)
+    ws = _workspace("targets_comp", wsb, device)
+    check(lib().tf_dense_overlap_targets_comp(ptr(boxes_d), ptr(offs_d), B, ptr(t_d), nt, tstride, vsy, vsx, ofy, ofx, sty, stx,
+                                              ptr(paste_d), ptr(flips_d), ptr(noise_d), ptr(noff_d), int(seed) & (2**64 - 1),
+                                              float(pos_thresh), float(neg_thresh), comp[0], comp[1], ptr(mc) if total else None,
+                                              ptr(cls), ptr(reg), ptr(ws), wsb, stream()), "tf_dense_overlap_targets_comp")
+    return mc
+
+
 def dense_overlap_targets(boxes_per_image, templates, heatmap_size=(63, 63), rf=RF, paste_boxes=None, flips=None,
-                          noise=None, seed=0, pos_thresh=0.7, neg_thresh=0.3, device=None):
+                          noise=None, seed=0, pos_thresh=0.7, neg_thresh=0.3, device=None, compensate=None, return_match_count=False):
     """compute_dense_overlap + DataProcessor.get_padding/get_regression/get_heatmaps fused
     (tinyfaces/datasets/dense_overlap.py:4-75, tinyfaces/datasets/processor.py:114-277).
 
     boxes_per_image: list of (G_i, 4) float64 arrays/tensors (x1,y1,x2,y2).
     noise: optional list of (vsy,vsx,nt,G_i_valid) float64 arrays = the np.random.rand draw of
            processor.py:195 (for bit-parity tests); default: device counter RNG seeded by `seed`.
+    compensate: None, or (N, T): every face is topped up to N positive anchors from its own best anchors with perturbed IoU >= T
+           (scale-compensated matching, the rule in include/tinyfaces_hip.h); the regression map does not change.
+    return_match_count: with compensate, also return the (total_valid_boxes,) int32 device tensor of positives per face.
     Returns class_map (B,nt,vsy,vsx) f32 and regression_map (B,4nt,vsy,vsx) f32 on `device`
     -- the CHW layout WIDERFace.__getitem__ hands to the trainer (wider_face.py:186-187)."""
+    comp = check_compensate(compensate, pos_thresh)
+    if return_match_count and comp is None:
+        raise ValueError("return_match_count needs compensate=(N, T)")
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
         raise RuntimeError("dense_overlap_targets: HIP kernel only (no CPU fallback)")
@@ -74,22 +121,20 @@ def dense_overlap_targets(boxes_per_image, templates, heatmap_size=(63, 63), rf=
         noff_d = torch.tensor(noff, dtype=torch.int64, device=device)
     cls = torch.empty(B, nt, vsy, vsx, dtype=torch.float32, device=device)
     reg = torch.empty(B, 4 * nt, vsy, vsx, dtype=torch.float32, device=device)
-    wsb = lib().tf_targets_workspace_bytes(total)
-    ws = _workspace("targets", wsb, device)
-    ofy, ofx = rf["offset"]
-    sty, stx = rf["stride"]
     with torch.cuda.device(device):
-        check(lib().tf_dense_overlap_targets(ptr(boxes_d), ptr(offs_d), B, ptr(t_d), nt, tstride, vsy, vsx, ofy, ofx, sty, stx,
-                                             ptr(paste_d), ptr(flips_d), ptr(noise_d), ptr(noff_d), int(seed) & (2**64 - 1),
-                                             float(pos_thresh), float(neg_thresh), ptr(cls), ptr(reg), ptr(ws), wsb, stream()),
-              "tf_dense_overlap_targets")
-    return cls, reg
+        mc = _launch_targets(comp, total, boxes_d, offs_d, B, t_d, nt, tstride, vsy, vsx, rf, paste_d, flips_d, noise_d, noff_d, seed,
+                             pos_thresh, neg_thresh, cls, reg, device, return_match_count)
+    return (cls, reg, mc) if return_match_count else (cls, reg)
 
 
 def dense_overlap_targets_device(boxes_d, offs_d, total_boxes, templates_d, heatmap_size=(63, 63), rf=RF, paste_d=None, flips_d=None,
-                                 seed=0, pos_thresh=0.7, neg_thresh=0.3, out=None):
+                                 seed=0, pos_thresh=0.7, neg_thresh=0.3, out=None, compensate=None, return_match_count=False):
     """Same kernel as dense_overlap_targets with every operand already resident in HBM:
-    boxes_d (total,4) f64 (degenerate boxes removed), offs_d (B+1,) i32, templates_d (nt,5) f64, paste_d (B,4) i32."""
+    boxes_d (total,4) f64 (degenerate boxes removed), offs_d (B+1,) i32, templates_d (nt,5) f64, paste_d (B,4) i32.
+    compensate / return_match_count: as in dense_overlap_targets."""
+    comp = check_compensate(compensate, pos_thresh)
+    if return_match_count and comp is None:
+        raise ValueError("return_match_count needs compensate=(N, T)")
     require_gpu(boxes_d, "dense_overlap_targets_device")
     B = offs_d.numel() - 1
     vsy, vsx = heatmap_size
@@ -98,14 +143,9 @@ def dense_overlap_targets_device(boxes_d, offs_d, total_boxes, templates_d, heat
     if out is None:
         out = (torch.empty(B, nt, vsy, vsx, dtype=torch.float32, device=dev), torch.empty(B, 4 * nt, vsy, vsx, dtype=torch.float32, device=dev))
     cls, reg = out
-    wsb = lib().tf_targets_workspace_bytes(total_boxes)
-    ws = _workspace("targets", wsb, dev)
-    ofy, ofx = rf["offset"]
-    sty, stx = rf["stride"]
-    check(lib().tf_dense_overlap_targets(ptr(boxes_d), ptr(offs_d), B, ptr(templates_d), nt, tstride, vsy, vsx, ofy, ofx, sty, stx,
-                                         ptr(paste_d), ptr(flips_d), None, None, int(seed) & (2**64 - 1), float(pos_thresh),
-                                         float(neg_thresh), ptr(cls), ptr(reg), ptr(ws), wsb, stream()), "tf_dense_overlap_targets")
-    return cls, reg
+    mc = _launch_targets(comp, int(total_boxes), boxes_d, offs_d, B, templates_d, nt, tstride, vsy, vsx, rf, paste_d, flips_d, None, None, seed,
+                         pos_thresh, neg_thresh, cls, reg, dev, return_match_count)
+    return (cls, reg, mc) if return_match_count else (cls, reg)
 
 
 def dense_overlap_iou(boxes, templates, heatmap_size=(63, 63), rf=RF, device="cuda"):

@@ -19,6 +19,20 @@ def print_state(idx, epoch, size, loss_cls, loss_reg):
     print(head + _LOSS_FMT.format(loss_cls, loss_reg))
 
 
+def print_compensation(idx, epoch, size, dataloader, lag=0):
+    """One line per logged interval when the loader's data set runs the scale-compensated matching (`compensation_stats`, datasets/synthetic.py):
+    how many faces of the batches read so far the stage looked after.  The counters sit on the device behind the targets of their batch, which
+    the loss meters' read has already waited for (`lag` as in DetectionCriterion.flush_meters).  Without the stage: nothing."""
+    stats = getattr(getattr(dataloader, "dataset", None), "compensation_stats", None)
+    if stats is None:
+        return
+    got = stats.pop(lag)
+    if got is not None:
+        faces, at_most, below = got
+        print(f"Epoch: [{epoch}][{idx}/{size}]\tanchor compensation: {at_most} of {faces} faces hold at most N = {stats.n} positives after the stage, "
+              f"{below} of them fewer (their candidates ran out)")
+
+
 def save_checkpoint(state, filename="checkpoint.pth", save_path="weights"):
     """trainer.py:20-26: `state` goes to <save_path>/<filename>; the directory is created on first use."""
     target = Path(save_path)
@@ -117,6 +131,7 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
                 if flush is not None:
                     flush()
                 print_state(step, epoch, n_batches, loss_fn.class_average.average, loss_fn.reg_average.average)
+                print_compensation(step, epoch, n_batches, dataloader)
             elif getattr(loss_fn, "_pending", None):
                 loss_fn._pending.clear()            # lazy meters are only ever read on the logging rank: do not pin device scalars elsewhere
     finally:
