@@ -101,6 +101,39 @@ int tf_dense_overlap_targets_comp(const double* boxes, const int32_t* box_offset
                                   int N, double T, int32_t* match_count,
                                   float* class_map, float* reg_map,
                                   void* ws, size_t ws_bytes, void* stream);
+/* ---- ignore regions of the training targets (S3FD / PyramidBox / RetinaFace pipelines; mmdetection's gt_bboxes_ignore) ----------
+ * tf_targets_apply_ignore is one pass over the class map tf_dense_overlap_targets[_comp] left, in place: a negative anchor that an
+ * ignore box of its image covers gets the don't-care label 0, which both criteria skip.  The reference has no such pass; the rule
+ * below is the contract.  Image b has the ignore boxes r_0 .. r_{K-1} = rows [ign_offsets[b], ign_offsets[b + 1]) of ign_boxes
+ * (x1, y1, x2, y2, float64, in the augmented frame, already mirrored where the image is).  Anchor a = template t at cell (y, x):
+ *   cx = ofx + x * stx, cy = ofy + y * sty;  ax1 = dx1 + cx, ay1 = dy1 + cy, ax2 = dx2 + cx, ay2 = dy2 + cy   (tf_dense_overlap_targets' anchor)
+ *   farea = (dx2 - dx1 + 1) * (dy2 - dy1 + 1);  rarea = (rx2 - rx1 + 1) * (ry2 - ry1 + 1)
+ *   iw = min(ax2, rx2) - max(ax1, rx1) + 1,  ih = min(ay2, ry2) - max(ay1, ry1) + 1                            (the +1 pixel convention)
+ *   if iw > 0 and ih > 0:  ia = iw * ih and
+ *        TF_IGNORE_IOF   ov = ia / farea                     (intersection over the ANCHOR's area: mmdetection's ignore_wrt_candidates)
+ *        TF_IGNORE_IOU   ov = ia / (farea + rarea - ia)
+ *   else ov = 0.
+ *   No rounding to 14 decimals, no noise; plain float64 in this operation order, without FMA contraction.
+ *   a is covered when ov >= thresh for ANY k (order-free in k).  thresh finite, in (0, 1].
+ *   A covered anchor whose label is -1 becomes 0.  Labels +1 and 0 are never changed: a real face keeps its positives inside an
+ *   ignore region.  Nothing else is written; the regression map is not an operand.
+ * Consequences: the pass runs behind everything else (phase C, and the compensation stage when that is on), so it composes with
+ * either call; one image's result does not depend on the rest of its batch.
+ *   class_map     [B][nt][vsy][vsx] f32, in place
+ *   ign_boxes     [total][4] f64; NULL = no ignore box in the batch: TF_OK, nothing is enqueued
+ *   ign_offsets   [B + 1] i32 on the device, ascending from 0
+ *   changed       [B] i32 or NULL: the number of labels turned is ADDED per image (integer atomics, one per wave that turned any);
+ *                 the caller zeroes it.  NULL: nothing is counted.
+ * One launch; no floating-point atomics, no grid barrier, no workspace, no host synchronisation: the same bits on every run.
+ * Refused before anything is enqueued (TF_ERR_ARG): thresh outside (0, 1] or not finite, an unknown measure, a negative size,
+ * tstride < 4, a NULL class_map / templates / ign_offsets next to ign_boxes.  B > 65535 or nt * vsy * vsx >= 2^31: TF_ERR_UNSUPPORTED. */
+#define TF_IGNORE_IOF 0
+#define TF_IGNORE_IOU 1
+int tf_targets_apply_ignore(float* class_map, int B, int nt, int vsy, int vsx,
+                            const double* templates, int tstride,
+                            int ofy, int ofx, int sty, int stx,
+                            const double* ign_boxes, const int32_t* ign_offsets,
+                            int measure, double thresh, int32_t* changed, void* stream);
 /* test hook: the raw rounded IoU tensor [vsy][vsx][nt][G] f64 for ONE image */
 int tf_dense_overlap_iou(const double* boxes, int G, const double* templates, int nt, int tstride,
                          int vsy, int vsx, int ofy, int ofx, int sty, int stx,

@@ -145,6 +145,35 @@ COMPENSATION_HELP = ("--anchor-compensation N T: scale-compensated anchor matchi
                      "default off")
 
 
+IGNORE_HELP = ("ignore regions for the training targets of a WIDER annotation file (S3FD, PyramidBox, RetinaFace; mmdetection's gt_bboxes_ignore): a face "
+               "the policy flags owns no positive anchor, and a negative anchor that what is left of it covers gets the don't-care label on the device. "
+               "--ignore-invalid: faces with invalid = 1; --ignore-blur L / --ignore-occlusion L: faces with blur / occlusion >= L, L in 1..2; "
+               "--ignore-min-size S: faces whose shorter side after the scale draw is below S pixels, S > 0; --ignore-truncated: what is left of the "
+               "faces the crop drops; any of them switches the feature on. --ignore-measure {iof,iou} (default iof: intersection over the anchor's "
+               "area) and --ignore-thresh T (0 < T <= 1, default 0.5) set when an anchor counts as covered; alone they are an error. Default off")
+
+
+def _ignore_level(text):
+    value = int(text)
+    if not 1 <= value <= 2:
+        raise argparse.ArgumentTypeError(f"must be a level in 1..2, got {text}")
+    return value
+
+
+def _ignore_min_size(text):
+    value = float(text)
+    if not (math.isfinite(value) and value > 0):
+        raise argparse.ArgumentTypeError(f"must be a finite number of pixels > 0, got {text}")
+    return value
+
+
+def _ignore_thresh(text):
+    value = float(text)
+    if not (math.isfinite(value) and 0.0 < value <= 1.0):
+        raise argparse.ArgumentTypeError(f"must be a finite number with 0 < T <= 1, got {text}")
+    return value
+
+
 def _compensation_value(text):
     """One of the two values of --anchor-compensation: what either may be (N is narrowed to an integer in 1..64 once both are known)."""
     value = float(text)
@@ -261,7 +290,7 @@ def _positive_float(text):
 
 
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP, JITTER_HELP, VAL_HELP, DETERMINISTIC_HELP, COMPENSATION_HELP)))
+    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP, JITTER_HELP, VAL_HELP, DETERMINISTIC_HELP, COMPENSATION_HELP, IGNORE_HELP)))
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
@@ -274,7 +303,8 @@ def trunk_arguments(argv=None):
     --focal-gamma, --focal-alpha and --focal-normalize, `reg_loss` ("smooth_l1" | "iou" | "giou" | "diou") from --reg-loss and `reg_weight` from
     --reg-weight, `optimizer` ("sgd" | "adamw"), `adam_beta1`, `adam_beta2` and `adam_eps` from --optimizer, --adam-beta1, --adam-beta2 and --adam-eps,
     `warmup_iters` and `warmup_factor` from --warmup-iters and --warmup-factor, `color_jitter` (None or the four amplitudes) from --color-jitter,
-    `anchor_compensation` (None or (N, T)) from --anchor-compensation,
+    `anchor_compensation` (None or (N, T)) from --anchor-compensation, `ignore_policy` (None or an augment.IgnorePolicy) and `ignore` (None or
+    (measure, thresh)) from the --ignore-* flags,
     `val_every`, `val_prob_thresh`, `val_nms_thresh`, `val_num_images` and `val_gt_dir` from --val-every and its companions.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
     options and the additions above."""
     parser = argparse.ArgumentParser(add_help=False)
@@ -307,7 +337,20 @@ def trunk_arguments(argv=None):
     parser.add_argument("--deterministic", dest="deterministic", action="store_true", help=DETERMINISTIC_HELP)
     parser.add_argument("--anchor-compensation", dest="anchor_compensation", default=None, type=_compensation_value, nargs=2, metavar=("N", "T"),
                         help=COMPENSATION_HELP)
+    parser.add_argument("--ignore-invalid", dest="ignore_invalid", action="store_true", help=IGNORE_HELP)
+    parser.add_argument("--ignore-blur", dest="ignore_blur", default=None, type=_ignore_level, metavar="L", help=IGNORE_HELP)
+    parser.add_argument("--ignore-occlusion", dest="ignore_occlusion", default=None, type=_ignore_level, metavar="L", help=IGNORE_HELP)
+    parser.add_argument("--ignore-min-size", dest="ignore_min_size", default=None, type=_ignore_min_size, metavar="S", help=IGNORE_HELP)
+    parser.add_argument("--ignore-truncated", dest="ignore_truncated", action="store_true", help=IGNORE_HELP)
+    parser.add_argument("--ignore-measure", dest="ignore_measure", default=None, choices=["iof", "iou"], help=IGNORE_HELP)
+    parser.add_argument("--ignore-thresh", dest="ignore_thresh", default=None, type=_ignore_thresh, metavar="T", help=IGNORE_HELP)
     known, rest = parser.parse_known_args(argv)
+    ignore_on = (known.ignore_invalid or known.ignore_truncated or known.ignore_blur is not None or known.ignore_occlusion is not None
+                 or known.ignore_min_size is not None)
+    if not ignore_on and known.ignore_measure is not None:
+        parser.error("--ignore-measure needs one of --ignore-invalid, --ignore-blur, --ignore-occlusion, --ignore-min-size, --ignore-truncated")
+    if not ignore_on and known.ignore_thresh is not None:
+        parser.error("--ignore-thresh needs one of --ignore-invalid, --ignore-blur, --ignore-occlusion, --ignore-min-size, --ignore-truncated")
     if known.anchor_compensation is not None:
         n, t = known.anchor_compensation
         if n != int(n) or not 1 <= int(n) <= 64:
@@ -343,7 +386,27 @@ def trunk_arguments(argv=None):
     args.val_prob_thresh, args.val_nms_thresh = known.val_prob_thresh, known.val_nms_thresh
     args.deterministic = known.deterministic
     args.anchor_compensation = None if known.anchor_compensation is None else (int(known.anchor_compensation[0]), float(known.anchor_compensation[1]))
+    args.ignore_policy = args.ignore = None
+    if ignore_on:
+        from tinyfaces.datasets.augment import IgnorePolicy
+        args.ignore_policy = IgnorePolicy(invalid=known.ignore_invalid, blur=known.ignore_blur, occlusion=known.ignore_occlusion,
+                                          min_size=known.ignore_min_size, truncated=known.ignore_truncated)
+        args.ignore = (known.ignore_measure or "iof", 0.5 if known.ignore_thresh is None else known.ignore_thresh)
     return args
+
+
+def ignore_description(args):
+    """The ignore regions as the start-up line prints them."""
+    p, ig = getattr(args, "ignore_policy", None), getattr(args, "ignore", None)
+    if p is None:
+        return "ignore regions off (every anchor outside the IoU band, the padding and the border is a negative)"
+    who = [text for on, text in ((p.invalid, "faces flagged invalid"), (p.blur, f"faces with blur >= {p.blur}"),
+                                 (p.occlusion, f"faces with occlusion >= {p.occlusion}"),
+                                 (p.min_size, f"faces whose shorter side is below {p.min_size:g} px after the scale draw" if p.min_size else ""),
+                                 (p.truncated, "what is left of the faces the crop drops")) if on]
+    measure = "intersection over the anchor's area" if ig[0] == "iof" else "IoU"
+    return (f"ignore regions: {'; '.join(who)} own no positive anchor, and a negative anchor they cover by {measure} >= {ig[1]:g} "
+            "gets the don't-care label (on the device; positives and the regression targets do not change)")
 
 
 def compensation_description(args):
@@ -407,6 +470,7 @@ def run_fused_epoch(engine, loss_fn, loader, epoch, device, base_lr, warmup=None
             loss_fn.flush_meters(lag=0 if idx + 1 == total else 1)      # one step behind: the host prepares batch idx + 1 while the GPU runs step idx
             trainer.print_state(idx, epoch, total, loss_fn.class_average.average, loss_fn.reg_average.average)
             trainer.print_compensation(idx, epoch, total, loader, lag=0 if idx + 1 == total else 1)      # (nothing unless --anchor-compensation)
+            trainer.print_ignore(idx, epoch, total, loader, lag=0 if idx + 1 == total else 1)            # (nothing unless an --ignore-* policy)
 
 
 def load_pretrained_trunk(model, path):
@@ -434,11 +498,14 @@ def main():
     args = trunk_arguments()
     if not torch.cuda.is_available():
         raise SystemExit("this build of the tiny-faces hot path runs on MI355X only (no CPU fallback)")
+    if args.ignore_policy is not None and (str(args.traindata) in ("synthetic", "synthetic-faces") or getattr(args, "synthetic", False)):
+        raise SystemExit("the --ignore-* flags apply to a WIDER annotation file: the synthetic data sets carry no attributes and no crop")
     parallel.init_from_env(os.environ.get("TINYFACES_DIST_BACKEND"))      # (gloo: several ranks on one device, the functional tests of a 1-GPU box)
     device = torch.device("cuda", torch.cuda.current_device())
     preprocess = transforms.Compose([transforms.ToTensor(), transforms.Normalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225])])
     train_loader, _ = get_dataloader(args.traindata, args, NUM_TEMPLATES, img_transforms=preprocess, color_jitter=args.color_jitter,
-                                     anchor_compensation=args.anchor_compensation)
+                                     anchor_compensation=args.anchor_compensation,
+                                     **({} if args.ignore_policy is None else {"ignore_policy": args.ignore_policy, "ignore": args.ignore}))
     model = DetectionModel(base_model=getattr(model_zoo, args.base_model), num_objects=1, num_templates=NUM_TEMPLATES).set_compute_dtype(args.dtype)
     model.freeze_batchnorm(args.freeze_bn).set_trainable_layers(args.trainable_layers)
     if parallel.rank() == 0:
@@ -454,6 +521,7 @@ def main():
         print(loss_description(args))
         print(jitter_description(args))
         print(compensation_description(args))
+        print(ignore_description(args))
         if args.deterministic:
             print(deterministic_description())
         if args.cls_loss == "focal":
@@ -542,6 +610,8 @@ def main():
             snapshot["model_ema"], snapshot["ema"] = ema.state_dict(), ema.settings()
         if args.anchor_compensation is not None:
             snapshot["args"] = {"anchor_compensation": list(args.anchor_compensation)}      # what the targets of this run were matched with
+        if args.ignore_policy is not None:
+            snapshot.setdefault("args", {}).update(ignore_policy=dict(args.ignore_policy._asdict()), ignore=list(args.ignore))
         if val_ap is not None:
             snapshot["val_ap"] = dict(val_ap)                         # of the last validation pass at or before this epoch
         return snapshot

@@ -14,7 +14,7 @@ from .templates import load_templates
 
 
 def get_dataloader(datapath, args, num_templates=25, template_file="templates.json", img_transforms=None, train=True,
-                   split="train", color_jitter=None, anchor_compensation=None):
+                   split="train", color_jitter=None, anchor_compensation=None, ignore_policy=None, ignore=None):
     """datasets/__init__.py:11-52.  `datapath == "synthetic"` (or a path that does not exist with
     args.synthetic set) yields seeded 500x500 crops + random boxes (BASELINE.json configs[2]);
     returns (loader, templates ndarray 25x5) like the reference.
@@ -22,6 +22,9 @@ def get_dataloader(datapath, args, num_templates=25, template_file="templates.js
     device inside `collate` (datasets/augment.py); None = off, the loaders are then exactly what they were.
     anchor_compensation = (N, T): scale-compensated anchor matching for the training targets of WIDERFace and SyntheticFaces (every face is topped
     up to N positive anchors from its own best anchors with IoU >= T: ops.dense_overlap_targets(compensate=)); None = off, as before.
+    ignore_policy (augment.IgnorePolicy) / ignore = (measure, thresh): ignore regions for the training targets of WIDERFace -- flagged, tiny and
+    cropped-away faces own no positive, and the negative anchors on them get the don't-care label (ops.dense_overlap_targets(ignore_boxes=));
+    None = off, as before.  The synthetic data sets carry no attributes and no crop: asking for a policy there is a ValueError.
 
     Data parallel (one process per GPU, tinyfaces/parallel.py): every rank walks ITS shard of the data -- a
     DistributedSampler for annotation files, a rank-dependent seed for the synthetic crops -- so an epoch is one pass over
@@ -29,6 +32,8 @@ def get_dataloader(datapath, args, num_templates=25, template_file="templates.js
     from .. import parallel
     templates = load_templates(num_templates)
     world, rank = (parallel.world_size(), parallel.rank()) if parallel.is_distributed() else (1, 0)
+    if (ignore_policy is not None or ignore is not None) and (str(datapath) in ("synthetic-faces", "synthetic") or getattr(args, "synthetic", False)):
+        raise ValueError("get_dataloader: ignore_policy / ignore apply to WIDER annotation files; the synthetic data sets have no ignore regions")
     if str(datapath) == "synthetic-faces":
         # r6: a small FIXED image list with pasted faces (datasets/synthetic.py: SyntheticFaces) -- the same images for training and evaluation,
         # so that train -> checkpoint -> pyramid evaluation -> result files -> AP can be closed without WIDER assets.  Data parallel: every global
@@ -64,7 +69,7 @@ def get_dataloader(datapath, args, num_templates=25, template_file="templates.js
     from .wider_face import WIDERFace
     ds = WIDERFace(Path(datapath).expanduser(), templates, split=split, img_transforms=img_transforms,
                    dataset_root=Path(getattr(args, "dataset_root", "")).expanduser(), debug=getattr(args, "debug", False), color_jitter=color_jitter,
-                   anchor_compensation=anchor_compensation)
+                   anchor_compensation=anchor_compensation, ignore_policy=ignore_policy, ignore=ignore)
     # decoding runs in the workers (identity collate there); the device half of a batch -- augmentation + targets -- runs in
     # this process, where the GPU context lives
     # training: equal shards (DistributedSampler pads the last ones with repeated samples when len(ds) % world != 0 -- a handful of

@@ -58,19 +58,60 @@ class CompensationStats:
         return faces, at_most, below
 
 
+class IgnoreStats:
+    """Per-batch counters of the ignore regions (ops.dense_overlap_targets(return_ignored_count=True)), kept on the device like
+    CompensationStats: pushing enqueues two reductions of the per-image counts of labels turned, popping reads the batches the loss meters
+    have already waited for."""
+
+    def __init__(self):
+        self._pending = []
+
+    def push(self, ignored_count):
+        self._pending.append((torch.stack([ignored_count.sum(), (ignored_count > 0).sum()]), int(ignored_count.numel())))
+
+    def pop(self, lag=0):
+        """(images, anchors turned from negative to ignored, images with any) summed over all but the `lag` most recent batches; None when
+        there is none."""
+        n = max(0, len(self._pending) - lag)
+        if n == 0:
+            return None
+        images = turned = with_any = 0
+        for counts, total in self._pending[:n]:
+            a, b = counts.tolist()
+            images, turned, with_any = images + total, turned + a, with_any + b
+        self._pending = self._pending[n:]
+        return images, turned, with_any
+
+
 class TargetAssigner:
     """boxes (+ paste box / flip) -> (class_map, regression_map) on the GPU.
     Replaces DataProcessor.get_padding/get_heatmaps (tinyfaces/datasets/processor.py:114-277).
-    compensate = (N, T): scale-compensated matching (ops.dense_overlap_targets(compensate=)); `stats` then collects its counters."""
+    compensate = (N, T): scale-compensated matching (ops.dense_overlap_targets(compensate=)); `stats` then collects its counters.
+    ignore = (measure, thresh): a call may then pass `ignore_boxes` (ops.dense_overlap_targets(ignore_boxes=)); `ignore_stats` collects the counters."""
 
-    def __init__(self, templates, heatmap_size=HEATMAP_SIZE, rf=ops.RF, pos_thresh=POS_THRESH, neg_thresh=NEG_THRESH, seed=0, compensate=None):
+    def __init__(self, templates, heatmap_size=HEATMAP_SIZE, rf=ops.RF, pos_thresh=POS_THRESH, neg_thresh=NEG_THRESH, seed=0, compensate=None,
+                 ignore=None):
         self.templates, self.heatmap_size, self.rf = templates, heatmap_size, rf
         self.pos_thresh, self.neg_thresh, self.seed, self.calls = pos_thresh, neg_thresh, seed, 0
         self.compensate = ops.check_compensate(compensate, pos_thresh)
         self.stats = None if self.compensate is None else CompensationStats(self.compensate[0])
+        self.ignore = ops.check_ignore(ignore)
+        self.ignore_stats = None if self.ignore is None else IgnoreStats()
 
-    def __call__(self, boxes_per_image, paste_boxes=None, flips=None, device="cuda", noise=None):
+    def __call__(self, boxes_per_image, paste_boxes=None, flips=None, device="cuda", noise=None, ignore_boxes=None):
         self.calls += 1
+        if ignore_boxes is not None:
+            if self.ignore is None:
+                raise ValueError("TargetAssigner: ignore_boxes needs ignore=(measure, thresh) at construction")
+            out = ops.dense_overlap_targets(boxes_per_image, self.templates, self.heatmap_size, self.rf, paste_boxes, flips,
+                                            noise=noise, seed=self.seed * 1000003 + self.calls, pos_thresh=self.pos_thresh,
+                                            neg_thresh=self.neg_thresh, device=device, compensate=self.compensate,
+                                            return_match_count=self.compensate is not None, ignore_boxes=ignore_boxes, ignore=self.ignore,
+                                            return_ignored_count=True)
+            if self.compensate is not None:
+                self.stats.push(out[2])
+            self.ignore_stats.push(out[-1])
+            return out[0], out[1]
         if self.compensate is None:
             return ops.dense_overlap_targets(boxes_per_image, self.templates, self.heatmap_size, self.rf, paste_boxes, flips,
                                              noise=noise, seed=self.seed * 1000003 + self.calls, pos_thresh=self.pos_thresh,

@@ -8,6 +8,9 @@ work moved to the GPU.
                            (datasets/augment.py -> tf_image_prepare) and target assignment (tf_dense_overlap_targets), so a
                            batch is (img (B,3,500,500), class_map (B,25,63,63), regression_map (B,100,63,63)) as
                            wider_face.py:219-222 + the default collate produce.
+                           With `ignore_policy` set (off by default) a training sample carries the attribute columns the policy
+                           reads as a third element, and `collate` hands the ignore boxes of augment.process_inputs to
+                           ops.dense_overlap_targets(ignore_boxes=); without it samples, calls and results are what they were.
   * val / test             image tensor + path, as wider_face.py:224-239.
 np.random is drawn in the reference's per-sample order (scale, crop x/y, paste x/y, flip; with `color_jitter` set, the jitter's order and factors
 after the flip); the balance sampling inside the
@@ -72,8 +75,19 @@ def parse_annotations(path, split="train"):
 class WIDERFace(dataset.Dataset):
     def __init__(self, path, templates, img_transforms=None, dataset_root="", split="train", input_size=(500, 500),
                  heatmap_size=(63, 63), pos_thresh=0.7, neg_thresh=0.3, pos_fraction=0.5, debug=False, device="cuda", seed=0, color_jitter=None,
-                 anchor_compensation=None):
+                 anchor_compensation=None, ignore_policy=None, ignore=None):
         super().__init__()
+        # ignore regions (augment.IgnorePolicy: which faces become don't-care regions instead of positives; ignore = (measure, thresh) of
+        # ops.dense_overlap_targets(ignore_boxes=, ignore=), None = ("iof", 0.5)), applied in `collate`; ignore_policy None = off
+        self.ignore_policy = augment.check_ignore_policy(ignore_policy)
+        self.ignore = ops.check_ignore(ignore)
+        if self.ignore is not None and self.ignore_policy is None:
+            raise ValueError("WIDERFace: ignore=(measure, thresh) needs an ignore_policy")
+        self.ignore_stats = None
+        if self.ignore_policy is not None:
+            from .synthetic import IgnoreStats
+            self.ignore = self.ignore or ops.IGNORE_DEFAULT
+            self.ignore_stats = IgnoreStats()
         # (N, T) of the scale-compensated matching (ops.dense_overlap_targets(compensate=)), applied in `collate`; None = off
         self.anchor_compensation = ops.check_compensate(anchor_compensation, pos_thresh)
         self.compensation_stats = None
@@ -111,6 +125,8 @@ class WIDERFace(dataset.Dataset):
         datum = self.data[index]
         image = self._open(datum)
         if self.split == "train":
+            if self.ignore_policy is not None:                    # the attribute columns the policy reads travel as a third element
+                return np.array(image, dtype=np.uint8), datum["bboxes"], {k: datum[k] for k in ("invalid", "blur", "occlusion")}
             return np.array(image, dtype=np.uint8), datum["bboxes"]
         if self.split == "val":
             return (transforms.to_tensor(image) if self.transforms is not None else image), datum["img_path"]
@@ -137,14 +153,31 @@ class WIDERFace(dataset.Dataset):
         # stream only, while the training stream is still busy with the previous step (bench.py --with-augment: 960 -> 1032 img/s)
         with torch.cuda.stream(self._in_stream):
             x = torch.empty(B, 3, *self.input_size, dtype=torch.float32, device=self.device)
-            boxes, pastes, flips = [], [], []
-            for i, (img, bb) in enumerate(samples):
+            boxes, pastes, flips, ignores = [], [], [], []
+            for i, sample in enumerate(samples):
+                img, bb = sample[0], sample[1]
                 u8 = torch.from_numpy(img).to(self.device)      # blocking on THIS stream only: the decoded (pageable) array is not ours to keep alive
-                _, b, paste, flip = augment.process_inputs(u8, bb, self.input_size, self.neg_thresh, out=x[i], mean=mean, std=std,
-                                                             color_jitter=self.color_jitter)
+                if self.ignore_policy is None:
+                    _, b, paste, flip = augment.process_inputs(u8, bb, self.input_size, self.neg_thresh, out=x[i], mean=mean, std=std,
+                                                                 color_jitter=self.color_jitter)
+                else:
+                    ign = []
+                    _, b, paste, flip = augment.process_inputs(u8, bb, self.input_size, self.neg_thresh, out=x[i], mean=mean, std=std,
+                                                                 color_jitter=self.color_jitter, ignore_policy=self.ignore_policy,
+                                                                 attributes=sample[2], ignore_out=ign)
+                    ignores.append(np.array(ign, dtype=np.float64).reshape(-1, 4))
                 boxes.append(b); pastes.append(paste); flips.append(int(flip))
             self._step += 1
-            if self.anchor_compensation is None:
+            if self.ignore_policy is not None:
+                out = ops.dense_overlap_targets(boxes, self.templates, self.heatmap_size, self.rf, paste_boxes=pastes, flips=flips,
+                                                seed=self._step, pos_thresh=self.pos_thresh, neg_thresh=self.neg_thresh, device=self.device,
+                                                compensate=self.anchor_compensation, return_match_count=self.anchor_compensation is not None,
+                                                ignore_boxes=ignores, ignore=self.ignore, return_ignored_count=True)
+                cm, rm = out[0], out[1]
+                if self.anchor_compensation is not None:
+                    self.compensation_stats.push(out[2])
+                self.ignore_stats.push(out[-1])
+            elif self.anchor_compensation is None:
                 cm, rm = ops.dense_overlap_targets(boxes, self.templates, self.heatmap_size, self.rf, paste_boxes=pastes, flips=flips,
                                                    seed=self._step, pos_thresh=self.pos_thresh, neg_thresh=self.neg_thresh, device=self.device)
             else:

@@ -49,6 +49,76 @@ def check_compensate(compensate, pos_thresh=0.7):
     return int(n), float(t)
 
 
+IGNORE_MEASURES = {"iof": 0, "iou": 1}                    # TF_IGNORE_* (include/tinyfaces_hip.h)
+IGNORE_DEFAULT = ("iof", 0.5)
+
+
+def check_ignore(ignore):
+    """ignore=(measure, thresh) of the ignore regions (include/tinyfaces_hip.h): measure "iof" (intersection over the anchor's area) or "iou",
+    thresh finite in (0, 1].  Returns (str measure, float thresh), or None for None; anything else raises ValueError."""
+    if ignore is None:
+        return None
+    try:
+        measure, thresh = ignore
+    except (TypeError, ValueError):
+        raise ValueError(f"ignore must be None or a pair (measure, thresh), not {ignore!r}") from None
+    if not isinstance(measure, str) or measure not in IGNORE_MEASURES:
+        raise ValueError(f"ignore: measure must be one of {sorted(IGNORE_MEASURES)}, not {measure!r}")
+    if isinstance(thresh, bool) or not isinstance(thresh, (int, float, np.integer, np.floating)) or not math.isfinite(float(thresh)) \
+            or not 0.0 < float(thresh) <= 1.0:
+        raise ValueError(f"ignore: thresh must be finite with 0 < thresh <= 1, not {thresh!r}")
+    return measure, float(thresh)
+
+
+def _valid_boxes(boxes_per_image):
+    """Per image the non-degenerate rows (processor.py:228-232) of (G_i, 4) arrays / tensors as float64 -> (list of kept, offsets)."""
+    kept, offs = [], [0]
+    for b in boxes_per_image:
+        b = torch.as_tensor(np.asarray(b.cpu() if torch.is_tensor(b) else b), dtype=torch.float64).reshape(-1, 4)
+        valid = ~((b[:, 2] <= b[:, 0]) | (b[:, 3] <= b[:, 1]))
+        kept.append(b[valid])
+        offs.append(offs[-1] + int(valid.sum()))
+    return kept, offs
+
+
+def _launch_ignore(cls, t_d, rf, ign_d, ioffs_d, total, ign, want_count):
+    """tf_targets_apply_ignore on resident operands, in place on cls (B, nt, vsy, vsx).  Returns the (B,) int32 counter of labels turned
+    (zeroed here) or None.  No ignore box in the batch: nothing is enqueued."""
+    B, nt, vsy, vsx = cls.shape
+    changed = torch.zeros(B, dtype=torch.int32, device=cls.device) if want_count else None
+    if int(total) > 0:
+        ofy, ofx = rf["offset"]
+        sty, stx = rf["stride"]
+        check(lib().tf_targets_apply_ignore(ptr(cls), B, nt, vsy, vsx, ptr(t_d), t_d.shape[1], ofy, ofx, sty, stx, ptr(ign_d), ptr(ioffs_d),
+                                            IGNORE_MEASURES[ign[0]], ign[1], ptr(changed), stream()), "tf_targets_apply_ignore")
+    return changed
+
+
+def targets_apply_ignore(class_map, ignore_boxes_per_image, templates, rf=RF, ignore=IGNORE_DEFAULT, return_count=False):
+    """Ignore regions on a class map (B, nt, vsy, vsx) f32 on the device, IN PLACE (tf_targets_apply_ignore; the rule is in
+    include/tinyfaces_hip.h): a negative anchor (-1) that one of its image's ignore boxes covers by at least thresh becomes 0; +1 and 0 stay.
+    ignore_boxes_per_image: list of (K_i, 4) float64 arrays / tensors (x1, y1, x2, y2) in the frame of the targets; degenerate ones
+    (x2 <= x1 or y2 <= y1) are dropped as faces are.  ignore = (measure, thresh), measure "iof" | "iou".
+    Returns class_map [, the (B,) int32 device tensor of labels turned per image]."""
+    ign = check_ignore(ignore)
+    if ign is None:
+        raise ValueError("targets_apply_ignore: ignore=(measure, thresh) is required")
+    require_gpu(class_map, "targets_apply_ignore")
+    if class_map.dtype != torch.float32 or class_map.dim() != 4 or not class_map.is_contiguous():
+        raise ValueError("targets_apply_ignore: class_map is a contiguous float32 (B, nt, vsy, vsx) tensor")
+    if len(ignore_boxes_per_image) != class_map.shape[0]:
+        raise ValueError(f"targets_apply_ignore: {len(ignore_boxes_per_image)} lists of ignore boxes for {class_map.shape[0]} images")
+    dev = class_map.device
+    t_d = torch.as_tensor(np.asarray(templates.cpu() if torch.is_tensor(templates) else templates), dtype=torch.float64).contiguous().to(dev)
+    kept, offs = _valid_boxes(ignore_boxes_per_image)
+    total = offs[-1]
+    ign_d = (torch.cat(kept) if total else torch.zeros(1, 4, dtype=torch.float64)).contiguous().to(dev)
+    ioffs_d = torch.tensor(offs, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        changed = _launch_ignore(class_map, t_d, rf, ign_d, ioffs_d, total, ign, return_count)
+    return (class_map, changed) if return_count else class_map
+
+
 def _launch_targets(comp, total, boxes_d, offs_d, B, t_d, nt, tstride, vsy, vsx, rf, paste_d, flips_d, noise_d, noff_d, seed, pos_thresh,
                     neg_thresh, cls, reg, device, return_match_count):
     """The one place both target wrappers call the library from: tf_dense_overlap_targets, or with comp = (N, T) its compensated form.
@@ -74,7 +144,8 @@ def _launch_targets(comp, total, boxes_d, offs_d, B, t_d, nt, tstride, vsy, vsx,
 
 
 def dense_overlap_targets(boxes_per_image, templates, heatmap_size=(63, 63), rf=RF, paste_boxes=None, flips=None,
-                          noise=None, seed=0, pos_thresh=0.7, neg_thresh=0.3, device=None, compensate=None, return_match_count=False):
+                          noise=None, seed=0, pos_thresh=0.7, neg_thresh=0.3, device=None, compensate=None, return_match_count=False,
+                          ignore_boxes=None, ignore=None, return_ignored_count=False):
     """compute_dense_overlap + DataProcessor.get_padding/get_regression/get_heatmaps fused
     (tinyfaces/datasets/dense_overlap.py:4-75, tinyfaces/datasets/processor.py:114-277).
 
@@ -84,11 +155,22 @@ def dense_overlap_targets(boxes_per_image, templates, heatmap_size=(63, 63), rf=
     compensate: None, or (N, T): every face is topped up to N positive anchors from its own best anchors with perturbed IoU >= T
            (scale-compensated matching, the rule in include/tinyfaces_hip.h); the regression map does not change.
     return_match_count: with compensate, also return the (total_valid_boxes,) int32 device tensor of positives per face.
+    ignore_boxes: None, or a list of (K_i, 4) float64 ignore boxes per image, in the frame of `boxes_per_image` (already mirrored where the
+           image is): behind everything else a negative anchor that one of them covers gets the don't-care label 0 (`targets_apply_ignore`,
+           the rule in include/tinyfaces_hip.h); positives and the regression map do not change.  ignore = (measure, thresh), None = ("iof", 0.5).
+    return_ignored_count: with ignore_boxes, also return the (B,) int32 device tensor of labels turned per image.
     Returns class_map (B,nt,vsy,vsx) f32 and regression_map (B,4nt,vsy,vsx) f32 on `device`
-    -- the CHW layout WIDERFace.__getitem__ hands to the trainer (wider_face.py:186-187)."""
+    -- the CHW layout WIDERFace.__getitem__ hands to the trainer (wider_face.py:186-187) -- [, match_count][, ignored_count]."""
     comp = check_compensate(compensate, pos_thresh)
     if return_match_count and comp is None:
         raise ValueError("return_match_count needs compensate=(N, T)")
+    ign = check_ignore(ignore)
+    if return_ignored_count and ignore_boxes is None:
+        raise ValueError("return_ignored_count needs ignore_boxes")
+    if ignore_boxes is not None:
+        ign = ign or IGNORE_DEFAULT
+        if len(ignore_boxes) != len(boxes_per_image):
+            raise ValueError(f"dense_overlap_targets: {len(ignore_boxes)} lists of ignore boxes for {len(boxes_per_image)} images")
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
         raise RuntimeError("dense_overlap_targets: HIP kernel only (no CPU fallback)")
@@ -124,17 +206,36 @@ def dense_overlap_targets(boxes_per_image, templates, heatmap_size=(63, 63), rf=
     with torch.cuda.device(device):
         mc = _launch_targets(comp, total, boxes_d, offs_d, B, t_d, nt, tstride, vsy, vsx, rf, paste_d, flips_d, noise_d, noff_d, seed,
                              pos_thresh, neg_thresh, cls, reg, device, return_match_count)
-    return (cls, reg, mc) if return_match_count else (cls, reg)
+        if ignore_boxes is not None:
+            ikept, ioffs = _valid_boxes(ignore_boxes)
+            ign_d = (torch.cat(ikept) if ioffs[-1] else torch.zeros(1, 4, dtype=torch.float64)).contiguous().to(device)
+            ic = _launch_ignore(cls, t_d, rf, ign_d, torch.tensor(ioffs, dtype=torch.int32, device=device), ioffs[-1], ign, return_ignored_count)
+    out = (cls, reg)
+    if return_match_count:
+        out += (mc,)
+    if return_ignored_count:
+        out += (ic,)
+    return out
 
 
 def dense_overlap_targets_device(boxes_d, offs_d, total_boxes, templates_d, heatmap_size=(63, 63), rf=RF, paste_d=None, flips_d=None,
-                                 seed=0, pos_thresh=0.7, neg_thresh=0.3, out=None, compensate=None, return_match_count=False):
+                                 seed=0, pos_thresh=0.7, neg_thresh=0.3, out=None, compensate=None, return_match_count=False,
+                                 ignore_d=None, ignore_offs_d=None, total_ignore=0, ignore=None, return_ignored_count=False):
     """Same kernel as dense_overlap_targets with every operand already resident in HBM:
     boxes_d (total,4) f64 (degenerate boxes removed), offs_d (B+1,) i32, templates_d (nt,5) f64, paste_d (B,4) i32.
-    compensate / return_match_count: as in dense_overlap_targets."""
+    compensate / return_match_count: as in dense_overlap_targets.
+    ignore_d (total_ignore, 4) f64 (degenerate boxes removed) under ignore_offs_d (B+1,) i32, total_ignore the host's copy of its last entry:
+    the ignore regions of dense_overlap_targets(ignore_boxes=); ignore / return_ignored_count as there."""
     comp = check_compensate(compensate, pos_thresh)
     if return_match_count and comp is None:
         raise ValueError("return_match_count needs compensate=(N, T)")
+    ign = check_ignore(ignore)
+    if return_ignored_count and ignore_d is None:
+        raise ValueError("return_ignored_count needs ignore_d / ignore_offs_d")
+    if ignore_d is not None:
+        ign = ign or IGNORE_DEFAULT
+        if ignore_offs_d is None or ignore_offs_d.numel() != offs_d.numel():
+            raise ValueError("dense_overlap_targets_device: ignore_offs_d is an int32 (B + 1,) device tensor next to ignore_d")
     require_gpu(boxes_d, "dense_overlap_targets_device")
     B = offs_d.numel() - 1
     vsy, vsx = heatmap_size
@@ -145,7 +246,14 @@ def dense_overlap_targets_device(boxes_d, offs_d, total_boxes, templates_d, heat
     cls, reg = out
     mc = _launch_targets(comp, int(total_boxes), boxes_d, offs_d, B, templates_d, nt, tstride, vsy, vsx, rf, paste_d, flips_d, None, None, seed,
                          pos_thresh, neg_thresh, cls, reg, dev, return_match_count)
-    return (cls, reg, mc) if return_match_count else (cls, reg)
+    res = (cls, reg)
+    if return_match_count:
+        res += (mc,)
+    if ignore_d is not None:
+        ic = _launch_ignore(cls, templates_d, rf, ignore_d, ignore_offs_d, int(total_ignore), ign, return_ignored_count)
+        if return_ignored_count:
+            res += (ic,)
+    return res
 
 
 def dense_overlap_iou(boxes, templates, heatmap_size=(63, 63), rf=RF, device="cuda"):

@@ -33,6 +33,20 @@ def print_compensation(idx, epoch, size, dataloader, lag=0):
               f"{below} of them fewer (their candidates ran out)")
 
 
+def print_ignore(idx, epoch, size, dataloader, lag=0):
+    """One line per logged interval when the loader's data set applies ignore regions (`ignore_stats`, datasets/synthetic.py: IgnoreStats): the
+    mean number of anchors turned from negative to ignored per image, and the share of images with any.  Read like `print_compensation`,
+    behind the loss meters' own host read.  Without the feature: nothing."""
+    stats = getattr(getattr(dataloader, "dataset", None), "ignore_stats", None)
+    if stats is None:
+        return
+    got = stats.pop(lag)
+    if got is not None:
+        images, turned, with_any = got
+        print(f"Epoch: [{epoch}][{idx}/{size}]\tignore regions: {turned / images:.1f} anchors per image turned from negative to ignored, "
+              f"{100.0 * with_any / images:.0f} % of {images} images with any")
+
+
 def save_checkpoint(state, filename="checkpoint.pth", save_path="weights"):
     """trainer.py:20-26: `state` goes to <save_path>/<filename>; the directory is created on first use."""
     target = Path(save_path)
@@ -132,6 +146,7 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
                     flush()
                 print_state(step, epoch, n_batches, loss_fn.class_average.average, loss_fn.reg_average.average)
                 print_compensation(step, epoch, n_batches, dataloader)
+                print_ignore(step, epoch, n_batches, dataloader)
             elif getattr(loss_fn, "_pending", None):
                 loss_fn._pending.clear()            # lazy meters are only ever read on the logging rank: do not pin device scalars elsewhere
     finally:
