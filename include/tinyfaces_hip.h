@@ -134,6 +134,48 @@ int tf_targets_apply_ignore(float* class_map, int B, int nt, int vsy, int vsx,
                             int ofy, int ofx, int sty, int stx,
                             const double* ign_boxes, const int32_t* ign_offsets,
                             int measure, double thresh, int32_t* changed, void* stream);
+/* ---- ATSS target assignment (Zhang et al. 2020, "Bridging the Gap Between Anchor-based and Anchor-free Detection"; mmdetection's
+ * ATSSAssigner; what SCRFD and TinaFace train with) ---------------------------------------------------------------------------------
+ * tf_targets_atss is an assigner of its own next to tf_dense_overlap_targets: the same operands and the same two maps in the same layout,
+ * no fixed thresholds.  The reference has no such assigner; the rule below is the contract (numpy restatement: tests/atss_ref.py).
+ * All symbols are per image.  Faces g = 0 .. G-1 = rows [box_offsets[b], box_offsets[b + 1]) of boxes (degenerate ones removed by the
+ * caller, input order).  Anchor a = template t at cell (y, x), exactly tf_dense_overlap_targets' anchor:
+ *   cx = ofx + x * stx, cy = ofy + y * sty;  ax1 = dx1 + cx, ay1 = dy1 + cy, ax2 = dx2 + cx, ay2 = dy2 + cy
+ *   anchor centre acx = (ax1 + ax2) / 2, acy = (ay1 + ay2) / 2;  pad(a) = get_padding's predicate (paste_boxes, mirrored in x where flips says so)
+ * Plain float64 in the stated operation order, without FMA contraction; no rounding to 14 decimals, no noise, no RNG: the result is a pure
+ * function of boxes, templates, geometry and k.
+ *   1 candidates  for face g and template t: the k unpadded cells of t nearest to the face centre fcx = (fx1 + fx2) / 2, fcy = (fy1 + fy2) / 2,
+ *                 by (acx - fcx)^2 + (acy - fcy)^2 ascending, the lower cell index y * vsx + x first on a tie; a template with fewer than k
+ *                 unpadded cells contributes all of them.  k in 1..16.  The face's list: t ascending, then that rank; length n <= k * nt.
+ *   2 IoU         v of each candidate with the face in dense_overlap's operation order (+1 pixel convention, 0 unless iw > 0 and ih > 0), unrounded.
+ *   3 threshold   mean = (v_0 + v_1 + ... + v_{n-1}) / n, summed serially in list order; var = sum (v_i - mean)^2 / (n - 1) in the same order
+ *                 (unbiased, torch.std's form), 0 when n = 1.  A candidate passes when d = v - mean >= 0 and d * d >= var: v >= mean + std
+ *                 without a square root.
+ *   4 positives   a passing candidate whose anchor centre lies strictly inside the face (fx1 < acx < fx2 and fy1 < acy < fy2) is a claim of g.
+ *   5 fallback    a face with candidates but no claim claims its single best candidate (largest v, the earlier list position on a tie), even
+ *                 when v is 0 or the centre lies outside: the counterpart of the reference's forced best anchor.  n = 0 claims nothing.
+ *   6 conflicts   an anchor claimed by several faces goes to the larger v, the lower g on a tie; the losers are not compensated.
+ *   7 output      class_map = +1 at every won claim, -1 everywhere else, padded anchors included (no grey band; tf_targets_apply_ignore
+ *                 behind this call, with the faces as ignore boxes, makes one).  reg_map = get_regression's four values of the winning face
+ *                 ((fcx - cx) / dw, (fcy - cy) / dh, log(fw / dw), log(fh / dh); f64, stored as f32) at every +1 anchor, exactly 0.f
+ *                 everywhere else.  Every element of both maps is written; they may arrive holding garbage.
+ *                 match_count [total_boxes] i32 or NULL: the number of anchors each face won.
+ *   8 one image's result does not depend on the rest of its batch.
+ * Four launches (fill, claim, owner, write); conflicts are resolved with 64- and 32-bit integer atomics only (max of the IoU's bit pattern,
+ * then min of the face index), so the bits are the same on every run; no grid barrier, no host synchronisation.  The claims of a face are
+ * kept in the workspace, not recomputed.  The number of boxes is only known on the device: a workspace too small for box_offsets[B] makes
+ * every kernel return without writing.
+ * Refused before anything is enqueued: k outside 1..16, a NULL class_map / reg_map / templates / box_offsets, a non-positive size,
+ * tstride < 4, a stride <= 0 (TF_ERR_ARG); a workspace below the size for one box (TF_ERR_WORKSPACE); nt * vsy * vsx >= 2^31 or a cell
+ * coordinate beyond int32 (TF_ERR_UNSUPPORTED). */
+size_t tf_targets_atss_workspace_bytes(int total_boxes, int B, int nt, int vsy, int vsx);
+int tf_targets_atss(const double* boxes, const int32_t* box_offsets, int B,
+                    const double* templates, int nt, int tstride,
+                    int vsy, int vsx, int ofy, int ofx, int sty, int stx,
+                    const int32_t* paste_boxes, const int32_t* flips,
+                    int k, int32_t* match_count,
+                    float* class_map, float* reg_map,
+                    void* ws, size_t ws_bytes, void* stream);
 /* test hook: the raw rounded IoU tensor [vsy][vsx][nt][G] f64 for ONE image */
 int tf_dense_overlap_iou(const double* boxes, int G, const double* templates, int nt, int tstride,
                          int vsy, int vsx, int ofy, int ofx, int sty, int stx,

@@ -145,6 +145,12 @@ COMPENSATION_HELP = ("--anchor-compensation N T: scale-compensated anchor matchi
                      "default off")
 
 
+ASSIGNER_HELP = ("--assigner atss: ATSS target assignment (Zhang et al. 2020; what SCRFD and TinaFace train with) for the training targets instead of "
+                 "the fixed IoU thresholds: per face the --atss-topk K (1..16, default 9) unpadded cells of every template nearest to its centre are "
+                 "candidates, positive from mean + std of their IoUs when the anchor centre lies inside the face; not together with "
+                 "--anchor-compensation; default dense-overlap (positive from IoU 0.7, negative below 0.3)")
+
+
 IGNORE_HELP = ("ignore regions for the training targets of a WIDER annotation file (S3FD, PyramidBox, RetinaFace; mmdetection's gt_bboxes_ignore): a face "
                "the policy flags owns no positive anchor, and a negative anchor that what is left of it covers gets the don't-care label on the device. "
                "--ignore-invalid: faces with invalid = 1; --ignore-blur L / --ignore-occlusion L: faces with blur / occlusion >= L, L in 1..2; "
@@ -172,6 +178,16 @@ def _ignore_thresh(text):
     if not (math.isfinite(value) and 0.0 < value <= 1.0):
         raise argparse.ArgumentTypeError(f"must be a finite number with 0 < T <= 1, got {text}")
     return value
+
+
+def _atss_topk(text):
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--atss-topk takes an integer in 1..16, got {text!r}") from None
+    if not 1 <= k <= 16:
+        raise argparse.ArgumentTypeError(f"--atss-topk takes an integer in 1..16, got {text!r}")
+    return k
 
 
 def _compensation_value(text):
@@ -303,7 +319,8 @@ def trunk_arguments(argv=None):
     --focal-gamma, --focal-alpha and --focal-normalize, `reg_loss` ("smooth_l1" | "iou" | "giou" | "diou") from --reg-loss and `reg_weight` from
     --reg-weight, `optimizer` ("sgd" | "adamw"), `adam_beta1`, `adam_beta2` and `adam_eps` from --optimizer, --adam-beta1, --adam-beta2 and --adam-eps,
     `warmup_iters` and `warmup_factor` from --warmup-iters and --warmup-factor, `color_jitter` (None or the four amplitudes) from --color-jitter,
-    `anchor_compensation` (None or (N, T)) from --anchor-compensation, `ignore_policy` (None or an augment.IgnorePolicy) and `ignore` (None or
+    `anchor_compensation` (None or (N, T)) from --anchor-compensation, `assigner` ("dense_overlap" | "atss") and `atss_topk` from --assigner and
+    --atss-topk, `ignore_policy` (None or an augment.IgnorePolicy) and `ignore` (None or
     (measure, thresh)) from the --ignore-* flags,
     `val_every`, `val_prob_thresh`, `val_nms_thresh`, `val_num_images` and `val_gt_dir` from --val-every and its companions.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
     options and the additions above."""
@@ -337,6 +354,8 @@ def trunk_arguments(argv=None):
     parser.add_argument("--deterministic", dest="deterministic", action="store_true", help=DETERMINISTIC_HELP)
     parser.add_argument("--anchor-compensation", dest="anchor_compensation", default=None, type=_compensation_value, nargs=2, metavar=("N", "T"),
                         help=COMPENSATION_HELP)
+    parser.add_argument("--assigner", dest="assigner", default="dense-overlap", choices=["dense-overlap", "atss"], help=ASSIGNER_HELP)
+    parser.add_argument("--atss-topk", dest="atss_topk", default=9, type=_atss_topk, metavar="K", help=ASSIGNER_HELP)
     parser.add_argument("--ignore-invalid", dest="ignore_invalid", action="store_true", help=IGNORE_HELP)
     parser.add_argument("--ignore-blur", dest="ignore_blur", default=None, type=_ignore_level, metavar="L", help=IGNORE_HELP)
     parser.add_argument("--ignore-occlusion", dest="ignore_occlusion", default=None, type=_ignore_level, metavar="L", help=IGNORE_HELP)
@@ -351,6 +370,8 @@ def trunk_arguments(argv=None):
         parser.error("--ignore-measure needs one of --ignore-invalid, --ignore-blur, --ignore-occlusion, --ignore-min-size, --ignore-truncated")
     if not ignore_on and known.ignore_thresh is not None:
         parser.error("--ignore-thresh needs one of --ignore-invalid, --ignore-blur, --ignore-occlusion, --ignore-min-size, --ignore-truncated")
+    if known.anchor_compensation is not None and known.assigner == "atss":
+        parser.error("--anchor-compensation tops up the owners that the dense-overlap assignment computes; it does not go with --assigner atss")
     if known.anchor_compensation is not None:
         n, t = known.anchor_compensation
         if n != int(n) or not 1 <= int(n) <= 64:
@@ -386,6 +407,10 @@ def trunk_arguments(argv=None):
     args.val_prob_thresh, args.val_nms_thresh = known.val_prob_thresh, known.val_nms_thresh
     args.deterministic = known.deterministic
     args.anchor_compensation = None if known.anchor_compensation is None else (int(known.anchor_compensation[0]), float(known.anchor_compensation[1]))
+    args.assigner, args.atss_topk = known.assigner.replace("-", "_"), known.atss_topk
+    if args.assigner == "atss" and (str(args.traindata) == "synthetic" or getattr(args, "synthetic", False)):
+        parser.error("--assigner atss applies to a WIDER annotation file or to synthetic-faces: the synthetic crops are a throughput workload of the "
+                     "dense-overlap assigner")
     args.ignore_policy = args.ignore = None
     if ignore_on:
         from tinyfaces.datasets.augment import IgnorePolicy
@@ -407,6 +432,16 @@ def ignore_description(args):
     measure = "intersection over the anchor's area" if ig[0] == "iof" else "IoU"
     return (f"ignore regions: {'; '.join(who)} own no positive anchor, and a negative anchor they cover by {measure} >= {ig[1]:g} "
             "gets the don't-care label (on the device; positives and the regression targets do not change)")
+
+
+def assigner_description(args):
+    """The target assigner as the start-up line prints it."""
+    if getattr(args, "assigner", "dense_overlap") != "atss":
+        return ("assigner dense-overlap: positives from the data set's positive IoU threshold plus every face's best anchor, negatives below its negative "
+                "threshold, the band between them ignored (0.7 / 0.3 for WIDER and the synthetic crops; synthetic-faces: 0.7 / 0.7 unless FACES_POS / FACES_NEG say otherwise)")
+    return (f"assigner ATSS: per face the {args.atss_topk} nearest unpadded cells of every template are candidates, positive from the mean plus the "
+            "standard deviation of their IoUs when the anchor centre lies inside the face, the best candidate otherwise; everything else is a "
+            "negative (on the device; the two IoU thresholds only filter crops)")
 
 
 def compensation_description(args):
@@ -505,6 +540,7 @@ def main():
     preprocess = transforms.Compose([transforms.ToTensor(), transforms.Normalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225])])
     train_loader, _ = get_dataloader(args.traindata, args, NUM_TEMPLATES, img_transforms=preprocess, color_jitter=args.color_jitter,
                                      anchor_compensation=args.anchor_compensation,
+                                     **({} if args.assigner == "dense_overlap" else {"assigner": args.assigner, "atss_topk": args.atss_topk}),
                                      **({} if args.ignore_policy is None else {"ignore_policy": args.ignore_policy, "ignore": args.ignore}))
     model = DetectionModel(base_model=getattr(model_zoo, args.base_model), num_objects=1, num_templates=NUM_TEMPLATES).set_compute_dtype(args.dtype)
     model.freeze_batchnorm(args.freeze_bn).set_trainable_layers(args.trainable_layers)
@@ -520,6 +556,7 @@ def main():
     if parallel.rank() == 0:
         print(loss_description(args))
         print(jitter_description(args))
+        print(assigner_description(args))
         print(compensation_description(args))
         print(ignore_description(args))
         if args.deterministic:
@@ -610,6 +647,8 @@ def main():
             snapshot["model_ema"], snapshot["ema"] = ema.state_dict(), ema.settings()
         if args.anchor_compensation is not None:
             snapshot["args"] = {"anchor_compensation": list(args.anchor_compensation)}      # what the targets of this run were matched with
+        if args.assigner == "atss":
+            snapshot.setdefault("args", {}).update(assigner=args.assigner, atss_topk=args.atss_topk)
         if args.ignore_policy is not None:
             snapshot.setdefault("args", {}).update(ignore_policy=dict(args.ignore_policy._asdict()), ignore=list(args.ignore))
         if val_ap is not None:

@@ -14,7 +14,8 @@ from .templates import load_templates
 
 
 def get_dataloader(datapath, args, num_templates=25, template_file="templates.json", img_transforms=None, train=True,
-                   split="train", color_jitter=None, anchor_compensation=None, ignore_policy=None, ignore=None):
+                   split="train", color_jitter=None, anchor_compensation=None, ignore_policy=None, ignore=None,
+                   assigner="dense_overlap", atss_topk=9):
     """datasets/__init__.py:11-52.  `datapath == "synthetic"` (or a path that does not exist with
     args.synthetic set) yields seeded 500x500 crops + random boxes (BASELINE.json configs[2]);
     returns (loader, templates ndarray 25x5) like the reference.
@@ -25,6 +26,9 @@ def get_dataloader(datapath, args, num_templates=25, template_file="templates.js
     ignore_policy (augment.IgnorePolicy) / ignore = (measure, thresh): ignore regions for the training targets of WIDERFace -- flagged, tiny and
     cropped-away faces own no positive, and the negative anchors on them get the don't-care label (ops.dense_overlap_targets(ignore_boxes=));
     None = off, as before.  The synthetic data sets carry no attributes and no crop: asking for a policy there is a ValueError.
+    assigner = "atss" / atss_topk: the training targets of WIDERFace and SyntheticFaces come from the ATSS assigner (ops.atss_targets: per face
+    the atss_topk nearest unpadded cells of every template, positive from mean + std of their IoUs); "dense_overlap" = the reference's
+    thresholds, as before.  anchor_compensation next to "atss" is a ValueError.
 
     Data parallel (one process per GPU, tinyfaces/parallel.py): every rank walks ITS shard of the data -- a
     DistributedSampler for annotation files, a rank-dependent seed for the synthetic crops -- so an epoch is one pass over
@@ -40,7 +44,7 @@ def get_dataloader(datapath, args, num_templates=25, template_file="templates.js
         # batch is split into disjoint rank shards (rotating, see below); evaluation: rank r takes images r, r + world, ...
         length = getattr(args, "synthetic_len", 8)
         ds = SyntheticFaces(templates, length=length, seed=getattr(args, "seed", 0), train=train, img_transforms=img_transforms, color_jitter=color_jitter,
-                            anchor_compensation=anchor_compensation)
+                            anchor_compensation=anchor_compensation, assigner=assigner, atss_topk=atss_topk)
         idx = list(range(rank, length, world)) if world > 1 else None
         if world > 1 and train:
             # the shard of a rank ROTATES with the global batch: a fixed stride would show rank 0 the even layouts only, and the BatchNorm running
@@ -52,6 +56,9 @@ def get_dataloader(datapath, args, num_templates=25, template_file="templates.js
         loader = data.DataLoader(ds, batch_size=args.batch_size, shuffle=False, sampler=idx, num_workers=0, collate_fn=ds.collate)
         return loader, templates
     if str(datapath) == "synthetic" or getattr(args, "synthetic", False):
+        if assigner != "dense_overlap":
+            raise ValueError("get_dataloader: the synthetic crops are a throughput workload of the reference's assigner; assigner applies to WIDER "
+                             "annotation files and to synthetic-faces")
         length = getattr(args, "synthetic_len", 256)
         if train:
             ds = SyntheticCrops(templates, length=max(1, length // world), seed=getattr(args, "seed", 0) * world + rank,
@@ -69,7 +76,8 @@ def get_dataloader(datapath, args, num_templates=25, template_file="templates.js
     from .wider_face import WIDERFace
     ds = WIDERFace(Path(datapath).expanduser(), templates, split=split, img_transforms=img_transforms,
                    dataset_root=Path(getattr(args, "dataset_root", "")).expanduser(), debug=getattr(args, "debug", False), color_jitter=color_jitter,
-                   anchor_compensation=anchor_compensation, ignore_policy=ignore_policy, ignore=ignore)
+                   anchor_compensation=anchor_compensation, ignore_policy=ignore_policy, ignore=ignore,
+                   assigner=assigner, atss_topk=atss_topk)
     # decoding runs in the workers (identity collate there); the device half of a batch -- augmentation + targets -- runs in
     # this process, where the GPU context lives
     # training: equal shards (DistributedSampler pads the last ones with repeated samples when len(ds) % world != 0 -- a handful of

@@ -243,13 +243,19 @@ def process_inputs(image_u8, bboxes, input_size=(500, 500), neg_thresh=0.3, rng=
     return x, bboxes, paste, flip
 
 
-def collate_device(samples, templates_d, seed=0, compensate=None, ignore_boxes=None, ignore=None):
+def collate_device(samples, templates_d, seed=0, compensate=None, ignore_boxes=None, ignore=None, assigner="dense_overlap", atss_topk=ops.ATSS_TOPK):
     """[(x, bboxes, paste_box, flip)] -> (img (B,3,H,W), class_map, regression_map) with the targets assigned on the GPU
     (what WIDERFace.__getitem__ + the default collate yield, wider_face.py:219-222).  compensate = (N, T): scale-compensated matching
     (ops.dense_overlap_targets(compensate=)); None = off.  ignore_boxes: per sample the (K, 4) ignore boxes process_inputs(ignore_out=)
-    collected, ignore = (measure, thresh) (ops.dense_overlap_targets(ignore_boxes=, ignore=)); None = off."""
+    collected, ignore = (measure, thresh) (ops.dense_overlap_targets(ignore_boxes=, ignore=)); None = off.
+    assigner = "atss": the targets come from ops.atss_targets(topk=atss_topk) (no seed, no thresholds; compensate is refused)."""
+    assigner, atss_topk = ops.check_assigner(assigner, atss_topk, compensate)
     xs = torch.stack([s[0] for s in samples])
     extra = {} if ignore_boxes is None else {"ignore_boxes": [np.array(b, dtype=np.float64).reshape(-1, 4) for b in ignore_boxes], "ignore": ignore}
+    if assigner == "atss":
+        cm, rm = ops.atss_targets([s[1] for s in samples], templates_d, paste_boxes=[s[2] for s in samples], flips=[int(s[3]) for s in samples],
+                                  topk=atss_topk, device=xs.device, **extra)
+        return xs, cm, rm
     cm, rm = ops.dense_overlap_targets([s[1] for s in samples], templates_d, paste_boxes=[s[2] for s in samples],
                                        flips=[int(s[3]) for s in samples], seed=seed, device=xs.device,      # boxes are already mirrored; flips mirrors the padding mask
                                        compensate=compensate, **extra)

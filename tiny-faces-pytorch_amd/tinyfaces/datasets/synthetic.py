@@ -36,17 +36,19 @@ def _stack_on_device(tensors, device):
 class CompensationStats:
     """Per-batch counters of the scale-compensated matching, kept on the device until the training loop reads them next to the loss meters
     (DetectionCriterion.flush_meters): pushing enqueues two reductions of the match counts, popping reads the batches the meters have
-    already waited for."""
+    already waited for.  The ATSS assigner (`atss=True`) pushes its match counts into the same object: the counters are then the faces that won
+    at most n = 3 positives and the faces that won none."""
 
-    def __init__(self, n):
-        self.n, self._pending = int(n), []
+    def __init__(self, n, atss=False):
+        self.n, self.atss, self._pending = int(n), bool(atss), []
+        self._below = 1 if atss else self.n
 
     def push(self, match_count):
-        self._pending.append((torch.stack([(match_count <= self.n).sum(), (match_count < self.n).sum()]), int(match_count.numel())))
+        self._pending.append((torch.stack([(match_count <= self.n).sum(), (match_count < self._below).sum()]), int(match_count.numel())))
 
     def pop(self, lag=0):
-        """(faces, faces with at most N positives after the stage, faces still below N) summed over all but the `lag` most recent batches;
-        None when there is none."""
+        """(faces, faces with at most N positives after the stage, faces still below N -- with ATSS: faces without a positive) summed over all
+        but the `lag` most recent batches; None when there is none."""
         n = max(0, len(self._pending) - lag)
         if n == 0:
             return None
@@ -87,22 +89,35 @@ class TargetAssigner:
     """boxes (+ paste box / flip) -> (class_map, regression_map) on the GPU.
     Replaces DataProcessor.get_padding/get_heatmaps (tinyfaces/datasets/processor.py:114-277).
     compensate = (N, T): scale-compensated matching (ops.dense_overlap_targets(compensate=)); `stats` then collects its counters.
-    ignore = (measure, thresh): a call may then pass `ignore_boxes` (ops.dense_overlap_targets(ignore_boxes=)); `ignore_stats` collects the counters."""
+    ignore = (measure, thresh): a call may then pass `ignore_boxes` (ops.dense_overlap_targets(ignore_boxes=)); `ignore_stats` collects the counters.
+    assigner = "atss": the maps come from ops.atss_targets(topk=atss_topk) instead; pos_thresh, neg_thresh, seed and noise are then unused, and
+    `stats` collects the faces that won at most 3 positives and those that won none."""
 
     def __init__(self, templates, heatmap_size=HEATMAP_SIZE, rf=ops.RF, pos_thresh=POS_THRESH, neg_thresh=NEG_THRESH, seed=0, compensate=None,
-                 ignore=None):
+                 ignore=None, assigner="dense_overlap", atss_topk=ops.ATSS_TOPK):
         self.templates, self.heatmap_size, self.rf = templates, heatmap_size, rf
         self.pos_thresh, self.neg_thresh, self.seed, self.calls = pos_thresh, neg_thresh, seed, 0
         self.compensate = ops.check_compensate(compensate, pos_thresh)
+        self.assigner, self.atss_topk = ops.check_assigner(assigner, atss_topk, self.compensate)
         self.stats = None if self.compensate is None else CompensationStats(self.compensate[0])
+        if self.assigner == "atss":
+            self.stats = CompensationStats(3, atss=True)
         self.ignore = ops.check_ignore(ignore)
         self.ignore_stats = None if self.ignore is None else IgnoreStats()
 
     def __call__(self, boxes_per_image, paste_boxes=None, flips=None, device="cuda", noise=None, ignore_boxes=None):
         self.calls += 1
+        if ignore_boxes is not None and self.ignore is None:
+            raise ValueError("TargetAssigner: ignore_boxes needs ignore=(measure, thresh) at construction")
+        if self.assigner == "atss":
+            extra = {} if ignore_boxes is None else dict(ignore_boxes=ignore_boxes, ignore=self.ignore, return_ignored_count=True)
+            out = ops.atss_targets(boxes_per_image, self.templates, self.heatmap_size, self.rf, paste_boxes, flips, topk=self.atss_topk, device=device,
+                                   return_match_count=True, **extra)
+            self.stats.push(out[2])
+            if ignore_boxes is not None:
+                self.ignore_stats.push(out[-1])
+            return out[0], out[1]
         if ignore_boxes is not None:
-            if self.ignore is None:
-                raise ValueError("TargetAssigner: ignore_boxes needs ignore=(measure, thresh) at construction")
             out = ops.dense_overlap_targets(boxes_per_image, self.templates, self.heatmap_size, self.rf, paste_boxes, flips,
                                             noise=noise, seed=self.seed * 1000003 + self.calls, pos_thresh=self.pos_thresh,
                                             neg_thresh=self.neg_thresh, device=device, compensate=self.compensate,
@@ -239,7 +254,7 @@ class SyntheticFaces(data.Dataset):
                           # the 1/4 level of a 500-pixel image raises IndexError: the mask indexes the 16 heat-map columns with the 25 template indices)
 
     def __init__(self, templates, length=8, seed=0, train=True, device="cuda", size=(500, 500), img_transforms=None, color_jitter=None,
-                 anchor_compensation=None):
+                 anchor_compensation=None, assigner="dense_overlap", atss_topk=ops.ATSS_TOPK):
         self.templates, self.length, self.seed, self.train, self.device, self.size = templates, length, seed, train, device, size
         # (b, c, s, h) of torchvision's ColorJitter for the training samples: they then travel as uint8 and `collate` jitters + normalises them on the
         # device (ops.image_prepare(jitter=), chains drawn from np.random per sample); None = off, samples are normalised on the host as before
@@ -248,8 +263,9 @@ class SyntheticFaces(data.Dataset):
         # anchors are positive from IoU 0.7 (like WIDER training, wider_face.py:26) and negative below 0.7 (there: 0.3): with eight layouts the wide "ignored"
         # band of the reference would stay untrained -- its anchors answer with arbitrary scores and unregressed boxes, which an AP at IoU 0.5 counts as misses
         # anchor_compensation = (N, T): every face is topped up to N positive anchors (ops.dense_overlap_targets(compensate=)); None = off
+        # assigner = "atss": the targets come from ops.atss_targets(topk=atss_topk); the two thresholds above are then unused
         self.assigner = TargetAssigner(templates, seed=seed, pos_thresh=float(os.environ.get("FACES_POS", "0.7")), neg_thresh=float(os.environ.get("FACES_NEG", "0.7")),
-                                       compensate=anchor_compensation)
+                                       compensate=anchor_compensation, assigner=assigner, atss_topk=atss_topk)
         self.compensation_stats = self.assigner.stats
         self.rf, self.transforms = ops.RF, img_transforms
         # the layouts (where the faces are) are the fixed part; `samples` = what evaluation sees: every layout on ONE background of its own.

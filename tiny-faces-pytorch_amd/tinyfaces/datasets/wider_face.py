@@ -75,7 +75,10 @@ def parse_annotations(path, split="train"):
 class WIDERFace(dataset.Dataset):
     def __init__(self, path, templates, img_transforms=None, dataset_root="", split="train", input_size=(500, 500),
                  heatmap_size=(63, 63), pos_thresh=0.7, neg_thresh=0.3, pos_fraction=0.5, debug=False, device="cuda", seed=0, color_jitter=None,
-                 anchor_compensation=None, ignore_policy=None, ignore=None):
+                 anchor_compensation=None, ignore_policy=None, ignore=None, assigner="dense_overlap", atss_topk=ops.ATSS_TOPK):
+        """assigner = "atss": the training targets come from ops.atss_targets(topk=atss_topk) (the rule in include/tinyfaces_hip.h) instead of the
+        reference's fixed thresholds.  pos_thresh / neg_thresh are then unused except by the crop filter of the augmentation, which keeps reading
+        neg_thresh; `compensation_stats` collects the faces that won at most 3 positives and those that won none."""
         super().__init__()
         # ignore regions (augment.IgnorePolicy: which faces become don't-care regions instead of positives; ignore = (measure, thresh) of
         # ops.dense_overlap_targets(ignore_boxes=, ignore=), None = ("iof", 0.5)), applied in `collate`; ignore_policy None = off
@@ -94,6 +97,10 @@ class WIDERFace(dataset.Dataset):
         if self.anchor_compensation is not None:
             from .synthetic import CompensationStats
             self.compensation_stats = CompensationStats(self.anchor_compensation[0])
+        self.assigner, self.atss_topk = ops.check_assigner(assigner, atss_topk, self.anchor_compensation)
+        if self.assigner == "atss":
+            from .synthetic import CompensationStats
+            self.compensation_stats = CompensationStats(3, atss=True)
         self.color_jitter = augment.check_color_jitter(color_jitter)      # (b, c, s, h) of torchvision's ColorJitter, applied in `collate`; None = off
         self.split = split
         self.data = parse_annotations(path, split)
@@ -168,7 +175,15 @@ class WIDERFace(dataset.Dataset):
                     ignores.append(np.array(ign, dtype=np.float64).reshape(-1, 4))
                 boxes.append(b); pastes.append(paste); flips.append(int(flip))
             self._step += 1
-            if self.ignore_policy is not None:
+            if self.assigner == "atss":
+                extra = {} if self.ignore_policy is None else dict(ignore_boxes=ignores, ignore=self.ignore, return_ignored_count=True)
+                out = ops.atss_targets(boxes, self.templates, self.heatmap_size, self.rf, paste_boxes=pastes, flips=flips, topk=self.atss_topk,
+                                       device=self.device, return_match_count=True, **extra)
+                cm, rm = out[0], out[1]
+                self.compensation_stats.push(out[2])
+                if self.ignore_policy is not None:
+                    self.ignore_stats.push(out[-1])
+            elif self.ignore_policy is not None:
                 out = ops.dense_overlap_targets(boxes, self.templates, self.heatmap_size, self.rf, paste_boxes=pastes, flips=flips,
                                                 seed=self._step, pos_thresh=self.pos_thresh, neg_thresh=self.neg_thresh, device=self.device,
                                                 compensate=self.anchor_compensation, return_match_count=self.anchor_compensation is not None,

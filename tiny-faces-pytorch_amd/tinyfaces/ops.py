@@ -256,6 +256,117 @@ def dense_overlap_targets_device(boxes_d, offs_d, total_boxes, templates_d, heat
     return res
 
 
+ASSIGNERS = ("dense_overlap", "atss")
+ATSS_TOPK = 9                                             # ATSSAssigner's default
+
+
+def check_assigner(assigner, atss_topk=ATSS_TOPK, compensate=None):
+    """assigner "dense_overlap" (the reference's fixed thresholds) or "atss" (include/tinyfaces_hip.h, "ATSS"); atss_topk an integer in 1..16,
+    the candidates per template and face.  compensate next to "atss" is refused: the compensation stage is defined on the perturbed-IoU owner
+    of dense_overlap's first stage, which ATSS does not compute.  Returns (str assigner, int atss_topk); anything else raises ValueError."""
+    if not isinstance(assigner, str) or assigner not in ASSIGNERS:
+        raise ValueError(f"assigner must be one of {list(ASSIGNERS)}, not {assigner!r}")
+    if isinstance(atss_topk, bool) or not isinstance(atss_topk, (int, np.integer)) or not 1 <= int(atss_topk) <= 16:
+        raise ValueError(f"atss_topk must be an integer in 1..16, not {atss_topk!r}")
+    if assigner == "atss" and compensate is not None:
+        raise ValueError("assigner='atss' does not take compensate / anchor_compensation: the compensation stage tops up the owner that the "
+                         "dense_overlap assignment computes; ATSS already gives every face a comparable number of positives")
+    return assigner, int(atss_topk)
+
+
+def _launch_atss(total, boxes_d, offs_d, B, t_d, vsy, vsx, rf, paste_d, flips_d, k, cls, reg, device, return_match_count):
+    """tf_targets_atss on resident operands.  Returns the match-count tensor (total,) int32, or None."""
+    ofy, ofx = rf["offset"]
+    sty, stx = rf["stride"]
+    nt, tstride = t_d.shape
+    mc = torch.empty(total, dtype=torch.int32, device=device) if return_match_count else None
+    wsb = lib().tf_targets_atss_workspace_bytes(total, B, nt, vsy, vsx)
+    ws = _workspace("targets_atss", wsb, device)
+    check(lib().tf_targets_atss(ptr(boxes_d), ptr(offs_d), B, ptr(t_d), nt, tstride, vsy, vsx, ofy, ofx, sty, stx, ptr(paste_d), ptr(flips_d),
+                                k, ptr(mc) if total else None, ptr(cls), ptr(reg), ptr(ws), wsb, stream()), "tf_targets_atss")
+    return mc
+
+
+def atss_targets(boxes_per_image, templates, heatmap_size=(63, 63), rf=RF, paste_boxes=None, flips=None, topk=ATSS_TOPK, device=None,
+                 return_match_count=False, ignore_boxes=None, ignore=None, return_ignored_count=False):
+    """ATSS target assignment (tf_targets_atss; the rule is in include/tinyfaces_hip.h): per face the `topk` unpadded cells of every template
+    nearest to its centre are candidates, positive from mean + std of their IoUs when the anchor centre lies inside the face, the best
+    candidate when there is none; an anchor two faces claim goes to the larger IoU.  No thresholds, no noise, no seed.
+    The operands and the two maps are those of dense_overlap_targets: class_map (B,nt,vsy,vsx) f32 in {-1, +1} (0 only through ignore_boxes),
+    regression_map (B,4nt,vsy,vsx) f32, zero away from the positives.
+    return_match_count: also the (total_valid_boxes,) int32 device tensor of anchors each face won.
+    ignore_boxes / ignore / return_ignored_count: the ignore pass behind the call, as in dense_overlap_targets; passing the faces themselves with
+    ignore=("iou", t) makes a grey band of near-miss negatives around them."""
+    _, k = check_assigner("atss", topk)
+    ign = check_ignore(ignore)
+    if return_ignored_count and ignore_boxes is None:
+        raise ValueError("return_ignored_count needs ignore_boxes")
+    if ignore_boxes is not None:
+        ign = ign or IGNORE_DEFAULT
+        if len(ignore_boxes) != len(boxes_per_image):
+            raise ValueError(f"atss_targets: {len(ignore_boxes)} lists of ignore boxes for {len(boxes_per_image)} images")
+    device = torch.device(device if device is not None else "cuda")
+    if device.type != "cuda":
+        raise RuntimeError("atss_targets: HIP kernel only (no CPU fallback)")
+    B = len(boxes_per_image)
+    vsy, vsx = heatmap_size
+    t_d = torch.as_tensor(np.asarray(templates.cpu() if torch.is_tensor(templates) else templates), dtype=torch.float64).contiguous().to(device)
+    nt = t_d.shape[0]
+    kept, offs = _valid_boxes(boxes_per_image)
+    total = offs[-1]
+    boxes_d = (torch.cat(kept) if total else torch.zeros(1, 4, dtype=torch.float64)).contiguous().to(device)
+    offs_d = torch.tensor(offs, dtype=torch.int32, device=device)
+    paste_d = None if paste_boxes is None else torch.as_tensor(np.asarray(paste_boxes), dtype=torch.int32).reshape(B, 4).to(device)
+    flips_d = None if flips is None else torch.as_tensor(np.asarray(flips), dtype=torch.int32).reshape(B).to(device)
+    cls = torch.empty(B, nt, vsy, vsx, dtype=torch.float32, device=device)
+    reg = torch.empty(B, 4 * nt, vsy, vsx, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        mc = _launch_atss(total, boxes_d, offs_d, B, t_d, vsy, vsx, rf, paste_d, flips_d, k, cls, reg, device, return_match_count)
+        if ignore_boxes is not None:
+            ikept, ioffs = _valid_boxes(ignore_boxes)
+            ign_d = (torch.cat(ikept) if ioffs[-1] else torch.zeros(1, 4, dtype=torch.float64)).contiguous().to(device)
+            ic = _launch_ignore(cls, t_d, rf, ign_d, torch.tensor(ioffs, dtype=torch.int32, device=device), ioffs[-1], ign, return_ignored_count)
+    out = (cls, reg)
+    if return_match_count:
+        out += (mc,)
+    if return_ignored_count:
+        out += (ic,)
+    return out
+
+
+def atss_targets_device(boxes_d, offs_d, total_boxes, templates_d, heatmap_size=(63, 63), rf=RF, paste_d=None, flips_d=None, topk=ATSS_TOPK,
+                        out=None, return_match_count=False, ignore_d=None, ignore_offs_d=None, total_ignore=0, ignore=None,
+                        return_ignored_count=False):
+    """Same kernels as atss_targets with every operand already resident in HBM, as dense_overlap_targets_device takes them:
+    boxes_d (total,4) f64 (degenerate boxes removed), offs_d (B+1,) i32, templates_d (nt,5) f64, paste_d (B,4) i32, flips_d (B,) i32;
+    out = (class_map, regression_map) to write into; ignore_d / ignore_offs_d / total_ignore / ignore / return_ignored_count as there."""
+    _, k = check_assigner("atss", topk)
+    ign = check_ignore(ignore)
+    if return_ignored_count and ignore_d is None:
+        raise ValueError("return_ignored_count needs ignore_d / ignore_offs_d")
+    if ignore_d is not None:
+        ign = ign or IGNORE_DEFAULT
+        if ignore_offs_d is None or ignore_offs_d.numel() != offs_d.numel():
+            raise ValueError("atss_targets_device: ignore_offs_d is an int32 (B + 1,) device tensor next to ignore_d")
+    require_gpu(boxes_d, "atss_targets_device")
+    B = offs_d.numel() - 1
+    vsy, vsx = heatmap_size
+    nt = templates_d.shape[0]
+    dev = boxes_d.device
+    if out is None:
+        out = (torch.empty(B, nt, vsy, vsx, dtype=torch.float32, device=dev), torch.empty(B, 4 * nt, vsy, vsx, dtype=torch.float32, device=dev))
+    cls, reg = out
+    mc = _launch_atss(int(total_boxes), boxes_d, offs_d, B, templates_d, vsy, vsx, rf, paste_d, flips_d, k, cls, reg, dev, return_match_count)
+    res = (cls, reg)
+    if return_match_count:
+        res += (mc,)
+    if ignore_d is not None:
+        ic = _launch_ignore(cls, templates_d, rf, ignore_d, ignore_offs_d, int(total_ignore), ign, return_ignored_count)
+        if return_ignored_count:
+            res += (ic,)
+    return res
+
+
 def dense_overlap_iou(boxes, templates, heatmap_size=(63, 63), rf=RF, device="cuda"):
     """Raw rounded IoU tensor (vsy,vsx,nt,G) f64 of compute_dense_overlap (dense_overlap.py:4-75); test hook."""
     vsy, vsx = heatmap_size

@@ -29,6 +29,9 @@ def print_compensation(idx, epoch, size, dataloader, lag=0):
     got = stats.pop(lag)
     if got is not None:
         faces, at_most, below = got
+        if getattr(stats, "atss", False):                 # the ATSS assigner pushes its match counts into the same object
+            print(f"Epoch: [{epoch}][{idx}/{size}]\tATSS: {at_most} of {faces} faces won at most {stats.n} positives, {below} of them none")
+            return
         print(f"Epoch: [{epoch}][{idx}/{size}]\tanchor compensation: {at_most} of {faces} faces hold at most N = {stats.n} positives after the stage, "
               f"{below} of them fewer (their candidates ran out)")
 
