@@ -449,6 +449,39 @@ int tf_criterion_focal_box_fwd_bwd(const float* output, const float* class_map, 
                                    float* grad_out, double* loss_out /*[2]*/, int32_t* npos_out /*[B], may be NULL*/,
                                    void* ws, size_t ws_bytes, void* stream);
 
+/* ---- detection criterion, quality focal form (QFL; Li et al. 2020, Generalized Focal Loss): IoU-aware classification targets ----
+ * The focal form with the hard target 1 of a positive replaced by the quality q of ITS OWN predicted box: same operands, same layout, the
+ * same three launches, normaliser, summation order and determinism as tf_criterion_focal_box_fwd_bwd.  There is no alpha.  For an element
+ * with label y, class logit s, p = (px, py, pw, ph) from channel blocks 1..4 of output and t = (tx, ty, tw, th) from reg_map:
+ *   y =  0   contributes nothing; all five gradient channels are 0
+ *   y = -1   q = 0
+ *   y = +1   q = min(1, IoU), the IoU of the overlap-loss section above: pw, ph clamped to [-C, C], C = log(1000 / 16), the targets not
+ *            clamped, no epsilon, fp32 from the centre offset and the half sizes (u = e^pw / 2, v = e^tw / 2, dx = px - tx:
+ *            iw = max(0, min(2u, 2v, u + v - |dx|)), ih likewise, I = iw ih, U = 4 u u' + 4 v v' - I, IoU = I (1 / U)).  A positive whose
+ *            boxes do not meet has q = 0 and its class logit is trained exactly like a negative's
+ *   sigma = sigmoid(s), d = sigma - q, BCE = softplus(s) - q s, softplus(v) = max(v, 0) + log1p(exp(-|v|)), with e = exp(-|s|):
+ *            sigma = 1 / (1 + e) for s >= 0 and e / (1 + e) otherwise, sigma (1 - sigma) = e / (1 + e)^2: finite for s = +-1e4
+ *   QFL      = |d|^beta BCE
+ *   dQFL/ds  = |d|^beta d + beta |d|^(beta - 1) sgn(d) sigma (1 - sigma) BCE,  sgn(0) = 0;  beta = 2 is d d and 2 d, without powf; any other
+ *            beta takes one powf, |d|^beta = |d|^(beta - 1) |d|
+ * q is a CONSTANT of the classification term: nothing flows from it into the four regression channels.  The regression term of a positive
+ * and its gradient are those of reg_form (TF_REG_*), by the arithmetic of tf_criterion_focal_box_fwd_bwd; with TF_REG_SMOOTH_L1 the IoU is
+ * computed for q alone.  normalize as in the focal form: both sums and all five gradient channels of image b times 1 / max(1, npos_b), the
+ * images summed.  beta must be finite and >= 1: below 1 the gradient is unbounded at sigma = q.  For 1 <= beta < 2 it is ill-conditioned
+ * where sigma is close to q (the factor |d|^(beta - 1) has an unbounded slope there), and for beta = 1 it jumps at sigma = q.
+ * loss_out[0] = sum cls, loss_out[1] = sum reg (unweighted), both normalised; loss_out[2] = sum of q over all positives of the batch, NOT
+ * normalised; loss_out[3] = sum_b npos_b as a double: [2] / [3] is the mean IoU of the predicted boxes with their targets.
+ * grad_out is written completely, every element exactly once (no memset needed).  No floating-point atomics: the same bits on every run.
+ * The workspace is one double per block larger than tf_criterion_focal_workspace_bytes.
+ * TF_ERR_ARG: a NULL operand, a non-positive dimension, beta not finite or < 1, reg_weight not finite, an unknown normalize or reg_form,
+ * TF_REG_DIOU without template_wh; TF_ERR_WORKSPACE: ws NULL or too small.  Nothing is enqueued in either case. */
+size_t tf_criterion_quality_workspace_bytes(int B, int nt, int H, int W);
+int tf_criterion_quality_fwd_bwd(const float* output, const float* class_map, const float* reg_map, int B, int nt, int H, int W,
+                                 float beta, int normalize, float reg_weight,
+                                 int reg_form, const float* template_wh /*[nt][2], device; may be NULL unless TF_REG_DIOU*/,
+                                 float* grad_out, double* loss_out /*[4]*/, int32_t* npos_out /*[B], may be NULL*/,
+                                 void* ws, size_t ws_bytes, void* stream);
+
 /* ---- fused SGD step (momentum, weight decay) over a flat fp32 segment ---------------
  * Replaces torch.optim.SGD.step as configured at main.py:67-70 for one parameter group. */
 int tf_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n,

@@ -20,6 +20,7 @@
 #   soft-nms                   cost of Soft-NMS: kernels vs the hard NMS at 65 536 candidates, pyramid plain / linear / gaussian, parity (scripts/soft_nms_numbers.py) -> $SOFT_NMS_OUT (default profiles/soft_nms.jsonl)
 #   topk                       cost of the pre-NMS top-k and the detection cap: select + NMS vs the full NMS at 65 536 / 600 000 candidates, Soft-NMS capped vs uncapped, pyramid plain / soft / soft + both bounds (scripts/topk_numbers.py) -> $TOPK_OUT (default profiles/topk.jsonl)
 #   color-jitter               cost of the colour jitter: image_prepare plain / three ops / four ops / contrast alone on the 500x500 window, batch building with / without it (scripts/color_jitter_numbers.py) -> $COLOR_JITTER_OUT (default profiles/color_jitter.jsonl)
+#   quality-loss               cost of the quality focal loss: the qfl call next to the focal call of the same reg_loss on the step's operands, the bf16 step with either (scripts/quality_loss_numbers.py) -> $QUALITY_LOSS_OUT (default profiles/quality_loss.jsonl)
 #   dist-smoke                 RCCL 1-rank group, 2 gloo ranks on one GPU, 2 nccl ranks on one GPU (expected refusal) -> gpurun_out/dist_smoke.txt
 #   final                      tests + bench + prof + pmc-traffic + layer-table + timeline + eval prof + smoke: the artefacts of a round
 set -u
@@ -109,6 +110,11 @@ print(d['value'], d['ms_per_step'], 'frac', r.get('frac'), 'fwd', r.get('forward
     timeout -k 10 ${COLOR_JITTER_TIMEOUT:-300} python scripts/color_jitter_numbers.py --step kernels > "$out" 2> "$err" &&
       timeout -k 10 ${COLOR_JITTER_TIMEOUT:-300} python scripts/color_jitter_numbers.py --step batch >> "$out" 2>> "$err"
     echo "color-jitter exit $?"; cat "$out"; tail -3 "$err" ;;
+  quality-loss)   # one process and one time limit per step; the second step only behind a clean first one
+    out=${QUALITY_LOSS_OUT:-$R/profiles/quality_loss.jsonl}; err=${out%.jsonl}.err
+    timeout -k 10 ${QUALITY_LOSS_TIMEOUT:-300} python scripts/quality_loss_numbers.py --step calls > "$out" 2> "$err" &&
+      timeout -k 10 ${QUALITY_LOSS_TIMEOUT:-300} python scripts/quality_loss_numbers.py --step steps >> "$out" 2>> "$err"
+    echo "quality-loss exit $?"; cat "$out"; tail -3 "$err" ;;
   dist-smoke) bash scripts/gpu_dist_smoke.sh ;;
   final)
     # the profile passes FIRST: bench.py quotes the committed kernel-stats / PMC files, so they are refreshed in the box's copy of profiles/
@@ -122,5 +128,5 @@ print(d['value'], d['ms_per_step'], 'frac', r.get('frac'), 'fwd', r.get('forward
     bash "$0" layer-table; bash "$0" timeline; bash "$0" prof eval; bash "$0" eval-table
     python scripts/gridbar.py 2>&1 | grep -v amdgpu.ids > "$R/gpurun_out/gridbar.txt"; tail -5 "$R/gpurun_out/gridbar.txt"
     timeout 200 python __graft_entry__.py smoke 2>&1 | tail -2 ;;
-  *) sed -n 2,23p "$0" ;;
+  *) sed -n 2,24p "$0" ;;
 esac

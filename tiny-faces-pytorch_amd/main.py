@@ -118,8 +118,14 @@ FOCAL_HELP = ("--cls-loss {soft-margin,focal}: classification loss of the criter
               "before the images are summed, none leaves the plain sum, default pos")
 
 
+QFL_HELP = ("--cls-loss qfl: quality focal loss (Li et al. 2020, Generalized Focal Loss; the classification loss of SCRFD) over every labelled "
+            "anchor: a positive's score is trained towards the IoU of its own predicted box with its target, a negative's towards 0, on the device; "
+            "no OHEM and no 256-sample draw, --focal-gamma and --focal-alpha are unused, --focal-normalize keeps its meaning, every --reg-loss goes "
+            "with it; --qfl-beta B: its exponent, finite, B >= 1, default 2 (below 2 the gradient is ill-conditioned where the score meets its target)")
+
+
 BOX_LOSS_HELP = ("--reg-loss {smooth-l1,iou,giou,diou}: regression loss of the criterion; iou / giou / diou (Rezatofighi et al. 2019, Zheng et al. 2020) "
-                 "put one box-overlap term per positive anchor in place of the four SmoothL1 terms and need --cls-loss focal (the soft-margin pass "
+                 "put one box-overlap term per positive anchor in place of the four SmoothL1 terms and need --cls-loss focal or qfl (the soft-margin pass "
                  "keeps the reference's SmoothL1), default smooth-l1; --reg-weight W: weight of the regression loss in the total, finite, W >= 0, "
                  "default 1 (an overlap loss is bounded by 2 per anchor and is normally weighted up)")
 
@@ -283,6 +289,13 @@ def _focal_alpha(text):
     return value
 
 
+def _qfl_beta(text):
+    value = float(text)
+    if not (math.isfinite(value) and value >= 1.0):
+        raise argparse.ArgumentTypeError(f"must be a finite number >= 1, got {text}")
+    return value
+
+
 def _accum_steps(text):
     value = int(text)
     if value < 1:
@@ -306,7 +319,7 @@ def _positive_float(text):
 
 
 def arguments(argv=None):
-    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP, JITTER_HELP, VAL_HELP, DETERMINISTIC_HELP, COMPENSATION_HELP, IGNORE_HELP)))
+    parser = argparse.ArgumentParser(epilog="; ".join((TRUNK_HELP, FREEZE_HELP, TRAINABLE_HELP, CLIP_HELP, SKIP_HELP, EMA_HELP, ACCUM_HELP, ACCUM_AVERAGE_HELP, FOCAL_HELP, QFL_HELP, BOX_LOSS_HELP, OPTIMIZER_HELP, WARMUP_HELP, JITTER_HELP, VAL_HELP, DETERMINISTIC_HELP, COMPENSATION_HELP, IGNORE_HELP)))
     for name, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         parser.add_argument(name, **kw)
     return parser.parse_args(argv)
@@ -315,7 +328,7 @@ def arguments(argv=None):
 def trunk_arguments(argv=None):
     """`arguments` plus `base_model` from --base-model, `freeze_bn` from --freeze-bn, `trainable_layers` from --trainable-layers, `clip_grad_norm`
     from --clip-grad-norm, `skip_nonfinite` from --skip-nonfinite, `model_ema` from --model-ema, `accum_steps` from --accum-steps and `accum_average`
-    from --accum-average, `cls_loss` ("soft_margin" | "focal") from --cls-loss, `focal_gamma`, `focal_alpha` and `focal_normalize` from
+    from --accum-average, `cls_loss` ("soft_margin" | "focal" | "qfl") from --cls-loss, `qfl_beta` from --qfl-beta, `focal_gamma`, `focal_alpha` and `focal_normalize` from
     --focal-gamma, --focal-alpha and --focal-normalize, `reg_loss` ("smooth_l1" | "iou" | "giou" | "diou") from --reg-loss and `reg_weight` from
     --reg-weight, `optimizer` ("sgd" | "adamw"), `adam_beta1`, `adam_beta2` and `adam_eps` from --optimizer, --adam-beta1, --adam-beta2 and --adam-eps,
     `warmup_iters` and `warmup_factor` from --warmup-iters and --warmup-factor, `color_jitter` (None or the four amplitudes) from --color-jitter,
@@ -333,7 +346,8 @@ def trunk_arguments(argv=None):
     parser.add_argument("--model-ema", dest="model_ema", default=None, type=_ema_decay, metavar="DECAY", help=EMA_HELP)
     parser.add_argument("--accum-steps", dest="accum_steps", default=1, type=_accum_steps, metavar="N", help=ACCUM_HELP)
     parser.add_argument("--accum-average", dest="accum_average", action="store_true", help=ACCUM_AVERAGE_HELP)
-    parser.add_argument("--cls-loss", dest="cls_loss", default="soft-margin", choices=["soft-margin", "focal"], help=FOCAL_HELP)
+    parser.add_argument("--cls-loss", dest="cls_loss", default="soft-margin", choices=["soft-margin", "focal", "qfl"], help=FOCAL_HELP)
+    parser.add_argument("--qfl-beta", dest="qfl_beta", default=2.0, type=_qfl_beta, metavar="B", help=QFL_HELP)
     parser.add_argument("--focal-gamma", dest="focal_gamma", default=2.0, type=_focal_gamma, metavar="G", help=FOCAL_HELP)
     parser.add_argument("--focal-alpha", dest="focal_alpha", default=0.25, type=_focal_alpha, metavar="A", help=FOCAL_HELP)
     parser.add_argument("--focal-normalize", dest="focal_normalize", default="pos", choices=["pos", "none"], help=FOCAL_HELP)
@@ -382,8 +396,8 @@ def trunk_arguments(argv=None):
         parser.error(f"--color-jitter: the hue amplitude H must be <= 0.5, got {known.color_jitter[3]:g}")
     if known.trainable_layers < 4 and not known.freeze_bn:
         parser.error(f"--trainable-layers {known.trainable_layers} freezes stages of the trunk, which is defined on frozen BatchNorm only: add --freeze-bn")
-    if known.reg_loss != "smooth-l1" and known.cls_loss != "focal":
-        parser.error(f"--reg-loss {known.reg_loss} needs --cls-loss focal: the soft-margin pass keeps the reference's SmoothL1")
+    if known.reg_loss != "smooth-l1" and known.cls_loss not in ("focal", "qfl"):
+        parser.error(f"--reg-loss {known.reg_loss} needs --cls-loss focal or qfl: the soft-margin pass keeps the reference's SmoothL1")
     args = arguments(rest)
     args.base_model = known.base_model
     args.freeze_bn = known.freeze_bn
@@ -394,6 +408,7 @@ def trunk_arguments(argv=None):
     args.accum_steps = known.accum_steps
     args.accum_average = known.accum_average
     args.cls_loss = known.cls_loss.replace("-", "_")
+    args.qfl_beta = known.qfl_beta
     args.focal_gamma = known.focal_gamma
     args.focal_alpha = known.focal_alpha
     args.focal_normalize = known.focal_normalize
@@ -467,6 +482,10 @@ def loss_description(args):
     reg = {"smooth_l1": "SmoothL1 on the four offsets", "iou": "IoU, one term per positive", "giou": "GIoU, one term per positive",
            "diou": "DIoU, one term per positive"}[reg_loss]
     reg = f"; regression loss {reg}, weight {reg_weight:g}"
+    if args.cls_loss == "qfl":
+        norm = "per image by its positives" if args.focal_normalize == "pos" else "not normalised"
+        return (f"classification loss quality focal (beta {getattr(args, 'qfl_beta', 2.0):g}, IoU of the predicted box as the target; {norm}; every labelled "
+                "anchor, every positive regresses)") + reg
     if args.cls_loss != "focal":
         return f"classification loss soft-margin (OHEM threshold {args.ohem_thresh:g}, 128 + 128 samples per image)" + reg
     alpha = f"alpha {args.focal_alpha:g}" if args.focal_alpha >= 0 else "no alpha weighting"
@@ -504,6 +523,7 @@ def run_fused_epoch(engine, loss_fn, loader, epoch, device, base_lr, warmup=None
         if parallel.rank() == 0:
             loss_fn.flush_meters(lag=0 if idx + 1 == total else 1)      # one step behind: the host prepares batch idx + 1 while the GPU runs step idx
             trainer.print_state(idx, epoch, total, loss_fn.class_average.average, loss_fn.reg_average.average)
+            trainer.print_quality(idx, epoch, total, loss_fn)                                            # (nothing unless --cls-loss qfl)
             trainer.print_compensation(idx, epoch, total, loader, lag=0 if idx + 1 == total else 1)      # (nothing unless --anchor-compensation)
             trainer.print_ignore(idx, epoch, total, loader, lag=0 if idx + 1 == total else 1)            # (nothing unless an --ignore-* policy)
 
@@ -551,7 +571,8 @@ def main():
               f"{args.accum_steps} x world {parallel.world_size()}" + (", gradients averaged over the window" if args.accum_average and args.accum_steps > 1 else ""))
     loss_fn = DetectionCriterion(NUM_TEMPLATES, reg_weight=args.reg_weight, seed=args.seed * parallel.world_size() + parallel.rank(), lazy_meters=True,
                                  cls_loss=args.cls_loss, focal_gamma=args.focal_gamma, focal_alpha=args.focal_alpha, focal_normalize=args.focal_normalize,
-                                 reg_loss=args.reg_loss, templates=load_templates(NUM_TEMPLATES) if args.reg_loss == "diou" else None)
+                                 reg_loss=args.reg_loss, templates=load_templates(NUM_TEMPLATES) if args.reg_loss == "diou" else None,
+                                 **({"qfl_beta": args.qfl_beta} if args.cls_loss == "qfl" else {}))
     loss_fn.ohem_thresh = args.ohem_thresh
     if parallel.rank() == 0:
         print(loss_description(args))
@@ -561,8 +582,8 @@ def main():
         print(ignore_description(args))
         if args.deterministic:
             print(deterministic_description())
-        if args.cls_loss == "focal":
-            print("--ohem-thresh is unused with --cls-loss focal: nothing is mined or sampled")
+        if args.cls_loss in ("focal", "qfl"):
+            print(f"--ohem-thresh is unused with --cls-loss {args.cls_loss}: nothing is mined or sampled")
 
     first_epoch = args.start_epoch
     state = None
@@ -649,6 +670,9 @@ def main():
             snapshot["args"] = {"anchor_compensation": list(args.anchor_compensation)}      # what the targets of this run were matched with
         if args.assigner == "atss":
             snapshot.setdefault("args", {}).update(assigner=args.assigner, atss_topk=args.atss_topk)
+        if args.cls_loss == "qfl":
+            snapshot.setdefault("args", {}).update(cls_loss=args.cls_loss, qfl_beta=args.qfl_beta, focal_normalize=args.focal_normalize,
+                                                   reg_loss=args.reg_loss, reg_weight=args.reg_weight)
         if args.ignore_policy is not None:
             snapshot.setdefault("args", {}).update(ignore_policy=dict(args.ignore_policy._asdict()), ignore=list(args.ignore))
         if val_ap is not None:

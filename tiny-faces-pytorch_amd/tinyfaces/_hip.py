@@ -140,6 +140,8 @@ _SIGNATURES = {
     "tf_criterion_focal_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "tf_criterion_focal_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, f32, vp, vp, vp, vp, sz, vp]),
     "tf_criterion_focal_box_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, f32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "tf_criterion_quality_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "tf_criterion_quality_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, f32, i32, vp, vp, vp, vp, vp, sz, vp]),
     "tf_image_prepare": (i32, [C.POINTER(ImagePrepareArgs), vp]),
     "tf_image_prepare_jitter_workspace_bytes": (sz, [i32, i32, i32, C.POINTER(i32)]),
     "tf_image_prepare_jitter": (i32, [C.POINTER(ImagePrepareArgs), i32, C.POINTER(i32), C.POINTER(f32), vp, sz, vp]),

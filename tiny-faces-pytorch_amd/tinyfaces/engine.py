@@ -739,8 +739,9 @@ class TrainEngine:
             ops.set_deterministic(prev)
 
     def _step(self, x, class_map, regression_map, apply=None):
-        """x (B,3,H,W) f32, class_map (B,nt,h,w) f32 (mined in place by the soft-margin criterion; only read with cls_loss="focal"), regression_map (B,4nt,h,w) f32: all on the device.
-        Returns the device tensor [sum cls loss, sum reg loss] (float64) without synchronising.
+        """x (B,3,H,W) f32, class_map (B,nt,h,w) f32 (mined in place by the soft-margin criterion; only read with cls_loss="focal" / "qfl"), regression_map (B,4nt,h,w) f32: all on the device.
+        Returns the device tensor [sum cls loss, sum reg loss] (float64) without synchronising; with cls_loss="qfl" it has two more elements,
+        [..., sum of the quality targets q over the positives, number of positives] (whatever the criterion's _fwd_bwd returns goes to its meters).
         The step follows the model's BatchNorm mode (DetectionModel.freeze_batchnorm): frozen, the forward and backward run the folded-BN
         graph, and the update skips the BatchNorm vectors (no weight decay, no momentum: their momentum buffers stay zero) and, with
         DetectionModel.set_trainable_layers(k < 4), the conv weights of the frozen stages; the bucket plan of the gradient exchange stays

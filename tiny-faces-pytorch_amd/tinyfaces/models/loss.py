@@ -3,7 +3,8 @@ one fused HIP pass (csrc/criterion.hip): OHEM, balance sampling, masked SoftMarg
 and d(total)/d(output), with no device->host->device round trip (loss.py:47-57 does one per step).
 `cls_loss="focal"` is the one addition to that surface: sigmoid focal loss over every labelled anchor, no mining and no sampling, by the
 focal form of the same pass (tf_criterion_focal_fwd_bwd); `reg_loss="iou" | "giou" | "diou"` gives that form an overlap regression loss, one
-term per positive in place of the four SmoothL1 terms (tf_criterion_focal_box_fwd_bwd)."""
+term per positive in place of the four SmoothL1 terms (tf_criterion_focal_box_fwd_bwd).  `cls_loss="qfl"` is the quality focal form of that pass
+(tf_criterion_quality_fwd_bwd): a positive's logit is trained towards the IoU of its own predicted box with its target."""
 import torch
 from torch import nn
 
@@ -63,23 +64,35 @@ class DetectionCriterion(nn.Module):
     template-normalised frame, predicted log sizes clamped to +-log(1000 / 16); include/tinyfaces_hip.h has the definition.  One term per
     positive, so `reg_average` receives a sum bounded by 2 per positive: `reg_weight` is normally raised with it.  `templates`: the (nt, 4 or 5)
     table of tinyfaces/datasets/templates.py, required for "diou" (its centre distance needs every template's aspect ratio).  It is held as a plain
-    tensor and moved to the output's device on first use, not as a registered buffer: the criterion stays a module without state."""
+    tensor and moved to the output's device on first use, not as a registered buffer: the criterion stays a module without state.
 
-    CLS_LOSSES = ("soft_margin", "focal")
+    `cls_loss="qfl"`: quality focal loss (Li et al. 2020, Generalized Focal Loss; the classification loss of SCRFD) with exponent `qfl_beta`
+    over EVERY labelled anchor: with sigma = sigmoid(logit), QFL = |sigma - q|^beta (softplus(logit) - q logit), q = 0 for a negative and
+    q = min(1, IoU) of the positive's OWN predicted box with its target (the IoU of the overlap losses above, computed in the same pass; q is a
+    constant: nothing flows from it into the regression channels), so the score says "face, and this well localised".  Every `reg_loss` goes
+    with it; no OHEM and no sampling, as with focal; `focal_gamma` and `focal_alpha` are unused, `focal_normalize` keeps its meaning.
+    `qfl_beta` must be finite and >= 1; for 1 <= beta < 2 the gradient is ill-conditioned where sigma is close to q, and for beta = 1 it
+    jumps at sigma = q.  The loss vector then has four elements, [cls, reg, sum of q over the positives, number of positives], and
+    `quality_average` (a third AvgMeter, fed with the last two) is the mean IoU of the predicted boxes of all positives seen with their targets."""
+
+    CLS_LOSSES = ("soft_margin", "focal", "qfl")
     REG_LOSSES = ("smooth_l1", "iou", "giou", "diou")
 
     def __init__(self, n_templates=25, reg_weight=1, pos_fraction=0.5, seed=0, lazy_meters=False, keep_labels=False,
-                 cls_loss="soft_margin", focal_gamma=2.0, focal_alpha=0.25, focal_normalize="pos", reg_loss="smooth_l1", templates=None):
+                 cls_loss="soft_margin", focal_gamma=2.0, focal_alpha=0.25, focal_normalize="pos", reg_loss="smooth_l1", templates=None,
+                 qfl_beta=2.0):
         super().__init__()
         if cls_loss not in self.CLS_LOSSES:
             raise ValueError(f"DetectionCriterion: cls_loss must be one of {self.CLS_LOSSES}, got {cls_loss!r}")
         ops.check_focal(focal_gamma, focal_alpha, focal_normalize)
+        ops.check_qfl(qfl_beta, focal_normalize)
         self._template_wh = None if templates is None else ops.template_wh(templates)
         ops.check_reg_loss(reg_loss, reg_weight, self._template_wh, n_templates)
         self._check_reg_with_cls(reg_loss, cls_loss)
         self.reg_loss = reg_loss
         self.cls_loss = cls_loss
         self.focal_gamma, self.focal_alpha, self.focal_normalize = float(focal_gamma), float(focal_alpha), focal_normalize
+        self.qfl_beta = float(qfl_beta)
         self.n_templates = n_templates
         self.reg_weight = reg_weight
         self.pos_fraction = pos_fraction
@@ -89,6 +102,7 @@ class DetectionCriterion(nn.Module):
         self.ohem_thresh = 0.03                                            # loss.py:62
         self.class_average = AvgMeter()
         self.reg_average = AvgMeter()
+        self.quality_average = AvgMeter()                                  # cls_loss="qfl" only: the mean IoU of the positives' predicted boxes
         self.masked_class_loss = None
         self.masked_reg_loss = None
         self.total_loss = None
@@ -113,15 +127,24 @@ class DetectionCriterion(nn.Module):
         each image, (B, nt*H*W) uint8 -- replays the reference's np.random.permutation draws."""
         if self.cls_loss == "focal":
             raise RuntimeError("DetectionCriterion.inject_sampling: cls_loss='focal' samples nothing (every labelled anchor contributes)")
+        if self.cls_loss == "qfl":
+            raise RuntimeError("DetectionCriterion.inject_sampling: cls_loss='qfl' samples nothing (every labelled anchor contributes)")
         self._pos_keep, self._neg_keep = pos_keep, neg_keep
 
     def _fwd_bwd(self, out, class_map, regression_map, want_labels=False):
         """The fused loss + gradient pass of this criterion's `cls_loss`, for the autograd function above and for TrainEngine.step:
         (loss[2] f64 device tensor, d(total)/d(out), labels that entered the loss).  soft_margin mines `class_map` in place and returns
-        the sampled labels if `want_labels`, else None; focal only reads `class_map`, which IS the labels that entered."""
+        the sampled labels if `want_labels`, else None; focal and qfl only read `class_map`, which IS the labels that entered.  With qfl the
+        loss tensor has four elements: [cls, reg, sum of q over the positives, number of positives]."""
         if self.reg_loss != "smooth_l1":
             ops.check_reg_loss(self.reg_loss, self.reg_weight, self._template_wh, self.n_templates)
             self._check_reg_with_cls(self.reg_loss, self.cls_loss)
+        if self.cls_loss == "qfl":
+            if self._template_wh is not None and self._template_wh.device != out.device:
+                self._template_wh = self._template_wh.to(out.device)
+            loss4, grad, _ = ops.criterion_quality_fwd_bwd(out, class_map, regression_map, self.n_templates, self.reg_weight, self.qfl_beta,
+                                                           self.focal_normalize, self.reg_loss, self._template_wh)
+            return loss4, grad, class_map
         if self.cls_loss == "focal" and self.reg_loss != "smooth_l1":
             if self._template_wh is not None and self._template_wh.device != out.device:
                 self._template_wh = self._template_wh.to(out.device)
@@ -144,9 +167,16 @@ class DetectionCriterion(nn.Module):
         n = max(0, len(self._pending) - lag)
         for loss2, size in self._pending[:n]:
             v = loss2.tolist()
-            self.class_average.update(v[0], size)
-            self.reg_average.update(v[1], size)
+            self._update_meters(v, size)
         self._pending = self._pending[n:]
+
+    def _update_meters(self, v, size):
+        """v: the host copy of one step's loss vector.  Elements 2 and 3 (qfl only) are the sum of q over the step's positives and their
+        number: `quality_average` is the mean IoU over all positives seen; a step without a positive leaves it alone."""
+        self.class_average.update(v[0], size)
+        self.reg_average.update(v[1], size)
+        if len(v) >= 4 and v[3] > 0:
+            self.quality_average.update(v[2], int(v[3]))
 
     def forward(self, output, class_map, regression_map):
         if not output.is_cuda:
@@ -160,11 +190,10 @@ class DetectionCriterion(nn.Module):
         if self.lazy_meters:
             self._pending.append((loss2, output.size(0)))
         else:
-            v = loss2.tolist()                                             # one sync instead of two (loss.py:90-91)
-            self.class_average.update(v[0], output.size(0))
-            self.reg_average.update(v[1], output.size(0))
+            self._update_meters(loss2.tolist(), output.size(0))            # one sync instead of two (loss.py:90-91)
         return total
 
     def reset(self):
         self.class_average.reset()
         self.reg_average.reset()
+        self.quality_average.reset()

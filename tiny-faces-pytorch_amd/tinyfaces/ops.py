@@ -1030,6 +1030,52 @@ def criterion_focal_box_fwd_bwd(output, class_map, regression_map, n_templates=2
     return loss, grad, npos
 
 
+def check_qfl(beta, normalize):
+    """ValueError unless beta is finite and >= 1 and normalize one of FOCAL_NORMALIZE.  (For 1 <= beta < 2 the gradient is ill-conditioned where
+    sigmoid(s) is close to the quality target, and for beta = 1 it jumps there: include/tinyfaces_hip.h.)"""
+    if not (isinstance(beta, (int, float, np.floating, np.integer)) and np.isfinite(beta) and beta >= 1):
+        raise ValueError(f"quality focal loss: beta must be a finite number >= 1, got {beta}")
+    if normalize not in FOCAL_NORMALIZE:
+        raise ValueError(f"quality focal loss: normalize must be one of {sorted(FOCAL_NORMALIZE)}, got {normalize!r}")
+
+
+def criterion_quality_fwd_bwd(output, class_map, regression_map, n_templates=25, reg_weight=1.0, beta=2.0, normalize="pos",
+                              reg_loss="smooth_l1", template_wh=None, grad=None):
+    """Quality focal loss (Li et al. 2020) over every labelled element + the regression loss `reg_loss` over every positive, loss and
+    d(total)/d(output) in one device pass (tf_criterion_quality_fwd_bwd): the class logit of a positive is trained towards q = min(1, IoU) of
+    its own predicted box with its target, that of a negative towards 0, QFL = |sigmoid(s) - q|^beta (softplus(s) - q s); q is a constant of
+    the classification term (include/tinyfaces_hip.h has the definition).  normalize, reg_loss and template_wh as in
+    criterion_focal_box_fwd_bwd; class_map is only read.
+    Returns (loss[4] f64 device tensor = [sum cls, sum reg, sum of q over the positives (not normalised), number of positives], grad wrt output,
+    npos[B] int32): loss[2] / loss[3] is the mean IoU of the predicted boxes of the positives with their targets.
+    grad: write the gradient into this contiguous fp32 tensor of output's shape (every element is written exactly once, no memset needed)."""
+    require_gpu(output, "criterion_quality")
+    check_qfl(beta, normalize)
+    check_reg_loss(reg_loss, reg_weight, template_wh, n_templates)
+    assert output.dtype == torch.float32 and class_map.dtype == torch.float32 and regression_map.dtype == torch.float32
+    output, regression_map = output.contiguous(), regression_map.contiguous()
+    assert class_map.is_contiguous()
+    B, C5, H, W = output.shape
+    nt = n_templates
+    assert C5 == 5 * nt and class_map.shape == (B, nt, H, W) and regression_map.shape == (B, 4 * nt, H, W)
+    dev = output.device
+    twh = None
+    if reg_loss == "diou":
+        twh = template_wh.to(device=dev, dtype=torch.float32).contiguous()
+    if grad is None:
+        grad = torch.empty_like(output)
+    assert grad.shape == output.shape and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == dev
+    loss = torch.empty(4, dtype=torch.float64, device=dev)
+    npos = torch.empty(B, dtype=torch.int32, device=dev)
+    wsb = lib().tf_criterion_quality_workspace_bytes(B, nt, H, W)
+    ws = _workspace("criterion_quality", wsb, dev)
+    with torch.cuda.device(dev):
+        check(lib().tf_criterion_quality_fwd_bwd(ptr(output), ptr(class_map), ptr(regression_map), B, nt, H, W, float(beta),
+                                                 FOCAL_NORMALIZE[normalize], float(reg_weight), REG_LOSSES[reg_loss], ptr(twh),
+                                                 ptr(grad), ptr(loss), ptr(npos), ptr(ws), wsb, stream()), "tf_criterion_quality_fwd_bwd")
+    return loss, grad, npos
+
+
 # --------------------------------------------------------------------------- SGD
 NMS_MAX_BOXES = 524160                                   # csrc/nms.hip: (n/64 + 2) 8-byte words must fit 64 KiB of LDS
 IMAGE_MEAN, IMAGE_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)        # main.py:44-46

@@ -19,6 +19,16 @@ def print_state(idx, epoch, size, loss_cls, loss_reg):
     print(head + _LOSS_FMT.format(loss_cls, loss_reg))
 
 
+def print_quality(idx, epoch, size, loss_fn):
+    """One line per logged interval when the criterion trains with the quality focal loss (`cls_loss="qfl"`): the mean IoU of the predicted boxes
+    of all positives seen so far with their targets (DetectionCriterion.quality_average), the quantity the scores are trained towards.  The
+    meter is fed by the loss meters' own host read, so nothing waits here.  With the other losses, or before a positive was seen: nothing."""
+    meter = getattr(loss_fn, "quality_average", None)
+    if getattr(loss_fn, "cls_loss", None) != "qfl" or meter is None or meter.num_averaged == 0:
+        return
+    print(f"Epoch: [{epoch}][{idx}/{size}]\tmean IoU of positives {meter.average:.4f} ({meter.num_averaged} positives)")
+
+
 def print_compensation(idx, epoch, size, dataloader, lag=0):
     """One line per logged interval when the loader's data set runs the scale-compensated matching (`compensation_stats`, datasets/synthetic.py):
     how many faces of the batches read so far the stage looked after.  The counters sit on the device behind the targets of their batch, which
@@ -148,6 +158,7 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
                 if flush is not None:
                     flush()
                 print_state(step, epoch, n_batches, loss_fn.class_average.average, loss_fn.reg_average.average)
+                print_quality(step, epoch, n_batches, loss_fn)
                 print_compensation(step, epoch, n_batches, dataloader)
                 print_ignore(step, epoch, n_batches, dataloader)
             elif getattr(loss_fn, "_pending", None):
