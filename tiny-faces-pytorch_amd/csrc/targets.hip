@@ -14,19 +14,11 @@
 // and best perturbed IoU, then
 //   D  per anchor: count the positives each GT owns (integer atomics, one per wave and owner)
 //   E  per GT, one workgroup: promote its N - count best candidates, one block arg-max per promotion
-#include "common.h"
+// Shared with csrc/targets_ignore.hip and csrc/targets_atss.hip through csrc/targets_shared.h: the anchor geometry (anchor_at, its single
+// definition), the image lookup (image_of) and the operand block of the two entry points (TgtParams, base_params).
+#include "targets_shared.h"
 
 namespace {
-
-struct TgtParams {
-  const double* boxes; const int32_t* box_off; const double* tpl; int nt, tstride;
-  int vsy, vsx, ofy, ofx, sty, stx;
-  const int32_t* paste; const int32_t* flips;
-  const double* noise; const int64_t* noise_off; uint64_t seed;
-  double pos_thresh, neg_thresh;
-  float* cls; float* reg;
-  unsigned long long* gmax; unsigned int* gidx;
-};
 
 // IoU of anchor (template t at cell y,x) with box g, rounded to 14 decimals: dense_overlap.py:32-75
 __device__ __forceinline__ double iou14(double x1, double y1, double x2, double y2, double farea,
@@ -84,11 +76,8 @@ __global__ void __launch_bounds__(256) targets_kernel(P p) {
   const int g0 = p.box_off[b], G = p.box_off[b + 1] - g0;
   const double* tp = p.tpl + (size_t)t * p.tstride;
   const double dx1 = tp[0], dy1 = tp[1], dx2 = tp[2], dy2 = tp[3];
-  const double cx = (double)p.ofx + (double)x * ((double)p.stx / 1.0);   // dense_overlap.py:50
-  const double cy = (double)p.ofy + (double)y * ((double)p.sty / 1.0);
-  const double ax1 = dx1 + cx, ay1 = dy1 + cy, ax2 = dx2 + cx, ay2 = dy2 + cy;
-  const double fh = dy2 - dy1 + 1.0, fw = dx2 - dx1 + 1.0;
-  const double farea = fw * fh;
+  const Anchor an = anchor_at(dx1, dy1, dx2, dy2, p.ofy, p.ofx, p.sty, p.stx, y, x);
+  const double fw = an.fw, fh = an.fh;
 
   double best = -1.0; int bestg = 0;
   for (int g = 0; g < G; ++g) {
@@ -96,7 +85,7 @@ __global__ void __launch_bounds__(256) targets_kernel(P p) {
     const double gx1 = bx[0], gy1 = bx[1], gx2 = bx[2], gy2 = bx[3];
     double v = -1.0;
     if (active) {
-      double r = iou14(ax1, ay1, ax2, ay2, farea, gx1, gy1, gx2, gy2);
+      double r = iou14(an.x1, an.y1, an.x2, an.y2, an.farea, gx1, gy1, gx2, gy2);
       v = r + 1e-6 * noise_at(p, b, flat, g, G);                      // processor.py:195
       if (v > best) { best = v; bestg = g; }                          // first arg-max (:197)
     }
@@ -146,9 +135,7 @@ __global__ void targets_best_anchor_kernel(TgtParams p, int total) {
   int gi = blockIdx.x * blockDim.x + threadIdx.x;
   if (gi >= total) return;
   if (__longlong_as_double((long long)p.gmax[gi]) > p.neg_thresh) {     // :255
-    // which image owns box gi
-    int b = 0;
-    while (p.box_off[b + 1] <= gi) ++b;
+    const int b = image_of(p.box_off, gi);
     unsigned int flat = p.gidx[gi];
     int t = flat % p.nt, cell = flat / p.nt;
     int y = cell / p.vsx, x = cell - y * p.vsx;
@@ -202,8 +189,7 @@ __global__ void __launch_bounds__(256) targets_select_kernel(TgtCompParams p, in
     if (threadIdx.x == 0 && p.match_count) p.match_count[gi] = cnt;
     return;
   }
-  int b = 0;
-  while (p.box_off[b + 1] <= gi) ++b;
+  const int b = image_of(p.box_off, gi);
   const int g = gi - p.box_off[b];
   const double* bx = p.boxes + 4 * (size_t)gi;
   const double gx1 = bx[0], gy1 = bx[1], gx2 = bx[2], gy2 = bx[3];
@@ -280,6 +266,8 @@ __global__ void iou_dump_kernel(const double* boxes, int G, const double* tpl, i
   if (flat >= vsy * vsx * nt) return;
   int t = flat % nt, cell = flat / nt, y = cell / vsx, x = cell % vsx;
   const double* tp = tpl + (size_t)t * tstride;
+  // anchor_at's geometry written out by hand: `out` may alias `tpl`, so the compiler re-reads the template row behind every store; anchor_at
+  // takes the row by value, which hoists those loads and changes the code of this test hook.  tests/test_gpu_targets.py pins it against numpy.
   double cx = (double)ofx + (double)x * ((double)stx / 1.0), cy = (double)ofy + (double)y * ((double)sty / 1.0);
   double fh = tp[3] - tp[1] + 1.0, fw = tp[2] - tp[0] + 1.0;
   for (int g = 0; g < G; ++g)
@@ -303,16 +291,12 @@ extern "C" int tf_dense_overlap_targets(const double* boxes, const int32_t* box_
                                         float* class_map, float* reg_map,
                                         void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (B <= 0 || nt <= 0 || vsy <= 0 || vsx <= 0 || !box_offsets || !templates || !class_map || !reg_map) return TF_ERR_ARG;
-  if (noise && !noise_offsets) return TF_ERR_ARG;
+  TgtParams p;
+  if (int rc = base_params(p, boxes, box_offsets, B, templates, nt, tstride, vsy, vsx, ofy, ofx, sty, stx, paste_boxes, flips, noise, noise_offsets,
+                           seed, pos_thresh, neg_thresh, class_map, reg_map)) return rc;
   // total boxes is only known on device; the caller sizes ws from its host copy.
   size_t nslots = (ws_bytes - 64) / 12;
   if (!ws || ws_bytes < 76) return TF_ERR_WORKSPACE;
-  TgtParams p;
-  p.boxes = boxes; p.box_off = box_offsets; p.tpl = templates; p.nt = nt; p.tstride = tstride;
-  p.vsy = vsy; p.vsx = vsx; p.ofy = ofy; p.ofx = ofx; p.sty = sty; p.stx = stx;
-  p.paste = paste_boxes; p.flips = flips; p.noise = noise; p.noise_off = noise_offsets; p.seed = seed;
-  p.pos_thresh = pos_thresh; p.neg_thresh = neg_thresh; p.cls = class_map; p.reg = reg_map;
   p.gmax = (unsigned long long*)ws;
   p.gidx = (unsigned int*)((char*)ws + nslots * 8);
   if (hipMemsetAsync(p.gmax, 0, nslots * 8, stream) != hipSuccess) return TF_ERR_LAUNCH;
@@ -344,8 +328,9 @@ extern "C" int tf_dense_overlap_targets_comp(const double* boxes, const int32_t*
                                              float* class_map, float* reg_map,
                                              void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (B <= 0 || nt <= 0 || vsy <= 0 || vsx <= 0 || !box_offsets || !templates || !class_map || !reg_map) return TF_ERR_ARG;
-  if (noise && !noise_offsets) return TF_ERR_ARG;
+  TgtCompParams p;
+  if (int rc = base_params(p, boxes, box_offsets, B, templates, nt, tstride, vsy, vsx, ofy, ofx, sty, stx, paste_boxes, flips, noise, noise_offsets,
+                           seed, pos_thresh, neg_thresh, class_map, reg_map)) return rc;
   if (sty <= 0 || stx <= 0) return TF_ERR_ARG;                       // the window of phase E divides by the stride
   if (N < 1 || N > 64) return TF_ERR_ARG;
   if (!(T >= 0.01) || !(T < pos_thresh) || !(T - T == 0.0)) return TF_ERR_ARG;       // (T - T: NaN for an infinite T)
@@ -356,11 +341,6 @@ extern "C" int tf_dense_overlap_targets_comp(const double* boxes, const int32_t*
   if (!ws || ws_bytes < tf_targets_comp_workspace_bytes(1, B, nt, vsy, vsx)) return TF_ERR_WORKSPACE;
   size_t nslots = (ws_bytes - 64 - anchors * 12) / 16;
   if (nslots > ((size_t)1 << 30)) nslots = (size_t)1 << 30;
-  TgtCompParams p;
-  p.boxes = boxes; p.box_off = box_offsets; p.tpl = templates; p.nt = nt; p.tstride = tstride;
-  p.vsy = vsy; p.vsx = vsx; p.ofy = ofy; p.ofx = ofx; p.sty = sty; p.stx = stx;
-  p.paste = paste_boxes; p.flips = flips; p.noise = noise; p.noise_off = noise_offsets; p.seed = seed;
-  p.pos_thresh = pos_thresh; p.neg_thresh = neg_thresh; p.cls = class_map; p.reg = reg_map;
   char* w = (char*)ws;
   p.gmax = (unsigned long long*)w;                 w += nslots * 8;
   p.best = (double*)w;                             w += anchors * 8;

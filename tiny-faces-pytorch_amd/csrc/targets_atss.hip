@@ -1,7 +1,8 @@
 // ATSS target assignment (the rule: include/tinyfaces_hip.h, "ATSS"; numpy restatement: tests/atss_ref.py).  Every face takes the k unpadded
 // cells of every template nearest to its centre as candidates, thresholds their IoUs at mean + std, keeps the passing ones whose anchor centre
 // lies strictly inside it (or, having none, its best candidate), and an anchor several faces claim goes to the larger IoU, then the lower face.
-// A file of its own so that csrc/targets.hip stays what it is, instruction for instruction.
+// The anchor whose IoU a candidate gets is anchor_at of csrc/targets_shared.h, the single definition csrc/targets.hip and
+// csrc/targets_ignore.hip use too; image_of comes from there as well.  Everything else -- candidates, statistics, claims -- is this file's own.
 // Compiled with -ffp-contract=off (build.py EXACT): every f64 op must round exactly like numpy's.
 //
 // Four stream-ordered launches, no memset:
@@ -23,7 +24,7 @@
 // cells), one column and one row more than needed, which holds both columns of such a pair (there is at most one pair per axis at the
 // window's edge), and ranks the cells of that window by counting through LDS, at most two cells per thread, with the rule's own key
 // (distance, then cell index).
-#include "common.h"
+#include "targets_shared.h"
 
 namespace {
 
@@ -78,12 +79,6 @@ __device__ __forceinline__ int nearest_window(int of, int st, int lo, int hi, in
   while (c0 > lo && sqdist(of, st, c0 - 1, d1, d2, fc) <= sqdist(of, st, c0 + w - 1, d1, d2, fc)) --c0;
   while (c0 + w <= hi && sqdist(of, st, c0 + w, d1, d2, fc) < sqdist(of, st, c0, d1, d2, fc)) ++c0;
   return c0;
-}
-
-__device__ __forceinline__ int image_of(const int32_t* box_off, int gi) {
-  int b = 0;
-  while (box_off[b + 1] <= gi) ++b;
-  return b;
 }
 
 __global__ void __launch_bounds__(kThreads) atss_init_kernel(AtssParams p) {
@@ -154,16 +149,12 @@ __global__ void __launch_bounds__(kThreads) atss_claim_kernel(AtssParams p) {
       }
       if (rank < nt_k) {
         const int y = cell / p.vsx, x = cell - y * p.vsx;
-        const double cx = (double)p.ofx + (double)x * ((double)p.stx / 1.0);   // targets_kernel's anchor and dense_overlap's operation order
-        const double cy = (double)p.ofy + (double)y * ((double)p.sty / 1.0);
-        const double ax1 = dx1 + cx, ay1 = dy1 + cy, ax2 = dx2 + cx, ay2 = dy2 + cy;
-        const double fh = dy2 - dy1 + 1.0, fw = dx2 - dx1 + 1.0;
-        const double farea = fw * fh;
-        const double iw = fmin(ax2, gx2) - fmax(ax1, gx1) + 1.0, ih = fmin(ay2, gy2) - fmax(ay1, gy1) + 1.0;
+        const Anchor an = anchor_at(dx1, dy1, dx2, dy2, p.ofy, p.ofx, p.sty, p.stx, y, x);
+        const double iw = fmin(an.x2, gx2) - fmax(an.x1, gx1) + 1.0, ih = fmin(an.y2, gy2) - fmax(an.y1, gy1) + 1.0;
         double v = 0.0;
         if (ih > 0.0 && iw > 0.0) {
           const double ia = iw * ih;
-          v = ia / (farea + barea - ia);
+          v = ia / (an.farea + barea - ia);
         }
         cv[n + rank] = (unsigned long long)__double_as_longlong(v);
         ci[n + rank] = t * cells + cell;

@@ -1,7 +1,8 @@
 // Ignore regions of the training targets (the rule: include/tinyfaces_hip.h, "ignore regions"; numpy restatement: tests/ignore_ref.py).
 // One pass behind tf_dense_overlap_targets[_comp] over the [B][nt][vsy][vsx] float class map, in place: a NEGATIVE anchor (label -1) that
 // an ignore box of its image covers by at least `thresh` gets the don't-care label 0.  Labels +1 and 0 are never touched, the regression
-// map is not an operand.  A file of its own so that csrc/targets.hip stays what it is, instruction for instruction.
+// map is not an operand.  The anchor it tests is anchor_at of csrc/targets_shared.h, the single definition csrc/targets.hip and
+// csrc/targets_atss.hip use too, so an anchor has the same corners and area in all three files; the rest of the pass is this file's own.
 // Compiled with -ffp-contract=off (build.py EXACT): every f64 op must round exactly like numpy's.
 //
 // One thread per (t, y, x) anchor, x fastest, 256 per block, grid (ceil(nt * cells / 256), B): targets_kernel's own geometry, so the map is
@@ -10,7 +11,7 @@
 // bounded by LDS; inside a tile every lane reads the same LDS word (a broadcast).  A lane whose label is not -1 only takes part in the
 // barriers; a lane stops testing at its first covering box.  `changed[b]` (optional) adds the labels turned: ballot + popcount, one integer
 // atomic per wave that turned any.  No floating-point atomic, no grid barrier, no host synchronisation: the same bits on every run.
-#include "common.h"
+#include "targets_shared.h"
 
 namespace {
 
@@ -35,11 +36,7 @@ __global__ void __launch_bounds__(kThreads) targets_ignore_kernel(float* __restr
   const int y = cell / vsx, x = cell - y * vsx;
   const double* tp = tpl + (size_t)t * tstride;
   const double dx1 = tp[0], dy1 = tp[1], dx2 = tp[2], dy2 = tp[3];
-  const double cx = (double)ofx + (double)x * ((double)stx / 1.0);     // targets_kernel's anchor
-  const double cy = (double)ofy + (double)y * ((double)sty / 1.0);
-  const double ax1 = dx1 + cx, ay1 = dy1 + cy, ax2 = dx2 + cx, ay2 = dy2 + cy;
-  const double fh = dy2 - dy1 + 1.0, fw = dx2 - dx1 + 1.0;
-  const double farea = fw * fh;
+  const Anchor an = anchor_at(dx1, dy1, dx2, dy2, ofy, ofx, sty, stx, y, x);
   float* label = cls + (size_t)b * nt * cells + idx;
   const bool negative = active && *label == -1.f;
 
@@ -56,11 +53,11 @@ __global__ void __launch_bounds__(kThreads) targets_ignore_kernel(float* __restr
     __syncthreads();
     if (negative && !covered) {
       for (int j = 0; j < m; ++j) {
-        const double iw = fmin(ax2, rx2[j]) - fmax(ax1, rx1[j]) + 1.0;
-        const double ih = fmin(ay2, ry2[j]) - fmax(ay1, ry1[j]) + 1.0;
+        const double iw = fmin(an.x2, rx2[j]) - fmax(an.x1, rx1[j]) + 1.0;
+        const double ih = fmin(an.y2, ry2[j]) - fmax(an.y1, ry1[j]) + 1.0;
         if (iw > 0.0 && ih > 0.0) {
           const double ia = iw * ih;
-          const double ov = MEASURE == TF_IGNORE_IOF ? ia / farea : ia / (farea + ra[j] - ia);
+          const double ov = MEASURE == TF_IGNORE_IOF ? ia / an.farea : ia / (an.farea + ra[j] - ia);
           if (ov >= thresh) { covered = true; break; }
         }
       }

@@ -9,7 +9,8 @@ import numpy as np
 import torch
 from torch.utils import data
 
-from .synthetic import SyntheticCrops, SyntheticFaces, TargetAssigner  # noqa: F401
+from .synthetic import SyntheticCrops, SyntheticFaces  # noqa: F401
+from .targets import CompensationStats, IgnoreStats, TargetAssigner  # noqa: F401
 from .templates import load_templates
 
 

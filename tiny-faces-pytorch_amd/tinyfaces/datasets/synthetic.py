@@ -1,5 +1,5 @@
-"""Synthetic 500x500 crops + random boxes (BASELINE.json configs[2]) and
-the device-side target assigner that replaces DataProcessor.get_heatmaps in the loader."""
+"""Synthetic 500x500 crops + random boxes (BASELINE.json configs[2]).  Their targets come from the
+device-side assigner of datasets/targets.py, re-exported here."""
 import os
 
 import numpy as np
@@ -7,10 +7,9 @@ import torch
 from torch.utils import data
 
 from .. import ops
+from .targets import HEATMAP_SIZE, NEG_THRESH, POS_THRESH, CompensationStats, IgnoreStats, TargetAssigner  # noqa: F401  (re-exported)
 
 INPUT_SIZE = (500, 500)          # tinyfaces/datasets/wider_face.py:24
-HEATMAP_SIZE = (63, 63)          # :25
-POS_THRESH, NEG_THRESH = 0.7, 0.3   # :26-27
 
 
 def random_boxes(rng, size=500):
@@ -32,110 +31,6 @@ def _stack_on_device(tensors, device):
     for i, t in enumerate(tensors):
         out[i].copy_(t)                  # (blocking: the pageable source of a sample may be freed or reused as soon as collate returns)
     return out
-
-class CompensationStats:
-    """Per-batch counters of the scale-compensated matching, kept on the device until the training loop reads them next to the loss meters
-    (DetectionCriterion.flush_meters): pushing enqueues two reductions of the match counts, popping reads the batches the meters have
-    already waited for.  The ATSS assigner (`atss=True`) pushes its match counts into the same object: the counters are then the faces that won
-    at most n = 3 positives and the faces that won none."""
-
-    def __init__(self, n, atss=False):
-        self.n, self.atss, self._pending = int(n), bool(atss), []
-        self._below = 1 if atss else self.n
-
-    def push(self, match_count):
-        self._pending.append((torch.stack([(match_count <= self.n).sum(), (match_count < self._below).sum()]), int(match_count.numel())))
-
-    def pop(self, lag=0):
-        """(faces, faces with at most N positives after the stage, faces still below N -- with ATSS: faces without a positive) summed over all
-        but the `lag` most recent batches; None when there is none."""
-        n = max(0, len(self._pending) - lag)
-        if n == 0:
-            return None
-        faces = at_most = below = 0
-        for counts, total in self._pending[:n]:
-            a, b = counts.tolist()
-            faces, at_most, below = faces + total, at_most + a, below + b
-        self._pending = self._pending[n:]
-        return faces, at_most, below
-
-
-class IgnoreStats:
-    """Per-batch counters of the ignore regions (ops.dense_overlap_targets(return_ignored_count=True)), kept on the device like
-    CompensationStats: pushing enqueues two reductions of the per-image counts of labels turned, popping reads the batches the loss meters
-    have already waited for."""
-
-    def __init__(self):
-        self._pending = []
-
-    def push(self, ignored_count):
-        self._pending.append((torch.stack([ignored_count.sum(), (ignored_count > 0).sum()]), int(ignored_count.numel())))
-
-    def pop(self, lag=0):
-        """(images, anchors turned from negative to ignored, images with any) summed over all but the `lag` most recent batches; None when
-        there is none."""
-        n = max(0, len(self._pending) - lag)
-        if n == 0:
-            return None
-        images = turned = with_any = 0
-        for counts, total in self._pending[:n]:
-            a, b = counts.tolist()
-            images, turned, with_any = images + total, turned + a, with_any + b
-        self._pending = self._pending[n:]
-        return images, turned, with_any
-
-
-class TargetAssigner:
-    """boxes (+ paste box / flip) -> (class_map, regression_map) on the GPU.
-    Replaces DataProcessor.get_padding/get_heatmaps (tinyfaces/datasets/processor.py:114-277).
-    compensate = (N, T): scale-compensated matching (ops.dense_overlap_targets(compensate=)); `stats` then collects its counters.
-    ignore = (measure, thresh): a call may then pass `ignore_boxes` (ops.dense_overlap_targets(ignore_boxes=)); `ignore_stats` collects the counters.
-    assigner = "atss": the maps come from ops.atss_targets(topk=atss_topk) instead; pos_thresh, neg_thresh, seed and noise are then unused, and
-    `stats` collects the faces that won at most 3 positives and those that won none."""
-
-    def __init__(self, templates, heatmap_size=HEATMAP_SIZE, rf=ops.RF, pos_thresh=POS_THRESH, neg_thresh=NEG_THRESH, seed=0, compensate=None,
-                 ignore=None, assigner="dense_overlap", atss_topk=ops.ATSS_TOPK):
-        self.templates, self.heatmap_size, self.rf = templates, heatmap_size, rf
-        self.pos_thresh, self.neg_thresh, self.seed, self.calls = pos_thresh, neg_thresh, seed, 0
-        self.compensate = ops.check_compensate(compensate, pos_thresh)
-        self.assigner, self.atss_topk = ops.check_assigner(assigner, atss_topk, self.compensate)
-        self.stats = None if self.compensate is None else CompensationStats(self.compensate[0])
-        if self.assigner == "atss":
-            self.stats = CompensationStats(3, atss=True)
-        self.ignore = ops.check_ignore(ignore)
-        self.ignore_stats = None if self.ignore is None else IgnoreStats()
-
-    def __call__(self, boxes_per_image, paste_boxes=None, flips=None, device="cuda", noise=None, ignore_boxes=None):
-        self.calls += 1
-        if ignore_boxes is not None and self.ignore is None:
-            raise ValueError("TargetAssigner: ignore_boxes needs ignore=(measure, thresh) at construction")
-        if self.assigner == "atss":
-            extra = {} if ignore_boxes is None else dict(ignore_boxes=ignore_boxes, ignore=self.ignore, return_ignored_count=True)
-            out = ops.atss_targets(boxes_per_image, self.templates, self.heatmap_size, self.rf, paste_boxes, flips, topk=self.atss_topk, device=device,
-                                   return_match_count=True, **extra)
-            self.stats.push(out[2])
-            if ignore_boxes is not None:
-                self.ignore_stats.push(out[-1])
-            return out[0], out[1]
-        if ignore_boxes is not None:
-            out = ops.dense_overlap_targets(boxes_per_image, self.templates, self.heatmap_size, self.rf, paste_boxes, flips,
-                                            noise=noise, seed=self.seed * 1000003 + self.calls, pos_thresh=self.pos_thresh,
-                                            neg_thresh=self.neg_thresh, device=device, compensate=self.compensate,
-                                            return_match_count=self.compensate is not None, ignore_boxes=ignore_boxes, ignore=self.ignore,
-                                            return_ignored_count=True)
-            if self.compensate is not None:
-                self.stats.push(out[2])
-            self.ignore_stats.push(out[-1])
-            return out[0], out[1]
-        if self.compensate is None:
-            return ops.dense_overlap_targets(boxes_per_image, self.templates, self.heatmap_size, self.rf, paste_boxes, flips,
-                                             noise=noise, seed=self.seed * 1000003 + self.calls, pos_thresh=self.pos_thresh,
-                                             neg_thresh=self.neg_thresh, device=device)
-        cm, rm, mc = ops.dense_overlap_targets(boxes_per_image, self.templates, self.heatmap_size, self.rf, paste_boxes, flips,
-                                               noise=noise, seed=self.seed * 1000003 + self.calls, pos_thresh=self.pos_thresh,
-                                               neg_thresh=self.neg_thresh, device=device, compensate=self.compensate, return_match_count=True)
-        self.stats.push(mc)
-        return cm, rm
 
 
 class SyntheticCrops(data.Dataset):

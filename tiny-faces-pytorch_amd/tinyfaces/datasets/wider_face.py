@@ -23,6 +23,7 @@ from torch.utils.data import dataset
 
 from .. import ops, transforms
 from . import augment
+from .targets import TargetAssigner
 
 RF = {"size": [859, 859], "stride": [8, 8], "offset": [-1, -1]}      # wider_face.py:53-55
 
@@ -83,24 +84,18 @@ class WIDERFace(dataset.Dataset):
         # ignore regions (augment.IgnorePolicy: which faces become don't-care regions instead of positives; ignore = (measure, thresh) of
         # ops.dense_overlap_targets(ignore_boxes=, ignore=), None = ("iof", 0.5)), applied in `collate`; ignore_policy None = off
         self.ignore_policy = augment.check_ignore_policy(ignore_policy)
-        self.ignore = ops.check_ignore(ignore)
-        if self.ignore is not None and self.ignore_policy is None:
+        ignore = ops.check_ignore(ignore)
+        if ignore is not None and self.ignore_policy is None:
             raise ValueError("WIDERFace: ignore=(measure, thresh) needs an ignore_policy")
-        self.ignore_stats = None
         if self.ignore_policy is not None:
-            from .synthetic import IgnoreStats
-            self.ignore = self.ignore or ops.IGNORE_DEFAULT
-            self.ignore_stats = IgnoreStats()
-        # (N, T) of the scale-compensated matching (ops.dense_overlap_targets(compensate=)), applied in `collate`; None = off
-        self.anchor_compensation = ops.check_compensate(anchor_compensation, pos_thresh)
-        self.compensation_stats = None
-        if self.anchor_compensation is not None:
-            from .synthetic import CompensationStats
-            self.compensation_stats = CompensationStats(self.anchor_compensation[0])
-        self.assigner, self.atss_topk = ops.check_assigner(assigner, atss_topk, self.anchor_compensation)
-        if self.assigner == "atss":
-            from .synthetic import CompensationStats
-            self.compensation_stats = CompensationStats(3, atss=True)
+            ignore = ignore or ops.IGNORE_DEFAULT
+        # the one assigner object of `collate` (datasets/targets.py) owns the thresholds, anchor_compensation = (N, T) of the scale-compensated
+        # matching (None = off), the ignore pair, the assigner and atss_topk, and the counters that go with them
+        self._targets = TargetAssigner(templates, heatmap_size, RF, pos_thresh, neg_thresh, compensate=anchor_compensation, ignore=ignore,
+                                       assigner=assigner, atss_topk=atss_topk)
+        self.ignore, self.ignore_stats = self._targets.ignore, self._targets.ignore_stats
+        self.anchor_compensation, self.compensation_stats = self._targets.compensate, self._targets.stats
+        self.assigner, self.atss_topk = self._targets.assigner, self._targets.atss_topk
         self.color_jitter = augment.check_color_jitter(color_jitter)      # (b, c, s, h) of torchvision's ColorJitter, applied in `collate`; None = off
         self.split = split
         self.data = parse_annotations(path, split)
@@ -175,31 +170,8 @@ class WIDERFace(dataset.Dataset):
                     ignores.append(np.array(ign, dtype=np.float64).reshape(-1, 4))
                 boxes.append(b); pastes.append(paste); flips.append(int(flip))
             self._step += 1
-            if self.assigner == "atss":
-                extra = {} if self.ignore_policy is None else dict(ignore_boxes=ignores, ignore=self.ignore, return_ignored_count=True)
-                out = ops.atss_targets(boxes, self.templates, self.heatmap_size, self.rf, paste_boxes=pastes, flips=flips, topk=self.atss_topk,
-                                       device=self.device, return_match_count=True, **extra)
-                cm, rm = out[0], out[1]
-                self.compensation_stats.push(out[2])
-                if self.ignore_policy is not None:
-                    self.ignore_stats.push(out[-1])
-            elif self.ignore_policy is not None:
-                out = ops.dense_overlap_targets(boxes, self.templates, self.heatmap_size, self.rf, paste_boxes=pastes, flips=flips,
-                                                seed=self._step, pos_thresh=self.pos_thresh, neg_thresh=self.neg_thresh, device=self.device,
-                                                compensate=self.anchor_compensation, return_match_count=self.anchor_compensation is not None,
-                                                ignore_boxes=ignores, ignore=self.ignore, return_ignored_count=True)
-                cm, rm = out[0], out[1]
-                if self.anchor_compensation is not None:
-                    self.compensation_stats.push(out[2])
-                self.ignore_stats.push(out[-1])
-            elif self.anchor_compensation is None:
-                cm, rm = ops.dense_overlap_targets(boxes, self.templates, self.heatmap_size, self.rf, paste_boxes=pastes, flips=flips,
-                                                   seed=self._step, pos_thresh=self.pos_thresh, neg_thresh=self.neg_thresh, device=self.device)
-            else:
-                cm, rm, mc = ops.dense_overlap_targets(boxes, self.templates, self.heatmap_size, self.rf, paste_boxes=pastes, flips=flips,
-                                                       seed=self._step, pos_thresh=self.pos_thresh, neg_thresh=self.neg_thresh, device=self.device,
-                                                       compensate=self.anchor_compensation, return_match_count=True)
-                self.compensation_stats.push(mc)
+            cm, rm = self._targets(boxes, pastes, flips, device=self.device, seed=self._step,
+                                   ignore_boxes=ignores if self.ignore_policy is not None else None)
         cur = torch.cuda.current_stream(self.device)
         cur.wait_stream(self._in_stream)
         for t in (x, cm, rm):

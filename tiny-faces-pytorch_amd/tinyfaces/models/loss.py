@@ -131,6 +131,12 @@ class DetectionCriterion(nn.Module):
             raise RuntimeError("DetectionCriterion.inject_sampling: cls_loss='qfl' samples nothing (every labelled anchor contributes)")
         self._pos_keep, self._neg_keep = pos_keep, neg_keep
 
+    def _template_wh_on(self, device):
+        """The (dw, dh) table of the overlap losses, moved to `device` the first time it is asked for there (None stays None)."""
+        if self._template_wh is not None and self._template_wh.device != device:
+            self._template_wh = self._template_wh.to(device)
+        return self._template_wh
+
     def _fwd_bwd(self, out, class_map, regression_map, want_labels=False):
         """The fused loss + gradient pass of this criterion's `cls_loss`, for the autograd function above and for TrainEngine.step:
         (loss[2] f64 device tensor, d(total)/d(out), labels that entered the loss).  soft_margin mines `class_map` in place and returns
@@ -140,16 +146,12 @@ class DetectionCriterion(nn.Module):
             ops.check_reg_loss(self.reg_loss, self.reg_weight, self._template_wh, self.n_templates)
             self._check_reg_with_cls(self.reg_loss, self.cls_loss)
         if self.cls_loss == "qfl":
-            if self._template_wh is not None and self._template_wh.device != out.device:
-                self._template_wh = self._template_wh.to(out.device)
             loss4, grad, _ = ops.criterion_quality_fwd_bwd(out, class_map, regression_map, self.n_templates, self.reg_weight, self.qfl_beta,
-                                                           self.focal_normalize, self.reg_loss, self._template_wh)
+                                                           self.focal_normalize, self.reg_loss, self._template_wh_on(out.device))
             return loss4, grad, class_map
         if self.cls_loss == "focal" and self.reg_loss != "smooth_l1":
-            if self._template_wh is not None and self._template_wh.device != out.device:
-                self._template_wh = self._template_wh.to(out.device)
             loss2, grad, _ = ops.criterion_focal_box_fwd_bwd(out, class_map, regression_map, self.n_templates, self.reg_weight, self.focal_gamma,
-                                                             self.focal_alpha, self.focal_normalize, self.reg_loss, self._template_wh)
+                                                             self.focal_alpha, self.focal_normalize, self.reg_loss, self._template_wh_on(out.device))
             return loss2, grad, class_map
         if self.cls_loss == "focal":
             loss2, grad, _ = ops.criterion_focal_fwd_bwd(out, class_map, regression_map, self.n_templates, self.reg_weight, self.focal_gamma,

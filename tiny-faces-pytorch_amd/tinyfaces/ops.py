@@ -3,6 +3,7 @@
 Each function is the MI355X replacement of the reference call cited in its docstring
 (file:line relative to the reference repo).  PyTorch only supplies memory and streams.
 """
+import contextlib
 import ctypes as C
 import math
 
@@ -51,6 +52,7 @@ def check_compensate(compensate, pos_thresh=0.7):
 
 IGNORE_MEASURES = {"iof": 0, "iou": 1}                    # TF_IGNORE_* (include/tinyfaces_hip.h)
 IGNORE_DEFAULT = ("iof", 0.5)
+_NO_GUARD = contextlib.nullcontext()                      # the resident entries launch on the caller's current device
 
 
 def check_ignore(ignore):
@@ -81,6 +83,22 @@ def _valid_boxes(boxes_per_image):
     return kept, offs
 
 
+def _upload_boxes(boxes_per_image, device):
+    """`_valid_boxes` on `device`, for faces and ignore boxes alike -> (boxes_d (total, 4) f64 -- one zero row when there is none --,
+    offs_d (B + 1,) i32, total)."""
+    kept, offs = _valid_boxes(boxes_per_image)
+    boxes_d = (torch.cat(kept) if offs[-1] else torch.zeros(1, 4, dtype=torch.float64)).contiguous().to(device)
+    return boxes_d, torch.tensor(offs, dtype=torch.int32, device=device), offs[-1]
+
+
+def _upload_templates(templates, device):
+    """The template table as a contiguous float64 tensor on `device`, from an ndarray, a CPU tensor or a device tensor; one that already is
+    all of that comes back as it is, without a copy."""
+    if torch.is_tensor(templates) and templates.is_cuda:
+        return templates.to(device=device, dtype=torch.float64).contiguous()
+    return torch.as_tensor(np.asarray(templates), dtype=torch.float64).contiguous().to(device)
+
+
 def _launch_ignore(cls, t_d, rf, ign_d, ioffs_d, total, ign, want_count):
     """tf_targets_apply_ignore on resident operands, in place on cls (B, nt, vsy, vsx).  Returns the (B,) int32 counter of labels turned
     (zeroed here) or None.  No ignore box in the batch: nothing is enqueued."""
@@ -109,13 +127,9 @@ def targets_apply_ignore(class_map, ignore_boxes_per_image, templates, rf=RF, ig
     if len(ignore_boxes_per_image) != class_map.shape[0]:
         raise ValueError(f"targets_apply_ignore: {len(ignore_boxes_per_image)} lists of ignore boxes for {class_map.shape[0]} images")
     dev = class_map.device
-    t_d = torch.as_tensor(np.asarray(templates.cpu() if torch.is_tensor(templates) else templates), dtype=torch.float64).contiguous().to(dev)
-    kept, offs = _valid_boxes(ignore_boxes_per_image)
-    total = offs[-1]
-    ign_d = (torch.cat(kept) if total else torch.zeros(1, 4, dtype=torch.float64)).contiguous().to(dev)
-    ioffs_d = torch.tensor(offs, dtype=torch.int32, device=dev)
+    t_d = _upload_templates(templates, dev)
     with torch.cuda.device(dev):
-        changed = _launch_ignore(class_map, t_d, rf, ign_d, ioffs_d, total, ign, return_count)
+        changed = _launch_ignore(class_map, t_d, rf, *_upload_boxes(ignore_boxes_per_image, dev), ign, return_count)
     return (class_map, changed) if return_count else class_map
 
 
@@ -143,6 +157,63 @@ def _launch_targets(comp, total, boxes_d, offs_d, B, t_d, nt, tstride, vsy, vsx,
     return mc
 
 
+def _upload_lists(who, boxes_per_image, templates, paste_boxes, flips, ignore_boxes, device):
+    """What the two list entries hand to `_assign_resident`: their host operands on `device`, in the layout it takes."""
+    if ignore_boxes is not None and len(ignore_boxes) != len(boxes_per_image):
+        raise ValueError(f"{who}: {len(ignore_boxes)} lists of ignore boxes for {len(boxes_per_image)} images")
+    device = torch.device(device if device is not None else "cuda")
+    if device.type != "cuda":
+        raise RuntimeError(f"{who}: HIP kernel only (no CPU fallback)")
+    B = len(boxes_per_image)
+    faces, t_d = _upload_boxes(boxes_per_image, device), _upload_templates(templates, device)
+    paste_d = None if paste_boxes is None else torch.as_tensor(np.asarray(paste_boxes), dtype=torch.int32).reshape(B, 4).to(device)
+    flips_d = None if flips is None else torch.as_tensor(np.asarray(flips), dtype=torch.int32).reshape(B).to(device)
+    return faces, t_d, paste_d, flips_d, None if ignore_boxes is None else _upload_boxes(ignore_boxes, device), None, None
+
+
+def _resident_operands(who, boxes_d, offs_d, total_boxes, templates_d, paste_d, flips_d, ignore_d, ignore_offs_d, total_ignore):
+    """What the two resident entries hand to `_assign_resident`: their operands as they are, in the layout it takes."""
+    if ignore_d is not None and (ignore_offs_d is None or ignore_offs_d.numel() != offs_d.numel()):
+        raise ValueError(f"{who}: ignore_offs_d is an int32 (B + 1,) device tensor next to ignore_d")
+    return ((boxes_d, offs_d, int(total_boxes)), templates_d, paste_d, flips_d,
+            None if ignore_d is None else (ignore_d, ignore_offs_d, int(total_ignore)), None, None)
+
+
+def _assign_resident(who, operands, heatmap_size, rf, out, has_ignore, ignore_names, ignore, return_match_count, return_ignored_count, comp=None,
+                     topk=None, seed=0, pos_thresh=0.7, neg_thresh=0.3):
+    """The one path of the four target entries (`who` names the caller in messages).  operands = ((boxes_d, offs_d, total), templates_d, paste_d,
+    flips_d, (ignore_d, ignore_offs_d, total_ignore) or None, noise_d, noise_offs_d), all resident -- or a function that uploads and returns
+    them, called under the guard of its device once every keyword has passed.  topk: the ATSS assigner; else dense_overlap, with comp = (N, T)
+    its compensated form.  Returns cls, reg[, match_count][, ignored_count]."""
+    ign = check_ignore(ignore)
+    if return_match_count and comp is None and topk is None:
+        raise ValueError("return_match_count needs compensate=(N, T)")
+    if return_ignored_count and not has_ignore:
+        raise ValueError(f"return_ignored_count needs {ignore_names}")
+    guard = _NO_GUARD
+    if callable(operands):
+        operands = operands()
+        guard = torch.cuda.device(operands[1].device)
+    (boxes_d, offs_d, total), t_d, paste_d, flips_d, ignores, noise_d, noff_d = operands
+    require_gpu(boxes_d, who)
+    B, (vsy, vsx), (nt, tstride), dev = offs_d.numel() - 1, heatmap_size, t_d.shape, boxes_d.device
+    if out is None:
+        out = (torch.empty(B, nt, vsy, vsx, dtype=torch.float32, device=dev), torch.empty(B, 4 * nt, vsy, vsx, dtype=torch.float32, device=dev))
+    cls, reg = out
+    with guard:
+        if topk is not None:
+            mc = _launch_atss(total, boxes_d, offs_d, B, t_d, vsy, vsx, rf, paste_d, flips_d, topk, cls, reg, dev, return_match_count)
+        else:
+            mc = _launch_targets(comp, total, boxes_d, offs_d, B, t_d, nt, tstride, vsy, vsx, rf, paste_d, flips_d, noise_d, noff_d, seed,
+                                 pos_thresh, neg_thresh, cls, reg, dev, return_match_count)
+        res = (cls, reg) + ((mc,) if return_match_count else ())
+        if ignores is not None:
+            ic = _launch_ignore(cls, t_d, rf, *ignores, ign or IGNORE_DEFAULT, return_ignored_count)
+            if return_ignored_count:
+                res += (ic,)
+    return res
+
+
 def dense_overlap_targets(boxes_per_image, templates, heatmap_size=(63, 63), rf=RF, paste_boxes=None, flips=None,
                           noise=None, seed=0, pos_thresh=0.7, neg_thresh=0.3, device=None, compensate=None, return_match_count=False,
                           ignore_boxes=None, ignore=None, return_ignored_count=False):
@@ -162,60 +233,23 @@ def dense_overlap_targets(boxes_per_image, templates, heatmap_size=(63, 63), rf=
     Returns class_map (B,nt,vsy,vsx) f32 and regression_map (B,4nt,vsy,vsx) f32 on `device`
     -- the CHW layout WIDERFace.__getitem__ hands to the trainer (wider_face.py:186-187) -- [, match_count][, ignored_count]."""
     comp = check_compensate(compensate, pos_thresh)
-    if return_match_count and comp is None:
-        raise ValueError("return_match_count needs compensate=(N, T)")
-    ign = check_ignore(ignore)
-    if return_ignored_count and ignore_boxes is None:
-        raise ValueError("return_ignored_count needs ignore_boxes")
-    if ignore_boxes is not None:
-        ign = ign or IGNORE_DEFAULT
-        if len(ignore_boxes) != len(boxes_per_image):
-            raise ValueError(f"dense_overlap_targets: {len(ignore_boxes)} lists of ignore boxes for {len(boxes_per_image)} images")
-    device = torch.device(device if device is not None else "cuda")
-    if device.type != "cuda":
-        raise RuntimeError("dense_overlap_targets: HIP kernel only (no CPU fallback)")
-    B = len(boxes_per_image)
-    vsy, vsx = heatmap_size
-    t = torch.as_tensor(np.asarray(templates), dtype=torch.float64)
-    nt, tstride = t.shape
-    kept, offs = [], [0]
-    for b in boxes_per_image:
-        b = torch.as_tensor(np.asarray(b.cpu() if torch.is_tensor(b) else b), dtype=torch.float64).reshape(-1, 4)
-        valid = ~((b[:, 2] <= b[:, 0]) | (b[:, 3] <= b[:, 1]))          # processor.py:228-232
-        kept.append(b[valid])
-        offs.append(offs[-1] + int(valid.sum()))
-    total = offs[-1]
-    boxes_d = (torch.cat(kept) if total else torch.zeros(1, 4, dtype=torch.float64)).contiguous().to(device)
-    offs_d = torch.tensor(offs, dtype=torch.int32, device=device)
-    t_d = t.contiguous().to(device)
-    paste_d = None if paste_boxes is None else torch.as_tensor(np.asarray(paste_boxes), dtype=torch.int32).reshape(B, 4).to(device)
-    flips_d = None if flips is None else torch.as_tensor(np.asarray(flips), dtype=torch.int32).reshape(B).to(device)
-    noise_d = noff_d = None
-    if noise is not None:
-        flat, noff = [], [0]
+
+    def upload():
+        operands = _upload_lists("dense_overlap_targets", boxes_per_image, templates, paste_boxes, flips, ignore_boxes, device)
+        if noise is None:
+            return operands
+        t_d, (vsy, vsx) = operands[1], heatmap_size
+        flat, noff, offs = [], [0], _valid_boxes(boxes_per_image)[1]
         for i, nz in enumerate(noise):
             nz = np.ascontiguousarray(np.asarray(nz, dtype=np.float64))
-            assert nz.shape == (vsy, vsx, nt, offs[i + 1] - offs[i]), nz.shape
+            assert nz.shape == (vsy, vsx, t_d.shape[0], offs[i + 1] - offs[i]), nz.shape
             flat.append(nz.reshape(-1))
             noff.append(noff[-1] + nz.size)
         cat = np.concatenate(flat) if noff[-1] else np.zeros(1)
-        noise_d = torch.from_numpy(cat).to(device)
-        noff_d = torch.tensor(noff, dtype=torch.int64, device=device)
-    cls = torch.empty(B, nt, vsy, vsx, dtype=torch.float32, device=device)
-    reg = torch.empty(B, 4 * nt, vsy, vsx, dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        mc = _launch_targets(comp, total, boxes_d, offs_d, B, t_d, nt, tstride, vsy, vsx, rf, paste_d, flips_d, noise_d, noff_d, seed,
-                             pos_thresh, neg_thresh, cls, reg, device, return_match_count)
-        if ignore_boxes is not None:
-            ikept, ioffs = _valid_boxes(ignore_boxes)
-            ign_d = (torch.cat(ikept) if ioffs[-1] else torch.zeros(1, 4, dtype=torch.float64)).contiguous().to(device)
-            ic = _launch_ignore(cls, t_d, rf, ign_d, torch.tensor(ioffs, dtype=torch.int32, device=device), ioffs[-1], ign, return_ignored_count)
-    out = (cls, reg)
-    if return_match_count:
-        out += (mc,)
-    if return_ignored_count:
-        out += (ic,)
-    return out
+        return operands[:5] + (torch.from_numpy(cat).to(t_d.device), torch.tensor(noff, dtype=torch.int64, device=t_d.device))
+
+    return _assign_resident("dense_overlap_targets", upload, heatmap_size, rf, None, ignore_boxes is not None, "ignore_boxes", ignore,
+                            return_match_count, return_ignored_count, comp=comp, seed=seed, pos_thresh=pos_thresh, neg_thresh=neg_thresh)
 
 
 def dense_overlap_targets_device(boxes_d, offs_d, total_boxes, templates_d, heatmap_size=(63, 63), rf=RF, paste_d=None, flips_d=None,
@@ -227,33 +261,10 @@ def dense_overlap_targets_device(boxes_d, offs_d, total_boxes, templates_d, heat
     ignore_d (total_ignore, 4) f64 (degenerate boxes removed) under ignore_offs_d (B+1,) i32, total_ignore the host's copy of its last entry:
     the ignore regions of dense_overlap_targets(ignore_boxes=); ignore / return_ignored_count as there."""
     comp = check_compensate(compensate, pos_thresh)
-    if return_match_count and comp is None:
-        raise ValueError("return_match_count needs compensate=(N, T)")
-    ign = check_ignore(ignore)
-    if return_ignored_count and ignore_d is None:
-        raise ValueError("return_ignored_count needs ignore_d / ignore_offs_d")
-    if ignore_d is not None:
-        ign = ign or IGNORE_DEFAULT
-        if ignore_offs_d is None or ignore_offs_d.numel() != offs_d.numel():
-            raise ValueError("dense_overlap_targets_device: ignore_offs_d is an int32 (B + 1,) device tensor next to ignore_d")
-    require_gpu(boxes_d, "dense_overlap_targets_device")
-    B = offs_d.numel() - 1
-    vsy, vsx = heatmap_size
-    nt, tstride = templates_d.shape
-    dev = boxes_d.device
-    if out is None:
-        out = (torch.empty(B, nt, vsy, vsx, dtype=torch.float32, device=dev), torch.empty(B, 4 * nt, vsy, vsx, dtype=torch.float32, device=dev))
-    cls, reg = out
-    mc = _launch_targets(comp, int(total_boxes), boxes_d, offs_d, B, templates_d, nt, tstride, vsy, vsx, rf, paste_d, flips_d, None, None, seed,
-                         pos_thresh, neg_thresh, cls, reg, dev, return_match_count)
-    res = (cls, reg)
-    if return_match_count:
-        res += (mc,)
-    if ignore_d is not None:
-        ic = _launch_ignore(cls, templates_d, rf, ignore_d, ignore_offs_d, int(total_ignore), ign, return_ignored_count)
-        if return_ignored_count:
-            res += (ic,)
-    return res
+    operands = _resident_operands("dense_overlap_targets_device", boxes_d, offs_d, total_boxes, templates_d, paste_d, flips_d, ignore_d, ignore_offs_d,
+                                  total_ignore)
+    return _assign_resident("dense_overlap_targets_device", operands, heatmap_size, rf, out, ignore_d is not None, "ignore_d / ignore_offs_d", ignore,
+                            return_match_count, return_ignored_count, comp=comp, seed=seed, pos_thresh=pos_thresh, neg_thresh=neg_thresh)
 
 
 ASSIGNERS = ("dense_overlap", "atss")
@@ -298,40 +309,8 @@ def atss_targets(boxes_per_image, templates, heatmap_size=(63, 63), rf=RF, paste
     ignore_boxes / ignore / return_ignored_count: the ignore pass behind the call, as in dense_overlap_targets; passing the faces themselves with
     ignore=("iou", t) makes a grey band of near-miss negatives around them."""
     _, k = check_assigner("atss", topk)
-    ign = check_ignore(ignore)
-    if return_ignored_count and ignore_boxes is None:
-        raise ValueError("return_ignored_count needs ignore_boxes")
-    if ignore_boxes is not None:
-        ign = ign or IGNORE_DEFAULT
-        if len(ignore_boxes) != len(boxes_per_image):
-            raise ValueError(f"atss_targets: {len(ignore_boxes)} lists of ignore boxes for {len(boxes_per_image)} images")
-    device = torch.device(device if device is not None else "cuda")
-    if device.type != "cuda":
-        raise RuntimeError("atss_targets: HIP kernel only (no CPU fallback)")
-    B = len(boxes_per_image)
-    vsy, vsx = heatmap_size
-    t_d = torch.as_tensor(np.asarray(templates.cpu() if torch.is_tensor(templates) else templates), dtype=torch.float64).contiguous().to(device)
-    nt = t_d.shape[0]
-    kept, offs = _valid_boxes(boxes_per_image)
-    total = offs[-1]
-    boxes_d = (torch.cat(kept) if total else torch.zeros(1, 4, dtype=torch.float64)).contiguous().to(device)
-    offs_d = torch.tensor(offs, dtype=torch.int32, device=device)
-    paste_d = None if paste_boxes is None else torch.as_tensor(np.asarray(paste_boxes), dtype=torch.int32).reshape(B, 4).to(device)
-    flips_d = None if flips is None else torch.as_tensor(np.asarray(flips), dtype=torch.int32).reshape(B).to(device)
-    cls = torch.empty(B, nt, vsy, vsx, dtype=torch.float32, device=device)
-    reg = torch.empty(B, 4 * nt, vsy, vsx, dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        mc = _launch_atss(total, boxes_d, offs_d, B, t_d, vsy, vsx, rf, paste_d, flips_d, k, cls, reg, device, return_match_count)
-        if ignore_boxes is not None:
-            ikept, ioffs = _valid_boxes(ignore_boxes)
-            ign_d = (torch.cat(ikept) if ioffs[-1] else torch.zeros(1, 4, dtype=torch.float64)).contiguous().to(device)
-            ic = _launch_ignore(cls, t_d, rf, ign_d, torch.tensor(ioffs, dtype=torch.int32, device=device), ioffs[-1], ign, return_ignored_count)
-    out = (cls, reg)
-    if return_match_count:
-        out += (mc,)
-    if return_ignored_count:
-        out += (ic,)
-    return out
+    return _assign_resident("atss_targets", lambda: _upload_lists("atss_targets", boxes_per_image, templates, paste_boxes, flips, ignore_boxes, device),
+                            heatmap_size, rf, None, ignore_boxes is not None, "ignore_boxes", ignore, return_match_count, return_ignored_count, topk=k)
 
 
 def atss_targets_device(boxes_d, offs_d, total_boxes, templates_d, heatmap_size=(63, 63), rf=RF, paste_d=None, flips_d=None, topk=ATSS_TOPK,
@@ -341,30 +320,9 @@ def atss_targets_device(boxes_d, offs_d, total_boxes, templates_d, heatmap_size=
     boxes_d (total,4) f64 (degenerate boxes removed), offs_d (B+1,) i32, templates_d (nt,5) f64, paste_d (B,4) i32, flips_d (B,) i32;
     out = (class_map, regression_map) to write into; ignore_d / ignore_offs_d / total_ignore / ignore / return_ignored_count as there."""
     _, k = check_assigner("atss", topk)
-    ign = check_ignore(ignore)
-    if return_ignored_count and ignore_d is None:
-        raise ValueError("return_ignored_count needs ignore_d / ignore_offs_d")
-    if ignore_d is not None:
-        ign = ign or IGNORE_DEFAULT
-        if ignore_offs_d is None or ignore_offs_d.numel() != offs_d.numel():
-            raise ValueError("atss_targets_device: ignore_offs_d is an int32 (B + 1,) device tensor next to ignore_d")
-    require_gpu(boxes_d, "atss_targets_device")
-    B = offs_d.numel() - 1
-    vsy, vsx = heatmap_size
-    nt = templates_d.shape[0]
-    dev = boxes_d.device
-    if out is None:
-        out = (torch.empty(B, nt, vsy, vsx, dtype=torch.float32, device=dev), torch.empty(B, 4 * nt, vsy, vsx, dtype=torch.float32, device=dev))
-    cls, reg = out
-    mc = _launch_atss(int(total_boxes), boxes_d, offs_d, B, templates_d, vsy, vsx, rf, paste_d, flips_d, k, cls, reg, dev, return_match_count)
-    res = (cls, reg)
-    if return_match_count:
-        res += (mc,)
-    if ignore_d is not None:
-        ic = _launch_ignore(cls, templates_d, rf, ignore_d, ignore_offs_d, int(total_ignore), ign, return_ignored_count)
-        if return_ignored_count:
-            res += (ic,)
-    return res
+    operands = _resident_operands("atss_targets_device", boxes_d, offs_d, total_boxes, templates_d, paste_d, flips_d, ignore_d, ignore_offs_d, total_ignore)
+    return _assign_resident("atss_targets_device", operands, heatmap_size, rf, out, ignore_d is not None, "ignore_d / ignore_offs_d", ignore,
+                            return_match_count, return_ignored_count, topk=k)
 
 
 def dense_overlap_iou(boxes, templates, heatmap_size=(63, 63), rf=RF, device="cuda"):
@@ -895,12 +853,10 @@ def decode_compact(score, templates_d, valid_x, valid_t, prob_thresh, scale, det
 
 
 # --------------------------------------------------------------------------- criterion
-def criterion_fwd_bwd(output, class_map, regression_map, n_templates=25, reg_weight=1.0, ohem_thresh=0.03, max_pos=128,
-                      max_neg=128, pos_keep=None, neg_keep=None, seed=0, want_labels=False, grad=None):
-    """DetectionCriterion.forward + backward (tinyfaces/models/loss.py:59-93).  class_map is mined in place.
-    Returns (loss[2] f64 device tensor = [sum cls, sum reg], grad wrt output, labels or None).
-    grad: write the gradient into this contiguous fp32 tensor of output's shape (every element is written exactly once, no memset needed)."""
-    require_gpu(output, "criterion")
+def _criterion_operands(output, class_map, regression_map, n_templates, grad, loss_len, template_wh=None, npos=True):
+    """What the four criterion wrappers do to their operands before they call the library: the dtype / shape / contiguity checks, then
+    -> (output and regression_map made contiguous, (B, nt, H, W), device, template_wh as float32 on the device or None, grad -- the caller's,
+    checked, or a new one --, loss (loss_len,) f64, npos (B,) int32 or None)."""
     assert output.dtype == torch.float32 and class_map.dtype == torch.float32 and regression_map.dtype == torch.float32
     output, regression_map = output.contiguous(), regression_map.contiguous()
     assert class_map.is_contiguous()
@@ -908,10 +864,21 @@ def criterion_fwd_bwd(output, class_map, regression_map, n_templates=25, reg_wei
     nt = n_templates
     assert C5 == 5 * nt and class_map.shape == (B, nt, H, W) and regression_map.shape == (B, 4 * nt, H, W)
     dev = output.device
+    twh = None if template_wh is None else template_wh.to(device=dev, dtype=torch.float32).contiguous()
     if grad is None:
         grad = torch.empty_like(output)
     assert grad.shape == output.shape and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == dev
-    loss = torch.empty(2, dtype=torch.float64, device=dev)
+    loss = torch.empty(loss_len, dtype=torch.float64, device=dev)
+    return output, regression_map, (B, nt, H, W), dev, twh, grad, loss, torch.empty(B, dtype=torch.int32, device=dev) if npos else None
+
+
+def criterion_fwd_bwd(output, class_map, regression_map, n_templates=25, reg_weight=1.0, ohem_thresh=0.03, max_pos=128,
+                      max_neg=128, pos_keep=None, neg_keep=None, seed=0, want_labels=False, grad=None):
+    """DetectionCriterion.forward + backward (tinyfaces/models/loss.py:59-93).  class_map is mined in place.
+    Returns (loss[2] f64 device tensor = [sum cls, sum reg], grad wrt output, labels or None).
+    grad: write the gradient into this contiguous fp32 tensor of output's shape (every element is written exactly once, no memset needed)."""
+    require_gpu(output, "criterion")
+    output, regression_map, (B, nt, H, W), dev, _, grad, loss, _ = _criterion_operands(output, class_map, regression_map, n_templates, grad, 2, npos=False)
     labels = torch.empty_like(class_map) if want_labels else None
     wsb = lib().tf_criterion_workspace_bytes(B, nt, H, W)
     ws = _workspace("criterion", wsb, dev)
@@ -946,18 +913,7 @@ def criterion_focal_fwd_bwd(output, class_map, regression_map, n_templates=25, r
     grad: write the gradient into this contiguous fp32 tensor of output's shape (every element is written exactly once, no memset needed)."""
     require_gpu(output, "criterion_focal")
     check_focal(gamma, alpha, normalize)
-    assert output.dtype == torch.float32 and class_map.dtype == torch.float32 and regression_map.dtype == torch.float32
-    output, regression_map = output.contiguous(), regression_map.contiguous()
-    assert class_map.is_contiguous()
-    B, C5, H, W = output.shape
-    nt = n_templates
-    assert C5 == 5 * nt and class_map.shape == (B, nt, H, W) and regression_map.shape == (B, 4 * nt, H, W)
-    dev = output.device
-    if grad is None:
-        grad = torch.empty_like(output)
-    assert grad.shape == output.shape and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == dev
-    loss = torch.empty(2, dtype=torch.float64, device=dev)
-    npos = torch.empty(B, dtype=torch.int32, device=dev)
+    output, regression_map, (B, nt, H, W), dev, _, grad, loss, npos = _criterion_operands(output, class_map, regression_map, n_templates, grad, 2)
     wsb = lib().tf_criterion_focal_workspace_bytes(B, nt, H, W)
     ws = _workspace("criterion_focal", wsb, dev)
     with torch.cuda.device(dev):
@@ -1006,21 +962,8 @@ def criterion_focal_box_fwd_bwd(output, class_map, regression_map, n_templates=2
     require_gpu(output, "criterion_focal_box")
     check_focal(gamma, alpha, normalize)
     check_reg_loss(reg_loss, reg_weight, template_wh, n_templates)
-    assert output.dtype == torch.float32 and class_map.dtype == torch.float32 and regression_map.dtype == torch.float32
-    output, regression_map = output.contiguous(), regression_map.contiguous()
-    assert class_map.is_contiguous()
-    B, C5, H, W = output.shape
-    nt = n_templates
-    assert C5 == 5 * nt and class_map.shape == (B, nt, H, W) and regression_map.shape == (B, 4 * nt, H, W)
-    dev = output.device
-    twh = None
-    if reg_loss == "diou":
-        twh = template_wh.to(device=dev, dtype=torch.float32).contiguous()
-    if grad is None:
-        grad = torch.empty_like(output)
-    assert grad.shape == output.shape and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == dev
-    loss = torch.empty(2, dtype=torch.float64, device=dev)
-    npos = torch.empty(B, dtype=torch.int32, device=dev)
+    output, regression_map, (B, nt, H, W), dev, twh, grad, loss, npos = _criterion_operands(output, class_map, regression_map, n_templates, grad, 2,
+                                                                                            template_wh if reg_loss == "diou" else None)
     wsb = lib().tf_criterion_focal_workspace_bytes(B, nt, H, W)
     ws = _workspace("criterion_focal", wsb, dev)
     with torch.cuda.device(dev):
@@ -1052,21 +995,8 @@ def criterion_quality_fwd_bwd(output, class_map, regression_map, n_templates=25,
     require_gpu(output, "criterion_quality")
     check_qfl(beta, normalize)
     check_reg_loss(reg_loss, reg_weight, template_wh, n_templates)
-    assert output.dtype == torch.float32 and class_map.dtype == torch.float32 and regression_map.dtype == torch.float32
-    output, regression_map = output.contiguous(), regression_map.contiguous()
-    assert class_map.is_contiguous()
-    B, C5, H, W = output.shape
-    nt = n_templates
-    assert C5 == 5 * nt and class_map.shape == (B, nt, H, W) and regression_map.shape == (B, 4 * nt, H, W)
-    dev = output.device
-    twh = None
-    if reg_loss == "diou":
-        twh = template_wh.to(device=dev, dtype=torch.float32).contiguous()
-    if grad is None:
-        grad = torch.empty_like(output)
-    assert grad.shape == output.shape and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == dev
-    loss = torch.empty(4, dtype=torch.float64, device=dev)
-    npos = torch.empty(B, dtype=torch.int32, device=dev)
+    output, regression_map, (B, nt, H, W), dev, twh, grad, loss, npos = _criterion_operands(output, class_map, regression_map, n_templates, grad, 4,
+                                                                                            template_wh if reg_loss == "diou" else None)
     wsb = lib().tf_criterion_quality_workspace_bytes(B, nt, H, W)
     ws = _workspace("criterion_quality", wsb, dev)
     with torch.cuda.device(dev):
