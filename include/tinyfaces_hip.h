@@ -176,6 +176,52 @@ int tf_targets_atss(const double* boxes, const int32_t* box_offsets, int B,
                     int k, int32_t* match_count,
                     float* class_map, float* reg_map,
                     void* ws, size_t ws_bytes, void* stream);
+/* ---- TAL: task-aligned target assignment (Feng et al. 2021, "TOOD: Task-aligned One-stage Object Detection"; mmdetection's
+ * TaskAlignedAssigner, defaults topk = 13, alpha = 1, beta = 6) ------------------------------------------------------------------------
+ * tf_targets_tal assigns from the network's own output: an anchor is positive for a face when the head already scores it highly AND its
+ * predicted box localises that face well.  It runs between the forward pass and the criterion, IN PLACE on two maps that arrive holding an
+ * assignment without faces (the base maps: tf_dense_overlap_targets with no box -- every label -1, padded anchors too, as after
+ * tf_targets_atss --, then 0 where tf_targets_apply_ignore turned a negative; regression map 0); the reference has no such assigner, the rule
+ * below is the contract (numpy restatement: tests/tal_ref.py).
+ * Symbols, faces, anchors, acx / acy and pad(a) are those of ATSS above.  output [B][5 nt][vsy][vsx] f32 is the head's output in the layout the
+ * criterion reads: channel t the class logit z of template t, channels nt + t, 2 nt + t, 3 nt + t, 4 nt + t its px, py, pw, ph.  Every operand is
+ * widened to float64 first; plain float64 in the stated operation order, without FMA contraction; exp and pow are the math library's.
+ *   1 metric      dw = dx2 - dx1 + 1, dh = dy2 - dy1 + 1 (the regression target's own normalisers), C = 4.135166556742356 (log(1000 / 16), the
+ *                 clamp of the overlap losses).  The predicted box of anchor a: centre bcx = cx + px * dw, bcy = cy + py * dh, size
+ *                 w = dw * exp(min(max(pw, -C), C)), h = dh * exp(min(max(ph, -C), C)), corners bcx -+ w / 2, bcy -+ h / 2.  The face as the
+ *                 target kernel measures it: centre fcx = (fx1 + fx2) / 2, fcy = (fy1 + fy2) / 2, size bw = fx2 - fx1 + 1, bh = fy2 - fy1 + 1,
+ *                 corners fcx -+ bw / 2, fcy -+ bh / 2.  iw = min(right edges) - max(left edges), ih alike (no + 1: both boxes are continuous);
+ *                 u = iw * ih / (w * h + bw * bh - iw * ih) when iw > 0 and ih > 0, else 0.  No epsilon.  A prediction equal to the anchor's
+ *                 regression target for g has u = 1.  s = 1 / (1 + exp(-z));  m = pow(s, alpha) * pow(u, beta).
+ *   2 candidates  of face g: every template at every unpadded cell whose anchor centre lies strictly inside the face (fx1 < acx < fx2 and
+ *                 fy1 < acy < fy2).  A face for which no template has such a cell (a 6-px face between the centres of the stride-8 grid) takes, per
+ *                 template, the single unpadded cell nearest its centre: ATSS's candidate at k = 1, in its distance and tie order.  Of these,
+ *                 one whose z, px, py, pw or ph is not finite, whose u is not > 0, or whose m is not finite is not a candidate.
+ *   3 selection   the face claims its topk candidates of largest m, the lower flat index (t * vsy + y) * vsx + x first on a tie; fewer if
+ *                 it has fewer.  topk in 1..32; alpha finite and >= 0; beta finite and > 0.
+ *   4 conflicts   an anchor claimed by several faces goes to the larger u, the lower g on a tie (ATSS's rule with the predicted box's IoU); the
+ *                 losers are not compensated.  There is no fallback: a face whose candidates all have u = 0 wins nothing.
+ *   5 output      class_map = +1 and reg_map = get_regression's four values of the winning face (as ATSS writes them) at every won anchor, even
+ *                 where the map held 0.  NOTHING else of either map is written: what arrived stays.  match_count [total_boxes] i32 or NULL:
+ *                 the number of anchors each face won.
+ *   6 one image's result does not depend on the rest of its batch; the same operands give the same bits on every run.
+ * Four launches (clear of the workspace's claim words, claim, owner, write).  claim: one 256-thread workgroup per face walks the face's window
+ * in tiles of 256 candidates and keeps its running topk in LDS (per-tile partial top-k, merged by counting ranks); neither the number of
+ * faces, nor a window's size, nor nt is bounded by LDS, and no candidate list exists in global memory.  Conflicts are resolved with 64- and
+ * 32-bit integer atomics only (max of u's bit pattern, then min of the face index); no floating-point atomic, no grid barrier, no host
+ * synchronisation, no memset of the maps.  The number of boxes is only known on the device: a workspace too small for box_offsets[B] makes
+ * every kernel return without writing.
+ * Refused before anything is enqueued: topk outside 1..32, alpha not finite or < 0, beta not finite or <= 0, a NULL output / class_map /
+ * reg_map / templates / box_offsets, a non-positive size, tstride < 4, a stride <= 0 (TF_ERR_ARG); a workspace below the size for one box
+ * (TF_ERR_WORKSPACE); nt * vsy * vsx >= 2^31 or a cell coordinate beyond int32 (TF_ERR_UNSUPPORTED). */
+size_t tf_targets_tal_workspace_bytes(int total_boxes, int B, int nt, int vsy, int vsx);
+int tf_targets_tal(const float* output, const double* boxes, const int32_t* box_offsets, int B,
+                   const double* templates, int nt, int tstride,
+                   int vsy, int vsx, int ofy, int ofx, int sty, int stx,
+                   const int32_t* paste_boxes, const int32_t* flips,
+                   int topk, double alpha, double beta, int32_t* match_count,
+                   float* class_map, float* reg_map,
+                   void* ws, size_t ws_bytes, void* stream);
 /* test hook: the raw rounded IoU tensor [vsy][vsx][nt][G] f64 for ONE image */
 int tf_dense_overlap_iou(const double* boxes, int G, const double* templates, int nt, int tstride,
                          int vsy, int vsx, int ofy, int ofx, int sty, int stx,

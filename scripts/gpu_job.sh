@@ -21,6 +21,7 @@
 #   topk                       cost of the pre-NMS top-k and the detection cap: select + NMS vs the full NMS at 65 536 / 600 000 candidates, Soft-NMS capped vs uncapped, pyramid plain / soft / soft + both bounds (scripts/topk_numbers.py) -> $TOPK_OUT (default profiles/topk.jsonl)
 #   color-jitter               cost of the colour jitter: image_prepare plain / three ops / four ops / contrast alone on the 500x500 window, batch building with / without it (scripts/color_jitter_numbers.py) -> $COLOR_JITTER_OUT (default profiles/color_jitter.jsonl)
 #   quality-loss               cost of the quality focal loss: the qfl call next to the focal call of the same reg_loss on the step's operands, the bf16 step with either (scripts/quality_loss_numbers.py) -> $QUALITY_LOSS_OUT (default profiles/quality_loss.jsonl)
+#   tal                        cost of the task-aligned assignment: the resident call next to the ATSS call at k = 9 on outputs of a real forward pass, the bf16 step assigning by TAL next to the step fed ATSS maps, two synthetic-faces epochs under either (scripts/tal_numbers.py) -> $TAL_OUT (default profiles/tal.jsonl)
 #   dist-smoke                 RCCL 1-rank group, 2 gloo ranks on one GPU, 2 nccl ranks on one GPU (expected refusal) -> gpurun_out/dist_smoke.txt
 #   final                      tests + bench + prof + pmc-traffic + layer-table + timeline + eval prof + smoke: the artefacts of a round
 set -u
@@ -115,6 +116,12 @@ print(d['value'], d['ms_per_step'], 'frac', r.get('frac'), 'fwd', r.get('forward
     timeout -k 10 ${QUALITY_LOSS_TIMEOUT:-300} python scripts/quality_loss_numbers.py --step calls > "$out" 2> "$err" &&
       timeout -k 10 ${QUALITY_LOSS_TIMEOUT:-300} python scripts/quality_loss_numbers.py --step steps >> "$out" 2>> "$err"
     echo "quality-loss exit $?"; cat "$out"; tail -3 "$err" ;;
+  tal)   # one process and one time limit per step; a step only behind a clean one before it
+    out=${TAL_OUT:-$R/profiles/tal.jsonl}; err=${out%.jsonl}.err
+    timeout -k 10 ${TAL_TIMEOUT:-300} python scripts/tal_numbers.py --step calls > "$out" 2> "$err" &&
+      timeout -k 10 ${TAL_TIMEOUT:-300} python scripts/tal_numbers.py --step steps >> "$out" 2>> "$err" &&
+      timeout -k 10 ${TAL_TIMEOUT:-300} python scripts/tal_numbers.py --step epochs >> "$out" 2>> "$err"
+    echo "tal exit $?"; cat "$out"; tail -3 "$err" ;;
   dist-smoke) bash scripts/gpu_dist_smoke.sh ;;
   final)
     # the profile passes FIRST: bench.py quotes the committed kernel-stats / PMC files, so they are refreshed in the box's copy of profiles/

@@ -17,7 +17,7 @@
 //
 // Candidate selection.  The unpadded cells of a template form a rectangle [xlo, xhi] x [ylo, yhi]: the padding predicate is a disjunction of
 // four one-sided tests, each monotone in the cell coordinate.  Its bounds are estimated by one division and then corrected with the predicate
-// itself, so they are exact.  The squared distance is separable and each axis term is unimodal in the cell coordinate, so the k nearest cells
+// itself, so they are exact (unpadded_range, nearest_window, centre and sqdist live in csrc/targets_shared.h: the TAL assigner uses them too).  The squared distance is separable and each axis term is unimodal in the cell coordinate, so the k nearest cells
 // lie inside the W nearest columns x the W nearest rows for any W >= k.  The window is chosen by the axis term alone while the rule ranks by
 // the ROUNDED sum of both terms: two columns that mirror each other about a face centre a hair off a column centre can tie in the sum with
 // unequal axis terms, and the rule then prefers the lower cell index.  The kernel therefore takes W = k + 1 at every k (up to 17 x 17 = 289
@@ -44,42 +44,6 @@ struct AtssParams {
   int32_t* cidx;                                   // [nslots * 16 * nt]   per candidate: t * cells + cell
   int32_t* ncand;                                  // [nslots]
 };
-
-// the two halves of get_padding's predicate along one axis, as pad_at of csrc/targets.hip forms them: c = of + i * st in int32, then double
-__device__ __forceinline__ bool pad_lo(int of, int st, int i, double d1, int lim) { return (double)(of + i * st) + d1 < (double)(lim + 1); }
-__device__ __forceinline__ bool pad_hi(int of, int st, int i, double d2, int lim) { return (double)(of + i * st) + d2 > (double)lim; }
-
-__device__ __forceinline__ int clamp_to_int(double v, int lo, int hi) {          // (a NaN goes to lo)
-  return v >= (double)hi ? hi : (v > (double)lo ? (int)v : lo);
-}
-
-// [lo, hi] = the indices i in [0, n) with neither half of the predicate set (empty: lo > hi)
-__device__ __forceinline__ void unpadded_range(int of, int st, int n, double d1, double d2, int lim_lo, int lim_hi, int& lo, int& hi) {
-  lo = clamp_to_int(ceil(((double)(lim_lo + 1) - d1 - (double)of) / (double)st), 0, n);
-  while (lo > 0 && !pad_lo(of, st, lo - 1, d1, lim_lo)) --lo;
-  while (lo < n && pad_lo(of, st, lo, d1, lim_lo)) ++lo;
-  hi = clamp_to_int(floor(((double)lim_hi - d2 - (double)of) / (double)st), -1, n - 1);
-  while (hi < n - 1 && !pad_hi(of, st, hi + 1, d2, lim_hi)) ++hi;
-  while (hi >= 0 && pad_hi(of, st, hi, d2, lim_hi)) --hi;
-}
-
-// the anchor centre along one axis: ((d1 + c) + (d2 + c)) / 2 with c = of + i * st as targets_kernel forms it
-__device__ __forceinline__ double centre(int of, int st, int i, double d1, double d2) {
-  const double c = (double)of + (double)i * ((double)st / 1.0);
-  return ((d1 + c) + (d2 + c)) / 2.0;
-}
-__device__ __forceinline__ double sqdist(int of, int st, int i, double d1, double d2, double fc) {
-  const double d = centre(of, st, i, d1, d2) - fc;
-  return d * d;
-}
-
-// first index of the w (<= hi - lo + 1) indices of [lo, hi] nearest to fc: squared distance ascending, the lower index on a tie
-__device__ __forceinline__ int nearest_window(int of, int st, int lo, int hi, int w, double d1, double d2, double fc) {
-  int c0 = clamp_to_int(floor((fc - (d1 + d2) / 2.0 - (double)of) / (double)st) - (double)(w / 2), lo, hi - w + 1);
-  while (c0 > lo && sqdist(of, st, c0 - 1, d1, d2, fc) <= sqdist(of, st, c0 + w - 1, d1, d2, fc)) --c0;
-  while (c0 + w <= hi && sqdist(of, st, c0 + w, d1, d2, fc) < sqdist(of, st, c0, d1, d2, fc)) ++c0;
-  return c0;
-}
 
 __global__ void __launch_bounds__(kThreads) atss_init_kernel(AtssParams p) {
   if (p.box_off[p.B] > p.nslots) return;                                       // more boxes than the workspace has slots for: touch nothing

@@ -21,7 +21,7 @@ from tinyfaces.datasets import get_dataloader
 from tinyfaces.datasets.templates import load_templates
 from tinyfaces.ema import ModelEma, ema_decay_at
 from tinyfaces.engine import TrainEngine
-from tinyfaces.models.loss import DetectionCriterion
+from tinyfaces.models.loss import DetectionCriterion, TaskAligned
 from tinyfaces.models import model as model_zoo
 from tinyfaces.models.model import DetectionModel
 
@@ -154,7 +154,11 @@ COMPENSATION_HELP = ("--anchor-compensation N T: scale-compensated anchor matchi
 ASSIGNER_HELP = ("--assigner atss: ATSS target assignment (Zhang et al. 2020; what SCRFD and TinaFace train with) for the training targets instead of "
                  "the fixed IoU thresholds: per face the --atss-topk K (1..16, default 9) unpadded cells of every template nearest to its centre are "
                  "candidates, positive from mean + std of their IoUs when the anchor centre lies inside the face; not together with "
-                 "--anchor-compensation; default dense-overlap (positive from IoU 0.7, negative below 0.3)")
+                 "--anchor-compensation; default dense-overlap (positive from IoU 0.7, negative below 0.3). "
+                 "--assigner tal: task-aligned assignment (Feng et al. 2021, TOOD; the YOLO-style face detectors after it) from the network's own output, "
+                 "every step, on the device between the forward pass and the loss: per face the anchors whose centre lies inside it are ranked by "
+                 "sigmoid(logit)^A * IoU(predicted box, face)^B and the best K become its positives, --tal-topk K (1..32, default 13), --tal-alpha A "
+                 "(>= 0, default 1), --tal-beta B (> 0, default 6); not together with --anchor-compensation")
 
 
 IGNORE_HELP = ("ignore regions for the training targets of a WIDER annotation file (S3FD, PyramidBox, RetinaFace; mmdetection's gt_bboxes_ignore): a face "
@@ -194,6 +198,30 @@ def _atss_topk(text):
     if not 1 <= k <= 16:
         raise argparse.ArgumentTypeError(f"--atss-topk takes an integer in 1..16, got {text!r}")
     return k
+
+
+def _tal_topk(text):
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--tal-topk takes an integer in 1..32, got {text!r}") from None
+    if not 1 <= k <= 32:
+        raise argparse.ArgumentTypeError(f"--tal-topk takes an integer in 1..32, got {text!r}")
+    return k
+
+
+def _tal_alpha(text):
+    value = float(text)
+    if not (math.isfinite(value) and value >= 0):
+        raise argparse.ArgumentTypeError(f"--tal-alpha takes a finite number >= 0, got {text}")
+    return value
+
+
+def _tal_beta(text):
+    value = float(text)
+    if not (math.isfinite(value) and value > 0):
+        raise argparse.ArgumentTypeError(f"--tal-beta takes a finite number > 0, got {text}")
+    return value
 
 
 def _compensation_value(text):
@@ -332,7 +360,7 @@ def trunk_arguments(argv=None):
     --focal-gamma, --focal-alpha and --focal-normalize, `reg_loss` ("smooth_l1" | "iou" | "giou" | "diou") from --reg-loss and `reg_weight` from
     --reg-weight, `optimizer` ("sgd" | "adamw"), `adam_beta1`, `adam_beta2` and `adam_eps` from --optimizer, --adam-beta1, --adam-beta2 and --adam-eps,
     `warmup_iters` and `warmup_factor` from --warmup-iters and --warmup-factor, `color_jitter` (None or the four amplitudes) from --color-jitter,
-    `anchor_compensation` (None or (N, T)) from --anchor-compensation, `assigner` ("dense_overlap" | "atss") and `atss_topk` from --assigner and
+    `anchor_compensation` (None or (N, T)) from --anchor-compensation, `assigner` ("dense_overlap" | "atss" | "tal"), `atss_topk` and `tal_topk` / `tal_alpha` / `tal_beta` from --assigner, --tal-* and
     --atss-topk, `ignore_policy` (None or an augment.IgnorePolicy) and `ignore` (None or
     (measure, thresh)) from the --ignore-* flags,
     `val_every`, `val_prob_thresh`, `val_nms_thresh`, `val_num_images` and `val_gt_dir` from --val-every and its companions.  Parsed apart, so that `arguments` keeps resolving exactly the reference's
@@ -368,8 +396,11 @@ def trunk_arguments(argv=None):
     parser.add_argument("--deterministic", dest="deterministic", action="store_true", help=DETERMINISTIC_HELP)
     parser.add_argument("--anchor-compensation", dest="anchor_compensation", default=None, type=_compensation_value, nargs=2, metavar=("N", "T"),
                         help=COMPENSATION_HELP)
-    parser.add_argument("--assigner", dest="assigner", default="dense-overlap", choices=["dense-overlap", "atss"], help=ASSIGNER_HELP)
+    parser.add_argument("--assigner", dest="assigner", default="dense-overlap", choices=["dense-overlap", "atss", "tal"], help=ASSIGNER_HELP)
     parser.add_argument("--atss-topk", dest="atss_topk", default=9, type=_atss_topk, metavar="K", help=ASSIGNER_HELP)
+    parser.add_argument("--tal-topk", dest="tal_topk", default=13, type=_tal_topk, metavar="K", help=ASSIGNER_HELP)
+    parser.add_argument("--tal-alpha", dest="tal_alpha", default=1.0, type=_tal_alpha, metavar="A", help=ASSIGNER_HELP)
+    parser.add_argument("--tal-beta", dest="tal_beta", default=6.0, type=_tal_beta, metavar="B", help=ASSIGNER_HELP)
     parser.add_argument("--ignore-invalid", dest="ignore_invalid", action="store_true", help=IGNORE_HELP)
     parser.add_argument("--ignore-blur", dest="ignore_blur", default=None, type=_ignore_level, metavar="L", help=IGNORE_HELP)
     parser.add_argument("--ignore-occlusion", dest="ignore_occlusion", default=None, type=_ignore_level, metavar="L", help=IGNORE_HELP)
@@ -386,6 +417,8 @@ def trunk_arguments(argv=None):
         parser.error("--ignore-thresh needs one of --ignore-invalid, --ignore-blur, --ignore-occlusion, --ignore-min-size, --ignore-truncated")
     if known.anchor_compensation is not None and known.assigner == "atss":
         parser.error("--anchor-compensation tops up the owners that the dense-overlap assignment computes; it does not go with --assigner atss")
+    if known.anchor_compensation is not None and known.assigner == "tal":
+        parser.error("--anchor-compensation tops up the owners that the dense-overlap assignment computes; it does not go with --assigner tal")
     if known.anchor_compensation is not None:
         n, t = known.anchor_compensation
         if n != int(n) or not 1 <= int(n) <= 64:
@@ -423,8 +456,9 @@ def trunk_arguments(argv=None):
     args.deterministic = known.deterministic
     args.anchor_compensation = None if known.anchor_compensation is None else (int(known.anchor_compensation[0]), float(known.anchor_compensation[1]))
     args.assigner, args.atss_topk = known.assigner.replace("-", "_"), known.atss_topk
-    if args.assigner == "atss" and (str(args.traindata) == "synthetic" or getattr(args, "synthetic", False)):
-        parser.error("--assigner atss applies to a WIDER annotation file or to synthetic-faces: the synthetic crops are a throughput workload of the "
+    args.tal_topk, args.tal_alpha, args.tal_beta = known.tal_topk, known.tal_alpha, known.tal_beta
+    if args.assigner != "dense_overlap" and (str(args.traindata) == "synthetic" or getattr(args, "synthetic", False)):
+        parser.error(f"--assigner {args.assigner} applies to a WIDER annotation file or to synthetic-faces: the synthetic crops are a throughput workload of the "
                      "dense-overlap assigner")
     args.ignore_policy = args.ignore = None
     if ignore_on:
@@ -451,6 +485,11 @@ def ignore_description(args):
 
 def assigner_description(args):
     """The target assigner as the start-up line prints it."""
+    if getattr(args, "assigner", "dense_overlap") == "tal":
+        return (f"assigner TAL: every step, from the network's own output: per face the anchors whose centre lies inside it are ranked by "
+                f"sigmoid(logit)^{args.tal_alpha:g} * IoU(predicted box, face)^{args.tal_beta:g} and the best {args.tal_topk} become its positives, an anchor "
+                "two faces claim goes to the larger IoU; everything else keeps the label of a map without faces (on the device, between the forward "
+                "pass and the loss; the two IoU thresholds only filter crops)")
     if getattr(args, "assigner", "dense_overlap") != "atss":
         return ("assigner dense-overlap: positives from the data set's positive IoU threshold plus every face's best anchor, negatives below its negative "
                 "threshold, the band between them ignored (0.7 / 0.3 for WIDER and the synthetic crops; synthetic-faces: 0.7 / 0.7 unless FACES_POS / FACES_NEG say otherwise)")
@@ -519,7 +558,12 @@ def run_fused_epoch(engine, loss_fn, loader, epoch, device, base_lr, warmup=None
         if warm:
             engine.set_lr(lr_with_warmup(base_lr, epoch, first + (engine.steps - steps0), warmup[0], warmup[1]))
         # the epoch's last batch ends its window, full or not: no checkpoint is ever written with gradients accumulated and not applied
-        engine.step(*(t.float().to(device, non_blocking=True) for t in batch), apply=True if idx + 1 == total else None)
+        # (a loader with --assigner tal delivers a fourth element, the resident faces of the batch: a record that is moved, not a tensor to convert)
+        maps = tuple(t.float().to(device, non_blocking=True) for t in batch[:3])
+        if len(batch) > 3:
+            engine.step_with_faces(*maps, batch[3].to(device, non_blocking=True), apply=True if idx + 1 == total else None)
+        else:
+            engine.step(*maps, apply=True if idx + 1 == total else None)
         if parallel.rank() == 0:
             loss_fn.flush_meters(lag=0 if idx + 1 == total else 1)      # one step behind: the host prepares batch idx + 1 while the GPU runs step idx
             trainer.print_state(idx, epoch, total, loss_fn.class_average.average, loss_fn.reg_average.average)
@@ -561,6 +605,7 @@ def main():
     train_loader, _ = get_dataloader(args.traindata, args, NUM_TEMPLATES, img_transforms=preprocess, color_jitter=args.color_jitter,
                                      anchor_compensation=args.anchor_compensation,
                                      **({} if args.assigner == "dense_overlap" else {"assigner": args.assigner, "atss_topk": args.atss_topk}),
+                                     **({"tal_topk": args.tal_topk, "tal_alpha": args.tal_alpha, "tal_beta": args.tal_beta} if args.assigner == "tal" else {}),
                                      **({} if args.ignore_policy is None else {"ignore_policy": args.ignore_policy, "ignore": args.ignore}))
     model = DetectionModel(base_model=getattr(model_zoo, args.base_model), num_objects=1, num_templates=NUM_TEMPLATES).set_compute_dtype(args.dtype)
     model.freeze_batchnorm(args.freeze_bn).set_trainable_layers(args.trainable_layers)
@@ -571,8 +616,9 @@ def main():
               f"{args.accum_steps} x world {parallel.world_size()}" + (", gradients averaged over the window" if args.accum_average and args.accum_steps > 1 else ""))
     loss_fn = DetectionCriterion(NUM_TEMPLATES, reg_weight=args.reg_weight, seed=args.seed * parallel.world_size() + parallel.rank(), lazy_meters=True,
                                  cls_loss=args.cls_loss, focal_gamma=args.focal_gamma, focal_alpha=args.focal_alpha, focal_normalize=args.focal_normalize,
-                                 reg_loss=args.reg_loss, templates=load_templates(NUM_TEMPLATES) if args.reg_loss == "diou" else None,
-                                 **({"qfl_beta": args.qfl_beta} if args.cls_loss == "qfl" else {}))
+                                 reg_loss=args.reg_loss, templates=load_templates(NUM_TEMPLATES) if args.reg_loss == "diou" or args.assigner == "tal" else None,
+                                 **({"qfl_beta": args.qfl_beta} if args.cls_loss == "qfl" else {}),
+                                 **({"assigner": TaskAligned(args.tal_topk, args.tal_alpha, args.tal_beta)} if args.assigner == "tal" else {}))
     loss_fn.ohem_thresh = args.ohem_thresh
     if parallel.rank() == 0:
         print(loss_description(args))
@@ -670,6 +716,8 @@ def main():
             snapshot["args"] = {"anchor_compensation": list(args.anchor_compensation)}      # what the targets of this run were matched with
         if args.assigner == "atss":
             snapshot.setdefault("args", {}).update(assigner=args.assigner, atss_topk=args.atss_topk)
+        if args.assigner == "tal":
+            snapshot.setdefault("args", {}).update(assigner=args.assigner, tal_topk=args.tal_topk, tal_alpha=args.tal_alpha, tal_beta=args.tal_beta)
         if args.cls_loss == "qfl":
             snapshot.setdefault("args", {}).update(cls_loss=args.cls_loss, qfl_beta=args.qfl_beta, focal_normalize=args.focal_normalize,
                                                    reg_loss=args.reg_loss, reg_weight=args.reg_weight)

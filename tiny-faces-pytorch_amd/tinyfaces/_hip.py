@@ -111,6 +111,8 @@ _SIGNATURES = {
     "tf_targets_apply_ignore": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, f64, vp, vp]),
     "tf_targets_atss_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "tf_targets_atss": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "tf_targets_tal_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "tf_targets_tal": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, f64, f64, vp, vp, vp, vp, sz, vp]),
     "tf_dense_overlap_iou": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "tf_pairwise_iou_distance": (i32, [vp, i32, vp, vp]),
     "tf_nms_workspace_bytes": (sz, [i32]),

@@ -10,13 +10,13 @@ import torch
 from torch.utils import data
 
 from .synthetic import SyntheticCrops, SyntheticFaces  # noqa: F401
-from .targets import CompensationStats, IgnoreStats, TargetAssigner  # noqa: F401
+from .targets import CompensationStats, IgnoreStats, ResidentFaces, TargetAssigner  # noqa: F401
 from .templates import load_templates
 
 
 def get_dataloader(datapath, args, num_templates=25, template_file="templates.json", img_transforms=None, train=True,
                    split="train", color_jitter=None, anchor_compensation=None, ignore_policy=None, ignore=None,
-                   assigner="dense_overlap", atss_topk=9):
+                   assigner="dense_overlap", atss_topk=9, tal_topk=13, tal_alpha=1.0, tal_beta=6.0):
     """datasets/__init__.py:11-52.  `datapath == "synthetic"` (or a path that does not exist with
     args.synthetic set) yields seeded 500x500 crops + random boxes (BASELINE.json configs[2]);
     returns (loader, templates ndarray 25x5) like the reference.
@@ -30,6 +30,9 @@ def get_dataloader(datapath, args, num_templates=25, template_file="templates.js
     assigner = "atss" / atss_topk: the training targets of WIDERFace and SyntheticFaces come from the ATSS assigner (ops.atss_targets: per face
     the atss_topk nearest unpadded cells of every template, positive from mean + std of their IoUs); "dense_overlap" = the reference's
     thresholds, as before.  anchor_compensation next to "atss" is a ValueError.
+    assigner = "tal" / tal_topk, tal_alpha, tal_beta: task-aligned assignment.  The loaders of WIDERFace and SyntheticFaces then deliver FOUR
+    elements per training batch -- images, the base maps (no face assigned) and the ResidentFaces record (datasets/targets.py) -- and the
+    criterion assigns from the predictions (DetectionCriterion(assigner=TaskAligned(...))).  anchor_compensation next to it is a ValueError.
 
     Data parallel (one process per GPU, tinyfaces/parallel.py): every rank walks ITS shard of the data -- a
     DistributedSampler for annotation files, a rank-dependent seed for the synthetic crops -- so an epoch is one pass over
@@ -45,7 +48,7 @@ def get_dataloader(datapath, args, num_templates=25, template_file="templates.js
         # batch is split into disjoint rank shards (rotating, see below); evaluation: rank r takes images r, r + world, ...
         length = getattr(args, "synthetic_len", 8)
         ds = SyntheticFaces(templates, length=length, seed=getattr(args, "seed", 0), train=train, img_transforms=img_transforms, color_jitter=color_jitter,
-                            anchor_compensation=anchor_compensation, assigner=assigner, atss_topk=atss_topk)
+                            anchor_compensation=anchor_compensation, assigner=assigner, atss_topk=atss_topk, tal_topk=tal_topk, tal_alpha=tal_alpha, tal_beta=tal_beta)
         idx = list(range(rank, length, world)) if world > 1 else None
         if world > 1 and train:
             # the shard of a rank ROTATES with the global batch: a fixed stride would show rank 0 the even layouts only, and the BatchNorm running
@@ -78,7 +81,7 @@ def get_dataloader(datapath, args, num_templates=25, template_file="templates.js
     ds = WIDERFace(Path(datapath).expanduser(), templates, split=split, img_transforms=img_transforms,
                    dataset_root=Path(getattr(args, "dataset_root", "")).expanduser(), debug=getattr(args, "debug", False), color_jitter=color_jitter,
                    anchor_compensation=anchor_compensation, ignore_policy=ignore_policy, ignore=ignore,
-                   assigner=assigner, atss_topk=atss_topk)
+                   assigner=assigner, atss_topk=atss_topk, tal_topk=tal_topk, tal_alpha=tal_alpha, tal_beta=tal_beta)
     # decoding runs in the workers (identity collate there); the device half of a batch -- augmentation + targets -- runs in
     # this process, where the GPU context lives
     # training: equal shards (DistributedSampler pads the last ones with repeated samples when len(ds) % world != 0 -- a handful of

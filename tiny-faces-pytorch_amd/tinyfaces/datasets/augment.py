@@ -248,10 +248,19 @@ def collate_device(samples, templates_d, seed=0, compensate=None, ignore_boxes=N
     (what WIDERFace.__getitem__ + the default collate yield, wider_face.py:219-222).  compensate = (N, T): scale-compensated matching
     (ops.dense_overlap_targets(compensate=)); None = off.  ignore_boxes: per sample the (K, 4) ignore boxes process_inputs(ignore_out=)
     collected, ignore = (measure, thresh) (ops.dense_overlap_targets(ignore_boxes=, ignore=)); None = off.
-    assigner = "atss": the targets come from ops.atss_targets(topk=atss_topk) (no seed, no thresholds; compensate is refused)."""
+    assigner = "atss": the targets come from ops.atss_targets(topk=atss_topk) (no seed, no thresholds; compensate is refused).
+    assigner = "tal": the maps are the base maps (no face assigned; the ignore pass as always) and a fourth element follows, the ResidentFaces
+    of the batch (datasets/targets.py): the criterion assigns from the predictions (compensate is refused)."""
     assigner, atss_topk = ops.check_assigner(assigner, atss_topk, compensate)
     xs = torch.stack([s[0] for s in samples])
     extra = {} if ignore_boxes is None else {"ignore_boxes": [np.array(b, dtype=np.float64).reshape(-1, 4) for b in ignore_boxes], "ignore": ignore}
+    if assigner == "tal":
+        from .targets import TargetAssigner
+        ta = TargetAssigner(templates_d, ignore=None if ignore_boxes is None else (ignore or ops.IGNORE_DEFAULT), assigner="tal")
+        cm, rm, faces = ta([s[1] for s in samples], paste_boxes=[s[2] for s in samples], flips=[int(s[3]) for s in samples], device=xs.device,
+                           ignore_boxes=extra.get("ignore_boxes"))
+        faces.stats = None                                    # nobody reads the counters of a one-off assigner
+        return xs, cm, rm, faces
     if assigner == "atss":
         cm, rm = ops.atss_targets([s[1] for s in samples], templates_d, paste_boxes=[s[2] for s in samples], flips=[int(s[3]) for s in samples],
                                   topk=atss_topk, device=xs.device, **extra)

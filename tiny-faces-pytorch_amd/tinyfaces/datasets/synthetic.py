@@ -149,7 +149,7 @@ class SyntheticFaces(data.Dataset):
                           # the 1/4 level of a 500-pixel image raises IndexError: the mask indexes the 16 heat-map columns with the 25 template indices)
 
     def __init__(self, templates, length=8, seed=0, train=True, device="cuda", size=(500, 500), img_transforms=None, color_jitter=None,
-                 anchor_compensation=None, assigner="dense_overlap", atss_topk=ops.ATSS_TOPK):
+                 anchor_compensation=None, assigner="dense_overlap", atss_topk=ops.ATSS_TOPK, tal_topk=ops.TAL_TOPK, tal_alpha=ops.TAL_ALPHA, tal_beta=ops.TAL_BETA):
         self.templates, self.length, self.seed, self.train, self.device, self.size = templates, length, seed, train, device, size
         # (b, c, s, h) of torchvision's ColorJitter for the training samples: they then travel as uint8 and `collate` jitters + normalises them on the
         # device (ops.image_prepare(jitter=), chains drawn from np.random per sample); None = off, samples are normalised on the host as before
@@ -159,8 +159,9 @@ class SyntheticFaces(data.Dataset):
         # band of the reference would stay untrained -- its anchors answer with arbitrary scores and unregressed boxes, which an AP at IoU 0.5 counts as misses
         # anchor_compensation = (N, T): every face is topped up to N positive anchors (ops.dense_overlap_targets(compensate=)); None = off
         # assigner = "atss": the targets come from ops.atss_targets(topk=atss_topk); the two thresholds above are then unused
+        # assigner = "tal": a training batch is (images, base maps, ResidentFaces): the criterion assigns (datasets/targets.py)
         self.assigner = TargetAssigner(templates, seed=seed, pos_thresh=float(os.environ.get("FACES_POS", "0.7")), neg_thresh=float(os.environ.get("FACES_NEG", "0.7")),
-                                       compensate=anchor_compensation, assigner=assigner, atss_topk=atss_topk)
+                                       compensate=anchor_compensation, assigner=assigner, atss_topk=atss_topk, tal_topk=tal_topk, tal_alpha=tal_alpha, tal_beta=tal_beta)
         self.compensation_stats = self.assigner.stats
         self.rf, self.transforms = ops.RF, img_transforms
         # the layouts (where the faces are) are the fixed part; `samples` = what evaluation sees: every layout on ONE background of its own.
@@ -240,5 +241,4 @@ class SyntheticFaces(data.Dataset):
                 ops.image_prepare(b[0].to(self.device), mean=self.MEAN, std=self.STD, out=imgs[k], jitter=draw_color_jitter(self.color_jitter))
         else:
             imgs = _stack_on_device([b[0] for b in batch], self.device)
-        cm, rm = self.assigner([b[1] for b in batch], paste_boxes=[[0, 0, W, H]] * len(batch), device=self.device)
-        return imgs, cm, rm
+        return (imgs,) + tuple(self.assigner([b[1] for b in batch], paste_boxes=[[0, 0, W, H]] * len(batch), device=self.device))

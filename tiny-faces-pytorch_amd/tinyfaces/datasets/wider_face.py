@@ -76,10 +76,12 @@ def parse_annotations(path, split="train"):
 class WIDERFace(dataset.Dataset):
     def __init__(self, path, templates, img_transforms=None, dataset_root="", split="train", input_size=(500, 500),
                  heatmap_size=(63, 63), pos_thresh=0.7, neg_thresh=0.3, pos_fraction=0.5, debug=False, device="cuda", seed=0, color_jitter=None,
-                 anchor_compensation=None, ignore_policy=None, ignore=None, assigner="dense_overlap", atss_topk=ops.ATSS_TOPK):
+                 anchor_compensation=None, ignore_policy=None, ignore=None, assigner="dense_overlap", atss_topk=ops.ATSS_TOPK, tal_topk=ops.TAL_TOPK, tal_alpha=ops.TAL_ALPHA, tal_beta=ops.TAL_BETA):
         """assigner = "atss": the training targets come from ops.atss_targets(topk=atss_topk) (the rule in include/tinyfaces_hip.h) instead of the
         reference's fixed thresholds.  pos_thresh / neg_thresh are then unused except by the crop filter of the augmentation, which keeps reading
-        neg_thresh; `compensation_stats` collects the faces that won at most 3 positives and those that won none."""
+        neg_thresh; `compensation_stats` collects the faces that won at most 3 positives and those that won none.
+        assigner = "tal": a training batch carries the base maps and, as a fourth element, the ResidentFaces of the batch (datasets/targets.py);
+        the criterion assigns from the predictions.  tal_topk / tal_alpha / tal_beta are checked and kept for whoever builds that criterion."""
         super().__init__()
         # ignore regions (augment.IgnorePolicy: which faces become don't-care regions instead of positives; ignore = (measure, thresh) of
         # ops.dense_overlap_targets(ignore_boxes=, ignore=), None = ("iof", 0.5)), applied in `collate`; ignore_policy None = off
@@ -92,7 +94,7 @@ class WIDERFace(dataset.Dataset):
         # the one assigner object of `collate` (datasets/targets.py) owns the thresholds, anchor_compensation = (N, T) of the scale-compensated
         # matching (None = off), the ignore pair, the assigner and atss_topk, and the counters that go with them
         self._targets = TargetAssigner(templates, heatmap_size, RF, pos_thresh, neg_thresh, compensate=anchor_compensation, ignore=ignore,
-                                       assigner=assigner, atss_topk=atss_topk)
+                                       assigner=assigner, atss_topk=atss_topk, tal_topk=tal_topk, tal_alpha=tal_alpha, tal_beta=tal_beta)
         self.ignore, self.ignore_stats = self._targets.ignore, self._targets.ignore_stats
         self.anchor_compensation, self.compensation_stats = self._targets.compensate, self._targets.stats
         self.assigner, self.atss_topk = self._targets.assigner, self._targets.atss_topk
@@ -170,10 +172,10 @@ class WIDERFace(dataset.Dataset):
                     ignores.append(np.array(ign, dtype=np.float64).reshape(-1, 4))
                 boxes.append(b); pastes.append(paste); flips.append(int(flip))
             self._step += 1
-            cm, rm = self._targets(boxes, pastes, flips, device=self.device, seed=self._step,
-                                   ignore_boxes=ignores if self.ignore_policy is not None else None)
+            cm, rm, *faces = self._targets(boxes, pastes, flips, device=self.device, seed=self._step,
+                                           ignore_boxes=ignores if self.ignore_policy is not None else None)
         cur = torch.cuda.current_stream(self.device)
         cur.wait_stream(self._in_stream)
-        for t in (x, cm, rm):
+        for t in (x, cm, rm) + tuple(t for f in faces for t in (f.boxes_d, f.offs_d, f.paste_d, f.flips_d) if t is not None):
             t.record_stream(cur)                              # the caching allocator must not recycle them under the consumer
-        return x, cm, rm
+        return (x, cm, rm) + tuple(faces)                     # assigner = "tal": the ResidentFaces as a fourth element

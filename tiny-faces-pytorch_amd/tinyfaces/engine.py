@@ -738,7 +738,21 @@ class TrainEngine:
         finally:
             ops.set_deterministic(prev)
 
-    def _step(self, x, class_map, regression_map, apply=None):
+    def step_with_faces(self, x, class_map, regression_map, faces, apply=None):
+        """`step` for a criterion with assigner=TaskAligned(...): faces is the ResidentFaces of the batch (tinyfaces/datasets/targets.py), the
+        two maps arrive as the base maps and the criterion completes them in place from the forward output before its loss pass (see _step).
+        A method of its own: `step` keeps the signature it had."""
+        if faces is None:
+            raise ValueError("TrainEngine.step_with_faces: faces (the ResidentFaces of the batch) is required; without an assigner call step()")
+        if not self.deterministic:
+            return self._step(x, class_map, regression_map, apply, faces)
+        prev = ops.set_deterministic(True)
+        try:
+            return self._step(x, class_map, regression_map, apply, faces)
+        finally:
+            ops.set_deterministic(prev)
+
+    def _step(self, x, class_map, regression_map, apply=None, faces=None):
         """x (B,3,H,W) f32, class_map (B,nt,h,w) f32 (mined in place by the soft-margin criterion; only read with cls_loss="focal" / "qfl"), regression_map (B,4nt,h,w) f32: all on the device.
         Returns the device tensor [sum cls loss, sum reg loss] (float64) without synchronising; with cls_loss="qfl" it has two more elements,
         [..., sum of the quality targets q over the positives, number of positives] (whatever the criterion's _fwd_bwd returns goes to its meters).
@@ -750,14 +764,19 @@ class TrainEngine:
         `steps` and still returns its loss.  With ema_decay the same launches also advance `self.ema` (see __init__).
         With accum_steps = N > 1 every call is one micro-batch (`micro_steps`), and the N-th of a window is the optimizer step (`steps`) on
         the sum of the window's gradients.  apply=True: apply now, over the k <= N micro-batches accumulated (the last batch of an epoch);
-        apply=False: accumulate only (ValueError on the micro-batch that fills the window); None: apply when the window is full."""
+        apply=False: accumulate only (ValueError on the micro-batch that fills the window); None: apply when the window is full.
+        faces: the ResidentFaces of the batch, for a criterion with assigner=TaskAligned(...): the two maps arrive as the base maps and the
+        criterion completes them from the forward output, in place, before its loss pass (DetectionCriterion._fwd_bwd)."""
         m, c = self.model, self.criterion
         accumulating = self.accum_steps > 1
         applies = self._applies(apply) if accumulating or apply is not None else True
         m._check_partial_freeze()
         m._sync_tables(x.device)
         out = m._run_forward(x, training=True)
-        loss2, grad, _ = c._fwd_bwd(out, class_map, regression_map)
+        if faces is None:
+            loss2, grad, _ = c._fwd_bwd(out, class_map, regression_map)
+        else:
+            loss2, grad, _ = c._fwd_bwd(out, class_map, regression_map, faces=faces)
         if self._native is not None:         # (bench.py measures a step without the exchange: the C hook is simply not installed for it)
             m._grad_callback = None if self.skip_allreduce else C.cast(lib().tf_comm_allreduce_hook, C.c_void_p)
             self._native["plan"].issued, self._native["plan"].rc = 0, 0       # a step that raised half-way must not poison the next one

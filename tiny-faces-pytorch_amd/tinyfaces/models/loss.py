@@ -4,7 +4,9 @@ and d(total)/d(output), with no device->host->device round trip (loss.py:47-57 d
 `cls_loss="focal"` is the one addition to that surface: sigmoid focal loss over every labelled anchor, no mining and no sampling, by the
 focal form of the same pass (tf_criterion_focal_fwd_bwd); `reg_loss="iou" | "giou" | "diou"` gives that form an overlap regression loss, one
 term per positive in place of the four SmoothL1 terms (tf_criterion_focal_box_fwd_bwd).  `cls_loss="qfl"` is the quality focal form of that pass
-(tf_criterion_quality_fwd_bwd): a positive's logit is trained towards the IoU of its own predicted box with its target."""
+(tf_criterion_quality_fwd_bwd): a positive's logit is trained towards the IoU of its own predicted box with its target.
+`assigner=TaskAligned(...)` puts the task-aligned target assignment (tf_targets_tal) in front of whichever pass is chosen: the maps arrive
+without a face assigned and the positives are chosen from the output itself."""
 import torch
 from torch import nn
 
@@ -31,10 +33,27 @@ class AvgMeter:
         self.average = (seen * self.average + float(loss)) / self.num_averaged
 
 
+class TaskAligned:
+    """The parameters of the task-aligned assignment (TOOD's TaskAlignedAssigner; the rule is in include/tinyfaces_hip.h, "TAL"): every face
+    claims its `topk` anchors of largest sigmoid(logit)^alpha * IoU(predicted box, face)^beta among those whose centre lies inside it.
+    topk an integer in 1..32, alpha finite and >= 0, beta finite and > 0 (ValueError otherwise).  Hand it to DetectionCriterion(assigner=)."""
+
+    __slots__ = ("topk", "alpha", "beta")
+
+    def __init__(self, topk=ops.TAL_TOPK, alpha=ops.TAL_ALPHA, beta=ops.TAL_BETA):
+        self.topk, self.alpha, self.beta = ops.check_tal(topk, alpha, beta)
+
+    def __repr__(self):
+        return f"TaskAligned(topk={self.topk}, alpha={self.alpha}, beta={self.beta})"
+
+
 class _CriterionFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, output, owner, class_map, regression_map):
-        loss2, grad, labels = owner._fwd_bwd(output.detach(), class_map, regression_map, want_labels=owner.keep_labels)
+    def forward(ctx, output, owner, class_map, regression_map, faces=None):
+        if faces is None:
+            loss2, grad, labels = owner._fwd_bwd(output.detach(), class_map, regression_map, want_labels=owner.keep_labels)
+        else:
+            loss2, grad, labels = owner._fwd_bwd(output.detach(), class_map, regression_map, want_labels=owner.keep_labels, faces=faces)
         ctx.save_for_backward(grad)
         owner._loss2 = loss2
         owner.sampled_class_map = labels
@@ -44,7 +63,7 @@ class _CriterionFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
-        return grad * g.to(grad.dtype), None, None, None
+        return grad * g.to(grad.dtype), None, None, None, None
 
 
 class DetectionCriterion(nn.Module):
@@ -73,15 +92,34 @@ class DetectionCriterion(nn.Module):
     with it; no OHEM and no sampling, as with focal; `focal_gamma` and `focal_alpha` are unused, `focal_normalize` keeps its meaning.
     `qfl_beta` must be finite and >= 1; for 1 <= beta < 2 the gradient is ill-conditioned where sigma is close to q, and for beta = 1 it
     jumps at sigma = q.  The loss vector then has four elements, [cls, reg, sum of q over the positives, number of positives], and
-    `quality_average` (a third AvgMeter, fed with the last two) is the mean IoU of the predicted boxes of all positives seen with their targets."""
+    `quality_average` (a third AvgMeter, fed with the last two) is the mean IoU of the predicted boxes of all positives seen with their targets.
+
+    `assigner=TaskAligned(topk, alpha, beta)`: task-aligned target assignment (Feng et al. 2021, TOOD) from the network's own output, on the device,
+    between the forward pass and the loss pass above (ops.tal_assign_device; the rule is in include/tinyfaces_hip.h, "TAL").  `forward` /
+    `_fwd_bwd` then take `faces`, the ResidentFaces of the batch (tinyfaces/datasets/targets.py; what a loader with assigner="tal" delivers as its
+    fourth element), and `class_map` / `regression_map` arrive as the base maps (no face assigned) and are completed IN PLACE, under no_grad,
+    before the loss pass reads them: every `cls_loss` / `reg_loss` combination works unchanged.  `templates` (the (nt, 4 or 5) table) and `rf`
+    (the receptive-field geometry) are required with it.  The match counts go to `faces.stats` (the loader's CompensationStats) when there is
+    one.  `faces` without an assigner, and an assigner without `faces`, is a ValueError.  Not implemented: TOOD's normalised alignment value as
+    the classification target (cls_loss="qfl" trains towards the IoU of the same predicted box instead), varifocal loss, score-weighted regression."""
 
     CLS_LOSSES = ("soft_margin", "focal", "qfl")
     REG_LOSSES = ("smooth_l1", "iou", "giou", "diou")
 
     def __init__(self, n_templates=25, reg_weight=1, pos_fraction=0.5, seed=0, lazy_meters=False, keep_labels=False,
                  cls_loss="soft_margin", focal_gamma=2.0, focal_alpha=0.25, focal_normalize="pos", reg_loss="smooth_l1", templates=None,
-                 qfl_beta=2.0):
+                 qfl_beta=2.0, assigner=None, rf=None):
         super().__init__()
+        if assigner is not None:
+            if not isinstance(assigner, TaskAligned):
+                raise ValueError(f"DetectionCriterion: assigner must be None or a TaskAligned, got {assigner!r}")
+            if templates is None:
+                raise ValueError("DetectionCriterion: assigner=TaskAligned(...) needs templates (the anchors the predictions are decoded against)")
+            t = ops._upload_templates(templates, "cpu")
+            if t.dim() != 2 or t.shape[0] != n_templates or t.shape[1] < 4:
+                raise ValueError(f"DetectionCriterion: templates must be an (n_templates, >= 4) table, got shape {tuple(t.shape)}")
+            self._templates_f64 = t
+        self.assigner, self.rf = assigner, (ops.RF if rf is None else rf)
         if cls_loss not in self.CLS_LOSSES:
             raise ValueError(f"DetectionCriterion: cls_loss must be one of {self.CLS_LOSSES}, got {cls_loss!r}")
         ops.check_focal(focal_gamma, focal_alpha, focal_normalize)
@@ -137,11 +175,29 @@ class DetectionCriterion(nn.Module):
             self._template_wh = self._template_wh.to(device)
         return self._template_wh
 
-    def _fwd_bwd(self, out, class_map, regression_map, want_labels=False):
+    def _assign(self, out, class_map, regression_map, faces):
+        """The task-aligned assignment in front of the loss pass: completes the two maps in place from `out` (only read, under no_grad)."""
+        if self.assigner is None:
+            raise ValueError("DetectionCriterion: faces= needs assigner=TaskAligned(...) at construction")
+        if self._templates_f64.device != out.device:
+            self._templates_f64 = self._templates_f64.to(out.device)
+        want = getattr(faces, "stats", None) is not None
+        with torch.no_grad():
+            res = ops.tal_assign_device(out.contiguous(), class_map, regression_map, faces.boxes_d, faces.offs_d, faces.total, self._templates_f64, None, self.rf,
+                                        faces.paste_d, faces.flips_d, self.assigner.topk, self.assigner.alpha, self.assigner.beta, return_match_count=want)
+        if want:
+            faces.stats.push(res[2])
+
+    def _fwd_bwd(self, out, class_map, regression_map, want_labels=False, faces=None):
         """The fused loss + gradient pass of this criterion's `cls_loss`, for the autograd function above and for TrainEngine.step:
         (loss[2] f64 device tensor, d(total)/d(out), labels that entered the loss).  soft_margin mines `class_map` in place and returns
         the sampled labels if `want_labels`, else None; focal and qfl only read `class_map`, which IS the labels that entered.  With qfl the
-        loss tensor has four elements: [cls, reg, sum of q over the positives, number of positives]."""
+        loss tensor has four elements: [cls, reg, sum of q over the positives, number of positives].
+        faces (with assigner=TaskAligned(...) only, and then required): the two maps are first completed in place by the task-aligned assignment."""
+        if faces is not None:
+            self._assign(out, class_map, regression_map, faces)
+        elif getattr(self, "assigner", None) is not None:
+            raise ValueError("DetectionCriterion: assigner=TaskAligned(...) needs faces= (the ResidentFaces of the batch)")
         if self.reg_loss != "smooth_l1":
             ops.check_reg_loss(self.reg_loss, self.reg_weight, self._template_wh, self.n_templates)
             self._check_reg_with_cls(self.reg_loss, self.cls_loss)
@@ -180,12 +236,18 @@ class DetectionCriterion(nn.Module):
         if len(v) >= 4 and v[3] > 0:
             self.quality_average.update(v[2], int(v[3]))
 
-    def forward(self, output, class_map, regression_map):
+    def forward(self, output, class_map, regression_map, faces=None):
+        if (faces is None) != (self.assigner is None):
+            raise ValueError("DetectionCriterion: faces= and assigner=TaskAligned(...) go together" if faces is not None else
+                             "DetectionCriterion: assigner=TaskAligned(...) needs faces= (the ResidentFaces of the batch)")
         if not output.is_cuda:
             raise RuntimeError("DetectionCriterion: HIP kernel only (no CPU fallback)")
         if class_map.dtype != torch.float32 or not class_map.is_contiguous():
             class_map = class_map.float().contiguous()
-        total = _CriterionFunction.apply(output, self, class_map, regression_map.float())
+        if faces is None:
+            total = _CriterionFunction.apply(output, self, class_map, regression_map.float())
+        else:
+            total = _CriterionFunction.apply(output, self, class_map, regression_map.float().contiguous(), faces)
         self.total_loss = total
         loss2 = self._loss2
         self.masked_class_loss, self.masked_reg_loss = loss2[0], loss2[1]   # already summed (loss.py:87-91 only uses .sum())

@@ -267,13 +267,14 @@ def dense_overlap_targets_device(boxes_d, offs_d, total_boxes, templates_d, heat
                             return_match_count, return_ignored_count, comp=comp, seed=seed, pos_thresh=pos_thresh, neg_thresh=neg_thresh)
 
 
-ASSIGNERS = ("dense_overlap", "atss")
+ASSIGNERS = ("dense_overlap", "atss", "tal")
 ATSS_TOPK = 9                                             # ATSSAssigner's default
 
 
 def check_assigner(assigner, atss_topk=ATSS_TOPK, compensate=None):
-    """assigner "dense_overlap" (the reference's fixed thresholds) or "atss" (include/tinyfaces_hip.h, "ATSS"); atss_topk an integer in 1..16,
-    the candidates per template and face.  compensate next to "atss" is refused: the compensation stage is defined on the perturbed-IoU owner
+    """assigner "dense_overlap" (the reference's fixed thresholds), "atss" (include/tinyfaces_hip.h, "ATSS") or "tal" (there, "TAL": the loader
+    delivers the base maps and the resident faces, the criterion assigns from the predictions; its own parameters go through `check_tal`);
+    atss_topk an integer in 1..16, the candidates per template and face.  compensate next to "atss" or "tal" is refused: the compensation stage is defined on the perturbed-IoU owner
     of dense_overlap's first stage, which ATSS does not compute.  Returns (str assigner, int atss_topk); anything else raises ValueError."""
     if not isinstance(assigner, str) or assigner not in ASSIGNERS:
         raise ValueError(f"assigner must be one of {list(ASSIGNERS)}, not {assigner!r}")
@@ -282,6 +283,9 @@ def check_assigner(assigner, atss_topk=ATSS_TOPK, compensate=None):
     if assigner == "atss" and compensate is not None:
         raise ValueError("assigner='atss' does not take compensate / anchor_compensation: the compensation stage tops up the owner that the "
                          "dense_overlap assignment computes; ATSS already gives every face a comparable number of positives")
+    if assigner == "tal" and compensate is not None:
+        raise ValueError("assigner='tal' does not take compensate / anchor_compensation: the compensation stage tops up the owner that the "
+                         "dense_overlap assignment computes; TAL gives every face up to tal_topk positives of its own choosing")
     return assigner, int(atss_topk)
 
 
@@ -323,6 +327,71 @@ def atss_targets_device(boxes_d, offs_d, total_boxes, templates_d, heatmap_size=
     operands = _resident_operands("atss_targets_device", boxes_d, offs_d, total_boxes, templates_d, paste_d, flips_d, ignore_d, ignore_offs_d, total_ignore)
     return _assign_resident("atss_targets_device", operands, heatmap_size, rf, out, ignore_d is not None, "ignore_d / ignore_offs_d", ignore,
                             return_match_count, return_ignored_count, topk=k)
+
+
+TAL_TOPK, TAL_ALPHA, TAL_BETA = 13, 1.0, 6.0              # mmdetection's TaskAlignedAssigner defaults
+
+
+def check_tal(topk=TAL_TOPK, alpha=TAL_ALPHA, beta=TAL_BETA):
+    """The parameters of the task-aligned assignment (include/tinyfaces_hip.h, "TAL"): topk an integer in 1..32, alpha finite and >= 0, beta
+    finite and > 0.  Returns (int topk, float alpha, float beta); anything else raises ValueError."""
+    if isinstance(topk, bool) or not isinstance(topk, (int, np.integer)) or not 1 <= int(topk) <= 32:
+        raise ValueError(f"tal: topk must be an integer in 1..32, not {topk!r}")
+    for name, v, ok in (("alpha", alpha, lambda x: x >= 0), ("beta", beta, lambda x: x > 0)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)) or not ok(float(v)):
+            raise ValueError(f"tal: {name} must be a finite number {'>= 0' if name == 'alpha' else '> 0'}, not {v!r}")
+    return int(topk), float(alpha), float(beta)
+
+
+def tal_assign_device(output, class_map, regression_map, boxes_d, offs_d, total_boxes, templates_d, heatmap_size=None, rf=RF, paste_d=None,
+                      flips_d=None, topk=TAL_TOPK, alpha=TAL_ALPHA, beta=TAL_BETA, return_match_count=False):
+    """Task-aligned assignment (tf_targets_tal; the rule is in include/tinyfaces_hip.h, "TAL") with every operand resident, IN PLACE on the two
+    maps: per face the anchors whose centre lies strictly inside it are measured by sigmoid(logit)^alpha * IoU(predicted box, face)^beta, the
+    face claims its `topk` best, an anchor two faces claim goes to the larger IoU, and every won anchor gets +1 and the face's four regression
+    values.  Nothing else of either map is written: they arrive as the base maps (an assignment without faces, ignore pass applied).
+    output (B, 5 nt, vsy, vsx) f32 contiguous, the head's output (only read; nothing flows back into it); class_map (B, nt, vsy, vsx) f32,
+    regression_map (B, 4 nt, vsy, vsx) f32, both contiguous; boxes_d (total, 4) f64 (degenerate boxes removed), offs_d (B + 1,) i32, total_boxes
+    the host's copy of its last entry, templates_d (nt, >= 4) f64, paste_d (B, 4) i32, flips_d (B,) i32.  heatmap_size, if given, must be the maps'.
+    Returns (class_map, regression_map[, match_count (total,) int32]).  No face in the batch: nothing is enqueued."""
+    k, a, bt = check_tal(topk, alpha, beta)
+    require_gpu(output, "tal_assign_device")
+    for name, v in (("output", output), ("class_map", class_map), ("regression_map", regression_map)):
+        if not torch.is_tensor(v) or v.dtype != torch.float32 or v.dim() != 4 or not v.is_contiguous() or v.device != output.device:
+            raise ValueError(f"tal_assign_device: {name} is a contiguous float32 4-d tensor on the output's device")
+    B, nt, vsy, vsx = class_map.shape
+    if output.shape != (B, 5 * nt, vsy, vsx) or regression_map.shape != (B, 4 * nt, vsy, vsx):
+        raise ValueError(f"tal_assign_device: output {tuple(output.shape)} / regression_map {tuple(regression_map.shape)} do not go with the "
+                         f"class map {tuple(class_map.shape)}")
+    if heatmap_size is not None and tuple(heatmap_size) != (vsy, vsx):
+        raise ValueError(f"tal_assign_device: heatmap_size {tuple(heatmap_size)} is not the maps' {(vsy, vsx)}")
+    if offs_d.numel() != B + 1 or templates_d.dim() != 2 or templates_d.shape[0] != nt or templates_d.dtype != torch.float64 or boxes_d.dtype != torch.float64:
+        raise ValueError("tal_assign_device: offs_d is (B + 1,) int32, templates_d (nt, >= 4) float64 and boxes_d (total, 4) float64")
+    total, dev = int(total_boxes), output.device
+    mc = torch.empty(total, dtype=torch.int32, device=dev) if return_match_count else None
+    if total > 0:
+        ofy, ofx = rf["offset"]
+        sty, stx = rf["stride"]
+        wsb = lib().tf_targets_tal_workspace_bytes(total, B, nt, vsy, vsx)
+        ws = _workspace("targets_tal", wsb, dev)
+        check(lib().tf_targets_tal(ptr(output), ptr(boxes_d), ptr(offs_d), B, ptr(templates_d), nt, templates_d.shape[1], vsy, vsx, ofy, ofx, sty, stx,
+                                   ptr(paste_d), ptr(flips_d), k, a, bt, ptr(mc), ptr(class_map), ptr(regression_map), ptr(ws), wsb, stream()),
+              "tf_targets_tal")
+    return (class_map, regression_map) + ((mc,) if return_match_count else ())
+
+
+def tal_assign(output, class_map, regression_map, boxes_per_image, templates, rf=RF, paste_boxes=None, flips=None, topk=TAL_TOPK,
+               alpha=TAL_ALPHA, beta=TAL_BETA, return_match_count=False):
+    """`tal_assign_device` from host lists: boxes_per_image a list of (G_i, 4) float64 arrays / tensors (degenerate ones are dropped), templates
+    the (nt, 4 or 5) table, paste_boxes (B, 4) and flips (B,) as dense_overlap_targets takes them.  IN PLACE on the two device maps."""
+    check_tal(topk, alpha, beta)
+    require_gpu(output, "tal_assign")
+    if len(boxes_per_image) != output.shape[0]:
+        raise ValueError(f"tal_assign: {len(boxes_per_image)} lists of boxes for {output.shape[0]} images")
+    with torch.cuda.device(output.device):
+        (boxes_d, offs_d, total), t_d, paste_d, flips_d, _, _, _ = _upload_lists("tal_assign", boxes_per_image, templates, paste_boxes, flips, None,
+                                                                                 output.device)
+        return tal_assign_device(output, class_map, regression_map, boxes_d, offs_d, total, t_d, None, rf, paste_d, flips_d, topk, alpha, beta,
+                                 return_match_count)
 
 
 def dense_overlap_iou(boxes, templates, heatmap_size=(63, 63), rf=RF, device="cuda"):

@@ -40,7 +40,7 @@ def print_compensation(idx, epoch, size, dataloader, lag=0):
     if got is not None:
         faces, at_most, below = got
         if getattr(stats, "atss", False):                 # the ATSS assigner pushes its match counts into the same object
-            print(f"Epoch: [{epoch}][{idx}/{size}]\tATSS: {at_most} of {faces} faces won at most {stats.n} positives, {below} of them none")
+            print(f"Epoch: [{epoch}][{idx}/{size}]\t{getattr(stats, 'label', 'ATSS')}: {at_most} of {faces} faces won at most {stats.n} positives, {below} of them none")
             return
         print(f"Epoch: [{epoch}][{idx}/{size}]\tanchor compensation: {at_most} of {faces} faces hold at most N = {stats.n} positives after the stage, "
               f"{below} of them fewer (their candidates ran out)")
@@ -109,6 +109,8 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
     this call found there times warmup_factor(first_T + k, N, F); the found values are put back at the end (the epoch scheduler goes on
     from them).  first_T is the global index of this epoch's first optimizer step.  None or N = 0: the groups are not touched.
 
+    A batch of four elements (a loader with assigner="tal") hands its fourth, the ResidentFaces record, to `loss_fn(..., faces=)`.
+
     deterministic: the library's deterministic switch (ops.set_deterministic) is on for the duration of the call and put back at its end: the
     native forward and backward under autograd then run without floating-point atomics (what torch's own optimizer and losses do is theirs).
     False (the default): no new call."""
@@ -131,8 +133,11 @@ def train(model, loss_fn, optimizer, dataloader, epoch, device, max_grad_norm=No
     det_prev = ops.set_deterministic(True) if deterministic else None
     try:
         for step, batch in enumerate(dataloader):
-            image, cls_target, reg_target = (t.float().to(device, non_blocking=True) for t in batch)
-            loss = loss_fn(net(image), cls_target, reg_target)
+            image, cls_target, reg_target = (t.float().to(device, non_blocking=True) for t in batch[:3])
+            if len(batch) > 3:                  # a loader with assigner="tal": the resident faces travel as they are; the criterion assigns
+                loss = loss_fn(net(image), cls_target, reg_target, faces=batch[3].to(device, non_blocking=True))
+            else:
+                loss = loss_fn(net(image), cls_target, reg_target)
             if window == 0:
                 optimizer.zero_grad()
             loss.backward()
