@@ -222,6 +222,36 @@ int tf_targets_tal(const float* output, const double* boxes, const int32_t* box_
                    int topk, double alpha, double beta, int32_t* match_count,
                    float* class_map, float* reg_map,
                    void* ws, size_t ws_bytes, void* stream);
+/* ---- TAL, step 7: the normalised alignment of every won anchor (TOOD's target of the classification loss and weight of the box loss) ----
+ * tf_targets_tal_aligned is tf_targets_tal -- the same operands, the same rule, the same bits in class_map, reg_map and match_count -- and
+ * one more output, align_map [B][nt][vsy][vsx] f32:
+ *   7 alignment   after step 4 let W_g be the anchors face g WON (not the anchors it claimed: a claim lost in a conflict does not count).  For a
+ *                 non-empty W_g:  M_g = max of m over W_g,  U_g = max of u over W_g  (comparisons: exact given the operands), with m and u the
+ *                 very float64 values steps 1-4 ranked and resolved by.  For a in W_g
+ *                     t(a) = (m_a / M_g) * U_g      float64, the division first, then the product, without contraction;
+ *                     t(a) = 0                      when M_g == 0 (every winner's sigmoid underflowed: logits of -1e4 with alpha = 1);
+ *                 align_map(a) = (float)t(a).  Every OTHER element of align_map is 1.0f: the map is written completely by every call, is never
+ *                 memset and may arrive holding anything (NaN included); an anchor whose +1 label is not this call's keeps the hard target 1.
+ *                 The face's best winner gets exactly (float)U_g, and 0 <= t <= U_g <= 1.
+ *                 NO epsilon.  mmdetection's TaskAlignedAssigner divides by (M_g + 1e-7).  At zero output a 6-px face lies inside the smallest
+ *                 of the 25 anchors (20.3 x 22.2 px): u = 36 / 452 = 0.080 and m = 0.5 * 0.080^6 = 1.3e-7, so that epsilon would cut every target
+ *                 of the face to 0.56 of U_g, and to a fifth for a face whose best u is 0.06 (m = 2e-8): the faces this detector exists for
+ *                 would be trained towards scores that are too low by such a factor at the start of training.  This project adds no epsilon
+ *                 anywhere; M_g == 0 is the one case a quotient is undefined in, and it is defined above.
+ * The same four launches: the clear also stores the 1.0f of every anchor, claim keeps every winner's m (its bits, not a value formed again)
+ * next to its key in the workspace, and write -- one wave per face -- reduces M_g and U_g over the lanes that won by wave shuffles and stores
+ * t beside the +1.  No further atomics, no fifth launch, no floating-point atomic, no grid barrier, no host synchronisation; the same bits on
+ * every run.  The workspace is 8 bytes per winner slot larger (tf_targets_tal_aligned_workspace_bytes); as in tf_targets_tal, a workspace too
+ * small for box_offsets[B] makes every kernel return without writing, align_map included.
+ * Refused before anything is enqueued: what tf_targets_tal refuses, and a NULL align_map (TF_ERR_ARG). */
+size_t tf_targets_tal_aligned_workspace_bytes(int total_boxes, int B, int nt, int vsy, int vsx);
+int tf_targets_tal_aligned(const float* output, const double* boxes, const int32_t* box_offsets, int B,
+                           const double* templates, int nt, int tstride,
+                           int vsy, int vsx, int ofy, int ofx, int sty, int stx,
+                           const int32_t* paste_boxes, const int32_t* flips,
+                           int topk, double alpha, double beta, int32_t* match_count,
+                           float* class_map, float* reg_map, float* align_map /*[B][nt][vsy][vsx]*/,
+                           void* ws, size_t ws_bytes, void* stream);
 /* test hook: the raw rounded IoU tensor [vsy][vsx][nt][G] f64 for ONE image */
 int tf_dense_overlap_iou(const double* boxes, int G, const double* templates, int nt, int tstride,
                          int vsy, int vsx, int ofy, int ofx, int sty, int stx,
@@ -524,6 +554,34 @@ int tf_criterion_focal_box_fwd_bwd(const float* output, const float* class_map, 
 size_t tf_criterion_quality_workspace_bytes(int B, int nt, int H, int W);
 int tf_criterion_quality_fwd_bwd(const float* output, const float* class_map, const float* reg_map, int B, int nt, int H, int W,
                                  float beta, int normalize, float reg_weight,
+                                 int reg_form, const float* template_wh /*[nt][2], device; may be NULL unless TF_REG_DIOU*/,
+                                 float* grad_out, double* loss_out /*[4]*/, int32_t* npos_out /*[B], may be NULL*/,
+                                 void* ws, size_t ws_bytes, void* stream);
+
+/* ---- detection criterion, task-aligned form (Feng et al. 2021, TOOD): the assigner's normalised alignment as target and box weight ----
+ * tf_criterion_quality_fwd_bwd with the target of a positive READ from align_map [B][nt][H][W] f32 (what tf_targets_tal_aligned wrote) in
+ * place of the IoU of its own box, and with the regression term of every positive weighted by that target: same layout, three launches,
+ * summation order and determinism.  For an element with label y, class logit s and map value a:
+ *   y =  0   contributes nothing; all five gradient channels are 0
+ *   y = -1   q = 0; a is not read
+ *   y = +1   q = fminf(1, fmaxf(0, a)): a NaN gives 0
+ *   classification  exactly the QFL arithmetic above with this q: sigma, d = sigma - q, BCE = softplus(s) - q s in their stable forms,
+ *            QFL = |d|^beta BCE and its derivative, beta = 2 without powf.  q is a constant
+ *   regression      the term of reg_form (all four TF_REG_*, by the arithmetic of tf_criterion_focal_box_fwd_bwd; TF_REG_SMOOTH_L1: the sum of
+ *            the four SmoothL1 terms, added in fp32) TIMES q; its four derivatives times q * (reg_weight * normaliser)
+ *   normalize       TF_FOCAL_NORM_NONE and TF_FOCAL_NORM_POS as in the focal form.  TF_FOCAL_NORM_ALIGN: both sums and all five gradient
+ *            channels of image b times 1 / max(1, Q_b), Q_b = the sum of q over ITS positives: TOOD's avg_factor, taken per image and not per
+ *            batch, so that an image's loss still depends neither on its batch nor on the number of ranks.  Q_b is an fp64 sum of per-block fp64
+ *            partials added in a fixed order by every block that needs it; the gradient's factor is (float)(1 / max(1, Q_b))
+ * loss_out[0] = sum cls, loss_out[1] = sum of the q-weighted regression terms (not weighted by reg_weight), both normalised;
+ * loss_out[2] = sum of q over all positives of the batch, NOT normalised; loss_out[3] = sum_b npos_b: [2] / [3] is the mean target.
+ * grad_out is written completely, every element exactly once.  No floating-point atomics: the same bits on every run.
+ * TF_ERR_ARG: what tf_criterion_quality_fwd_bwd refuses, a NULL align_map, a normalize outside the three values (TF_FOCAL_NORM_ALIGN passed to
+ * any other entry point stays TF_ERR_ARG); TF_ERR_WORKSPACE: ws NULL or below tf_criterion_aligned_workspace_bytes.  Nothing is enqueued then. */
+#define TF_FOCAL_NORM_ALIGN 2
+size_t tf_criterion_aligned_workspace_bytes(int B, int nt, int H, int W);
+int tf_criterion_aligned_fwd_bwd(const float* output, const float* class_map, const float* reg_map, const float* align_map,
+                                 int B, int nt, int H, int W, float beta, int normalize, float reg_weight,
                                  int reg_form, const float* template_wh /*[nt][2], device; may be NULL unless TF_REG_DIOU*/,
                                  float* grad_out, double* loss_out /*[4]*/, int32_t* npos_out /*[B], may be NULL*/,
                                  void* ws, size_t ws_bytes, void* stream);

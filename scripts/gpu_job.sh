@@ -22,6 +22,7 @@
 #   color-jitter               cost of the colour jitter: image_prepare plain / three ops / four ops / contrast alone on the 500x500 window, batch building with / without it (scripts/color_jitter_numbers.py) -> $COLOR_JITTER_OUT (default profiles/color_jitter.jsonl)
 #   quality-loss               cost of the quality focal loss: the qfl call next to the focal call of the same reg_loss on the step's operands, the bf16 step with either (scripts/quality_loss_numbers.py) -> $QUALITY_LOSS_OUT (default profiles/quality_loss.jsonl)
 #   tal                        cost of the task-aligned assignment: the resident call next to the ATSS call at k = 9 on outputs of a real forward pass, the bf16 step assigning by TAL next to the step fed ATSS maps, two synthetic-faces epochs under either (scripts/tal_numbers.py) -> $TAL_OUT (default profiles/tal.jsonl)
+#   tal-aligned                cost of TOOD's task-aligned loss: the assignment with align_out next to the plain call, the aligned criterion next to the qfl call, the bf16 step with either, two synthetic-faces epochs under either (scripts/tal_aligned_numbers.py) -> $TAL_ALIGNED_OUT (default profiles/tal_aligned.jsonl)
 #   dist-smoke                 RCCL 1-rank group, 2 gloo ranks on one GPU, 2 nccl ranks on one GPU (expected refusal) -> gpurun_out/dist_smoke.txt
 #   final                      tests + bench + prof + pmc-traffic + layer-table + timeline + eval prof + smoke: the artefacts of a round
 set -u
@@ -122,6 +123,12 @@ print(d['value'], d['ms_per_step'], 'frac', r.get('frac'), 'fwd', r.get('forward
       timeout -k 10 ${TAL_TIMEOUT:-300} python scripts/tal_numbers.py --step steps >> "$out" 2>> "$err" &&
       timeout -k 10 ${TAL_TIMEOUT:-300} python scripts/tal_numbers.py --step epochs >> "$out" 2>> "$err"
     echo "tal exit $?"; cat "$out"; tail -3 "$err" ;;
+  tal-aligned)   # one process and one time limit per step; a step only behind a clean one before it
+    out=${TAL_ALIGNED_OUT:-$R/profiles/tal_aligned.jsonl}; err=${out%.jsonl}.err
+    timeout -k 10 ${TAL_ALIGNED_TIMEOUT:-300} python scripts/tal_aligned_numbers.py --step calls > "$out" 2> "$err" &&
+      timeout -k 10 ${TAL_ALIGNED_TIMEOUT:-300} python scripts/tal_aligned_numbers.py --step steps >> "$out" 2>> "$err" &&
+      timeout -k 10 ${TAL_ALIGNED_TIMEOUT:-300} python scripts/tal_aligned_numbers.py --step epochs >> "$out" 2>> "$err"
+    echo "tal-aligned exit $?"; cat "$out"; tail -3 "$err" ;;
   dist-smoke) bash scripts/gpu_dist_smoke.sh ;;
   final)
     # the profile passes FIRST: bench.py quotes the committed kernel-stats / PMC files, so they are refreshed in the box's copy of profiles/
@@ -135,5 +142,5 @@ print(d['value'], d['ms_per_step'], 'frac', r.get('frac'), 'fwd', r.get('forward
     bash "$0" layer-table; bash "$0" timeline; bash "$0" prof eval; bash "$0" eval-table
     python scripts/gridbar.py 2>&1 | grep -v amdgpu.ids > "$R/gpurun_out/gridbar.txt"; tail -5 "$R/gpurun_out/gridbar.txt"
     timeout 200 python __graft_entry__.py smoke 2>&1 | tail -2 ;;
-  *) sed -n 2,24p "$0" ;;
+  *) sed -n 2,25p "$0" ;;
 esac

@@ -7,6 +7,7 @@ static const char* const kSymbols[] = {
     "tf_targets_workspace_bytes", "tf_dense_overlap_targets", "tf_dense_overlap_iou", "tf_pairwise_iou_distance",
     "tf_targets_comp_workspace_bytes", "tf_dense_overlap_targets_comp", "tf_targets_apply_ignore",
     "tf_targets_atss_workspace_bytes", "tf_targets_atss", "tf_targets_tal_workspace_bytes", "tf_targets_tal",
+    "tf_targets_tal_aligned_workspace_bytes", "tf_targets_tal_aligned",
     "tf_nms_workspace_bytes", "tf_nms_f64", "tf_nms_batched_workspace_bytes", "tf_nms_f64_batched",
     "tf_decode_workspace_bytes", "tf_decode_compact",
     "tf_box_vote_f64", "tf_box_vote_f64_batched", "tf_boxes_unflip_f64",
@@ -16,6 +17,7 @@ static const char* const kSymbols[] = {
     "tf_wider_match_workspace_bytes", "tf_wider_match_f64_batched", "tf_wider_pr_accumulate",
     "tf_criterion_workspace_bytes", "tf_criterion_fwd_bwd", "tf_criterion_focal_workspace_bytes", "tf_criterion_focal_fwd_bwd",
     "tf_criterion_focal_box_fwd_bwd", "tf_criterion_quality_workspace_bytes", "tf_criterion_quality_fwd_bwd",
+    "tf_criterion_aligned_workspace_bytes", "tf_criterion_aligned_fwd_bwd",
     "tf_sgd_step", "tf_sgd_step_segments", "tf_image_prepare", "tf_image_prepare_jitter_workspace_bytes", "tf_image_prepare_jitter",
     "tf_grad_norm_workspace_bytes", "tf_grad_clip_coef", "tf_sgd_step_clipped", "tf_sgd_step_segments_clipped", "tf_scale_segments",
     "tf_sgd_step_ema", "tf_sgd_step_segments_ema", "tf_ema_update_segments",

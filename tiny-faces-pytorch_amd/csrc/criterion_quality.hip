@@ -32,17 +32,6 @@ __device__ __forceinline__ float box_iou(float px, float py, float pw, float ph,
   return I * rU;
 }
 
-// |d|^beta and beta |d|^(beta - 1) sgn(d); beta = 2 takes no powf, any other beta ONE: |d|^beta = |d|^(beta - 1) |d| (every labelled element
-// pays for it, and a second powf made the pass 1.3 times the focal one).  beta >= 1, so the exponent is not negative: finite at d = 0, where
-// both are 0 (sgn(0) = 0, also for beta = 1 where powf(0, 0) = 1).
-__device__ __forceinline__ void qfl_weight(float d, float beta, float& w, float& dw) {
-  if (beta == 2.f) { w = d * d; dw = 2.f * d; return; }
-  const float ad = fabsf(d), sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-  const float w1 = powf(ad, beta - 1.f);
-  w = w1 * ad;
-  dw = beta * w1 * sg;
-}
-
 template <int REG>
 __global__ void __launch_bounds__(256) quality_apply_kernel(FocalParams p) {
   const int b = blockIdx.y, blk = blockIdx.x;

@@ -1,6 +1,7 @@
-// What the passes of the detection criterion share: csrc/criterion.hip (soft-margin and focal forms) and csrc/criterion_quality.hip (quality
-// focal form).  The block geometry, the parameter block of the focal-shaped passes, the overlap term of one positive (box_term), the per-block
-// count of +1 labels (focal_count_kernel) and the per-image total every block forms from it (focal_image_npos).  Everything sits in an
+// What the passes of the detection criterion share: csrc/criterion.hip (soft-margin and focal forms), csrc/criterion_quality.hip (quality
+// focal form) and csrc/criterion_aligned.hip (task-aligned form).  The block geometry, the parameter block of the focal-shaped passes, the
+// overlap term of one positive (box_term), the weight of the quality focal forms (qfl_weight), the per-block count of +1 labels
+// (focal_count_kernel) and the per-image total every block forms from it (focal_image_npos).  Everything sits in an
 // anonymous namespace: each translation unit gets its own copy of the kernels, and nothing here leaves the library.
 #pragma once
 #include <cmath>
@@ -75,6 +76,18 @@ __device__ __forceinline__ float box_term(float px, float py, float pw, float ph
   }
   g[2] *= mw; g[3] *= mh;
   return term;
+}
+
+// The weight of the quality focal forms (csrc/criterion_quality.hip, csrc/criterion_aligned.hip), d = sigma - q:
+// |d|^beta and beta |d|^(beta - 1) sgn(d); beta = 2 takes no powf, any other beta ONE: |d|^beta = |d|^(beta - 1) |d| (every labelled element
+// pays for it, and a second powf made the pass 1.3 times the focal one).  beta >= 1, so the exponent is not negative: finite at d = 0, where
+// both are 0 (sgn(0) = 0, also for beta = 1 where powf(0, 0) = 1).
+__device__ __forceinline__ void qfl_weight(float d, float beta, float& w, float& dw) {
+  if (beta == 2.f) { w = d * d; dw = 2.f * d; return; }
+  const float ad = fabsf(d), sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+  const float w1 = powf(ad, beta - 1.f);
+  w = w1 * ad;
+  dw = beta * w1 * sg;
 }
 
 __device__ __forceinline__ int wave_sum_int(int v) {

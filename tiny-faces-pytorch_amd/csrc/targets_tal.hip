@@ -24,6 +24,14 @@
 // distinct, so the list after the last tile does not depend on how the window was cut into tiles.  Nothing is bounded by LDS: the templates pass
 // in tiles of 64 (their windows' rectangles and a prefix sum of their sizes), the candidates of such a tile in tiles of 256.
 // The winners of a face (<= 32 anchors and their keys) are kept in the workspace for owner and write; there is no candidate list anywhere.
+//
+// tf_targets_tal_aligned (step 7 of the rule) is the same four launches with the aligned instantiations of init, claim and write: init also
+// stores 1.0f to every element of align_map, claim keeps the m it ranked by next to the winner's key (the bits themselves, not a value formed
+// again), and write -- one wave per face -- takes the maxima of m and of u over the lanes that WON by wave shuffles and stores
+// (float)((m / M_g) * U_g) beside the +1.  The kernels are templates over their parameter block: tf_targets_tal instantiates them with
+// TalParams and is, kernel argument for kernel argument, what it was.
+#include <type_traits>
+
 #include "targets_shared.h"
 
 namespace {
@@ -48,6 +56,12 @@ struct TalParams {
   int32_t* widx;                                   // [nslots * 32]   per winner: t * cells + cell
   int32_t* nwin;                                   // [nslots]
 };
+
+struct TalAlignedParams : TalParams {              // tf_targets_tal_aligned: step 7
+  float* align;                                    // [B * A]   1.0f everywhere, the normalised alignment at the anchors won
+  double* wm;                                      // [nslots * 32]   per winner: the m the claim kernel ranked it by
+};
+template <class P> constexpr bool kAligned = std::is_same<P, TalAlignedParams>::value;
 
 // [a, b] = the indices i of [lo, hi] whose anchor centre lies strictly between g1 and g2 (empty: a > b).  The centre is monotone in i: one
 // division estimates each bound and the predicate itself corrects it, so the bounds are exact; a NaN face gives the empty range.
@@ -115,16 +129,19 @@ __device__ __forceinline__ Rect nearest_rect(const TalParams& p, const Face& f, 
 
 __device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and Inf
 
-__global__ void __launch_bounds__(kThreads) tal_init_kernel(TalParams p) {
+template <class P>
+__global__ void __launch_bounds__(kThreads) tal_init_kernel(P p) {
   if (p.box_off[p.B] > p.nslots) return;                                       // more boxes than the workspace has slots for: touch nothing
   const size_t BA = (size_t)p.B * p.nt * p.vsy * p.vsx;
   for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < BA; i += (size_t)gridDim.x * kThreads) {
     p.amax[i] = 0ull;
     p.aown[i] = 0xffffffffu;
+    if constexpr (kAligned<P>) p.align[i] = 1.f;                                // an anchor labelled +1 by something else keeps the hard target
   }
 }
 
-__global__ void __launch_bounds__(kThreads) tal_claim_kernel(TalParams p) {
+template <class P>
+__global__ void __launch_bounds__(kThreads) tal_claim_kernel(P p) {
   __shared__ double e_m[kEntries], e_u[kEntries];  // [0, 32): the running list, best first; [32, 288): the tile.  m < 0: no entry
   __shared__ int e_i[kEntries];
   __shared__ double n_m[kMaxTop], n_u[kMaxTop];    // the list of the next tile, while the ranks are being formed
@@ -239,6 +256,7 @@ __global__ void __launch_bounds__(kThreads) tal_claim_kernel(TalParams p) {
     const int a = e_i[tid];
     p.wkey[(size_t)gi * kMaxTop + tid] = key;
     p.widx[(size_t)gi * kMaxTop + tid] = a;
+    if constexpr (kAligned<P>) p.wm[(size_t)gi * kMaxTop + tid] = e_m[tid];
     atomicMax(&p.amax[(size_t)f.b * E + a], key);
   }
 }
@@ -253,7 +271,8 @@ __global__ void __launch_bounds__(kWave) tal_owner_kernel(TalParams p) {
   if (p.wkey[(size_t)gi * kMaxTop + threadIdx.x] == p.amax[a]) atomicMin(&p.aown[a], (unsigned int)gi);     // faces of one image: the lower gi is the lower g
 }
 
-__global__ void __launch_bounds__(kWave) tal_write_kernel(TalParams p) {
+template <class P>
+__global__ void __launch_bounds__(kWave) tal_write_kernel(P p) {
   const int gi = blockIdx.x;
   const int total = p.box_off[p.B];
   if (total > p.nslots || gi >= total) return;
@@ -261,9 +280,12 @@ __global__ void __launch_bounds__(kWave) tal_write_kernel(TalParams p) {
   const int cells = p.vsy * p.vsx;
   const size_t img = (size_t)b * p.nt * cells;
   bool won = false;
+  int a = 0;
+  unsigned long long key = 0ull;
   if ((int)threadIdx.x < p.nwin[gi]) {
-    const int a = p.widx[(size_t)gi * kMaxTop + threadIdx.x];
-    won = p.wkey[(size_t)gi * kMaxTop + threadIdx.x] == p.amax[img + a] && p.aown[img + a] == (unsigned int)gi;
+    a = p.widx[(size_t)gi * kMaxTop + threadIdx.x];
+    key = p.wkey[(size_t)gi * kMaxTop + threadIdx.x];
+    won = key == p.amax[img + a] && p.aown[img + a] == (unsigned int)gi;
     if (won) {
       const double* bx = p.boxes + 4 * (size_t)gi;
       const double gx1 = bx[0], gy1 = bx[1], gx2 = bx[2], gy2 = bx[3];
@@ -282,30 +304,51 @@ __global__ void __launch_bounds__(kWave) tal_write_kernel(TalParams p) {
       r[(size_t)3 * p.nt * plane] = (float)log((gy2 - gy1 + 1.0) / fh);
     }
   }
+  if constexpr (kAligned<P>) {                                                 // step 7: every lane of the wave takes part in the shuffles
+    const double m = won ? p.wm[(size_t)gi * kMaxTop + threadIdx.x] : -1.0;    // m >= 0 and u > 0 for every winner
+    const double u = won ? __longlong_as_double((long long)key) : 0.0;
+    double M = m, U = u;
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+      const double vm = __shfl_xor(M, o, kWave), vu = __shfl_xor(U, o, kWave);
+      M = vm > M ? vm : M;
+      U = vu > U ? vu : U;
+    }
+    if (won) p.align[img + a] = M == 0.0 ? 0.f : (float)((m / M) * U);
+  }
   if (!p.match_count) return;                                                  // kernel-uniform
   const int n = __popcll(__ballot(won));
   if (threadIdx.x == 0) p.match_count[gi] = n;
 }
 
-// per box slot: 32 winners of key (8) + anchor index (4), and the winner count (4)
-inline size_t slot_bytes() { return (size_t)kMaxTop * 12 + 4; }
+// per box slot: 32 winners of key (8) + anchor index (4) [+ m (8), aligned], and the winner count (4)
+template <class P> inline size_t slot_bytes() { return (size_t)kMaxTop * (kAligned<P> ? 20 : 12) + 4; }
+
+// workspace: per anchor the claim key (8) + the owner (4), per box slot slot_bytes()
+template <class P> inline size_t workspace_bytes(int total_boxes, int B, int nt, int vsy, int vsx) {
+  const size_t n = (size_t)(total_boxes > 0 ? total_boxes : 1);
+  const size_t anchors = (size_t)(B > 0 ? B : 0) * (size_t)(nt > 0 ? nt : 0) * (size_t)(vsy > 0 ? vsy : 0) * (size_t)(vsx > 0 ? vsx : 0);
+  return n * slot_bytes<P>() + anchors * 12 + 64;
+}
 
 }  // namespace
 
-// workspace: per anchor the claim key (8) + the owner (4), per box slot slot_bytes()
 extern "C" size_t tf_targets_tal_workspace_bytes(int total_boxes, int B, int nt, int vsy, int vsx) {
-  const size_t n = (size_t)(total_boxes > 0 ? total_boxes : 1);
-  const size_t anchors = (size_t)(B > 0 ? B : 0) * (size_t)(nt > 0 ? nt : 0) * (size_t)(vsy > 0 ? vsy : 0) * (size_t)(vsx > 0 ? vsx : 0);
-  return n * slot_bytes() + anchors * 12 + 64;
+  return workspace_bytes<TalParams>(total_boxes, B, nt, vsy, vsx);
 }
 
-extern "C" int tf_targets_tal(const float* output, const double* boxes, const int32_t* box_offsets, int B,
-                              const double* templates, int nt, int tstride,
-                              int vsy, int vsx, int ofy, int ofx, int sty, int stx,
-                              const int32_t* paste_boxes, const int32_t* flips,
-                              int topk, double alpha, double beta, int32_t* match_count,
-                              float* class_map, float* reg_map,
-                              void* ws, size_t ws_bytes, void* stream_) {
+extern "C" size_t tf_targets_tal_aligned_workspace_bytes(int total_boxes, int B, int nt, int vsy, int vsx) {
+  return workspace_bytes<TalAlignedParams>(total_boxes, B, nt, vsy, vsx);
+}
+
+namespace {
+
+// both entry points: the refusals, the workspace carved, the four launches
+template <class P>
+int tal_launch(const float* output, const double* boxes, const int32_t* box_offsets, int B, const double* templates, int nt, int tstride,
+               int vsy, int vsx, int ofy, int ofx, int sty, int stx, const int32_t* paste_boxes, const int32_t* flips,
+               int topk, double alpha, double beta, int32_t* match_count, float* class_map, float* reg_map, float* align_map,
+               void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (B <= 0 || nt <= 0 || vsy <= 0 || vsx <= 0 || !output || !box_offsets || !templates || !class_map || !reg_map) return TF_ERR_ARG;
   if (tstride < 4 || sty <= 0 || stx <= 0) return TF_ERR_ARG;
@@ -317,11 +360,11 @@ extern "C" int tf_targets_tal(const float* output, const double* boxes, const in
   if ((double)(vsx - 1) * stx + fabs((double)ofx) > 2147483647.0 || (double)(vsy - 1) * sty + fabs((double)ofy) > 2147483647.0) return TF_ERR_UNSUPPORTED;
   // total boxes is only known on device; the caller sizes ws from its host copy, and every kernel leaves at once if the device's total
   // exceeds the slots the workspace holds
-  if (!ws || ws_bytes < tf_targets_tal_workspace_bytes(1, B, nt, vsy, vsx)) return TF_ERR_WORKSPACE;
+  if (!ws || ws_bytes < workspace_bytes<P>(1, B, nt, vsy, vsx)) return TF_ERR_WORKSPACE;
   const size_t anchors = (size_t)B * per_image;
-  size_t nslots = (ws_bytes - 64 - anchors * 12) / slot_bytes();
+  size_t nslots = (ws_bytes - 64 - anchors * 12) / slot_bytes<P>();
   if (nslots > ((size_t)1 << 30)) nslots = (size_t)1 << 30;
-  TalParams p;
+  P p;
   p.out = output; p.boxes = boxes; p.box_off = box_offsets; p.tpl = templates; p.B = B; p.nt = nt; p.tstride = tstride;
   p.vsy = vsy; p.vsx = vsx; p.ofy = ofy; p.ofx = ofx; p.sty = sty; p.stx = stx;
   p.paste = paste_boxes; p.flips = flips; p.topk = topk; p.alpha = alpha; p.beta = beta; p.nslots = (int)nslots;
@@ -329,14 +372,40 @@ extern "C" int tf_targets_tal(const float* output, const double* boxes, const in
   char* w = (char*)ws;                                                         // the 8-byte arrays first
   p.amax = (unsigned long long*)w;                 w += anchors * 8;
   p.wkey = (unsigned long long*)w;                 w += nslots * kMaxTop * 8;
+  if constexpr (kAligned<P>) { p.align = align_map; p.wm = (double*)w; w += nslots * kMaxTop * 8; }
   p.aown = (unsigned int*)w;                       w += anchors * 4;
   p.widx = (int32_t*)w;                            w += nslots * kMaxTop * 4;
   p.nwin = (int32_t*)w;
   const size_t init_blocks = (anchors + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(tal_init_kernel, dim3((unsigned)(init_blocks < 4096 ? init_blocks : 4096)), dim3(kThreads), 0, stream, p);
-  hipLaunchKernelGGL(tal_claim_kernel, dim3((unsigned)nslots), dim3(kThreads), 0, stream, p);
+  hipLaunchKernelGGL(tal_init_kernel<P>, dim3((unsigned)(init_blocks < 4096 ? init_blocks : 4096)), dim3(kThreads), 0, stream, p);
+  hipLaunchKernelGGL(tal_claim_kernel<P>, dim3((unsigned)nslots), dim3(kThreads), 0, stream, p);
   hipLaunchKernelGGL(tal_owner_kernel, dim3((unsigned)nslots), dim3(kWave), 0, stream, p);
-  hipLaunchKernelGGL(tal_write_kernel, dim3((unsigned)nslots), dim3(kWave), 0, stream, p);
+  hipLaunchKernelGGL(tal_write_kernel<P>, dim3((unsigned)nslots), dim3(kWave), 0, stream, p);
   TF_CHECK_LAUNCH();
   return TF_OK;
+}
+
+}  // namespace
+
+extern "C" int tf_targets_tal(const float* output, const double* boxes, const int32_t* box_offsets, int B,
+                              const double* templates, int nt, int tstride,
+                              int vsy, int vsx, int ofy, int ofx, int sty, int stx,
+                              const int32_t* paste_boxes, const int32_t* flips,
+                              int topk, double alpha, double beta, int32_t* match_count,
+                              float* class_map, float* reg_map,
+                              void* ws, size_t ws_bytes, void* stream) {
+  return tal_launch<TalParams>(output, boxes, box_offsets, B, templates, nt, tstride, vsy, vsx, ofy, ofx, sty, stx, paste_boxes, flips, topk, alpha, beta,
+                               match_count, class_map, reg_map, nullptr, ws, ws_bytes, stream);
+}
+
+extern "C" int tf_targets_tal_aligned(const float* output, const double* boxes, const int32_t* box_offsets, int B,
+                                      const double* templates, int nt, int tstride,
+                                      int vsy, int vsx, int ofy, int ofx, int sty, int stx,
+                                      const int32_t* paste_boxes, const int32_t* flips,
+                                      int topk, double alpha, double beta, int32_t* match_count,
+                                      float* class_map, float* reg_map, float* align_map,
+                                      void* ws, size_t ws_bytes, void* stream) {
+  if (!align_map) return TF_ERR_ARG;
+  return tal_launch<TalAlignedParams>(output, boxes, box_offsets, B, templates, nt, tstride, vsy, vsx, ofy, ofx, sty, stx, paste_boxes, flips, topk, alpha,
+                                      beta, match_count, class_map, reg_map, align_map, ws, ws_bytes, stream);
 }

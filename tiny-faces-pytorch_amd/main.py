@@ -114,8 +114,9 @@ def deterministic_description():
 FOCAL_HELP = ("--cls-loss {soft-margin,focal}: classification loss of the criterion; focal = sigmoid focal loss (Lin et al. 2017) over every "
               "labelled anchor and SmoothL1 over every positive, with no OHEM and no 256-sample draw (--ohem-thresh is unused), default soft-margin; "
               "--focal-gamma G: its focusing exponent, G >= 0, default 2; --focal-alpha A: weight A on positives and 1 - A on negatives, A <= 1, "
-              "negative = no weighting, default 0.25; --focal-normalize {pos,none}: pos divides every image's loss by max(1, its positives) "
-              "before the images are summed, none leaves the plain sum, default pos")
+              "negative = no weighting, default 0.25; --focal-normalize {pos,none,align}: pos divides every image's loss by max(1, its positives) "
+              "before the images are summed, none leaves the plain sum, align (with --tal-aligned-targets only) divides it by max(1, the sum of its "
+              "aligned targets), default pos")
 
 
 QFL_HELP = ("--cls-loss qfl: quality focal loss (Li et al. 2020, Generalized Focal Loss; the classification loss of SCRFD) over every labelled "
@@ -151,6 +152,10 @@ COMPENSATION_HELP = ("--anchor-compensation N T: scale-compensated anchor matchi
                      "default off")
 
 
+TAL_ALIGNED_HELP = ("--tal-aligned-targets (with --assigner tal --cls-loss qfl): TOOD's task-aligned loss.  Every positive keeps the assigner's "
+                    "normalised alignment m / max m * max IoU (the maxima over the anchors its face won) as its classification target in place of the "
+                    "IoU of its own box, and its regression term is weighted by it; --focal-normalize align then divides every image's loss by "
+                    "max(1, the sum of its aligned targets)")
 ASSIGNER_HELP = ("--assigner atss: ATSS target assignment (Zhang et al. 2020; what SCRFD and TinaFace train with) for the training targets instead of "
                  "the fixed IoU thresholds: per face the --atss-topk K (1..16, default 9) unpadded cells of every template nearest to its centre are "
                  "candidates, positive from mean + std of their IoUs when the anchor centre lies inside the face; not together with "
@@ -378,7 +383,7 @@ def trunk_arguments(argv=None):
     parser.add_argument("--qfl-beta", dest="qfl_beta", default=2.0, type=_qfl_beta, metavar="B", help=QFL_HELP)
     parser.add_argument("--focal-gamma", dest="focal_gamma", default=2.0, type=_focal_gamma, metavar="G", help=FOCAL_HELP)
     parser.add_argument("--focal-alpha", dest="focal_alpha", default=0.25, type=_focal_alpha, metavar="A", help=FOCAL_HELP)
-    parser.add_argument("--focal-normalize", dest="focal_normalize", default="pos", choices=["pos", "none"], help=FOCAL_HELP)
+    parser.add_argument("--focal-normalize", dest="focal_normalize", default="pos", choices=["pos", "none", "align"], help=FOCAL_HELP)
     parser.add_argument("--reg-loss", dest="reg_loss", default="smooth-l1", choices=["smooth-l1", "iou", "giou", "diou"], help=BOX_LOSS_HELP)
     parser.add_argument("--reg-weight", dest="reg_weight", default=1.0, type=_reg_weight, metavar="W", help=BOX_LOSS_HELP)
     parser.add_argument("--optimizer", dest="optimizer", default="sgd", choices=["sgd", "adamw"], help=OPTIMIZER_HELP)
@@ -401,6 +406,7 @@ def trunk_arguments(argv=None):
     parser.add_argument("--tal-topk", dest="tal_topk", default=13, type=_tal_topk, metavar="K", help=ASSIGNER_HELP)
     parser.add_argument("--tal-alpha", dest="tal_alpha", default=1.0, type=_tal_alpha, metavar="A", help=ASSIGNER_HELP)
     parser.add_argument("--tal-beta", dest="tal_beta", default=6.0, type=_tal_beta, metavar="B", help=ASSIGNER_HELP)
+    parser.add_argument("--tal-aligned-targets", dest="tal_aligned_targets", action="store_true", help=TAL_ALIGNED_HELP)
     parser.add_argument("--ignore-invalid", dest="ignore_invalid", action="store_true", help=IGNORE_HELP)
     parser.add_argument("--ignore-blur", dest="ignore_blur", default=None, type=_ignore_level, metavar="L", help=IGNORE_HELP)
     parser.add_argument("--ignore-occlusion", dest="ignore_occlusion", default=None, type=_ignore_level, metavar="L", help=IGNORE_HELP)
@@ -419,6 +425,11 @@ def trunk_arguments(argv=None):
         parser.error("--anchor-compensation tops up the owners that the dense-overlap assignment computes; it does not go with --assigner atss")
     if known.anchor_compensation is not None and known.assigner == "tal":
         parser.error("--anchor-compensation tops up the owners that the dense-overlap assignment computes; it does not go with --assigner tal")
+    if known.tal_aligned_targets and (known.assigner != "tal" or known.cls_loss != "qfl"):
+        parser.error("--tal-aligned-targets trains towards the alignment values of the task-aligned assignment in the quality focal form: it needs "
+                     "--assigner tal --cls-loss qfl")
+    if known.focal_normalize == "align" and not known.tal_aligned_targets:
+        parser.error("--focal-normalize align divides by the sum of the aligned targets: it needs --tal-aligned-targets")
     if known.anchor_compensation is not None:
         n, t = known.anchor_compensation
         if n != int(n) or not 1 <= int(n) <= 64:
@@ -457,6 +468,7 @@ def trunk_arguments(argv=None):
     args.anchor_compensation = None if known.anchor_compensation is None else (int(known.anchor_compensation[0]), float(known.anchor_compensation[1]))
     args.assigner, args.atss_topk = known.assigner.replace("-", "_"), known.atss_topk
     args.tal_topk, args.tal_alpha, args.tal_beta = known.tal_topk, known.tal_alpha, known.tal_beta
+    args.tal_aligned_targets = known.tal_aligned_targets
     if args.assigner != "dense_overlap" and (str(args.traindata) == "synthetic" or getattr(args, "synthetic", False)):
         parser.error(f"--assigner {args.assigner} applies to a WIDER annotation file or to synthetic-faces: the synthetic crops are a throughput workload of the "
                      "dense-overlap assigner")
@@ -485,6 +497,12 @@ def ignore_description(args):
 
 def assigner_description(args):
     """The target assigner as the start-up line prints it."""
+    if getattr(args, "assigner", "dense_overlap") == "tal" and getattr(args, "tal_aligned_targets", False):
+        return (f"assigner TAL: every step, from the network's own output: per face the anchors whose centre lies inside it are ranked by "
+                f"m = sigmoid(logit)^{args.tal_alpha:g} * IoU(predicted box, face)^{args.tal_beta:g} and the best {args.tal_topk} become its positives, an "
+                "anchor two faces claim goes to the larger IoU, and every positive keeps its aligned target m / max m * max IoU over the anchors its face "
+                "won; everything else keeps the label of a map without faces (on the device, between the forward pass and the loss; the two IoU "
+                "thresholds only filter crops)")
     if getattr(args, "assigner", "dense_overlap") == "tal":
         return (f"assigner TAL: every step, from the network's own output: per face the anchors whose centre lies inside it are ranked by "
                 f"sigmoid(logit)^{args.tal_alpha:g} * IoU(predicted box, face)^{args.tal_beta:g} and the best {args.tal_topk} become its positives, an anchor "
@@ -521,6 +539,10 @@ def loss_description(args):
     reg = {"smooth_l1": "SmoothL1 on the four offsets", "iou": "IoU, one term per positive", "giou": "GIoU, one term per positive",
            "diou": "DIoU, one term per positive"}[reg_loss]
     reg = f"; regression loss {reg}, weight {reg_weight:g}"
+    if args.cls_loss == "qfl" and getattr(args, "tal_aligned_targets", False):
+        norm = {"pos": "per image by its positives", "align": "per image by the sum of its aligned targets"}.get(args.focal_normalize, "not normalised")
+        return (f"classification loss task-aligned quality focal (beta {getattr(args, 'qfl_beta', 2.0):g}, the assigner's aligned target of the positive as "
+                f"the target; {norm}; every labelled anchor, every positive regresses, weighted by its aligned target)") + reg
     if args.cls_loss == "qfl":
         norm = "per image by its positives" if args.focal_normalize == "pos" else "not normalised"
         return (f"classification loss quality focal (beta {getattr(args, 'qfl_beta', 2.0):g}, IoU of the predicted box as the target; {norm}; every labelled "
@@ -618,7 +640,8 @@ def main():
                                  cls_loss=args.cls_loss, focal_gamma=args.focal_gamma, focal_alpha=args.focal_alpha, focal_normalize=args.focal_normalize,
                                  reg_loss=args.reg_loss, templates=load_templates(NUM_TEMPLATES) if args.reg_loss == "diou" or args.assigner == "tal" else None,
                                  **({"qfl_beta": args.qfl_beta} if args.cls_loss == "qfl" else {}),
-                                 **({"assigner": TaskAligned(args.tal_topk, args.tal_alpha, args.tal_beta)} if args.assigner == "tal" else {}))
+                                 **({"assigner": TaskAligned(args.tal_topk, args.tal_alpha, args.tal_beta, **({"aligned_targets": True} if args.tal_aligned_targets else {}))}
+                                    if args.assigner == "tal" else {}))
     loss_fn.ohem_thresh = args.ohem_thresh
     if parallel.rank() == 0:
         print(loss_description(args))
@@ -718,6 +741,8 @@ def main():
             snapshot.setdefault("args", {}).update(assigner=args.assigner, atss_topk=args.atss_topk)
         if args.assigner == "tal":
             snapshot.setdefault("args", {}).update(assigner=args.assigner, tal_topk=args.tal_topk, tal_alpha=args.tal_alpha, tal_beta=args.tal_beta)
+            if args.tal_aligned_targets:
+                snapshot["args"].update(tal_aligned_targets=True)
         if args.cls_loss == "qfl":
             snapshot.setdefault("args", {}).update(cls_loss=args.cls_loss, qfl_beta=args.qfl_beta, focal_normalize=args.focal_normalize,
                                                    reg_loss=args.reg_loss, reg_weight=args.reg_weight)

@@ -113,6 +113,8 @@ _SIGNATURES = {
     "tf_targets_atss": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
     "tf_targets_tal_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "tf_targets_tal": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, f64, f64, vp, vp, vp, vp, sz, vp]),
+    "tf_targets_tal_aligned_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "tf_targets_tal_aligned": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, f64, f64, vp, vp, vp, vp, vp, sz, vp]),
     "tf_dense_overlap_iou": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "tf_pairwise_iou_distance": (i32, [vp, i32, vp, vp]),
     "tf_nms_workspace_bytes": (sz, [i32]),
@@ -144,6 +146,8 @@ _SIGNATURES = {
     "tf_criterion_focal_box_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, f32, i32, vp, vp, vp, vp, vp, sz, vp]),
     "tf_criterion_quality_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "tf_criterion_quality_fwd_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, f32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "tf_criterion_aligned_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "tf_criterion_aligned_fwd_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, f32, i32, vp, vp, vp, vp, vp, sz, vp]),
     "tf_image_prepare": (i32, [C.POINTER(ImagePrepareArgs), vp]),
     "tf_image_prepare_jitter_workspace_bytes": (sz, [i32, i32, i32, C.POINTER(i32)]),
     "tf_image_prepare_jitter": (i32, [C.POINTER(ImagePrepareArgs), i32, C.POINTER(i32), C.POINTER(f32), vp, sz, vp]),

@@ -6,7 +6,8 @@ focal form of the same pass (tf_criterion_focal_fwd_bwd); `reg_loss="iou" | "gio
 term per positive in place of the four SmoothL1 terms (tf_criterion_focal_box_fwd_bwd).  `cls_loss="qfl"` is the quality focal form of that pass
 (tf_criterion_quality_fwd_bwd): a positive's logit is trained towards the IoU of its own predicted box with its target.
 `assigner=TaskAligned(...)` puts the task-aligned target assignment (tf_targets_tal) in front of whichever pass is chosen: the maps arrive
-without a face assigned and the positives are chosen from the output itself."""
+without a face assigned and the positives are chosen from the output itself; `TaskAligned(aligned_targets=True)` also keeps the assignment's
+normalised alignment of every positive and trains towards it with TOOD's loss (tf_targets_tal_aligned, tf_criterion_aligned_fwd_bwd)."""
 import torch
 from torch import nn
 
@@ -36,15 +37,21 @@ class AvgMeter:
 class TaskAligned:
     """The parameters of the task-aligned assignment (TOOD's TaskAlignedAssigner; the rule is in include/tinyfaces_hip.h, "TAL"): every face
     claims its `topk` anchors of largest sigmoid(logit)^alpha * IoU(predicted box, face)^beta among those whose centre lies inside it.
-    topk an integer in 1..32, alpha finite and >= 0, beta finite and > 0 (ValueError otherwise).  Hand it to DetectionCriterion(assigner=)."""
+    topk an integer in 1..32, alpha finite and >= 0, beta finite and > 0 (ValueError otherwise).  Hand it to DetectionCriterion(assigner=).
+    aligned_targets=True: TOOD's loss on top of its assignment (step 7 of the rule).  The assignment also stores every won anchor's normalised
+    alignment t = m / max m * max u (the maxima over the anchors its face won), and the criterion -- cls_loss="qfl" is required -- trains the
+    class logit of a positive towards t instead of the IoU of its own box and weights its regression term by t."""
 
-    __slots__ = ("topk", "alpha", "beta")
+    __slots__ = ("topk", "alpha", "beta", "aligned_targets")
 
-    def __init__(self, topk=ops.TAL_TOPK, alpha=ops.TAL_ALPHA, beta=ops.TAL_BETA):
+    def __init__(self, topk=ops.TAL_TOPK, alpha=ops.TAL_ALPHA, beta=ops.TAL_BETA, aligned_targets=False):
         self.topk, self.alpha, self.beta = ops.check_tal(topk, alpha, beta)
+        if not isinstance(aligned_targets, bool):
+            raise ValueError(f"TaskAligned: aligned_targets must be True or False, got {aligned_targets!r}")
+        self.aligned_targets = aligned_targets
 
     def __repr__(self):
-        return f"TaskAligned(topk={self.topk}, alpha={self.alpha}, beta={self.beta})"
+        return f"TaskAligned(topk={self.topk}, alpha={self.alpha}, beta={self.beta}" + (", aligned_targets=True)" if self.aligned_targets else ")")
 
 
 class _CriterionFunction(torch.autograd.Function):
@@ -100,8 +107,15 @@ class DetectionCriterion(nn.Module):
     fourth element), and `class_map` / `regression_map` arrive as the base maps (no face assigned) and are completed IN PLACE, under no_grad,
     before the loss pass reads them: every `cls_loss` / `reg_loss` combination works unchanged.  `templates` (the (nt, 4 or 5) table) and `rf`
     (the receptive-field geometry) are required with it.  The match counts go to `faces.stats` (the loader's CompensationStats) when there is
-    one.  `faces` without an assigner, and an assigner without `faces`, is a ValueError.  Not implemented: TOOD's normalised alignment value as
-    the classification target (cls_loss="qfl" trains towards the IoU of the same predicted box instead), varifocal loss, score-weighted regression."""
+    one.  `faces` without an assigner, and an assigner without `faces`, is a ValueError.
+
+    `assigner=TaskAligned(..., aligned_targets=True)` (with cls_loss="qfl" only; ValueError otherwise): TOOD's task-aligned loss.  The assignment
+    also writes every won anchor's normalised alignment t = m / max m * max u, the maxima over the anchors its face won (step 7 of the rule;
+    ops.tal_assign_device(align_out=) into a buffer of the maps' shape the criterion keeps), and the loss pass is tf_criterion_aligned_fwd_bwd
+    (ops.criterion_aligned_fwd_bwd): the quality focal form with q = min(1, max(0, t)) as the target of a positive, and every positive's
+    regression term -- whichever `reg_loss` -- weighted by q.  `focal_normalize="align"` (accepted only here) divides every image's sums and
+    gradient by max(1, the sum of q over its positives): TOOD's avg_factor, per image.  `quality_average` then reports the mean TARGET of all
+    positives seen (sum of q / number of positives), not a mean IoU.  Not implemented: varifocal loss."""
 
     CLS_LOSSES = ("soft_margin", "focal", "qfl")
     REG_LOSSES = ("smooth_l1", "iou", "giou", "diou")
@@ -122,8 +136,16 @@ class DetectionCriterion(nn.Module):
         self.assigner, self.rf = assigner, (ops.RF if rf is None else rf)
         if cls_loss not in self.CLS_LOSSES:
             raise ValueError(f"DetectionCriterion: cls_loss must be one of {self.CLS_LOSSES}, got {cls_loss!r}")
-        ops.check_focal(focal_gamma, focal_alpha, focal_normalize)
-        ops.check_qfl(qfl_beta, focal_normalize)
+        self.aligned_targets = bool(getattr(assigner, "aligned_targets", False))
+        if self.aligned_targets and cls_loss != "qfl":
+            raise ValueError(f"DetectionCriterion: TaskAligned(aligned_targets=True) needs cls_loss='qfl' (the aligned target takes the place of the IoU "
+                             f"in the quality focal form), got cls_loss={cls_loss!r}")
+        if focal_normalize == "align" and not self.aligned_targets:
+            raise ValueError("DetectionCriterion: focal_normalize='align' divides by the sum of the aligned targets: it needs "
+                             "assigner=TaskAligned(..., aligned_targets=True)")
+        ops.check_focal(focal_gamma, focal_alpha, "pos" if focal_normalize == "align" else focal_normalize)
+        ops.check_qfl(qfl_beta, "pos" if focal_normalize == "align" else focal_normalize)
+        self._align_map = None
         self._template_wh = None if templates is None else ops.template_wh(templates)
         ops.check_reg_loss(reg_loss, reg_weight, self._template_wh, n_templates)
         self._check_reg_with_cls(reg_loss, cls_loss)
@@ -182,9 +204,15 @@ class DetectionCriterion(nn.Module):
         if self._templates_f64.device != out.device:
             self._templates_f64 = self._templates_f64.to(out.device)
         want = getattr(faces, "stats", None) is not None
+        more = {}
+        if getattr(self, "aligned_targets", False):                     # the aligned targets of this step's positives: a buffer of the maps' shape, kept
+            if self._align_map is None or self._align_map.shape != class_map.shape or self._align_map.device != class_map.device:
+                self._align_map = torch.empty_like(class_map, dtype=torch.float32, memory_format=torch.contiguous_format)
+            more["align_out"] = self._align_map
         with torch.no_grad():
             res = ops.tal_assign_device(out.contiguous(), class_map, regression_map, faces.boxes_d, faces.offs_d, faces.total, self._templates_f64, None, self.rf,
-                                        faces.paste_d, faces.flips_d, self.assigner.topk, self.assigner.alpha, self.assigner.beta, return_match_count=want)
+                                        faces.paste_d, faces.flips_d, self.assigner.topk, self.assigner.alpha, self.assigner.beta, return_match_count=want,
+                                        **more)
         if want:
             faces.stats.push(res[2])
 
@@ -201,6 +229,12 @@ class DetectionCriterion(nn.Module):
         if self.reg_loss != "smooth_l1":
             ops.check_reg_loss(self.reg_loss, self.reg_weight, self._template_wh, self.n_templates)
             self._check_reg_with_cls(self.reg_loss, self.cls_loss)
+        if getattr(self, "aligned_targets", False):
+            if self.cls_loss != "qfl":
+                raise ValueError(f"DetectionCriterion: TaskAligned(aligned_targets=True) needs cls_loss='qfl', got cls_loss={self.cls_loss!r}")
+            loss4, grad, _ = ops.criterion_aligned_fwd_bwd(out, class_map, regression_map, self._align_map, self.n_templates, self.reg_weight, self.qfl_beta,
+                                                           self.focal_normalize, self.reg_loss, self._template_wh_on(out.device))
+            return loss4, grad, class_map
         if self.cls_loss == "qfl":
             loss4, grad, _ = ops.criterion_quality_fwd_bwd(out, class_map, regression_map, self.n_templates, self.reg_weight, self.qfl_beta,
                                                            self.focal_normalize, self.reg_loss, self._template_wh_on(out.device))
@@ -230,7 +264,8 @@ class DetectionCriterion(nn.Module):
 
     def _update_meters(self, v, size):
         """v: the host copy of one step's loss vector.  Elements 2 and 3 (qfl only) are the sum of q over the step's positives and their
-        number: `quality_average` is the mean IoU over all positives seen; a step without a positive leaves it alone."""
+        number: `quality_average` is the mean IoU over all positives seen (with aligned targets: their mean target); a step without a positive
+        leaves it alone."""
         self.class_average.update(v[0], size)
         self.reg_average.update(v[1], size)
         if len(v) >= 4 and v[3] > 0:

@@ -344,7 +344,7 @@ def check_tal(topk=TAL_TOPK, alpha=TAL_ALPHA, beta=TAL_BETA):
 
 
 def tal_assign_device(output, class_map, regression_map, boxes_d, offs_d, total_boxes, templates_d, heatmap_size=None, rf=RF, paste_d=None,
-                      flips_d=None, topk=TAL_TOPK, alpha=TAL_ALPHA, beta=TAL_BETA, return_match_count=False):
+                      flips_d=None, topk=TAL_TOPK, alpha=TAL_ALPHA, beta=TAL_BETA, return_match_count=False, align_out=None):
     """Task-aligned assignment (tf_targets_tal; the rule is in include/tinyfaces_hip.h, "TAL") with every operand resident, IN PLACE on the two
     maps: per face the anchors whose centre lies strictly inside it are measured by sigmoid(logit)^alpha * IoU(predicted box, face)^beta, the
     face claims its `topk` best, an anchor two faces claim goes to the larger IoU, and every won anchor gets +1 and the face's four regression
@@ -352,9 +352,15 @@ def tal_assign_device(output, class_map, regression_map, boxes_d, offs_d, total_
     output (B, 5 nt, vsy, vsx) f32 contiguous, the head's output (only read; nothing flows back into it); class_map (B, nt, vsy, vsx) f32,
     regression_map (B, 4 nt, vsy, vsx) f32, both contiguous; boxes_d (total, 4) f64 (degenerate boxes removed), offs_d (B + 1,) i32, total_boxes
     the host's copy of its last entry, templates_d (nt, >= 4) f64, paste_d (B, 4) i32, flips_d (B,) i32.  heatmap_size, if given, must be the maps'.
-    Returns (class_map, regression_map[, match_count (total,) int32]).  No face in the batch: nothing is enqueued."""
+    align_out: a contiguous float32 tensor of class_map's shape selects tf_targets_tal_aligned (step 7 of the rule): the same assignment, and
+    align_out is written COMPLETELY (it may arrive holding anything): 1 everywhere, and at every won anchor TOOD's normalised alignment
+    m / max m * max u, the maxima over the anchors the face won.  It is the align_map of criterion_aligned_fwd_bwd.
+    Returns (class_map, regression_map[, match_count (total,) int32]).  No face in the batch: nothing is enqueued (align_out is filled with 1)."""
     k, a, bt = check_tal(topk, alpha, beta)
     require_gpu(output, "tal_assign_device")
+    if align_out is not None and (not torch.is_tensor(align_out) or align_out.dtype != torch.float32 or not align_out.is_contiguous() or
+                                  align_out.device != output.device or align_out.shape != class_map.shape):
+        raise ValueError("tal_assign_device: align_out is a contiguous float32 tensor of class_map's shape on the output's device")
     for name, v in (("output", output), ("class_map", class_map), ("regression_map", regression_map)):
         if not torch.is_tensor(v) or v.dtype != torch.float32 or v.dim() != 4 or not v.is_contiguous() or v.device != output.device:
             raise ValueError(f"tal_assign_device: {name} is a contiguous float32 4-d tensor on the output's device")
@@ -368,7 +374,17 @@ def tal_assign_device(output, class_map, regression_map, boxes_d, offs_d, total_
         raise ValueError("tal_assign_device: offs_d is (B + 1,) int32, templates_d (nt, >= 4) float64 and boxes_d (total, 4) float64")
     total, dev = int(total_boxes), output.device
     mc = torch.empty(total, dtype=torch.int32, device=dev) if return_match_count else None
-    if total > 0:
+    if total > 0 and align_out is not None:
+        ofy, ofx = rf["offset"]
+        sty, stx = rf["stride"]
+        wsb = lib().tf_targets_tal_aligned_workspace_bytes(total, B, nt, vsy, vsx)
+        ws = _workspace("targets_tal_aligned", wsb, dev)
+        check(lib().tf_targets_tal_aligned(ptr(output), ptr(boxes_d), ptr(offs_d), B, ptr(templates_d), nt, templates_d.shape[1], vsy, vsx, ofy, ofx, sty,
+                                           stx, ptr(paste_d), ptr(flips_d), k, a, bt, ptr(mc), ptr(class_map), ptr(regression_map), ptr(align_out),
+                                           ptr(ws), wsb, stream()), "tf_targets_tal_aligned")
+    elif align_out is not None:
+        align_out.fill_(1.0)
+    elif total > 0:
         ofy, ofx = rf["offset"]
         sty, stx = rf["stride"]
         wsb = lib().tf_targets_tal_workspace_bytes(total, B, nt, vsy, vsx)
@@ -380,9 +396,10 @@ def tal_assign_device(output, class_map, regression_map, boxes_d, offs_d, total_
 
 
 def tal_assign(output, class_map, regression_map, boxes_per_image, templates, rf=RF, paste_boxes=None, flips=None, topk=TAL_TOPK,
-               alpha=TAL_ALPHA, beta=TAL_BETA, return_match_count=False):
+               alpha=TAL_ALPHA, beta=TAL_BETA, return_match_count=False, align_out=None):
     """`tal_assign_device` from host lists: boxes_per_image a list of (G_i, 4) float64 arrays / tensors (degenerate ones are dropped), templates
-    the (nt, 4 or 5) table, paste_boxes (B, 4) and flips (B,) as dense_overlap_targets takes them.  IN PLACE on the two device maps."""
+    the (nt, 4 or 5) table, paste_boxes (B, 4) and flips (B,) as dense_overlap_targets takes them.  IN PLACE on the two device maps.  align_out as
+    tal_assign_device takes it."""
     check_tal(topk, alpha, beta)
     require_gpu(output, "tal_assign")
     if len(boxes_per_image) != output.shape[0]:
@@ -390,8 +407,11 @@ def tal_assign(output, class_map, regression_map, boxes_per_image, templates, rf
     with torch.cuda.device(output.device):
         (boxes_d, offs_d, total), t_d, paste_d, flips_d, _, _, _ = _upload_lists("tal_assign", boxes_per_image, templates, paste_boxes, flips, None,
                                                                                  output.device)
+        if align_out is None:
+            return tal_assign_device(output, class_map, regression_map, boxes_d, offs_d, total, t_d, None, rf, paste_d, flips_d, topk, alpha, beta,
+                                     return_match_count)
         return tal_assign_device(output, class_map, regression_map, boxes_d, offs_d, total, t_d, None, rf, paste_d, flips_d, topk, alpha, beta,
-                                 return_match_count)
+                                 return_match_count, align_out=align_out)
 
 
 def dense_overlap_iou(boxes, templates, heatmap_size=(63, 63), rf=RF, device="cuda"):
@@ -1072,6 +1092,44 @@ def criterion_quality_fwd_bwd(output, class_map, regression_map, n_templates=25,
         check(lib().tf_criterion_quality_fwd_bwd(ptr(output), ptr(class_map), ptr(regression_map), B, nt, H, W, float(beta),
                                                  FOCAL_NORMALIZE[normalize], float(reg_weight), REG_LOSSES[reg_loss], ptr(twh),
                                                  ptr(grad), ptr(loss), ptr(npos), ptr(ws), wsb, stream()), "tf_criterion_quality_fwd_bwd")
+    return loss, grad, npos
+
+
+ALIGNED_NORMALIZE = {"none": 0, "pos": 1, "align": 2}    # TF_FOCAL_NORM_*: "align" belongs to the task-aligned form alone
+
+
+def check_aligned(beta, normalize):
+    """ValueError unless beta is finite and >= 1 (check_qfl's bound) and normalize one of ALIGNED_NORMALIZE."""
+    check_qfl(beta, "pos")
+    if normalize not in ALIGNED_NORMALIZE:
+        raise ValueError(f"task-aligned loss: normalize must be one of {sorted(ALIGNED_NORMALIZE)}, got {normalize!r}")
+
+
+def criterion_aligned_fwd_bwd(output, class_map, regression_map, align_map, n_templates=25, reg_weight=1.0, beta=2.0, normalize="align",
+                              reg_loss="smooth_l1", template_wh=None, grad=None):
+    """TOOD's task-aligned loss (Feng et al. 2021; tf_criterion_aligned_fwd_bwd, the definition is in include/tinyfaces_hip.h): the quality focal
+    form with the target of a positive READ from align_map (what tal_assign_device(..., align_out=) wrote: the face's normalised alignment),
+    q = min(1, max(0, a)), a NaN giving 0, and the regression term of every positive -- `reg_loss`, as in criterion_quality_fwd_bwd --
+    weighted by the same q.  align_map: float32 of class_map's shape, read at the +1 labels only.  normalize: "none", "pos" (per image by
+    max(1, its positives)) or "align": per image by max(1, the sum of q over its positives), TOOD's avg_factor taken per image, so that an
+    image's loss still does not depend on its batch.  class_map is only read.
+    Returns (loss[4] f64 device tensor = [sum cls, sum of q-weighted reg, sum of q over the positives (not normalised), number of positives],
+    grad wrt output, npos[B] int32): loss[2] / loss[3] is the mean target of the positives.
+    grad: write the gradient into this contiguous fp32 tensor of output's shape (every element is written exactly once, no memset needed)."""
+    require_gpu(output, "criterion_aligned")
+    check_aligned(beta, normalize)
+    check_reg_loss(reg_loss, reg_weight, template_wh, n_templates)
+    output, regression_map, (B, nt, H, W), dev, twh, grad, loss, npos = _criterion_operands(output, class_map, regression_map, n_templates, grad, 4,
+                                                                                            template_wh if reg_loss == "diou" else None)
+    if not torch.is_tensor(align_map) or align_map.dtype != torch.float32 or not align_map.is_contiguous() or align_map.device != dev or \
+            align_map.shape != class_map.shape:
+        raise ValueError("criterion_aligned_fwd_bwd: align_map is a contiguous float32 tensor of class_map's shape on the output's device")
+    wsb = lib().tf_criterion_aligned_workspace_bytes(B, nt, H, W)
+    ws = _workspace("criterion_aligned", wsb, dev)
+    with torch.cuda.device(dev):
+        check(lib().tf_criterion_aligned_fwd_bwd(ptr(output), ptr(class_map), ptr(regression_map), ptr(align_map), B, nt, H, W, float(beta),
+                                                 ALIGNED_NORMALIZE[normalize], float(reg_weight), REG_LOSSES[reg_loss], ptr(twh),
+                                                 ptr(grad), ptr(loss), ptr(npos), ptr(ws), wsb, stream()), "tf_criterion_aligned_fwd_bwd")
     return loss, grad, npos
 
 

@@ -22,9 +22,13 @@ def print_state(idx, epoch, size, loss_cls, loss_reg):
 def print_quality(idx, epoch, size, loss_fn):
     """One line per logged interval when the criterion trains with the quality focal loss (`cls_loss="qfl"`): the mean IoU of the predicted boxes
     of all positives seen so far with their targets (DetectionCriterion.quality_average), the quantity the scores are trained towards.  The
-    meter is fed by the loss meters' own host read, so nothing waits here.  With the other losses, or before a positive was seen: nothing."""
+    meter is fed by the loss meters' own host read, so nothing waits here.  With the other losses, or before a positive was seen: nothing.
+    With TaskAligned(aligned_targets=True) the meter holds the mean aligned TARGET of the positives, and the line says so."""
     meter = getattr(loss_fn, "quality_average", None)
     if getattr(loss_fn, "cls_loss", None) != "qfl" or meter is None or meter.num_averaged == 0:
+        return
+    if getattr(loss_fn, "aligned_targets", False):
+        print(f"Epoch: [{epoch}][{idx}/{size}]\tmean aligned target of positives {meter.average:.4f} ({meter.num_averaged} positives)")
         return
     print(f"Epoch: [{epoch}][{idx}/{size}]\tmean IoU of positives {meter.average:.4f} ({meter.num_averaged} positives)")
 
