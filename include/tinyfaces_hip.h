@@ -367,6 +367,50 @@ int tf_soft_nms_f64_capped(const double* boxes /*[n][4]*/, const double* scores 
                            double score_thresh, int score_mode, int max_keep, int64_t* keep_out /*[n]*/, double* score_out /*[n]*/,
                            int32_t* num_keep /*device [1]*/, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Matrix NMS, float64 (Wang et al., SOLOv2, NeurIPS 2020; PaddleDetection's matrix_nms, used for boxes in PP-YOLO) ----------
+ * An addition next to Soft-NMS: the same kind of decay in closed form.  A candidate's factor depends only on the better-scored candidates
+ * and on THEIR largest overlap with something still better, so nothing is selected in turn and nothing is serial.  Per segment (batching
+ * as tf_nms_f64_batched), with p_i the vote weight of scores[i] under score_mode (TF_VOTE_WEIGHT_SIGMOID: 1 / (1 + exp(-scores[i])),
+ * TF_VOTE_WEIGHT_SCORE: scores[i]):
+ *   1. Admission.  Candidate i is admitted iff p_i >= score_thresh; a NaN fails the test.  An unadmitted candidate is never emitted and
+ *      decays nothing (a candidate is only ever decayed by better-scored ones, so dropping them first loses nothing).
+ *   2. Rank.  The admitted are ranked by p descending, the lower input index first on an equal p (-0.0 == +0.0).  Below, i < j means
+ *      "ranked above".
+ *   3. IoU.  iou(i, j) is tf_nms_f64's IoU in the same operation order: areas without +1, inter / (a_i + a_j - inter); the file is
+ *      compiled without FMA contraction.  inter == 0 or a NaN quotient counts as 0, as in Soft-NMS.
+ *   4. Compensation.  comp_j = max_{i<j} iou(i, j); 0 for the best candidate.
+ *   5. Decay.  d_0 = 1.  For j > 0:
+ *      TF_MATRIX_NMS_LINEAR:   d_j = min over {i < j : comp_i < 1} of (1 - iou(i, j)) / (1 - comp_i), each term one float64 subtract,
+ *        subtract, divide.  A candidate with comp_i >= 1 is an exact duplicate of a better box, which stands in for it: it contributes no
+ *        term.  Rank 0 always contributes a term <= 1, so 0 <= d_j <= 1.  There is no IoU threshold.
+ *      TF_MATRIX_NMS_GAUSSIAN: x_j = max_{i<j} (iou(i, j) * iou(i, j) - comp_i * comp_i), d_j = exp(-x_j / sigma): ONE exp per candidate, on
+ *        the extremal argument.  sigma is the Soft-NMS sigma, a divisor (SOLOv2's and Paddle's multiplier 2.0 is sigma = 0.5).  x_j >= 0:
+ *        rank 0 contributes iou^2.
+ *   6. Emission.  s_j = p_j * d_j; candidate j is emitted iff s_j >= score_thresh.  Rows are ordered by s descending, the better rank
+ *      first on an equal s: keep_out[off + r] = the candidate (an index into the CONCATENATED input), score_out[off + r] = s, the decayed
+ *      PROBABILITY as in Soft-NMS.  num_keep[s] = min(K_s, max_keep) for K_s emitted candidates; max_keep == 0: no cap.
+ * Rows r >= num_keep[s] of keep_out / score_out are NOT written, nothing outside [off[s], off[s] + num_keep[s]) is.  max and min are exact
+ * and order-independent and there is no floating-point atomic: the same bits on every run; the linear method is a chain of single IEEE
+ * operations behind p.  Five launches whatever n and S; no memset is asked of the caller beyond num_keep for n == 0, no host
+ * synchronisation.  An unknown method or score mode, sigma that is not > 0, a negative or NaN score_thresh, max_keep < 0 and bad segment
+ * tables (S outside 1..TF_NMS_MAX_SEGMENTS, offsets that do not start at 0 or descend) are TF_ERR_ARG.  n == 0 launches nothing and leaves
+ * num_keep as the caller zeroed it.  A segment longer than TF_MATRIX_NMS_MAX_BOXES is TF_ERR_UNSUPPORTED.  ws:
+ * tf_matrix_nms_batched_workspace_bytes(): 68 bytes per candidate (no n^2 / 8 adjacency bits), every byte read is written by the call
+ * first; 0 for n == 0. */
+#define TF_MATRIX_NMS_LINEAR   1
+#define TF_MATRIX_NMS_GAUSSIAN 2
+#define TF_MATRIX_NMS_MAX_BOXES 524160   /* the hard NMS's largest segment: the kernels hold nothing per segment in one workgroup, so they need no less */
+size_t tf_matrix_nms_batched_workspace_bytes(const int32_t* host_seg_offsets, int num_segments);
+int tf_matrix_nms_f64_batched(const double* boxes /*[n][4]*/, const double* scores /*[n]*/, const int32_t* host_seg_offsets /*[S+1]*/,
+                              int num_segments, int method, double sigma, double score_thresh, int score_mode /* TF_VOTE_WEIGHT_* */,
+                              int max_keep, int64_t* keep_out /*[n], indices into the concatenated input*/, double* score_out /*[n]*/,
+                              int32_t* num_keep /*device [S]*/, void* ws, size_t ws_bytes, void* stream);
+/* one segment: the batched form with S = 1 */
+size_t tf_matrix_nms_workspace_bytes(int n);
+int tf_matrix_nms_f64(const double* boxes /*[n][4]*/, const double* scores /*[n]*/, int n, int method, double sigma, double score_thresh,
+                      int score_mode, int max_keep, int64_t* keep_out /*[n]*/, double* score_out /*[n]*/, int32_t* num_keep /*device [1]*/,
+                      void* ws, size_t ws_bytes, void* stream);
+
 /* ---- deterministic top-k selection on float64 scores (the `top_k` / `topk_candidates` step in front of the suppression) ----------
  * An addition in front of tf_nms_f64 / tf_soft_nms_f64, both O(n^2): it bounds the candidates that reach them, and cuts a list too long
  * for either to one they take.  Segments as for tf_nms_f64_batched: a HOST offset table, [0] == 0, S <= TF_NMS_MAX_SEGMENTS.  For segment

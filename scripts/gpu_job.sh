@@ -18,6 +18,7 @@
 #   contention | floor | nms   the round-3 micro-benchmarks (scripts/contention.py, floor.py, nms_bench.py under the tracer)
 #   tta                        cost of the test-time augmentation: vote vs NMS kernels, pyramid with / without flip and voting (scripts/tta_numbers.py) -> $TTA_OUT (default profiles/tta.jsonl)
 #   soft-nms                   cost of Soft-NMS: kernels vs the hard NMS at 65 536 candidates, pyramid plain / linear / gaussian, parity (scripts/soft_nms_numbers.py) -> $SOFT_NMS_OUT (default profiles/soft_nms.jsonl)
+#   matrix-nms                 cost of Matrix NMS: kernels vs the hard NMS and Soft-NMS (uncapped, capped at 750) at 65 536 candidates, pyramid plain / soft linear / matrix linear / matrix gaussian, parity (scripts/matrix_nms_numbers.py) -> $MATRIX_NMS_OUT (default profiles/matrix_nms.jsonl)
 #   topk                       cost of the pre-NMS top-k and the detection cap: select + NMS vs the full NMS at 65 536 / 600 000 candidates, Soft-NMS capped vs uncapped, pyramid plain / soft / soft + both bounds (scripts/topk_numbers.py) -> $TOPK_OUT (default profiles/topk.jsonl)
 #   color-jitter               cost of the colour jitter: image_prepare plain / three ops / four ops / contrast alone on the 500x500 window, batch building with / without it (scripts/color_jitter_numbers.py) -> $COLOR_JITTER_OUT (default profiles/color_jitter.jsonl)
 #   quality-loss               cost of the quality focal loss: the qfl call next to the focal call of the same reg_loss on the step's operands, the bf16 step with either (scripts/quality_loss_numbers.py) -> $QUALITY_LOSS_OUT (default profiles/quality_loss.jsonl)
@@ -102,6 +103,12 @@ print(d['value'], d['ms_per_step'], 'frac', r.get('frac'), 'fwd', r.get('forward
       timeout -k 10 ${SOFT_NMS_TIMEOUT:-300} python scripts/soft_nms_numbers.py --step pyramid >> "$out" 2>> "$err" &&
       timeout -k 10 ${SOFT_NMS_TIMEOUT:-300} python scripts/soft_nms_numbers.py --step parity > "$par" 2>> "$err"
     echo "soft-nms exit $?"; cat "$out"; tail -3 "$err" ;;
+  matrix-nms)   # one process and one time limit per step; a step only behind a clean one before it
+    out=${MATRIX_NMS_OUT:-$R/profiles/matrix_nms.jsonl}; err=${out%.jsonl}.err; par=${out%.jsonl}_parity.txt
+    timeout -k 10 ${MATRIX_NMS_TIMEOUT:-300} python scripts/matrix_nms_numbers.py --step kernels > "$out" 2> "$err" &&
+      timeout -k 10 ${MATRIX_NMS_TIMEOUT:-300} python scripts/matrix_nms_numbers.py --step pyramid >> "$out" 2>> "$err" &&
+      timeout -k 10 ${MATRIX_NMS_TIMEOUT:-300} python scripts/matrix_nms_numbers.py --step parity > "$par" 2>> "$err"
+    echo "matrix-nms exit $?"; cat "$out"; tail -3 "$err" ;;
   topk)   # one process and one time limit per step; the second step only behind a clean first one
     out=${TOPK_OUT:-$R/profiles/topk.jsonl}; err=${out%.jsonl}.err
     timeout -k 10 ${TOPK_TIMEOUT:-300} python scripts/topk_numbers.py --step kernels > "$out" 2> "$err" &&

@@ -20,7 +20,7 @@ EXPORTS = os.path.join(CSRC, "exports.map")   # only tf_* leaves the library
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # files whose float64 arithmetic must round exactly like numpy's: no FMA contraction
-EXACT = {"targets.hip", "nms.hip", "decode.hip", "augment.hip", "vote.hip", "soft_nms.hip", "adamw.hip", "wider_eval.hip", "targets_ignore.hip", "targets_atss.hip", "targets_tal.hip"}
+EXACT = {"targets.hip", "nms.hip", "decode.hip", "augment.hip", "vote.hip", "soft_nms.hip", "matrix_nms.hip", "adamw.hip", "wider_eval.hip", "targets_ignore.hip", "targets_atss.hip", "targets_tal.hip"}
 
 
 def _deps_mtime():

@@ -13,6 +13,7 @@ static const char* const kSymbols[] = {
     "tf_box_vote_f64", "tf_box_vote_f64_batched", "tf_boxes_unflip_f64",
     "tf_soft_nms_workspace_bytes", "tf_soft_nms_f64", "tf_soft_nms_batched_workspace_bytes", "tf_soft_nms_f64_batched",
     "tf_soft_nms_f64_capped", "tf_soft_nms_f64_batched_capped",
+    "tf_matrix_nms_workspace_bytes", "tf_matrix_nms_f64", "tf_matrix_nms_batched_workspace_bytes", "tf_matrix_nms_f64_batched",
     "tf_topk_workspace_bytes", "tf_topk_select_f64", "tf_topk_batched_workspace_bytes", "tf_topk_select_f64_batched",
     "tf_wider_match_workspace_bytes", "tf_wider_match_f64_batched", "tf_wider_pr_accumulate",
     "tf_criterion_workspace_bytes", "tf_criterion_fwd_bwd", "tf_criterion_focal_workspace_bytes", "tf_criterion_focal_fwd_bwd",
@@ -45,7 +46,7 @@ void set_next_stop_event(hipEvent_t e) { g_next_stop_event = e; }
 hipEvent_t take_next_stop_event() { hipEvent_t e = g_next_stop_event; g_next_stop_event = nullptr; return e; }
 }  // namespace tf
 
-extern "C" int tf_version(void) { return 800; }   // 800: task-aligned target assignment (tf_targets_tal, tf_targets_tal_workspace_bytes); 790: quality focal loss (tf_criterion_quality_fwd_bwd, tf_criterion_quality_workspace_bytes); 780: ATSS target assignment (tf_targets_atss, tf_targets_atss_workspace_bytes); 770: ignore regions of the training targets (tf_targets_apply_ignore); 760: scale-compensated anchor matching (tf_dense_overlap_targets_comp, tf_targets_comp_workspace_bytes); 750: deterministic training (tf_set_deterministic, tf_conv2d_wgrad_det, tf_stem_wgrad_det and their workspace queries); 740: WIDER evaluation on the device (tf_wider_match_f64_batched, tf_wider_pr_accumulate, tf_wider_match_workspace_bytes); 730: colour jitter (tf_image_prepare_jitter, tf_image_prepare_jitter_workspace_bytes); 720: top-k selection + the Soft-NMS cap (tf_topk_select_f64[_batched], tf_soft_nms_f64[_batched]_capped); 710: AdamW (tf_adamw_advance, tf_adamw_step, tf_adamw_step_segments); 700: IoU / GIoU / DIoU regression losses (tf_criterion_focal_box_fwd_bwd); 690: focal loss (tf_criterion_focal_fwd_bwd); 680: Soft-NMS (tf_soft_nms_f64, tf_soft_nms_f64_batched); 670: gradient accumulation (tf_grad_accumulate_segments); 660: test-time augmentation (tf_box_vote_f64, tf_box_vote_f64_batched, tf_boxes_unflip_f64); 650: model EMA (tf_sgd_step_ema, tf_sgd_step_segments_ema, tf_ema_update_segments); 640: gradient-norm clipping + the non-finite-step guard (tf_grad_clip_coef, tf_sgd_step*_clipped, tf_scale_segments); 630: partial freeze (tf_detnet_trunk_backward_frozen_from_ctx); 620: frozen BatchNorm (training = 2, tf_detnet_*backward_frozen_ctx, tf_sgd_step_segments); 610: tf_detnet_trunk_* (ResNet-50 / -152 trunks); r6: tf_build_id; r4: context + hooks + communicator entry points
+extern "C" int tf_version(void) { return 810; }   // 810: Matrix NMS (tf_matrix_nms_f64, tf_matrix_nms_f64_batched and their workspace queries); 800: task-aligned target assignment (tf_targets_tal, tf_targets_tal_workspace_bytes); 790: quality focal loss (tf_criterion_quality_fwd_bwd, tf_criterion_quality_workspace_bytes); 780: ATSS target assignment (tf_targets_atss, tf_targets_atss_workspace_bytes); 770: ignore regions of the training targets (tf_targets_apply_ignore); 760: scale-compensated anchor matching (tf_dense_overlap_targets_comp, tf_targets_comp_workspace_bytes); 750: deterministic training (tf_set_deterministic, tf_conv2d_wgrad_det, tf_stem_wgrad_det and their workspace queries); 740: WIDER evaluation on the device (tf_wider_match_f64_batched, tf_wider_pr_accumulate, tf_wider_match_workspace_bytes); 730: colour jitter (tf_image_prepare_jitter, tf_image_prepare_jitter_workspace_bytes); 720: top-k selection + the Soft-NMS cap (tf_topk_select_f64[_batched], tf_soft_nms_f64[_batched]_capped); 710: AdamW (tf_adamw_advance, tf_adamw_step, tf_adamw_step_segments); 700: IoU / GIoU / DIoU regression losses (tf_criterion_focal_box_fwd_bwd); 690: focal loss (tf_criterion_focal_fwd_bwd); 680: Soft-NMS (tf_soft_nms_f64, tf_soft_nms_f64_batched); 670: gradient accumulation (tf_grad_accumulate_segments); 660: test-time augmentation (tf_box_vote_f64, tf_box_vote_f64_batched, tf_boxes_unflip_f64); 650: model EMA (tf_sgd_step_ema, tf_sgd_step_segments_ema, tf_ema_update_segments); 640: gradient-norm clipping + the non-finite-step guard (tf_grad_clip_coef, tf_sgd_step*_clipped, tf_scale_segments); 630: partial freeze (tf_detnet_trunk_backward_frozen_from_ctx); 620: frozen BatchNorm (training = 2, tf_detnet_*backward_frozen_ctx, tf_sgd_step_segments); 610: tf_detnet_trunk_* (ResNet-50 / -152 trunks); r6: tf_build_id; r4: context + hooks + communicator entry points
 #ifndef TF_BUILD_ID
 #define TF_BUILD_ID "unstamped"
 #endif

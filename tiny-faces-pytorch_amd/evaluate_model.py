@@ -139,6 +139,24 @@ def limits_arguments(argv=None):
     return args
 
 
+MATRIX_NMS_HELP = ("--soft-nms {matrix-linear,matrix-gaussian}: Matrix NMS -- Soft-NMS's decay in closed form, with no serial selection (linear: "
+                   "min (1 - IoU) / (1 - comp); gaussian: exp(-(IoU^2 - comp^2) / S) with --soft-nms-sigma S, comp being the better candidate's own "
+                   "largest overlap); --soft-nms-score-thresh as for Soft-NMS; --nms_thresh is not used")
+
+
+def matrix_nms_arguments(argv=None):
+    """`limits_arguments` with --soft-nms also taking matrix-linear / matrix-gaussian (`soft_nms` = "matrix_linear" / "matrix_gaussian", the
+    values get_detections takes), parsed apart in the same way: the flag is resolved here and the older parsers, whose choices stay as they
+    are, see the rest."""
+    parser = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    parser.add_argument("--soft-nms", dest="soft_nms", choices=["linear", "gaussian", "matrix-linear", "matrix-gaussian"], default=None,
+                        help=MATRIX_NMS_HELP)
+    known, rest = parser.parse_known_args(argv)
+    args = limits_arguments(rest)
+    args.soft_nms = None if known.soft_nms is None else known.soft_nms.replace("-", "_")
+    return args
+
+
 def check_ap(args):
     """--ap is refused, before anything is loaded, where it cannot be answered: under several ranks (every rank sees a shard of the images; the
     table is not reduced across ranks) and for a WIDER annotation file without --gt-dir."""
@@ -230,7 +248,7 @@ def run(model, val_loader, templates, prob_thresh, nms_thresh, device, split, re
 
 
 def main():
-    args = limits_arguments()
+    args = matrix_nms_arguments()
     check_ap(args)
     if not torch.cuda.is_available():
         raise SystemExit("this build of the tiny-faces hot path runs on MI355X only (no CPU fallback)")

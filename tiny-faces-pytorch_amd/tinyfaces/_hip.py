@@ -132,6 +132,10 @@ _SIGNATURES = {
     "tf_soft_nms_f64_batched": (i32, [vp, vp, C.POINTER(i32), i32, i32, f64, f64, f64, i32, vp, vp, vp, vp, sz, vp]),
     "tf_soft_nms_f64_capped": (i32, [vp, vp, i32, i32, f64, f64, f64, i32, i32, vp, vp, vp, vp, sz, vp]),
     "tf_soft_nms_f64_batched_capped": (i32, [vp, vp, C.POINTER(i32), i32, i32, f64, f64, f64, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "tf_matrix_nms_workspace_bytes": (sz, [i32]),
+    "tf_matrix_nms_f64": (i32, [vp, vp, i32, i32, f64, f64, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "tf_matrix_nms_batched_workspace_bytes": (sz, [C.POINTER(i32), i32]),
+    "tf_matrix_nms_f64_batched": (i32, [vp, vp, C.POINTER(i32), i32, i32, f64, f64, i32, i32, vp, vp, vp, vp, sz, vp]),
     "tf_topk_workspace_bytes": (sz, [i32, i32]),
     "tf_topk_select_f64": (i32, [vp, i32, i32, vp, vp, sz, vp]),
     "tf_topk_batched_workspace_bytes": (sz, [C.POINTER(i32), i32, i32]),

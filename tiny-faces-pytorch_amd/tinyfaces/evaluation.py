@@ -118,13 +118,26 @@ def _decode_image(model, levels, flip, *args):
     _decode_levels(model, levels[half:], *args, mirrored=True)
 
 
+MATRIX_NMS = {"matrix_linear": "linear", "matrix_gaussian": "gaussian"}      # soft_nms= values that select ops.matrix_nms, and its method
+
+
 def _check_soft_nms(soft_nms, nms_thresh, sigma, score_thresh):
     """The keywords of get_detections / get_detections_batch, refused before the model runs."""
     if soft_nms is None:
         return
+    if soft_nms in MATRIX_NMS:
+        ops._matrix_nms_mode(MATRIX_NMS[soft_nms], sigma, score_thresh, "sigmoid", None)     # nms_thresh plays no part
+        return
     if soft_nms not in ops.SOFT_NMS_METHODS:
-        raise ValueError(f"soft_nms={soft_nms!r}: expected None or one of {sorted(ops.SOFT_NMS_METHODS)}")
+        raise ValueError(f"soft_nms={soft_nms!r}: expected None or one of {sorted(ops.SOFT_NMS_METHODS) + sorted(MATRIX_NMS)}")
     ops._soft_nms_mode(soft_nms, nms_thresh if soft_nms == "linear" else 0.0, sigma, score_thresh, "sigmoid")
+
+
+def _suppression_limit(soft_nms):
+    """(largest candidate list the method of `soft_nms` takes, its name in a message)."""
+    if soft_nms in MATRIX_NMS:
+        return ops.MATRIX_NMS_MAX_BOXES, "Matrix NMS"
+    return ops.SOFT_NMS_MAX_BOXES, "Soft-NMS"
 
 
 def _check_limits(pre_nms_topk, max_detections):
@@ -146,12 +159,16 @@ def _pre_nms_cut(cand, offs, pre_nms_topk):
 
 
 def _soft_nms_rows(cand, offs, method, nms_thresh, sigma, score_thresh, box_voting, max_keep=None):
-    """Soft-NMS over the segments `offs` of the device candidate list (rows x1, y1, x2, y2, logit) -> ([keep], [(K_s, 5) device rows]):
+    """Soft-NMS (or, for a method of MATRIX_NMS, Matrix NMS) over the segments `offs` of the device candidate list (rows x1, y1, x2, y2, logit)
+    -> ([keep], [(K_s, 5) device rows]):
     cand[keep] in selection order, or the voted rows, with the decayed probability in column 4.  One synchronisation."""
     boxes, scores = cand[:, :4].contiguous(), cand[:, 4].contiguous()
     thr = nms_thresh if method == "linear" else 0.0             # the gaussian method ignores it
     vote = {} if box_voting is None else {"vote": (box_voting, "sigmoid")}
-    if max_keep is None:                                        # without a cap the call is the one it was
+    if method in MATRIX_NMS:                                    # Matrix NMS: no IoU threshold; the cap is an argument of the one call
+        res = ops.matrix_nms_batched(boxes, scores, offs, MATRIX_NMS[method], sigma, score_thresh, max_keep=None if max_keep is None else int(max_keep),
+                                     **vote)
+    elif max_keep is None:                                      # without a cap the call is the one it was
         res = ops.soft_nms_batched(boxes, scores, offs, method, thr, sigma, score_thresh, **vote)
     else:
         res = ops.soft_nms_batched_capped(boxes, scores, offs, int(max_keep), method, thr, sigma, score_thresh, **vote)
@@ -181,6 +198,12 @@ def get_detections(model, img, templates, rf, img_transforms, prob_thresh=0.65, 
     nms_thresh is the linear method's IoU threshold, soft_nms_sigma the gaussian method's (which ignores nms_thresh).  The rows are
     cand[keep] in selection order with column 4 replaced by the DECAYED PROBABILITY (not a logit); with box_voting the voted rows, column 4
     likewise; return_candidates returns that keep.
+    soft_nms="matrix_linear" | "matrix_gaussian" (an addition as well): Matrix NMS (`ops.matrix_nms`, method "linear" / "gaussian") -- the same
+    kind of decay in closed form, with no serial selection: a candidate's factor depends on the better-scored candidates and on their own
+    largest overlap with something still better.  soft_nms_sigma and soft_nms_score_thresh keep their meaning (SOLOv2's multiplier 2.0 is
+    sigma 0.5); nms_thresh is NOT USED by either matrix method (there is no IoU threshold).  Rows, column 4, box_voting, flip, pre_nms_topk
+    and return_candidates as with Soft-NMS; max_detections goes into the call as its max_keep; the candidate-count limit is
+    ops.MATRIX_NMS_MAX_BOXES.
     The two bounds every WIDER FACE pipeline has (additions; None: off, the same launches and rows bit for bit):
     pre_nms_topk=K (S3FD / PyramidBox / RetinaFace `top_k`, torchvision's `topk_candidates`): when more than K candidates pass prob_thresh, only
     the K best -- larger score, the earlier candidate on a tie, the hard NMS's own order -- reach the NMS / Soft-NMS / vote
@@ -217,9 +240,10 @@ def get_detections(model, img, templates, rf, img_transforms, prob_thresh=0.65, 
                            "takes (64 KiB of LDS for the suppression bitmap); a trained detector keeps a few thousand -- untrained weights?  "
                            "pre_nms_topk=K bounds what reaches the NMS without touching prob_thresh")
     full = dets[:n]
-    if soft_nms is not None and reach > ops.SOFT_NMS_MAX_BOXES:
-        raise RuntimeError(f"get_detections: {reach} candidates above prob_thresh={prob_thresh} exceed the {ops.SOFT_NMS_MAX_BOXES} boxes one "
-                           f"Soft-NMS call takes (the hard NMS takes {ops.NMS_MAX_BOXES}): pass pre_nms_topk <= {ops.SOFT_NMS_MAX_BOXES}, "
+    limit, what = _suppression_limit(soft_nms)
+    if soft_nms is not None and reach > limit:
+        raise RuntimeError(f"get_detections: {reach} candidates above prob_thresh={prob_thresh} exceed the {limit} boxes one "
+                           f"{what} call takes (the hard NMS takes {ops.NMS_MAX_BOXES}): pass pre_nms_topk <= {limit}, "
                            "raise prob_thresh or use soft_nms=None")
     cand, offs, idx = _pre_nms_cut(full, [0, n], pre_nms_topk)
     if soft_nms is not None:
@@ -252,7 +276,8 @@ def get_detections_batch(model, imgs, templates, rf, img_transforms, prob_thresh
     suppressed by ONE tf_nms_f64_batched call (three launches whatever the number of images; BASELINE.json configs[4]) and the
     only host synchronisation of the whole batch is the read of the candidate counts.  Row for row identical to the loop.
     flip / box_voting: as in get_detections; an image's mirrored candidates follow its unmirrored ones, so its segment stays contiguous.
-    soft_nms / soft_nms_sigma / soft_nms_score_thresh: as in get_detections, one tf_soft_nms_f64_batched call over the per-image segments.
+    soft_nms / soft_nms_sigma / soft_nms_score_thresh: as in get_detections, one tf_soft_nms_f64_batched call over the per-image segments
+    (soft_nms="matrix_linear" | "matrix_gaussian": one tf_matrix_nms_f64_batched call; nms_thresh is not used).
     pre_nms_topk / max_detections: as in get_detections, per image: one tf_topk_select_f64_batched call cuts every image's segment that is
     longer than pre_nms_topk, behind the one synchronisation the call already has."""
     device = torch.device(device if device is not None else "cuda")
@@ -283,10 +308,11 @@ def get_detections_batch(model, imgs, templates, rf, img_transforms, prob_thresh
     if longest > ops.NMS_MAX_BOXES:
         raise RuntimeError(f"get_detections_batch: an image has more than {ops.NMS_MAX_BOXES} candidates above prob_thresh={prob_thresh}; "
                            "pre_nms_topk=K bounds what reaches the NMS without touching prob_thresh")
-    if soft_nms is not None and longest > ops.SOFT_NMS_MAX_BOXES:
+    limit, what = _suppression_limit(soft_nms)
+    if soft_nms is not None and longest > limit:
         raise RuntimeError(f"get_detections_batch: an image has {longest} candidates above prob_thresh={prob_thresh}, more than the "
-                           f"{ops.SOFT_NMS_MAX_BOXES} boxes one Soft-NMS call takes (the hard NMS takes {ops.NMS_MAX_BOXES}): pass "
-                           f"pre_nms_topk <= {ops.SOFT_NMS_MAX_BOXES}")
+                           f"{limit} boxes one {what} call takes (the hard NMS takes {ops.NMS_MAX_BOXES}): pass "
+                           f"pre_nms_topk <= {limit}")
     cand, offs, _ = _pre_nms_cut(dets[:offs[-1]], offs, pre_nms_topk)
     if soft_nms is not None:
         _, rows = _soft_nms_rows(cand, offs, soft_nms, nms_thresh, soft_nms_sigma, soft_nms_score_thresh, box_voting, max_detections)

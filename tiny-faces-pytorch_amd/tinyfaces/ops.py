@@ -759,6 +759,80 @@ def _soft_nms_call(boxes, scores, offs, mode, vote, cap=0):
     return keep, kept, cnt, voted
 
 
+# --------------------------------------------------------------------------- Matrix NMS
+MATRIX_NMS_METHODS = {"linear": 1, "gaussian": 2}         # TF_MATRIX_NMS_* (include/tinyfaces_hip.h)
+MATRIX_NMS_MAX_BOXES = 524160                             # TF_MATRIX_NMS_MAX_BOXES: the hard NMS's limit; nothing of a segment lives in one workgroup
+
+
+def _matrix_nms_mode(method, sigma, score_threshold, score, max_keep):
+    """The host-side refusals of tf_matrix_nms_f64_batched, raised before anything is launched."""
+    if method not in MATRIX_NMS_METHODS:
+        raise ValueError(f"matrix_nms: method={method!r}, expected one of {sorted(MATRIX_NMS_METHODS)}")
+    if score not in VOTE_WEIGHTS:
+        raise ValueError(f"matrix_nms: score={score!r}, expected one of {sorted(VOTE_WEIGHTS)}")
+    sg, st = float(sigma), float(score_threshold)
+    if not sg > 0.0:
+        raise ValueError(f"matrix_nms: sigma={sigma!r} is not > 0")
+    if not st >= 0.0:
+        raise ValueError(f"matrix_nms: score_threshold={score_threshold!r} is negative or NaN")
+    cap = 0 if max_keep is None else _max_keep(max_keep, "matrix_nms")
+    return MATRIX_NMS_METHODS[method], sg, st, VOTE_WEIGHTS[score], cap
+
+
+def matrix_nms(boxes, scores, method="gaussian", sigma=0.5, score_threshold=0.001, score="sigmoid", max_keep=None):
+    """Matrix NMS (Wang et al., SOLOv2; PaddleDetection's matrix_nms) on float64 device tensors, tf_matrix_nms_f64: Soft-NMS's kind of decay in
+    closed form, with no serial selection.  Every candidate with p >= score_threshold is ranked by p; comp_j = its largest IoU with a better
+    one; "linear": d_j = min over the better i (comp_i < 1) of (1 - IoU(i, j)) / (1 - comp_i); "gaussian": d_j = exp(-max_i (IoU(i, j)^2 -
+    comp_i^2) / sigma) (SOLOv2's multiplier 2.0 is sigma = 0.5); s = p * d, emitted while s >= score_threshold.  There is no IoU threshold.
+    score: "sigmoid" (p = 1 / (1 + exp(-score)): decode_compact's scores are logits) or "score" (p = score as given).  max_keep: at most that
+    many rows, the first ones of the uncapped call.
+    Returns (keep int64 (K,), kept_scores float64 (K,)) by s descending: the decayed probabilities."""
+    res = matrix_nms_batched(boxes, scores, [0, int(boxes.shape[0])], method, sigma, score_threshold, score, max_keep)
+    return res[0]
+
+
+def matrix_nms_batched(boxes, scores, seg_offsets, method="gaussian", sigma=0.5, score_threshold=0.001, score="sigmoid", max_keep=None, vote=None):
+    """`matrix_nms` per segment [seg_offsets[s], seg_offsets[s+1]) in ONE tf_matrix_nms_f64_batched call (the workspace is 68 bytes per
+    candidate: there is no bit matrix to budget for, hence no grouping).  Returns a list of S (keep, kept_scores): keep indexes the CONCATENATED
+    input.
+    vote = (vote_thresh, weight): `box_voting_batched` is enqueued behind the call on its device-side keep list and counts, before the one
+    synchronisation, as for `soft_nms_batched`: weights and membership from the candidates' ORIGINAL scores, column 4 of a voted row the
+    decayed score.  Returns (the list above, [(K_s, 5) voted rows in keep order])."""
+    method, sigma, st, smode, cap = _matrix_nms_mode(method, sigma, score_threshold, score, max_keep)     # ValueError: needs no device
+    if vote is not None:
+        _vote_mode(vote[0], vote[1])
+    require_gpu(boxes, "matrix_nms_batched")
+    require_gpu(scores, "matrix_nms_batched")
+    offs = [int(o) for o in seg_offsets]
+    S = len(offs) - 1
+    if S < 1 or S > NMS_MAX_SEGMENTS or offs[0] != 0 or any(b < a for a, b in zip(offs, offs[1:])) or offs[-1] != boxes.shape[0]:
+        raise ValueError(f"matrix_nms_batched: bad segment offsets {offs[:4]}... for {boxes.shape[0]} boxes (1..{NMS_MAX_SEGMENTS} segments)")
+    longest = max(b - a for a, b in zip(offs, offs[1:]))
+    if longest > MATRIX_NMS_MAX_BOXES:
+        raise RuntimeError(f"matrix_nms_batched: a segment of {longest} boxes exceeds the {MATRIX_NMS_MAX_BOXES} one call takes (TF_MATRIX_NMS_MAX_BOXES)")
+    boxes = boxes.to(torch.float64).contiguous()
+    scores = scores.to(torch.float64).contiguous()
+    n, dev = offs[-1], boxes.device
+    keep = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    kept = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+    cnt = torch.zeros(S, dtype=torch.int32, device=dev)
+    host = (C.c_int32 * (S + 1))(*offs)
+    wsb = lib().tf_matrix_nms_batched_workspace_bytes(host, S)
+    ws = _workspace("matrix_nms", wsb, dev)
+    with torch.cuda.device(dev):
+        check(lib().tf_matrix_nms_f64_batched(ptr(boxes), ptr(scores), host, S, method, sigma, st, smode, cap, ptr(keep), ptr(kept), ptr(cnt),
+                                              ptr(ws), wsb, stream()), "tf_matrix_nms_f64_batched")
+    voted = None
+    if vote is not None:
+        voted = _box_vote_launch(boxes, scores, host, S, keep, cnt, vote[0], vote[1])[0]
+        voted[:, 4] = kept                                    # the vote kernel wrote the original score there; rows >= counts[s] hold nothing either way
+    counts = cnt.tolist()                                     # the one synchronisation
+    res = [(keep[offs[s]: offs[s] + counts[s]], kept[offs[s]: offs[s] + counts[s]]) for s in range(S)]
+    if vote is None:
+        return res
+    return res, [voted[offs[s]: offs[s] + counts[s]] for s in range(S)]
+
+
 # --------------------------------------------------------------------------- top-k selection in front of the suppression
 def _topk_arguments(scores, seg_offsets, k, what):
     """The host-side refusals of tf_topk_select_f64_batched, raised before anything is enqueued (and before a device is asked for)."""
